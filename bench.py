@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: time steps per second of the stabilized_schur step.
 
-  python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--config c3|c2|c4|c5] [--dump-outputs DIR] [--full]
 
 Default workload = BASELINE.json configs[2], the one its metric is quoted on: DFG 2D-1 refined to ~1M P1/P1 DOF.
 Other configs (same harness, for the per-config lines in DESIGN.md): c2 lid-driven cavity nx=288 (250 k DOF),
@@ -10,10 +10,12 @@ dt = 0.001 (~8 M DOF).
 
 N=1 runs in-process; for N>1 the driver launches one rank per GPU with torch.distributed.run.  A "step" is one full
 time step (moments, Newton with fused residual/Jacobian assembly, FGMRES + Schur/AMG preconditioner, wall shear
-stress, u_prev update) with every field resident in HBM.  Rank 0 prints ONE JSON line carrying `roofline` (dominant
-instrumented kernel, HIP-event timed), and at N=1 `cpu_baseline` (the CPU oracle running the same algorithm on the
-same mesh for a bounded number of steps on the host cores) and `parity` (GPU vs oracle functionals with both sides
-converged tightly).
+stress, u_prev update) with every field resident in HBM.  A plain run sets up, warms up, times K steps and prints ONE
+JSON line (rank 0).  `--dump-outputs DIR` writes the fields the last timed step produced as DIR/<name>.npy.  `--full`
+adds the legs that run after the timed region: the rest of the config's run (`end_to_end_measured`), the reference's
+literal state-copy loop, `results` (functionals), `roofline` and `kernels` (HIP-event timed steps), and at N=1 the
+zero-initial-guess check, `cpu_baseline` (the CPU oracle running the same algorithm on the same mesh for a bounded
+number of steps on the host cores) and `parity` (GPU vs oracle functionals with both sides converged tightly).
 """
 from __future__ import annotations
 
@@ -211,6 +213,27 @@ def functionals(args, sc):
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, solver, write):
+    """The fields a caller of the timed path receives after its last step, float64 per node: velocity, pressure and wall
+    shear stress.  Above DUMP_LIMIT_BYTES in all, every field is cut to the same seeded sample of nodes, whose indices are
+    written as node_index.npy.  Reading the fields gathers them from every rank, so every rank calls this; `write` on one."""
+    import numpy as np
+    fields = {"velocity": solver.u_sol.x.array, "pressure": solver.p_sol.x.array, "wall_shear_stress": solver.shear_stress.x.array}
+    nv = fields["pressure"].size
+    fields = {k: np.asarray(v, dtype=np.float64).reshape((nv, -1) if v.size > nv else (nv,)) for k, v in fields.items()}
+    per_node = sum(v.nbytes // nv for v in fields.values())
+    if nv * per_node > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(nv, (DUMP_LIMIT_BYTES - 4096) // (per_node + 8), replace=False))
+        fields = dict({k: v[idx] for k, v in fields.items()}, node_index=idx.astype(np.float64))
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        for k, v in fields.items():
+            np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py ...`
     as a child process (one rank per GPU, RCCL inside libcfdh.so), pass rank 0's JSON line through, return its exit code.
@@ -275,7 +298,14 @@ def main():
     ap.add_argument("--verbose", type=int, default=0)
     ap.add_argument("--solver", default="stabilized_schur", choices=["stabilized_schur", "stabilized_schur_bdf2"],
                     help="solver plugin (default: the headline one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write velocity, pressure and wall shear stress after the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the rest of the config's run, the literal loop, the functionals, the kernel "
+                         "timings / roofline, the zero-initial-guess check, the CPU baseline and parity (off: the headline figure only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.dt is None:
         args.dt = 0.001 if args.config == "c5" else 0.01
     if args.v_max is None:
@@ -392,15 +422,17 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver, rank == 0)
 
-    # The rest of the config's own run (T / dt steps from t = 0), so that the end-to-end rate is MEASURED, not extrapolated from the
-    # timed region: with the projected initial guess the steps get cheaper as the flow settles.  Bounded (20 s); every step so far
-    # was clocked, the first one with its preconditioner build and graph captures included.
+    # --full: the rest of the config's own run (T / dt steps from t = 0), so that the end-to-end rate is MEASURED, not extrapolated
+    # from the timed region: with the projected initial guess the steps get cheaper as the flow settles.  Bounded (20 s); every step
+    # so far was clocked, the first one with its preconditioner build and graph captures included.
     n_run_total = run_length(args)
     steps_before = kstep
     t_rest0 = time.perf_counter()
     rest_failure = None
-    while world == 1 and kstep < n_run_total and time.perf_counter() - t_rest0 < 20.0:
+    while args.full and world == 1 and kstep < n_run_total and time.perf_counter() - t_rest0 < 20.0:
         try:
             step_hook(sc, kstep, dt)
             solver.solveStep()
@@ -421,7 +453,7 @@ def main():
 
     # the reference's literal loop: u_prev.x.array[:] = u_sol.x.array[:] (scenario.py:306-307), reported beside `value`
     literal_rate = None
-    if world == 1 and args.host_loop_steps > 0:
+    if args.full and world == 1 and args.host_loop_steps > 0:
         sync_all()
         t0h = time.perf_counter()
         for _ in range(args.host_loop_steps):
@@ -434,13 +466,13 @@ def main():
         sync_all()
         literal_rate = args.host_loop_steps / (time.perf_counter() - t0h)
 
-    results = functionals(args, sc)
+    results = functionals(args, sc) if args.full else None
 
-    # Kernel durations: HIP events on the library's stream around every launch of the hot kernels, over `prof_steps`
+    # Kernel durations (--full): HIP events on the library's stream around every launch of the hot kernels, over `prof_steps`
     # further steps of the same run (the preconditioner's hipGraph replay is switched off while events are recorded;
     # the kernels and their data are the same)
     kern, roof = [], None
-    if args.prof_steps > 0:
+    if args.full and args.prof_steps > 0:
         ctx.profile_reset()
         ctx.profile_enable(True)
         for _ in range(args.prof_steps):
@@ -524,13 +556,11 @@ def main():
         "solves_stopped_at_attainable_accuracy": int(ctx.info(72)),
         "pressure_level1_rows": int(ctx.info(23)),  # rows of level 1 of the pressure hierarchy: the coarse right-hand side a partitioned run all-reduces
         "setup_s": t_setup,
+    }
+    if args.full:
         # the reference's literal loop `u_prev.x.array[:] = u_sol.x.array[:]` (scenario.py:306-307): the lazy array proxy maps
         # that idiom to a device copy, so no field crosses PCIe in it
-        "literal_reference_loop_steps_per_s": literal_rate,
-        "results": results,
-        "roofline": roof,
-        "kernels": kern,
-    }
+        out.update(literal_reference_loop_steps_per_s=literal_rate, results=results, roofline=roof, kernels=kern)
     # The config's own run, end to end: T / dt steps from t = 0 INCLUDING the first step's preconditioner build (measured:
     # wall-clock of step 1 of this run) -- next to the steady-state `value`.  `hierarchy_build_s` = preconditioner set-up
     # time of all steps before the timed region (the AMG hierarchies are built in step 1 and lagged after).
@@ -552,13 +582,13 @@ def main():
     else:
         out["end_to_end_steps_per_s"] = n_run / (t_first + (n_run - 1) * elapsed / args.steps)
         out["end_to_end_steps_per_s_incl_setup"] = n_run / (t_setup + t_first + (n_run - 1) * elapsed / args.steps)
-    if args.config == "c3":
+    if args.full and args.config == "c3":
         out["drag_coefficient"], out["lift_coefficient"], out["velocity_l2"] = results["drag"], results["lift"], results["velocity_l2"]
 
-    if args.config == "c5b":
+    if args.full and args.config == "c5b":
         qi, q1, q2 = sc.flow_rates()
         out["results"].update({"inflow": qi, "outflow_1": q1, "outflow_2": q2})
-    if world == 1 and rank == 0 and int(sc.solver.options.ksp_guess) > 0 and args.config in ("c2", "c3", "c4", "c5b", "q1", "q1h"):
+    if args.full and world == 1 and rank == 0 and int(sc.solver.options.ksp_guess) > 0 and args.config in ("c2", "c3", "c4", "c5b", "q1", "q1h"):
         # The same timed region with the linear solver configured like the reference's KSP: zero initial guess in every solve (and
         # the fp64 basis throughout) -- so that the line carries both numbers and the share of `value` that is due to the projected
         # guess can be read off.  A fresh scenario from t = 0, the same warm-up and step counts, the same clock.
@@ -584,7 +614,7 @@ def main():
                                            "krylov_its_per_step": its0 / args.steps,
                                            "note": "same timed region, linear solves started from zero as the reference's KSP does"}
         del sc0
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         # CPU baseline and parity: the same Scenario class on the oracle-backed test double of the solver plugin
         # (tests/oracle_solver.py over oracle/cfdh_oracle.c) -- checker and reported baseline only, never the product.
         import oracle_solver

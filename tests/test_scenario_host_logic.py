@@ -217,3 +217,33 @@ def test_bench_contract_host_side():
         assert bench.run_length(types.SimpleNamespace(config=cfg, dt=dt)) == n
     a, b = bench.kernel_source_sha16(), bench.kernel_source_sha16()
     assert a == b and len(a) == 16 and int(a, 16) >= 0
+
+
+def test_bench_dump_outputs_host_side(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: one float64 file per field, node-major; above the size limit every field is cut to the same
+    seeded sample of nodes (indices written too) and the files stay within the limit; `--steps` below 1 is refused."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    rng = np.random.default_rng(3)
+    nv = 5000
+    field = lambda a: types.SimpleNamespace(x=types.SimpleNamespace(array=a))
+    s = types.SimpleNamespace(u_sol=field(rng.random(2 * nv)), p_sol=field(rng.random(nv)), shear_stress=field(rng.random(2 * nv)))
+    bench.dump_outputs(str(tmp_path / "all"), s, True)
+    assert sorted(os.listdir(tmp_path / "all")) == ["pressure.npy", "velocity.npy", "wall_shear_stress.npy"]
+    v = np.load(tmp_path / "all" / "velocity.npy")
+    assert v.dtype == np.float64 and np.array_equal(v, s.u_sol.x.array.reshape(nv, 2))
+    bench.dump_outputs(str(tmp_path / "none"), s, False)
+    assert not (tmp_path / "none").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), s, True)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 100_000
+    idx = np.load(tmp_path / "a" / "node_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "node_index.npy")) and len(np.unique(idx)) == len(idx) > 0
+    assert np.array_equal(np.load(tmp_path / "a" / "pressure.npy"), s.p_sol.x.array[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "wall_shear_stress.npy"), s.shear_stress.x.array.reshape(nv, 2)[idx.astype(np.int64)])
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()

@@ -17,17 +17,17 @@ PY
 }
 for cfg in "$@"; do
 case $cfg in
- c2) run c2 --config c2 ;;
- c4) run c4 --config c4 ;;
- c5) run c5 --config c5 ;;
- c5bdf2) run c5_bdf2_vmax0.5 --config c5 --solver stabilized_schur_bdf2 --v-max 0.5 --no-cpu-baseline ;;
- c5b) run c5b_1m --config c5b ;;
- c5bmean) run c5b_1m_remove_p_mean1 --config c5b --remove-p-mean 1 ;;
- c5b8) run c5b_8m --config c5b --res3 1e-4 --no-cpu-baseline --parity-steps 0 ;;
- q1) run q1 --config q1 ;;
- q1h) run q1h --config q1h ;;
- p2) run p2 --config p2 ;;
- p2s) run p2s --config p2s --no-cpu-baseline ;;
- p2t) run p2t --config p2t ;;
+ c2) run c2 --config c2 --full ;;
+ c4) run c4 --config c4 --full ;;
+ c5) run c5 --config c5 --full ;;
+ c5bdf2) run c5_bdf2_vmax0.5 --config c5 --solver stabilized_schur_bdf2 --v-max 0.5 --no-cpu-baseline --full ;;
+ c5b) run c5b_1m --config c5b --full ;;
+ c5bmean) run c5b_1m_remove_p_mean1 --config c5b --remove-p-mean 1 --full ;;
+ c5b8) run c5b_8m --config c5b --res3 1e-4 --no-cpu-baseline --parity-steps 0 --full ;;
+ q1) run q1 --config q1 --full ;;
+ q1h) run q1h --config q1h --full ;;
+ p2) run p2 --config p2 --full ;;
+ p2s) run p2s --config p2s --no-cpu-baseline --full ;;
+ p2t) run p2t --config p2t --full ;;
 esac
 done
