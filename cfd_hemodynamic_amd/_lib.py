@@ -44,7 +44,7 @@ SYMBOLS = [
     "cfdh_create", "cfdh_create_elem", "cfdh_create_elem_part", "cfdh_set_facet_markers", "cfdh_destroy", "cfdh_last_error", "cfdh_abi_version", "cfdh_set_params", "cfdh_default_options",
     "cfdh_set_options", "cfdh_clear_dirichlet", "cfdh_add_dirichlet", "cfdh_update_dirichlet", "cfdh_set_state", "cfdh_get_solution",
     "cfdh_get_previous", "cfdh_get_residual", "cfdh_advance", "cfdh_advance_field", "cfdh_set_time_scheme", "cfdh_set_previous2", "cfdh_get_previous2",
-    "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
+    "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_set_formulation", "cfdh_set_pressure_boundaries", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
 ]
@@ -97,6 +97,8 @@ def lib():
     L.cfdh_shift_history.argtypes = [vp]
     L.cfdh_wall_shear_stress.argtypes = [vp, dp]
     L.cfdh_set_boundary_terms.argtypes = [vp, C.c_int, C.c_int, C.c_double]
+    L.cfdh_set_formulation.argtypes = [vp, C.c_int]
+    L.cfdh_set_pressure_boundaries.argtypes = [vp, C.c_int, ip, dp, C.c_double]
     L.cfdh_get_residual.argtypes = [vp, dp, dp]
     L.cfdh_get_previous.argtypes = [vp, dp, dp]
     L.cfdh_advance.argtypes = [vp]
@@ -142,6 +144,9 @@ def _raise(code, msg):
     if code == -1:
         raise ValueError(msg)
     raise CfdhError(msg)
+
+
+FORM_CONVECTIVE, FORM_ROTATIONAL = 0, 1  # cfdh_set_formulation
 
 
 class Context:
@@ -270,6 +275,19 @@ class Context:
 
     def set_boundary_terms(self, ds_terms=True, backflow_marker=-1, beta=0.0):
         self._chk(self.L.cfdh_set_boundary_terms(self.h, int(bool(ds_terms)), int(backflow_marker), float(beta)))
+
+    def set_formulation(self, form):
+        """FORM_CONVECTIVE (default) or FORM_ROTATIONAL (the curl-curl form of the pressure-driven solvers)."""
+        self._chk(self.L.cfdh_set_formulation(self.h, int(form)))
+
+    def set_pressure_boundaries(self, markers, values, beta_nitsche=0.0):
+        """Natural pressure + Nitsche tangential terms on the exterior facets of each marker (rotational form).  A call that
+        changes only `values` keeps the Jacobian and the preconditioner."""
+        m = np.ascontiguousarray(markers, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if len(m) != len(v):
+            raise ValueError("one value per pressure-boundary marker")
+        self._chk(self.L.cfdh_set_pressure_boundaries(self.h, len(m), _ip(m), _dp(v), float(beta_nitsche)))
 
     def wall_shear_stress(self, download=True):
         if not download:

@@ -339,14 +339,23 @@ int cfdh_set_time_scheme(cfdh_ctx *c, double theta, double a0, double a1, double
   return 0;
 }
 
-// per-cell facet bits of the assembly kernel: bits 0..d exterior facet, bits d+1..2d+1 backflow facet (marker == bf_marker)
+// per-cell facet bits of the assembly kernel: bits 0..d exterior facet, bits d+1..2d+1 backflow facet (marker == bf_marker);
+// generic elements: bit f exterior, 4 + f pressure boundary (slot in gpbidx), 8 + f backflow
 static int upload_cell_facet_flags(cfdh_ctx *c) {
   if (c->gen) {
     std::vector<unsigned short> gf((size_t)c->nc, 0);
+    std::vector<unsigned char> pbi;
+    if (!c->pb_markers.empty()) pbi.assign(4 * (size_t)c->nc, 0);
     for (int k = 0; k < c->nfac; k++) {
       gf[c->fac_cell[k]] |= (unsigned short)(1u << c->fac_local[k]);
       if (c->bf_marker >= 0 && c->fac_marker[k] == c->bf_marker) gf[c->fac_cell[k]] |= (unsigned short)(256u << c->fac_local[k]);
+      for (size_t b = 0; b < c->pb_markers.size(); b++)
+        if (c->fac_marker[k] == c->pb_markers[b]) {
+          gf[c->fac_cell[k]] |= (unsigned short)(16u << c->fac_local[k]);
+          pbi[4 * (size_t)c->fac_cell[k] + c->fac_local[k]] = (unsigned char)b;
+        }
     }
+    if (!pbi.empty()) HIPCHK(c, c->gpbidx.upload(pbi, c->stream));
     HIPCHK(c, c->gflag.upload(gf, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->jac_valid = false;
@@ -369,6 +378,8 @@ static int upload_cell_facet_flags(cfdh_ctx *c) {
 int cfdh_set_boundary_terms(cfdh_ctx *c, int ds_terms, int backflow_marker, double beta) {
   ENTER(c);
   if (beta < 0) return cfdh_fail(c, CFDH_E_ARG, "backflow beta must be >= 0");
+  if (beta > 0 && c->form == CFDH_FORM_ROTATIONAL)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_boundary_terms: the backflow term is not available with the rotational formulation");
   if (!(beta > 0)) backflow_marker = -1;
   const bool changed = (ds_terms != 0) != c->ds_terms || beta != c->bf_beta || backflow_marker != c->bf_marker;
   c->ds_terms = ds_terms != 0; c->bf_beta = beta; c->bf_marker = backflow_marker;
@@ -385,9 +396,59 @@ int cfdh_set_facet_markers(cfdh_ctx *c, int64_t nfacets, const int32_t *markers)
     HIPCHK(c, c->d_fac_marker.upload(c->fac_marker, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  // the backflow term follows the outlet marker: refresh the per-cell flags (invalidates Jacobian and preconditioner)
-  if (c->bf_marker >= 0) return upload_cell_facet_flags(c);
+  // the backflow term and the pressure boundaries follow the markers: refresh the per-cell flags (invalidates Jacobian and preconditioner)
+  if (c->bf_marker >= 0 || !c->pb_markers.empty()) return upload_cell_facet_flags(c);
   return 0;
+}
+
+// contexts the rotational form exists for (the rest are follow-ups)
+static int rotational_supported(cfdh_ctx *c, const char *who) {
+  if (c->dim != 2) return cfdh_fail(c, CFDH_E_ARG, "%s: the rotational formulation exists for gdim 2 only", who);
+  if (!c->gen)
+    return cfdh_fail(c, CFDH_E_ARG, "%s: the rotational formulation runs on the generic element kernels; create P1 contexts with CFDH_ELEM_P1_GENERIC", who);
+  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "%s: the rotational formulation is not available in partitioned runs", who);
+  return 0;
+}
+
+int cfdh_set_formulation(cfdh_ctx *c, int form) {
+  ENTER(c);
+  if (form != CFDH_FORM_CONVECTIVE && form != CFDH_FORM_ROTATIONAL) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: unknown form %d", form);
+  if (form == c->form) return 0;
+  if (form == CFDH_FORM_ROTATIONAL) {
+    CHK(rotational_supported(c, "cfdh_set_formulation"));
+    if (c->bf_marker >= 0 && c->bf_beta > 0)
+      return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: the rotational formulation cannot be combined with the backflow term (beta > 0)");
+  } else if (!c->pb_markers.empty()) {
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: pressure boundaries are set (they belong to the rotational formulation)");
+  }
+  c->form = form;
+  c->jac_valid = false;
+  c->pc_valid = false;
+  return 0;
+}
+
+int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, const double *values, double beta_nitsche) {
+  ENTER(c);
+  if (n < 0 || n > CFDH_MAX_PBND) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: 0 <= n <= %d", CFDH_MAX_PBND);
+  if (n > 0 && (!markers || !values)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: null marker / value array");
+  if (!(beta_nitsche >= 0) || !std::isfinite(beta_nitsche)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: beta_nitsche must be finite and >= 0");
+  for (int k = 0; k < n; k++) {
+    if (!std::isfinite(values[k])) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: value %d is not finite", k);
+    for (int l = 0; l < k; l++)
+      if (markers[l] == markers[k]) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: marker %d listed twice", (int)markers[k]);
+  }
+  if (n > 0) {
+    CHK(rotational_supported(c, "cfdh_set_pressure_boundaries"));
+    if (c->form != CFDH_FORM_ROTATIONAL)
+      return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: pressure boundaries need the rotational formulation (cfdh_set_formulation)");
+  }
+  bool same = (size_t)n == c->pb_markers.size() && beta_nitsche == c->pb_beta;
+  for (int k = 0; same && k < n; k++) same = markers[k] == c->pb_markers[k];
+  c->pb_values.assign(values, values + n);
+  if (same) return 0;  // values only: they enter the residual, Jacobian and preconditioner stay valid
+  c->pb_markers.assign(markers, markers + n);
+  c->pb_beta = beta_nitsche;
+  return upload_cell_facet_flags(c);
 }
 
 int cfdh_set_previous2(cfdh_ctx *c, const double *u_prev2) {
@@ -756,6 +817,10 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 71: return c->n_guess_solves ? (int64_t)(1e6 * c->guess_reduction_sum / (double)c->n_guess_solves) : 0;  // mean |r0| / |b| of those, in 1e-6
     case 29: return c->nloc;
     case 73: return c->n_krylov_discarded;  // FGMRES iterations launched ahead of the host's convergence test and discarded (not in krylov_its)
+    case 74: return c->n_pc_builds;
+    case 75: return c->pc_valid ? 1 : 0;
+    case 76: return c->singular;
+    case 77: return c->form;
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type == 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;

@@ -134,6 +134,10 @@ struct GenArgs {
   double dt, rho, mu, muf, f0, f1, theta, a0, a1, a2, beta;
   int ds_terms;
   double *F, *A00, *A01, *A10, *A11;
+  // rotational form only (ROT = true): pressure boundaries -- slot of local facet f in pbidx[4 cell + f] (flag bit 4 + f), values
+  // P_k in pval, Nitsche penalty pbeta
+  const unsigned char *pbidx;
+  double pval[CFDH_MAX_PBND], pbeta;
 };
 
 __device__ __forceinline__ void tau_pair(double s, double h, double dt, double nu, double &tau, double &tauL) {
@@ -160,7 +164,14 @@ struct CellData {
 
 // JAC = false: residual-only pass (trial point of the line search).  The element Jacobian is then formed only in cells whose
 // Dirichlet nodes still need lifting (F += J (g - x)) -- none once the first Newton update has put the boundary values in place.
-template <int ET, bool JAC>
+//
+// ROT = true: the rotational form of the pressure-driven solvers (/root/reference/src/solvers/stabilized_schur_pressurebc.py:123-160,
+// 177-205; cfdh_set_formulation).  With omega = omega(ubar) = d_x ubar_y - d_y ubar_x and omega x a := (-omega a_y, omega a_x):
+//   rho w_t . v + mu omega(ubar) omega(v) - p div v + rho (omega x ubar) . v - rho/2 |ubar|^2 div v - rho f . v + q div ubar
+//   + SUPG / PSPG / LSIC with R = rho (w_t + omega x ubar) + grad p - rho f (no viscous part: no Hessians in this pass),
+// and on the facets of pressure boundary k (flag bit 4 + f, value P_k, outward n, tangent t = (-n_y, n_x)):
+//   P_k v . n - mu omega(ubar) (t . v) - mu omega(v) (t . ubar) + (beta mu / h) (t . ubar)(t . v).
+template <int ET, bool JAC, bool ROT>
 __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
   constexpr int NL = ET == 0 ? 3 : (ET == 1 ? 6 : 4);
   constexpr int CPB = TPB / NL;  // cells per workgroup
@@ -203,7 +214,7 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
   // physical Hessians of all basis functions (cell constants): (xx, xy, yy); viscous part of the strong residual
   double Hs[NL][3], visc[2] = {0.0, 0.0};
 #pragma unroll
-  for (int b = 0; b < NL; b++) {
+  for (int b = 0; b < NL && !ROT; b++) {
     double Hr[3];
     ref_hessian<ET>(b, Hr);
     Hs[b][0] = Hr[0] * Ji[0][0] * Ji[0][0] + 2.0 * Hr[1] * Ji[0][0] * Ji[1][0] + Hr[2] * Ji[1][0] * Ji[1][0];
@@ -257,6 +268,41 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
       pq += ph[b] * D.p[b];
     }
     const double divu = G[0][0] + G[1][1];
+    if constexpr (ROT) {
+      const double om = G[0][1] - G[1][0], ke = 0.5 * rho * (uq[0] * uq[0] + uq[1] * uq[1]);
+      const double Cr[2] = {-om * uq[1], om * uq[0]};
+      const double R[2] = {rho * (wv[0] + Cr[0]) + gp[0] - rho * P.f0, rho * (wv[1] + Cr[1]) + gp[1] - rho * P.f1};
+      const double tau = sh_tau[lc][q][0], tauL = sh_tau[lc][q][1];
+      const double bga = uq[0] * g[a][0] + uq[1] * g[a][1];
+      const double fvec[2] = {P.f0, P.f1}, oma[2] = {-g[a][1], g[a][0]};  // omega(phi_a e_i)
+#pragma unroll
+      for (int i = 0; i < 2; i++) {
+        double v = rho * ph[a] * (wv[i] + Cr[i] - fvec[i]) + mu * om * oma[i];
+        v += -(pq + ke) * g[a][i] + tau * R[i] * bga + tauL * rho * divu * g[a][i];
+        Fa[i] += dv * v;
+      }
+      Fa[2] += dv * (ph[a] * divu + tau / rho * (R[0] * g[a][0] + R[1] * g[a][1]));
+      if (!needj) continue;
+#pragma unroll
+      for (int b = 0; b < NL; b++) {
+        const double gg = g[a][0] * g[b][0] + g[a][1] * g[b][1], omb[2] = {-g[b][1], g[b][0]};
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          // d/du_(b,j) of rho (w_t + omega x ubar): the time term and theta (omega(phi_b e_j) x ubar + omega x phi_b e_j)
+          const double dR[2] = {rho * (a0dt * ph[b] * (j == 0 ? 1.0 : 0.0) - th * (omb[j] * uq[1] + (j == 1 ? om * ph[b] : 0.0))),
+                                rho * (a0dt * ph[b] * (j == 1 ? 1.0 : 0.0) + th * (omb[j] * uq[0] + (j == 0 ? om * ph[b] : 0.0)))};
+#pragma unroll
+          for (int i = 0; i < 2; i++)
+            Juu[b][i][j] += dv * (ph[a] * dR[i] + mu * th * oma[i] * omb[j] - rho * th * ph[b] * uq[j] * g[a][i] + tau * dR[i] * bga +
+                                  th * tau * R[i] * ph[b] * g[a][j] + rho * th * tauL * g[b][j] * g[a][i]);
+          Jpu[b][j] += dv * (th * ph[a] * g[b][j] + tau / rho * (dR[0] * g[a][0] + dR[1] * g[a][1]));
+        }
+        Jup[b][0] += dv * (-ph[b] * g[a][0] + tau * g[b][0] * bga);
+        Jup[b][1] += dv * (-ph[b] * g[a][1] + tau * g[b][1] * bga);
+        Jpp[b] += dv * tau / rho * gg;
+      }
+      continue;
+    }
     const double C[2] = {uq[0] * G[0][0] + uq[1] * G[1][0], uq[0] * G[0][1] + uq[1] * G[1][1]};
     const double R[2] = {rho * (wv[0] + C[0]) - visc[0] + gp[0] - rho * P.f0, rho * (wv[1] + C[1]) - visc[1] + gp[1] - rho * P.f1};
     const double tau = sh_tau[lc][q][0], tauL = sh_tau[lc][q][1];
@@ -305,8 +351,10 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
     for (int q = 0; q < NV; q++) { cen[0] += D.X[q][0] * (1.0 / NV); cen[1] += D.X[q][1] * (1.0 / NV); }
     constexpr int NQF = ET == 1 ? 4 : 2;
     for (int f = 0; f < NF; f++) {
-      const bool ext = P.ds_terms && ((fl >> f) & 1u), bfl = P.beta != 0.0 && ((fl >> (8 + f)) & 1u);
-      if (!ext && !bfl) continue;
+      // (the rotational form has no ds pair, :177-205; its backflow combination is refused by the API)
+      const bool ext = !ROT && P.ds_terms && ((fl >> f) & 1u), bfl = P.beta != 0.0 && ((fl >> (8 + f)) & 1u);
+      const bool pfl = ROT && ((fl >> (4 + f)) & 1u);
+      if (!ext && !bfl && !pfl) continue;
       const int va = facet_node<ET>(f, 0), vb = facet_node<ET>(f, 1);
       const double tx = D.X[vb][0] - D.X[va][0], ty = D.X[vb][1] - D.X[va][1], elen = hypot(tx, ty);
       double n[2] = {ty / elen, -tx / elen};
@@ -317,7 +365,7 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
         const double t = ET == 1 ? d_gl4[0][q] : d_gl2[0][q], m = elen * (ET == 1 ? d_gl4[1][q] : d_gl2[1][q]);
         double ph[GEN_MAXL], dr[GEN_MAXL][2], g[NL][2];
         tabulate<ET>((1 - t) * ra[0] + t * rb[0], (1 - t) * ra[1] + t * rb[1], ph, dr);
-        if (ph[a] == 0.0) continue;  // test function vanishes on this facet
+        if (ph[a] == 0.0 && !pfl) continue;  // test function vanishes on this facet (omega(v) does not: Nitsche symmetry term)
 #pragma unroll
         for (int b = 0; b < NL; b++) { g[b][0] = dr[b][0] * Ji[0][0] + dr[b][1] * Ji[1][0]; g[b][1] = dr[b][0] * Ji[0][1] + dr[b][1] * Ji[1][1]; }
         double uq[2] = {0, 0}, G[2][2] = {{0, 0}, {0, 0}}, pq = 0.0, sn = 0.0;
@@ -350,6 +398,25 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
             Fa[i] -= cq * ph[a] * uq[i];
 #pragma unroll
             for (int b = 0; b < NL; b++) Juu[b][i][i] -= th * cq * ph[a] * ph[b];
+          }
+        }
+        if (pfl) {
+          // pressure boundary: natural pressure (residual only) + Nitsche tangential condition, omega from this cell's gradients
+          const int slot = P.pbidx[4 * (size_t)cell + f];
+          double pk = 0.0;
+#pragma unroll
+          for (int k = 0; k < CFDH_MAX_PBND; k++) pk = k == slot ? P.pval[k] : pk;  // static indices: the argument block stays in SGPRs
+          const double t[2] = {-n[1], n[0]}, om = G[0][1] - G[1][0], ut = t[0] * uq[0] + t[1] * uq[1];
+          const double oma[2] = {-g[a][1], g[a][0]}, nit = P.pbeta * mu / h;
+#pragma unroll
+          for (int i = 0; i < 2; i++) {
+            Fa[i] += m * (ph[a] * (pk * n[i] - mu * om * t[i] + nit * ut * t[i]) - mu * oma[i] * ut);
+#pragma unroll
+            for (int b = 0; b < NL; b++) {
+              const double omb[2] = {-g[b][1], g[b][0]};
+#pragma unroll
+              for (int j = 0; j < 2; j++) Juu[b][i][j] += th * m * (-mu * omb[j] * ph[a] * t[i] - mu * oma[i] * ph[b] * t[j] + nit * ph[a] * t[i] * ph[b] * t[j]);
+            }
           }
         }
       }
@@ -891,13 +958,22 @@ int kg_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   P.ds_terms = c->ds_terms ? 1 : 0;
   P.F = c->F.p; P.A00 = c->A00.p; P.A01 = c->A01.p; P.A10 = c->A10.p; P.A11 = c->A11.p;
   P.fdst = c->g_fdst.p; P.E = c->gE.p; P.EF = c->gEF.p;
+  const bool rot = c->form == CFDH_FORM_ROTATIONAL;
+  P.pbidx = c->gpbidx.p; P.pbeta = c->pb_beta;
+  for (int k = 0; k < CFDH_MAX_PBND; k++) P.pval[k] = k < (int)c->pb_values.size() ? c->pb_values[k] : 0.0;
   const dim3 grid((c->nc + cpb - 1) / cpb), block(TPB);
   prof_begin(c, 0);
-#define CFDH_GEN_LAUNCH(ET) do { if (mode == 1) hipLaunchKernelGGL((gen_asm_kernel<ET, true>), grid, block, 0, c->stream, P); \
-                                 else hipLaunchKernelGGL((gen_asm_kernel<ET, false>), grid, block, 0, c->stream, P); } while (0)
-  if (c->etype == 1) CFDH_GEN_LAUNCH(1);
-  else if (c->etype == 2) CFDH_GEN_LAUNCH(2);
-  else CFDH_GEN_LAUNCH(0);
+#define CFDH_GEN_LAUNCH(ET, ROT) do { if (mode == 1) hipLaunchKernelGGL((gen_asm_kernel<ET, true, ROT>), grid, block, 0, c->stream, P); \
+                                      else hipLaunchKernelGGL((gen_asm_kernel<ET, false, ROT>), grid, block, 0, c->stream, P); } while (0)
+  if (rot) {
+    if (c->etype == 1) CFDH_GEN_LAUNCH(1, true);
+    else if (c->etype == 2) CFDH_GEN_LAUNCH(2, true);
+    else CFDH_GEN_LAUNCH(0, true);
+  } else {
+    if (c->etype == 1) CFDH_GEN_LAUNCH(1, false);
+    else if (c->etype == 2) CFDH_GEN_LAUNCH(2, false);
+    else CFDH_GEN_LAUNCH(0, false);
+  }
 #undef CFDH_GEN_LAUNCH
   hipLaunchKernelGGL(gen_gather_F_kernel, dim3((c->nvo + TPB - 1) / TPB), block, 0, c->stream, c->nvo, c->g_fptr.p, c->gEF.p, c->F.p);
   if (mode == 1)

@@ -159,7 +159,8 @@ struct cfdh_ctx {
   // the extents of every block entry / node in them
   dbuf<int> g_eptr, g_fptr, g_fdst;   // [nnzv + 1], [nv + 1], [nc][nloc]
   dbuf<double> gE, gEF;               // [nc nloc^2][9], [nc nloc][3]
-  dbuf<unsigned short> gflag;  // [nc] bit f: exterior facet f, bit 8 + f: backflow facet f
+  dbuf<unsigned short> gflag;  // [nc] bit f: exterior facet f, bit 4 + f: pressure-boundary facet f, bit 8 + f: backflow facet f
+  dbuf<unsigned char> gpbidx;  // [nc][4] index into pb_values of the pressure boundary that holds local facet f (bit 4 + f set)
   dbuf<int> g3_fcells;         // 3-D generic elements: the cells with an exterior facet (gen3_facet_kernel)
   int g3_nfcells = 0;
   // P2: the P1 subspace as the first coarse level of both hierarchies (p-multigrid step): prolongator [nodes x vertex nodes],
@@ -246,6 +247,11 @@ struct cfdh_ctx {
   bool ds_terms = true;      // cfdh_set_boundary_terms
   double bf_beta = 0.0;
   int bf_marker = -1;
+  // cfdh_set_formulation / cfdh_set_pressure_boundaries (rotational form of the pressure-driven solvers, cfdh_gen.hip)
+  int form = 0;                      // CFDH_FORM_*
+  std::vector<int> pb_markers;       // facet markers of the pressure boundaries, at most CFDH_MAX_PBND
+  std::vector<double> pb_values;     // their values P_k (residual only)
+  double pb_beta = 0.0;              // Nitsche penalty beta of the tangential condition
   bool state_set = false;
 
   // reductions
@@ -385,7 +391,10 @@ struct cfdh_ctx {
   // of the solve, FGMRES iterations, all-gathers -- cumulative, reset by cfdh_profile_reset
   long long n_allreduce = 0, n_halo = 0, n_host_sync = 0, n_krylov = 0, n_allgather = 0;
   long long n_attainable_stops = 0;  // FGMRES solves ended by the attainable-accuracy rule (cfdh_info 72), cumulative over the context's life
+  long long n_pc_builds = 0;         // preconditioner (re)builds since cfdh_create (cfdh_info 74)
 };
+
+#define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
 
 // ---- error helpers -----------------------------------------------------------
 int cfdh_fail(cfdh_ctx *c, int code, const char *fmt, ...);

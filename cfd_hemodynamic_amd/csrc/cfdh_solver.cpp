@@ -88,8 +88,9 @@ static int build_schur_host(cfdh_ctx *c, CsrHost &S) {
   return 0;
 }
 
-// Do-nothing boundary (ds_terms off): the nodes of every exterior facet that is not a no-slip / inflow facet (all velocity
-// components of all its nodes constrained) form the outflow boundary of the preconditioner's pressure Poisson problem: bit 1.
+// Do-nothing boundary (ds_terms off) and the natural pressure boundaries of the rotational form (which has no ds pair): the nodes
+// of every exterior facet that is not a no-slip / inflow facet (all velocity components of all its nodes constrained) form the
+// outflow boundary of the preconditioner's pressure Poisson problem: bit 1.
 static void mark_outflow_nodes(const cfdh_ctx *c, std::vector<unsigned char> &pbc) {
   const unsigned umask = (1u << c->dim) - 1u;
   const int nvo = c->nvo;
@@ -288,7 +289,7 @@ static int build_cc_host(cfdh_ctx *c) {
   std::vector<unsigned char> pbc(nvo);
   const unsigned pbit = 1u << c->dim;  // bits 0..dim-1: velocity components, bit dim: pressure
   for (int i = 0; i < nvo; i++) pbc[i] = (c->h_bcflag[i] & pbit) ? 1 : 0;
-  if (!c->ds_terms) mark_outflow_nodes(c, pbc);
+  if (!c->ds_terms || c->form == CFDH_FORM_ROTATIONAL) mark_outflow_nodes(c, pbc);
   if (!c->hL.valid || c->hL_pbc != pbc || c->hL_singular != c->singular) {
     CsrHost Lh;
     Lh.n = Lh.m = nvo;
@@ -406,7 +407,7 @@ static int build_cc_dev(cfdh_ctx *c) {
   std::vector<unsigned char> pbc(nvo);
   const unsigned pbit = 1u << c->dim;
   for (int i = 0; i < nvo; i++) pbc[i] = (c->h_bcflag[i] & pbit) ? 1 : 0;
-  if (!c->ds_terms) mark_outflow_nodes(c, pbc);
+  if (!c->ds_terms || c->form == CFDH_FORM_ROTATIONAL) mark_outflow_nodes(c, pbc);
   if (!c->hL.valid || c->hL_pbc != pbc || c->hL_singular != c->singular) {
     CsrHost Lh;
     Lh.n = Lh.m = nvo;
@@ -483,6 +484,7 @@ int cfdh_pc_update(cfdh_ctx *c, bool refresh_amg) {
       c->pc_its_ref = 0;
       c->steps_since_refresh = 0;
       c->last_stats.pc_refreshes++;
+    c->n_pc_builds++;
     }
     return 0;
   }
@@ -514,6 +516,7 @@ int cfdh_pc_update(cfdh_ctx *c, bool refresh_amg) {
     c->pc_its_ref = 0;
     c->steps_since_refresh = 0;
     c->last_stats.pc_refreshes++;
+    c->n_pc_builds++;
   }
   return 0;
 }

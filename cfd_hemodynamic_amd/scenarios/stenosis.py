@@ -11,7 +11,11 @@ pressure is then in the null space of every Jacobian even with an open outlet, a
 Newton systems with a prescribed inflow are inconsistent (FGMRES stagnates at ~1e-2; the
 CPU oracle shows the same).  `outlet_pressure=0.0` (default here) therefore fixes p at the
 outlet like the other open-boundary scenarios (dfg_1.py:79-91); `outlet_pressure=None`
-reproduces the reference literally."""
+reproduces the reference literally.
+
+Pressure-driven solvers (`stabilized_schur_pressurebc`, `stabilized_schur_vascularbc`): `p_inlet` / `p_outlet` are given in mmHg
+(defaults 75 / 10) and forwarded in Pa (x 133.322) with `beta_nitsche`; with `R_resistance` the scenario forwards `R_resistance`
+and `initial_ffr` instead of `p_outlet` (stenosis.py:84-99).  Those solvers ignore `bcp`; the other solvers ignore these keywords."""
 from __future__ import annotations
 
 import os
@@ -22,6 +26,8 @@ from ..boundaryCondition import BoundaryCondition
 from ..fem import Function
 from ..mesh import create_stenosis_channel
 from ..scenario import Scenario
+
+_MMHG = 133.322  # Pa per mmHg (stenosis.py:17-18)
 
 
 class StenosisSimulation(Scenario):
@@ -39,7 +45,8 @@ class StenosisSimulation(Scenario):
 
     def __init__(self, solver_name, dt, T, f: tuple[float, float] = (0, 0), grade="severe", *, rho=1.06e-3, mu=3.5e-3,
                  ny=None, res=0.15, L=138.0, R_in=1.57, R_out=1.2, x_sten=30.0, x_position_stenosis=None, severity=None,
-                 slope=None, tension=0.5, v_max=None, outlet_pressure=0.0, **solver_kwargs):
+                 slope=None, tension=0.5, v_max=None, outlet_pressure=0.0, p_inlet=75.0, p_outlet=10.0, beta_nitsche=100.0,
+                 R_resistance=None, initial_ffr=0.8, **solver_kwargs):
         """Geometry defaults of stenosis.py:60-69 (L 138, R_in 1.57, R_out 1.2, stenosis at x = 30, res 0.15,
         severity 0.567, slope 0.4).  The reference writes those defaults into its mesh options BEFORE the grade
         table is consulted (:70-77: `if k not in self.mesh_options`), so `grade` never takes effect there: every
@@ -62,6 +69,14 @@ class StenosisSimulation(Scenario):
         self.quiet = bool(solver_kwargs.get("quiet", False))
         if v_max is not None:
             solver_kwargs["v_max"] = float(v_max)  # stenosis.py:92-94 (required by the backflow solver)
+        # stenosis.py:84-99: pressures in mmHg -> Pa; a resistance outlet replaces the outlet pressure
+        solver_kwargs["p_inlet"] = float(p_inlet) * _MMHG
+        solver_kwargs["beta_nitsche"] = beta_nitsche
+        if R_resistance is not None:
+            solver_kwargs["R_resistance"] = float(R_resistance)
+            solver_kwargs["initial_ffr"] = initial_ffr
+        else:
+            solver_kwargs["p_outlet"] = float(p_outlet) * _MMHG
         super().__init__(solver_name, "stenosis", rho, mu, dt, T, f, **solver_kwargs)
         self.setup()
 

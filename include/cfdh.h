@@ -219,6 +219,27 @@ int cfdh_set_time_scheme(cfdh_ctx *ctx, double theta, double a0, double a1, doub
  * 2-point Gauss on edges, the 6-point Strang-Fix rule on the triangles of a tetrahedral mesh. */
 int cfdh_set_boundary_terms(cfdh_ctx *ctx, int ds_terms, int backflow_marker, double beta);
 
+/* ---- pressure-driven flow (the `stabilized_schur_pressurebc` / `_vascularbc` variants) -------- */
+
+/* Weak form assembled by the generic 2-D element kernels.  CFDH_FORM_CONVECTIVE (default): the form of
+ * stabilized_schur.py:67-123.  CFDH_FORM_ROTATIONAL: the curl-curl / rotational form of
+ * stabilized_schur_pressurebc.py:123-160 -- mu omega(u_mid) omega(v), rho (omega(u_mid) x u_mid) . v - rho/2 |u_mid|^2 div v, no
+ * viscous part in the strong residual (omega = d_x u_y - d_y u_x; omega x a = (-omega a_y, omega a_x)); the time scheme of
+ * cfdh_set_time_scheme applies as before.  CFDH_E_ARG on the closed-form P1 path (CFDH_ELEM_P1: create the context with
+ * CFDH_ELEM_P1_GENERIC), for gdim 3, on a part of a partitioned run, with an active backflow term (beta > 0), and when switching
+ * back to the convective form while pressure boundaries are set.  A change invalidates Jacobian and preconditioner. */
+enum { CFDH_FORM_CONVECTIVE = 0, CFDH_FORM_ROTATIONAL = 1 };
+int cfdh_set_formulation(cfdh_ctx *ctx, int form);
+/* Natural pressure boundaries of the rotational form (stabilized_schur_pressurebc.py:177-205): on the exterior facets whose marker
+ * is markers[k] (k < n <= 8, distinct), with outward normal n, tangent t = (-n_y, n_x) and the owning cell's size h,
+ *   + values[k] v . n  - mu omega(u_mid) (t . v) - mu omega(v) (t . u_mid) + (beta_nitsche mu / h) (t . u_mid)(t . v).
+ * values[k] enters the residual only (the caller passes the reference's halved values, e.g. p_inlet / 2).  The facets follow later
+ * cfdh_set_facet_markers calls.  A call that changes only `values` keeps Jacobian and preconditioner valid (the per-step resistance
+ * update of the vascular outlet); any other change invalidates both.  n = 0 removes the terms.  Requires CFDH_FORM_ROTATIONAL
+ * (and the contexts it allows).  Use with ds_terms = 0 (cfdh_set_boundary_terms): the preconditioner's pressure Laplacian then
+ * takes Dirichlet rows on every exterior facet that is not fully velocity-constrained, the pressure boundaries among them. */
+int cfdh_set_pressure_boundaries(cfdh_ctx *ctx, int n, const int32_t *markers, const double *values, double beta_nitsche);
+
 /* u_prev2 (stabilized_schur_bdf2.py:72): upload / download; nv local vertices x gdim */
 int cfdh_set_previous2(cfdh_ctx *ctx, const double *u_prev2);
 int cfdh_get_previous2(cfdh_ctx *ctx, double *u_prev2);
@@ -312,7 +333,9 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 27: microseconds the last preconditioner build took on the device (0: it was built on the host); 28: element type (CFDH_ELEM_*),
  * 29: nodes per cell;
  * 30 + l / 40 + l: rows / entries of level l of the velocity hierarchy, 50 + l / 60 + l: of the pressure hierarchy (l < 10, 0 past the end);
- * 70: linear solves that started from a projected initial guess (cfdh_options.ksp_guess), 71: their mean |r0| / |b| in units of 1e-6 */
+ * 70: linear solves that started from a projected initial guess (cfdh_options.ksp_guess), 71: their mean |r0| / |b| in units of 1e-6;
+ * 74: preconditioner builds since cfdh_create, 75: 1 while the preconditioner is valid (built, not invalidated since), 76: 1 when the
+ * last null-space test of cfdh_solve_step found the constant pressure in the null space of the Jacobian, 77: formulation (CFDH_FORM_*) */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
