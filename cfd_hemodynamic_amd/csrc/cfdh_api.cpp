@@ -340,22 +340,37 @@ int cfdh_set_time_scheme(cfdh_ctx *c, double theta, double a0, double a1, double
 }
 
 // per-cell facet bits of the assembly kernel: bits 0..d exterior facet, bits d+1..2d+1 backflow facet (marker == bf_marker);
-// generic elements: bit f exterior, 4 + f pressure boundary (slot in gpbidx), 8 + f backflow
+// generic elements: bit f exterior, 4 + f pressure boundary (gdim 2: slot in gpbidx), 8 + f backflow.  gdim 3 (up to 6 facets per
+// cell): the pressure boundaries are not in the flag word but in the slot array g3_pbslot [nc][NF] (0xff: none) and the cell list g3_pcells
 static int upload_cell_facet_flags(cfdh_ctx *c) {
   if (c->gen) {
+    const bool g3 = c->dim == 3;
+    const int nf = g3 ? (c->etype == 2 ? 6 : 4) : 4;
     std::vector<unsigned short> gf((size_t)c->nc, 0);
     std::vector<unsigned char> pbi;
-    if (!c->pb_markers.empty()) pbi.assign(4 * (size_t)c->nc, 0);
+    if (!c->pb_markers.empty()) pbi.assign(nf * (size_t)c->nc, g3 ? 0xff : 0);
     for (int k = 0; k < c->nfac; k++) {
       gf[c->fac_cell[k]] |= (unsigned short)(1u << c->fac_local[k]);
       if (c->bf_marker >= 0 && c->fac_marker[k] == c->bf_marker) gf[c->fac_cell[k]] |= (unsigned short)(256u << c->fac_local[k]);
       for (size_t b = 0; b < c->pb_markers.size(); b++)
         if (c->fac_marker[k] == c->pb_markers[b]) {
-          gf[c->fac_cell[k]] |= (unsigned short)(16u << c->fac_local[k]);
-          pbi[4 * (size_t)c->fac_cell[k] + c->fac_local[k]] = (unsigned char)b;
+          if (!g3) gf[c->fac_cell[k]] |= (unsigned short)(16u << c->fac_local[k]);
+          pbi[nf * (size_t)c->fac_cell[k] + c->fac_local[k]] = (unsigned char)b;
         }
     }
-    if (!pbi.empty()) HIPCHK(c, c->gpbidx.upload(pbi, c->stream));
+    if (g3) {
+      std::vector<int> pcl;
+      for (int e = 0; e < (int)pbi.size() / nf; e++)
+        for (int f = 0; f < nf; f++)
+          if (pbi[nf * (size_t)e + f] != 0xff) { pcl.push_back(e); break; }
+      c->g3_npcells = (int)pcl.size();
+      if (!pcl.empty()) {
+        HIPCHK(c, c->g3_pbslot.upload(pbi, c->stream));
+        HIPCHK(c, c->g3_pcells.upload(pcl, c->stream));
+      }
+    } else if (!pbi.empty()) {
+      HIPCHK(c, c->gpbidx.upload(pbi, c->stream));
+    }
     HIPCHK(c, c->gflag.upload(gf, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->jac_valid = false;
@@ -401,9 +416,11 @@ int cfdh_set_facet_markers(cfdh_ctx *c, int64_t nfacets, const int32_t *markers)
   return 0;
 }
 
-// contexts the rotational form exists for (the rest are follow-ups)
+// contexts the rotational form exists for (the rest are follow-ups): gdim 2 on the generic kernels, and P2 tetrahedra / Q1 hexahedra
+// in gdim 3 (the P1 tetrahedron, closed-form or generic, has no rotational variant)
 static int rotational_supported(cfdh_ctx *c, const char *who) {
-  if (c->dim != 2) return cfdh_fail(c, CFDH_E_ARG, "%s: the rotational formulation exists for gdim 2 only", who);
+  if (c->dim != 2 && !(c->dim == 3 && c->gen && (c->etype == 1 || c->etype == 2)))
+    return cfdh_fail(c, CFDH_E_ARG, "%s: the rotational formulation exists for gdim 2, and for P2 / Q1 cells in gdim 3", who);
   if (!c->gen)
     return cfdh_fail(c, CFDH_E_ARG, "%s: the rotational formulation runs on the generic element kernels; create P1 contexts with CFDH_ELEM_P1_GENERIC", who);
   if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "%s: the rotational formulation is not available in partitioned runs", who);

@@ -60,8 +60,13 @@ __device__ __host__ inline void ref_vertex3(int et, int v, double r[3]) {
   else { r[0] = v == 1; r[1] = v == 2; r[2] = v == 3; }
 }
 
-// value and reference gradient of basis function a at the reference point pt
-template <int ET>
+// edge e of the tetrahedron from packed nibbles: no indexed local table (the rotational kernels stay free of scratch)
+__device__ __host__ inline void tet_edge_packed(int e, int &i, int &j) { i = (0x000112 >> (4 * e)) & 15; j = (0x123233 >> (4 * e)) & 15; }
+// vertex k of facet f: the tetrahedron's facet f holds the vertices other than f, in increasing order
+__device__ __host__ inline int facet_vertex_packed(int et, int f, int k) { return et == 2 ? facet_vertex(et, f, k) : k + (k >= f ? 1 : 0); }
+
+// value and reference gradient of basis function a at the reference point pt (PACKED: tetrahedra by arithmetic, no local tables)
+template <int ET, bool PACKED = false>
 __device__ __host__ inline void basis3(int a, const double pt[3], double &phi, double d[3]) {
   const double x = pt[0], y = pt[1], z = pt[2];
   if (ET == 2) {
@@ -70,6 +75,22 @@ __device__ __host__ inline void basis3(int a, const double pt[3], double &phi, d
     const double dx = i ? 1.0 : -1.0, dy = j ? 1.0 : -1.0, dz = k ? 1.0 : -1.0;
     phi = fx * fy * fz;
     d[0] = dx * fy * fz; d[1] = fx * dy * fz; d[2] = fx * fy * dz;
+    return;
+  }
+  if (PACKED) {  // barycentric coordinates and their gradients by arithmetic: no indexed local tables
+    auto lam = [&](int v) { return v == 0 ? 1.0 - x - y - z : pt[v - 1]; };
+    auto dlam = [](int v, int k) { return v == 0 ? -1.0 : (k == v - 1 ? 1.0 : 0.0); };
+    if (ET == 0 || a < 4) {
+      const double la = lam(a), s = ET == 0 ? 1.0 : 4.0 * la - 1.0;
+      phi = ET == 0 ? la : la * (2.0 * la - 1.0);
+      for (int k = 0; k < 3; k++) d[k] = s * dlam(a, k);
+    } else {
+      int i, j;
+      tet_edge_packed(a - 4, i, j);
+      const double li = lam(i), lj = lam(j);
+      phi = 4.0 * li * lj;
+      for (int k = 0; k < 3; k++) d[k] = 4.0 * (li * dlam(j, k) + lj * dlam(i, k));
+    }
     return;
   }
   const double l[4] = {1.0 - x - y - z, x, y, z};
@@ -150,10 +171,11 @@ __device__ __host__ inline void geom3(const XT &X, double Ji[3][3], double &adet
     }
 }
 // outward unit normal and measure of local facet f
-template <int ET, typename XT>
+template <int ET, typename XT, bool PACKED = false>
 __device__ __host__ inline void facet_geom3(const XT &X, int f, double n[3], double &area) {
   constexpr int NV = ET == 2 ? 8 : 4, et = ET;
-  const int v0 = facet_vertex(et, f, 0), v1 = facet_vertex(et, f, 1), v2 = facet_vertex(et, f, 2);
+  auto fv = [&](int k) { return PACKED ? facet_vertex_packed(et, f, k) : facet_vertex(et, f, k); };
+  const int v0 = fv(0), v1 = fv(1), v2 = fv(2);
   double e1[3], e2[3], cen[3] = {0, 0, 0}, fc[3] = {0, 0, 0};
   for (int i = 0; i < 3; i++) { e1[i] = X[v1][i] - X[v0][i]; e2[i] = X[v2][i] - X[v0][i]; }
   n[0] = e1[1] * e2[2] - e1[2] * e2[1]; n[1] = e1[2] * e2[0] - e1[0] * e2[2]; n[2] = e1[0] * e2[1] - e1[1] * e2[0];
@@ -161,17 +183,17 @@ __device__ __host__ inline void facet_geom3(const XT &X, int f, double n[3], dou
   area = ET == 2 ? nn : 0.5 * nn;
   for (int a = 0; a < NV; a++) for (int i = 0; i < 3; i++) cen[i] += X[a][i] * (1.0 / NV);
   const int nfv = facet_nvert(et);
-  for (int k = 0; k < nfv; k++) for (int i = 0; i < 3; i++) fc[i] += X[facet_vertex(et, f, k)][i] / nfv;
+  for (int k = 0; k < nfv; k++) for (int i = 0; i < 3; i++) fc[i] += X[fv(k)][i] / nfv;
   const double sg = ((fc[0] - cen[0]) * n[0] + (fc[1] - cen[1]) * n[1] + (fc[2] - cen[2]) * n[2]) < 0 ? -1.0 : 1.0;
   for (int i = 0; i < 3; i++) n[i] *= sg / nn;
 }
 // facet quadrature: number of points; point q of local facet f in cell reference coordinates, weight (sum 1)
 template <int ET> __device__ __host__ constexpr int facet_nq() { return ET == 2 ? 4 : (ET == 1 ? CFDH_NQ : 6); }
-template <int ET>
+template <int ET, bool PACKED = false>
 __device__ inline void facet_point(int f, int q, double pt[3], double &w) {
   constexpr int et = ET;
   double rv[4][3];
-  for (int k = 0; k < facet_nvert(et); k++) ref_vertex3(et, facet_vertex(et, f, k), rv[k]);
+  for (int k = 0; k < facet_nvert(et); k++) ref_vertex3(et, PACKED ? facet_vertex_packed(et, f, k) : facet_vertex(et, f, k), rv[k]);
   if (ET == 2) {
     const double s = d3_gl2[0][q >> 1], t = d3_gl2[0][q & 1];
     for (int i = 0; i < 3; i++) pt[i] = (1 - s) * (1 - t) * rv[0][i] + s * (1 - t) * rv[1][i] + (1 - s) * t * rv[2][i] + s * t * rv[3][i];
@@ -204,6 +226,10 @@ struct Gen3Args {
   double dt, rho, mu, muf, f[3], theta, a0, a1, a2, beta;
   int ds_terms;
   double *E, *EF;                // [nc nloc^2][16] (A00 row-major 9 | A01 3 | A10 3 | A11), [nc nloc^2][4]
+  // rotational form only (ROT = true): pressure boundaries -- slot of local facet f of the cell in pbslot[NF cell + f] (0xff: none),
+  // values P_k in pval, Nitsche penalty pbeta
+  const unsigned char *pbslot;
+  double pval[CFDH_MAX_PBND], pbeta;
 };
 
 template <int NL>
@@ -213,8 +239,15 @@ struct Cell3 {
 };
 
 #define FLD 23  // per-point record: uq 0-2 | G 3-11 (G[i][j] = d_i ubar_j) | R 12-14 | rho (w + C - f) 15-17 | pq 18 | tau 19 | tauL 20 | dv 21
+                // ROT: uq 0-2 | omega 3-5 | div ubar 6 | R 12-14 | rho (w + omega x ubar - f) 15-17 | pq + rho/2 |ubar|^2 18 | 19-21 as above
 
-template <int ET, bool JAC>
+// ROT = true: the rotational form of the pressure-driven solvers in 3-D (the reference's
+// src/solvers/stabilized_schur_pressurebc.py:111-160; cfdh_set_formulation).  With omega = curl ubar:
+//   rho w_t . v + mu curl ubar . curl v - p div v + rho (omega x ubar) . v - rho/2 |ubar|^2 div v - rho f . v + q div ubar
+//   + SUPG / PSPG / LSIC with R = rho (w_t + omega x ubar) + grad p - rho f (no viscous part: no Hessians are staged).
+// For v = phi_a e_i, curl v = grad phi_a x e_i, so mu curl ubar . curl v = mu (omega x grad phi_a)_i.  The facet terms of the
+// pressure boundaries are added by gen3_facet_kernel<ET, true>.
+template <int ET, bool JAC, bool ROT>
 __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
   constexpr int NL = g3_nloc(ET), WGS = g3_wgs(ET), GS = g3_gs(ET), NG = WGS / GS;
   constexpr int CH = ET == 2 ? 32 : 64;              // points per chunk (32 on hexahedra: their per-point Hessians would cost a third workgroup per CU)
@@ -222,7 +255,7 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
   __shared__ Cell3<NL> D;
   __shared__ double fld[CH][FLD];
   __shared__ double bas[CH][NL][4];                  // physical (phi, grad phi) of every node at the chunk's points
-  __shared__ double hes[ET == 2 ? CH : 1][NL][6];    // physical second derivatives: per point on hexahedra, cell constants on P2 tetrahedra
+  __shared__ double hes[ET == 2 && !ROT ? CH : 1][NL][6];  // physical second derivatives: per point on hexahedra, cell constants on P2 tetrahedra
   __shared__ double geo[12];                         // Ji (9), |det|, h, needj
   const int cell = blockIdx.x, t = threadIdx.x;
   const int grp = t / GS, blk = t % GS;
@@ -256,7 +289,7 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
       for (int c = 0; c < NL; c++) nj = nj || D.lift[c][0] != 0.0 || D.lift[c][1] != 0.0 || D.lift[c][2] != 0.0 || D.lift[c][3] != 0.0;
     geo[11] = nj ? 1.0 : 0.0;
   }
-  if (ET != 2 && t < NL) {  // constant second derivatives (P2 tetrahedra; zero for P1): needs Ji, formed redundantly here
+  if (!ROT && ET != 2 && t < NL) {  // constant second derivatives (P2 tetrahedra; zero for P1): needs Ji, formed redundantly here
     double Ji0[3][3], ad, hh, Hr[6], Hs[6];
     const double p0[3] = {0.25, 0.25, 0.25};
     geom3<ET>(D.X, Ji0, ad, hh);
@@ -279,19 +312,48 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
       if (q >= NQ) continue;
       const double *pt = d3_pts[ET == 2 ? 1 : 0][q];
       double ph, dr[3];
-      basis3<ET>(c, pt, ph, dr);
+      basis3<ET, ROT>(c, pt, ph, dr);
       bas[sp][c][0] = ph;
       for (int i = 0; i < 3; i++) bas[sp][c][1 + i] = dr[0] * Ji[0][i] + dr[1] * Ji[1][i] + dr[2] * Ji[2][i];
-      if (ET == 2) {
+      if (ET == 2 && !ROT) {
         double Hr[6], Hs[6];
         hess3<ET>(c, pt, Hr);
         hess_phys(Hr, Ji, Hs);
-        for (int k = 0; k < 6; k++) hes[sp][c][k] = Hs[k];
+        for (int k = 0; k < 6; k++) hes[ET == 2 && !ROT ? sp : 0][c][k] = Hs[k];
       }
     }
     __syncthreads();
     const int q = ch * CH + t;
-    if (t < CH && q < NQ) {
+    if (ROT && t < CH && q < NQ) {
+      // ---- everything that belongs to the point, once (rotational form: no Hessians)
+      const double *pt = d3_pts[ET == 2 ? 1 : 0][q];
+      double uq[3] = {0, 0, 0}, wv[3] = {0, 0, 0}, unq[3] = {0, 0, 0}, G[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, gp[3] = {0, 0, 0}, pq = 0.0;
+#pragma unroll
+      for (int c = 0; c < NL; c++) {
+        const double ph = bas[t][c][0], g[3] = {bas[t][c][1], bas[t][c][2], bas[t][c][3]};
+        for (int i = 0; i < 3; i++) {
+          uq[i] += ph * D.ub[c][i]; wv[i] += ph * D.wn[c][i]; unq[i] += ph * D.un[c][i];
+          gp[i] += g[i] * D.p[c];
+          for (int j = 0; j < 3; j++) G[i][j] += g[i] * D.ub[c][j];
+        }
+        pq += ph * D.p[c];
+      }
+      double tau, tauL;
+      tau_pair3(unq[0] * unq[0] + unq[1] * unq[1] + unq[2] * unq[2], h, P.dt, nu, tau, tauL);
+      const double om[3] = {G[1][2] - G[2][1], G[2][0] - G[0][2], G[0][1] - G[1][0]};
+      const double Cr[3] = {om[1] * uq[2] - om[2] * uq[1], om[2] * uq[0] - om[0] * uq[2], om[0] * uq[1] - om[1] * uq[0]};
+      double *fr = fld[t];
+      for (int i = 0; i < 3; i++) {
+        fr[i] = uq[i];
+        fr[3 + i] = om[i];
+        fr[12 + i] = rho * (wv[i] + Cr[i]) + gp[i] - rho * P.f[i];
+        fr[15 + i] = rho * (wv[i] + Cr[i] - P.f[i]);
+      }
+      fr[6] = G[0][0] + G[1][1] + G[2][2];
+      fr[18] = pq + 0.5 * rho * (uq[0] * uq[0] + uq[1] * uq[1] + uq[2] * uq[2]);
+      fr[19] = tau; fr[20] = tauL; fr[21] = adet * pt[3];
+    }
+    if (!ROT && t < CH && q < NQ) {
       // ---- everything that belongs to the point, once
       const double *pt = d3_pts[ET == 2 ? 1 : 0][q];
       double uq[3] = {0, 0, 0}, wv[3] = {0, 0, 0}, unq[3] = {0, 0, 0}, G[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, gp[3] = {0, 0, 0}, pq = 0.0;
@@ -300,7 +362,7 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
       for (int c = 0; c < NL; c++) {
         const double ph = bas[t][c][0], g[3] = {bas[t][c][1], bas[t][c][2], bas[t][c][3]};
         double Hs[6];
-        for (int k = 0; k < 6; k++) Hs[k] = hes[ET == 2 ? t : 0][c][k];
+        for (int k = 0; k < 6; k++) Hs[k] = hes[ET == 2 && !ROT ? t : 0][c][k];
         const double lapc = Hs[0] + Hs[3] + Hs[5];
         for (int i = 0; i < 3; i++) {
           uq[i] += ph * D.ub[c][i]; wv[i] += ph * D.wn[c][i]; unq[i] += ph * D.un[c][i];
@@ -325,8 +387,9 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
     __syncthreads();
     const int npt = min(CH, NQ - ch * CH);
     // residual-only pass of a cell without lifting: no Jacobian block is needed, so the NL lanes of a row share the row's points
-    // (lane (a, b) takes the points grp + NG b, grp + NG (b + NL), ...) and the row is summed over b at the end
-    const bool fsplit = !needj;
+    // (lane (a, b) takes the points grp + NG b, grp + NG (b + NL), ...) and the row is summed over b at the end.  Not in the rotational
+    // form: its residual-only pass (line search) gives the bits of the full pass, as in 2-D
+    const bool fsplit = !ROT && !needj;
     if (live) {
       for (int s = fsplit ? grp + NG * b : grp; s < npt; s += fsplit ? NG * NL : NG) {
         const double *fr = fld[s];
@@ -334,6 +397,45 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
         const double uq[3] = {fr[0], fr[1], fr[2]}, R[3] = {fr[12], fr[13], fr[14]};
         const double tau = fr[19], tauL = fr[20], dv = fr[21];
         const double bga = uq[0] * ga[0] + uq[1] * ga[1] + uq[2] * ga[2];
+        if constexpr (ROT) {
+          const double om[3] = {fr[3], fr[4], fr[5]};
+          const double oxg[3] = {om[1] * ga[2] - om[2] * ga[1], om[2] * ga[0] - om[0] * ga[2], om[0] * ga[1] - om[1] * ga[0]};  // omega x grad phi_a
+          if (b == 0 || fsplit) {
+            const double pk = fr[18], divu = fr[6];
+#pragma unroll
+            for (int i = 0; i < 3; i++) Fa[i] += dv * (pha * fr[15 + i] + mu * oxg[i] - pk * ga[i] + tau * R[i] * bga + tauL * rho * divu * ga[i]);
+            Fa[3] += dv * (pha * divu + tau / rho * (R[0] * ga[0] + R[1] * ga[1] + R[2] * ga[2]));
+          }
+          if (!needj) continue;
+          // ---- block (a, b): with dR_i(j) = sd delta_ij - rho th gb_i ubar_j + k1 (omega x e_j)_i (the time term and th times
+          //      d (omega x ubar) = (curl(phi_b e_j) x ubar) + phi_b omega x e_j), and mu th (curl phi_b e_j) . (curl phi_a e_i) =
+          //      mu th (gg delta_ij - gb_i ga_j):
+          //   Juu[i][j] += A1 dR_i(j) + dv mu th (gg delta_ij - gb_i ga_j) - dv k1 ubar_j ga_i + c3 R_i ga_j + c4 gb_j ga_i
+          const double phb = bas[s][b][0], gb[3] = {bas[s][b][1], bas[s][b][2], bas[s][b][3]};
+          const double bgb = uq[0] * gb[0] + uq[1] * gb[1] + uq[2] * gb[2];
+          const double gg = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
+          const double ct = dv * tau, ctb = ct * bga, mt = mu * th, dmt = dv * mt;
+          const double A1 = dv * pha + ctb, k1 = rho * th * phb, sd = rho * (a0dt * phb + th * bgb);
+          const double B1 = A1 * k1, Dg = A1 * sd + dmt * gg, c3 = ct * th * phb, c4 = dv * rho * th * tauL, ar = A1 * rho * th, dk = dv * k1;
+          const double W[3][3] = {{0.0, -om[2], om[1]}, {om[2], 0.0, -om[0]}, {-om[1], om[0], 0.0}};  // omega x e_j = W[.][j]
+          const double xv[3] = {-ar * uq[0] - dmt * ga[0], -ar * uq[1] - dmt * ga[1], -ar * uq[2] - dmt * ga[2]};
+          const double yv[3] = {c4 * gb[0] - dk * uq[0], c4 * gb[1] - dk * uq[1], c4 * gb[2] - dk * uq[2]};
+#pragma unroll
+          for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) Juu[i][j] += gb[i] * xv[j] + ga[i] * yv[j] + c3 * R[i] * ga[j] + B1 * W[i][j];
+            Juu[i][i] += Dg;
+          }
+          // Jpu[j] += dv th pha gb_j + (dv tau / rho) sum_i ga_i dR_i(j), sum_i ga_i (omega x e_j)_i = -(omega x ga)_j
+          const double cr = ct / rho, e1 = dv * th * pha, rg = rho * th * gg;
+#pragma unroll
+          for (int j = 0; j < 3; j++) Jpu[j] += e1 * gb[j] + cr * (sd * ga[j] - rg * uq[j] - k1 * oxg[j]);
+          const double f1 = -dv * phb;
+#pragma unroll
+          for (int i = 0; i < 3; i++) Jup[i] += f1 * ga[i] + ctb * gb[i];
+          Jpp += cr * gg;
+          continue;
+        }
         if (b == 0 || fsplit) {
           const double pq = fr[18], divu = fr[3] + fr[7] + fr[11];
 #pragma unroll
@@ -351,7 +453,7 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
         //   dWC_i(j) = k1 G[j][i] + delta_ij s_d,   dR_i(j) = dWC_i(j) - mu th (delta_ij lap_b + H_b[i][j])
         //   Juu[i][j] += A1 dWC_i(j) - A2 (delta_ij lap_b + H_b[i][j]) + ga[j] w_i + z_j ga[i] + delta_ij dv mu th (ga . gb)
         const double phb = bas[s][b][0], gb[3] = {bas[s][b][1], bas[s][b][2], bas[s][b][3]};
-        const double *Hb = hes[ET == 2 ? s : 0][b];
+        const double *Hb = hes[ET == 2 && !ROT ? s : 0][b];
         const double lapb = Hb[0] + Hb[3] + Hb[5];
         const double bgb = uq[0] * gb[0] + uq[1] * gb[1] + uq[2] * gb[2];
         const double gg = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
@@ -411,7 +513,7 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
     for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) Juu[i][j] = acc[3 * i + j]; Jup[i] = acc[9 + i]; Jpu[i] = acc[12 + i]; }
     Jpp = acc[15];
     for (int i = 0; i < 4; i++) Fa[i] = acc[16 + i];
-    if (!needj) {  // rows shared by their NL lanes: sum over b in the order 0, 1, ..., NL - 1 (uniform in the workgroup)
+    if (!ROT && !needj) {  // rows shared by their NL lanes: sum over b in the order 0, 1, ..., NL - 1 (uniform in the workgroup)
       if (live && grp == 0) for (int i = 0; i < 4; i++) red[4 * blk + i] = Fa[i];
       __syncthreads();
       if (live && grp == 0 && b == 0)
@@ -449,11 +551,17 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
 // staged: every (cell, a, b) entry of E / EF belongs to one lane, so the update needs no atomics and keeps the fixed summation order.
 // The Dirichlet handling is linear in the block, so lifting and masks apply to the facet part on its own.  A kernel of its own
 // because inlined into the volume kernel it cost that kernel a third of its registers (314 instead of 218) on every cell.
-template <int ET>
+//
+// ROT = true: the facets of the pressure boundaries of the rotational form instead (stabilized_schur_pressurebc.py:177-205; fcells
+// then lists the cells with such a facet).  On local facet f with slot k = pbslot[NF cell + f] (value P_k, outward n, h of the cell):
+//   P_k v . n - mu (omega x n) . v_T - mu (curl v x n) . ubar_T + (beta mu / h) ubar_T . v_T,   omega = curl ubar,
+// where (omega x n) . v_T = (omega x n) . v, and for v = phi_a e_i: (curl v x n) . ubar = ubar_i (ga . n) - (ga . ubar) n_i.
+// curl v does not vanish off the facet: every lane of a cell with a pressure facet contributes, whatever its test function there.
+template <int ET, bool ROT>
 __global__ __launch_bounds__(128) void gen3_facet_kernel(Gen3Args P, const int *__restrict__ fcells) {
   constexpr int NL = g3_nloc(ET), NF = ET == 2 ? 6 : 4;
   __shared__ Cell3<NL> D;
-  __shared__ double geo[9];
+  __shared__ double geo[ROT ? 10 : 9];
   const int cell = fcells[blockIdx.x], t = threadIdx.x;
   const int blk = t, a = blk / NL, b = blk % NL;
   const bool live = blk < NL * NL;
@@ -478,6 +586,7 @@ __global__ __launch_bounds__(128) void gen3_facet_kernel(Gen3Args P, const int *
     double Ji0[3][3], ad, hh;
     geom3<ET>(D.X, Ji0, ad, hh);
     for (int k = 0; k < 9; k++) geo[k] = Ji0[k / 3][k % 3];
+    if constexpr (ROT) geo[9] = hh;
   }
   __syncthreads();
   if (!live) return;
@@ -489,7 +598,54 @@ __global__ __launch_bounds__(128) void gen3_facet_kernel(Gen3Args P, const int *
   // the facet terms enter the velocity rows of node a only: when all three are Dirichlet rows (a node on a no-slip wall) they would
   // be dropped below -- and the lanes of the nodes off the facet see a vanishing test function.  Most exterior facets are walls.
   if ((D.bc[a] & 7u) == 7u) return;
-  if (fl) {
+  if constexpr (ROT) {
+    const double h = geo[9], mu = P.mu, nit = P.pbeta * mu / h;
+    for (int f = 0; f < NF; f++) {
+      const int slot = P.pbslot[NF * (size_t)cell + f];
+      if (slot == 0xff) continue;  // not a pressure-boundary facet (uniform in the workgroup)
+      double pk = 0.0;
+#pragma unroll
+      for (int k = 0; k < CFDH_MAX_PBND; k++) pk = k == slot ? P.pval[k] : pk;  // static indices: the argument block stays in SGPRs
+      double n[3], area;
+      facet_geom3<ET, decltype(D.X), true>(D.X, f, n, area);
+      for (int q = 0; q < facet_nq<ET>(); q++) {
+        double pt[3], w;
+        facet_point<ET, true>(f, q, pt, w);
+        const double m = area * w;
+        double pha, dra[3], phb, drb[3], ga[3], gb[3];
+        basis3<ET, true>(a, pt, pha, dra);
+        basis3<ET, true>(b, pt, phb, drb);
+        for (int i = 0; i < 3; i++) {
+          ga[i] = dra[0] * Ji[0][i] + dra[1] * Ji[1][i] + dra[2] * Ji[2][i];
+          gb[i] = drb[0] * Ji[0][i] + drb[1] * Ji[1][i] + drb[2] * Ji[2][i];
+        }
+        double uq[3] = {0, 0, 0}, G[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        for (int c = 0; c < NL; c++) {
+          double ph, dr[3];
+          basis3<ET, true>(c, pt, ph, dr);
+          for (int i = 0; i < 3; i++) {
+            const double gi = dr[0] * Ji[0][i] + dr[1] * Ji[1][i] + dr[2] * Ji[2][i];
+            uq[i] += ph * D.ub[c][i];
+            for (int j = 0; j < 3; j++) G[i][j] += gi * D.ub[c][j];
+          }
+        }
+        const double om[3] = {G[1][2] - G[2][1], G[2][0] - G[0][2], G[0][1] - G[1][0]};
+        const double oxn[3] = {om[1] * n[2] - om[2] * n[1], om[2] * n[0] - om[0] * n[2], om[0] * n[1] - om[1] * n[0]};
+        const double un = uq[0] * n[0] + uq[1] * n[1] + uq[2] * n[2];
+        const double gan = ga[0] * n[0] + ga[1] * n[1] + ga[2] * n[2], gbn = gb[0] * n[0] + gb[1] * n[1] + gb[2] * n[2];
+        const double bga = ga[0] * uq[0] + ga[1] * uq[1] + ga[2] * uq[2];
+        if (b == 0)
+          for (int i = 0; i < 3; i++)
+            Fa[i] += m * (pha * (pk * n[i] - mu * oxn[i] + nit * (uq[i] - un * n[i])) - mu * (uq[i] * gan - bga * n[i]));
+        // d/du_(b,j): -mu pha ((gb x e_j) x n)_i - mu phb ((ga x e_i) x n)_j + nit pha phb (delta_ij - n_i n_j)
+        const double tm = th * m, cab = tm * (nit * pha * phb - mu * (pha * gbn + phb * gan));
+        for (int i = 0; i < 3; i++) {
+          for (int j = 0; j < 3; j++) Juu[i][j] += tm * (mu * (pha * gb[i] * n[j] + phb * ga[j] * n[i]) - nit * pha * phb * n[i] * n[j]);
+          Juu[i][i] += cab;
+        }
+      }
+    }
+  } else if (fl) {
     for (int f = 0; f < NF; f++) {
       const bool ext = P.ds_terms && ((fl >> f) & 1u), bfl = P.beta != 0.0 && ((fl >> (8 + f)) & 1u);
       if (!ext && !bfl) continue;
@@ -1086,19 +1242,33 @@ int kg3_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   P.beta = c->bf_marker >= 0 ? c->bf_beta : 0.0;
   P.ds_terms = c->ds_terms ? 1 : 0;
   P.E = c->gE.p; P.EF = c->gEF.p;
+  const bool rot = c->form == CFDH_FORM_ROTATIONAL;
+  P.pbslot = c->g3_pbslot.p; P.pbeta = c->pb_beta;
+  for (int k = 0; k < CFDH_MAX_PBND; k++) P.pval[k] = k < (int)c->pb_values.size() ? c->pb_values[k] : 0.0;
   const dim3 grid(c->nc);
   prof_begin(c, 0);
-#define G3_LAUNCH(ET) do { if (mode == 1) hipLaunchKernelGGL((gen3_asm_kernel<ET, true>), grid, dim3(g3_wgs(ET)), 0, c->stream, P); \
-                           else hipLaunchKernelGGL((gen3_asm_kernel<ET, false>), grid, dim3(g3_wgs(ET)), 0, c->stream, P); } while (0)
-  if (c->etype == 1) G3_LAUNCH(1);
-  else if (c->etype == 2) G3_LAUNCH(2);
-  else G3_LAUNCH(0);
+#define G3_LAUNCH(ET, ROT) do { if (mode == 1) hipLaunchKernelGGL((gen3_asm_kernel<ET, true, ROT>), grid, dim3(g3_wgs(ET)), 0, c->stream, P); \
+                                else hipLaunchKernelGGL((gen3_asm_kernel<ET, false, ROT>), grid, dim3(g3_wgs(ET)), 0, c->stream, P); } while (0)
+  if (rot) {  // P1 tetrahedra are refused by the API (rotational_supported): no <0, *, true> instantiation
+    if (c->etype == 1) G3_LAUNCH(1, true);
+    else G3_LAUNCH(2, true);
+  } else {
+    if (c->etype == 1) G3_LAUNCH(1, false);
+    else if (c->etype == 2) G3_LAUNCH(2, false);
+    else G3_LAUNCH(0, false);
+  }
 #undef G3_LAUNCH
-  if (c->g3_nfcells > 0 && (P.ds_terms || P.beta != 0.0)) {
+  // (the rotational form has no ds pair, :177-205; its backflow combination is refused by the API)
+  if (!rot && c->g3_nfcells > 0 && (P.ds_terms || P.beta != 0.0)) {
     const dim3 fg(c->g3_nfcells), fb(128);
-    if (c->etype == 1) hipLaunchKernelGGL((gen3_facet_kernel<1>), fg, fb, 0, c->stream, P, c->g3_fcells.p);
-    else if (c->etype == 2) hipLaunchKernelGGL((gen3_facet_kernel<2>), fg, fb, 0, c->stream, P, c->g3_fcells.p);
-    else hipLaunchKernelGGL((gen3_facet_kernel<0>), fg, fb, 0, c->stream, P, c->g3_fcells.p);
+    if (c->etype == 1) hipLaunchKernelGGL((gen3_facet_kernel<1, false>), fg, fb, 0, c->stream, P, c->g3_fcells.p);
+    else if (c->etype == 2) hipLaunchKernelGGL((gen3_facet_kernel<2, false>), fg, fb, 0, c->stream, P, c->g3_fcells.p);
+    else hipLaunchKernelGGL((gen3_facet_kernel<0, false>), fg, fb, 0, c->stream, P, c->g3_fcells.p);
+  }
+  if (rot && c->g3_npcells > 0) {  // the pressure-boundary facets (set: cfdh_set_pressure_boundaries)
+    const dim3 fg(c->g3_npcells), fb(128);
+    if (c->etype == 1) hipLaunchKernelGGL((gen3_facet_kernel<1, true>), fg, fb, 0, c->stream, P, c->g3_pcells.p);
+    else hipLaunchKernelGGL((gen3_facet_kernel<2, true>), fg, fb, 0, c->stream, P, c->g3_pcells.p);
   }
   const dim3 block(TPB);
   hipLaunchKernelGGL(gen3_gather_F_kernel, dim3((c->nvo + TPB - 1) / TPB), block, 0, c->stream, c->nvo, c->g_fptr.p, c->gEF.p, c->F.p);

@@ -163,6 +163,11 @@ struct cfdh_ctx {
   dbuf<unsigned char> gpbidx;  // [nc][4] index into pb_values of the pressure boundary that holds local facet f (bit 4 + f set)
   dbuf<int> g3_fcells;         // 3-D generic elements: the cells with an exterior facet (gen3_facet_kernel)
   int g3_nfcells = 0;
+  // 3-D generic elements, rotational form: pressure boundary of local facet f of cell e in g3_pbslot[NF e + f] (index into pb_values,
+  // 0xff: none; NF = 6 on hexahedra, 4 on tetrahedra) and the cells with such a facet (gen3_facet_kernel<ET, true>)
+  dbuf<unsigned char> g3_pbslot;
+  dbuf<int> g3_pcells;
+  int g3_npcells = 0;
   // P2: the P1 subspace as the first coarse level of both hierarchies (p-multigrid step): prolongator [nodes x vertex nodes],
   // 1 at a vertex node, 1/2 + 1/2 at an edge node (host copy; internal numbering)
   CsrHost gen_P1;

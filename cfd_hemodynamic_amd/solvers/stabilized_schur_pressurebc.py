@@ -9,8 +9,9 @@
 
 The reference stores HALF the given pressures (`_p_inlet_val = p_inlet / 2`, :64-65) and that is what enters the form; the same
 halving is reproduced here.  Constructor as in the reference: `p_inlet` and `p_outlet` are required (ValueError otherwise, :59-63),
-`beta_nitsche` defaults to 100, `p_grade` 1 or 2.  Runs on the generic element kernels (csrc/cfdh_gen.hip, P1 triangles through
-CFDH_ELEM_P1_GENERIC) on one GPU, gdim 2; a partitioned `comm` is refused.
+`beta_nitsche` defaults to 100, `p_grade` 1 or 2.  Runs on the generic element kernels on one GPU: gdim 2 (csrc/cfdh_gen.hip,
+P1 triangles through CFDH_ELEM_P1_GENERIC), and gdim 3 (csrc/cfdh_gen3.hip, the curl form of :111-121) on hexahedra (Q1/Q1) and on
+tetrahedra with `p_grade=2` (P2/P2).  P1 tetrahedra and a partitioned `comm` are refused before any device work.
 """
 from __future__ import annotations
 
@@ -26,9 +27,12 @@ from .stabilized_schur import Solver as _MidpointSolver
 _FOREIGN = ("v_max", "beta_backflow", "R_resistance", "initial_ffr", "p_outlet")
 
 
-def _refuse_unsupported(p_grade, kwargs):
+def _refuse_unsupported(mesh, p_grade, kwargs):
     if int(p_grade) not in (1, 2):
         raise NotImplementedError("p_grade=%r: P1/P1 and P2/P2 run on the gfx950 kernels" % (p_grade,))
+    if mesh.geometry.dim == 3 and mesh.topology.cell_name() == "tetrahedron" and int(p_grade) == 1:
+        raise NotImplementedError("the pressure-driven solvers have no P1 tetrahedron variant in 3-D: "
+                                  "pass p_grade=2 (P2/P2 tetrahedra) or use hexahedra (Q1/Q1)")
     comm = kwargs.get("comm", None)
     if comm is not None and comm.size > 1:
         raise NotImplementedError("the pressure-driven solvers run on one GPU: partitioned runs are not supported")
@@ -48,7 +52,7 @@ class Solver(_MidpointSolver):
         self._init_pressure_driven(mesh, dt, rho, mu, f, initial_velocity, float(p_inlet), float(p_outlet), beta_nitsche, p_grade, kwargs)
 
     def _init_pressure_driven(self, mesh, dt, rho, mu, f, initial_velocity, p_inlet, p_outlet, beta_nitsche, p_grade, kwargs):
-        _refuse_unsupported(p_grade, kwargs)
+        _refuse_unsupported(mesh, p_grade, kwargs)
         self._p_inlet_val = p_inlet / 2   # :64-65
         self._p_outlet_val = p_outlet / 2
         self.beta_nitsche = float(beta_nitsche)

@@ -221,18 +221,24 @@ int cfdh_set_boundary_terms(cfdh_ctx *ctx, int ds_terms, int backflow_marker, do
 
 /* ---- pressure-driven flow (the `stabilized_schur_pressurebc` / `_vascularbc` variants) -------- */
 
-/* Weak form assembled by the generic 2-D element kernels.  CFDH_FORM_CONVECTIVE (default): the form of
- * stabilized_schur.py:67-123.  CFDH_FORM_ROTATIONAL: the curl-curl / rotational form of
- * stabilized_schur_pressurebc.py:123-160 -- mu omega(u_mid) omega(v), rho (omega(u_mid) x u_mid) . v - rho/2 |u_mid|^2 div v, no
- * viscous part in the strong residual (omega = d_x u_y - d_y u_x; omega x a = (-omega a_y, omega a_x)); the time scheme of
- * cfdh_set_time_scheme applies as before.  CFDH_E_ARG on the closed-form P1 path (CFDH_ELEM_P1: create the context with
- * CFDH_ELEM_P1_GENERIC), for gdim 3, on a part of a partitioned run, with an active backflow term (beta > 0), and when switching
- * back to the convective form while pressure boundaries are set.  A change invalidates Jacobian and preconditioner. */
+/* Weak form assembled by the generic element kernels.  CFDH_FORM_CONVECTIVE (default): the form of stabilized_schur.py:67-123.
+ * CFDH_FORM_ROTATIONAL: the curl-curl / rotational form of stabilized_schur_pressurebc.py:111-160, with omega = curl(u_mid) --
+ *   rho w_t . v + mu omega . curl(v) - p div v + rho (omega x u_mid) . v - rho/2 |u_mid|^2 div v - rho f . v + q div u_mid
+ *   + SUPG / PSPG / LSIC with the strong residual R = rho (w_t + omega x u_mid) + grad p - rho f (no viscous part).
+ * In gdim 2 omega = d_x u_y - d_y u_x is a scalar and omega x a = (-omega a_y, omega a_x).  The time scheme of
+ * cfdh_set_time_scheme applies as before.  Contexts: gdim 2 on the generic kernels, gdim 3 for CFDH_ELEM_P2 (tetrahedra) and
+ * CFDH_ELEM_Q1 (hexahedra).  CFDH_E_ARG on the closed-form P1 path (gdim 2: create the context with CFDH_ELEM_P1_GENERIC), for
+ * P1 tetrahedra in gdim 3 (closed-form or generic), on a part of a partitioned run, with an active backflow term (beta > 0), and
+ * when switching back to the convective form while pressure boundaries are set.  A change invalidates Jacobian and
+ * preconditioner. */
 enum { CFDH_FORM_CONVECTIVE = 0, CFDH_FORM_ROTATIONAL = 1 };
 int cfdh_set_formulation(cfdh_ctx *ctx, int form);
 /* Natural pressure boundaries of the rotational form (stabilized_schur_pressurebc.py:177-205): on the exterior facets whose marker
- * is markers[k] (k < n <= 8, distinct), with outward normal n, tangent t = (-n_y, n_x) and the owning cell's size h,
- *   + values[k] v . n  - mu omega(u_mid) (t . v) - mu omega(v) (t . u_mid) + (beta_nitsche mu / h) (t . u_mid)(t . v).
+ * is markers[k] (k < n <= 8, distinct), with outward normal n, w_T = w - (w . n) n, omega = curl(u_mid) and the owning cell's size
+ * h (largest vertex distance),
+ *   + values[k] v . n  - mu (omega x n) . v_T - mu (curl(v) x n) . u_mid_T + (beta_nitsche mu / h) u_mid_T . v_T;
+ * in gdim 2, with the tangent t = (-n_y, n_x): values[k] v . n - mu omega (t . v) - mu omega(v) (t . u_mid)
+ * + (beta_nitsche mu / h) (t . u_mid)(t . v).
  * values[k] enters the residual only (the caller passes the reference's halved values, e.g. p_inlet / 2).  The facets follow later
  * cfdh_set_facet_markers calls.  A call that changes only `values` keeps Jacobian and preconditioner valid (the per-step resistance
  * update of the vascular outlet); any other change invalidates both.  n = 0 removes the terms.  Requires CFDH_FORM_ROTATIONAL
