@@ -47,6 +47,7 @@ SYMBOLS = [
     "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_set_formulation", "cfdh_set_pressure_boundaries", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
+    "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner",
 ]
 
 
@@ -118,6 +119,11 @@ def lib():
     L.cfdh_profile_reset.argtypes = [vp]
     L.cfdh_info.argtypes = [vp, C.c_int]
     L.cfdh_info.restype = C.c_int64
+    L.cfdh_set_schur_pcd.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.cfdh_set_ksp_forcing.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.cfdh_get_newton_history.argtypes = [vp, ip, dp, dp, ip, dp]
+    L.cfdh_get_pcd_operator.argtypes = [vp, lp, ip, ip, dp, dp]
+    L.cfdh_apply_preconditioner.argtypes = [vp, dp, dp]
     _LIB = L
     return L
 
@@ -147,6 +153,9 @@ def _raise(code, msg):
 
 
 FORM_CONVECTIVE, FORM_ROTATIONAL = 0, 1  # cfdh_set_formulation
+PC_SELFP, PC_CAHOUET_CHABARD, PC_PCD = 0, 1, 2  # cfdh_options.pc_type
+# Eisenstat-Walker version 2 with PETSc's defaults: rtol_0, rtol_max, gamma, alpha, threshold (cfdh_set_ksp_forcing)
+EW_DEFAULTS = (0.3, 0.9, 1.0, (1.0 + 5.0 ** 0.5) / 2.0, 0.1)
 
 
 class Context:
@@ -382,6 +391,46 @@ class Context:
 
     def info(self, what):
         return int(self.L.cfdh_info(self.h, int(what)))
+
+    def set_schur_pcd(self, inlet_marker, outlet_marker, time_term=1):
+        """Operator data of the PCD Schur approximation (options.pc_type = 2): inlet facets of the Robin term, outlet facets of
+        A_p's Dirichlet rows, with (1) or without (0) the time term rho a0 / (theta dt) M in K."""
+        self._chk(self.L.cfdh_set_schur_pcd(self.h, int(inlet_marker), int(outlet_marker), int(time_term)))
+
+    def set_ksp_forcing(self, version=2, rtol_0=None, rtol_max=None, gamma=None, alpha=None, threshold=None):
+        """Eisenstat-Walker forcing of the linear tolerance: version 0 off, 2 PETSc's default variant (defaults EW_DEFAULTS)."""
+        a = [d if v is None else float(v) for v, d in zip((rtol_0, rtol_max, gamma, alpha, threshold), EW_DEFAULTS)]
+        self._chk(self.L.cfdh_set_ksp_forcing(self.h, int(version), *a))
+
+    def newton_history(self):
+        """Per Newton iteration of the last step: dict of |F|, the linear tolerance, FGMRES iterations, achieved true |r| / |b|."""
+        n = C.c_int32()
+        self._chk(self.L.cfdh_get_newton_history(self.h, C.byref(n), None, None, None, None))
+        fn, rt, rr = np.zeros(n.value), np.zeros(n.value), np.zeros(n.value)
+        its = np.zeros(n.value, dtype=np.int32)
+        self._chk(self.L.cfdh_get_newton_history(self.h, C.byref(n), _dp(fn), _dp(rt), _ip(its), _dp(rr)))
+        return {"fnorm": fn, "ksp_rtol": rt, "ksp_its": its, "ksp_rel_res": rr}
+
+    def get_pcd_operator(self):
+        """(K as scipy CSR [nvo x nv] at the current state, M_d [nvo])."""
+        import scipy.sparse as sp
+        nnz = C.c_int64()
+        self._chk(self.L.cfdh_get_pcd_operator(self.h, C.byref(nnz), None, None, None, None))
+        rowptr = np.empty(self.nvo + 1, dtype=np.int32)
+        col = np.empty(nnz.value, dtype=np.int32)
+        val = np.empty(nnz.value)
+        md = np.empty(self.nvo)
+        self._chk(self.L.cfdh_get_pcd_operator(self.h, C.byref(nnz), _ip(rowptr), _ip(col), _dp(val), _dp(md)))
+        return sp.csr_matrix((val, col, rowptr), shape=(self.nvo, self.nv)), md
+
+    def apply_preconditioner(self, r):
+        """z = P^-1 r with the current preconditioner on the assembled Jacobian (monolithic [u | p] vectors)."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.size != (self.dim + 1) * self.nv:
+            raise ValueError("monolithic vector of (gdim + 1) nv entries expected")
+        z = np.zeros_like(r)
+        self._chk(self.L.cfdh_apply_preconditioner(self.h, _dp(r), _dp(z)))
+        return z
 
 
 def rccl_unique_id():

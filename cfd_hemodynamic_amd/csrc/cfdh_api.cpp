@@ -411,6 +411,8 @@ int cfdh_set_facet_markers(cfdh_ctx *c, int64_t nfacets, const int32_t *markers)
     HIPCHK(c, c->d_fac_marker.upload(c->fac_marker, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  // the PCD operator's inlet facets and outlet rows follow the markers
+  if (c->pcd_set) { c->pcd_ready = false; c->pc_valid = false; }
   // the backflow term and the pressure boundaries follow the markers: refresh the per-cell flags (invalidates Jacobian and preconditioner)
   if (c->bf_marker >= 0 || !c->pb_markers.empty()) return upload_cell_facet_flags(c);
   return 0;
@@ -466,6 +468,93 @@ int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, con
   c->pb_markers.assign(markers, markers + n);
   c->pb_beta = beta_nitsche;
   return upload_cell_facet_flags(c);
+}
+
+int cfdh_set_schur_pcd(cfdh_ctx *c, int inlet_marker, int outlet_marker, int time_term) {
+  ENTER(c);
+  if (c->gen) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: PCD exists for P1 triangles and tetrahedra on the closed-form kernels only");
+  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: PCD is not available in partitioned runs");
+  if (time_term != 0 && time_term != 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: time_term must be 0 or 1");
+  const bool markers_changed = !c->pcd_set || inlet_marker != c->pcd_in || outlet_marker != c->pcd_out;
+  c->pcd_in = inlet_marker; c->pcd_out = outlet_marker; c->pcd_time = time_term;
+  c->pcd_set = true;
+  if (markers_changed) { c->pcd_ready = false; c->pc_valid = false; }
+  return 0;
+}
+
+int cfdh_set_ksp_forcing(cfdh_ctx *c, int version, double rtol_0, double rtol_max, double gamma, double alpha, double threshold) {
+  ENTER(c);
+  if (version != 0 && version != 2) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_ksp_forcing: version 0 (off) or 2");
+  if (version == 2 && !(rtol_0 > 0 && rtol_0 < 1 && rtol_max > 0 && rtol_max < 1 && gamma > 0 && gamma <= 1 && alpha > 1 && alpha <= 2 &&
+                        threshold > 0 && threshold < 1))
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_ksp_forcing: need 0 < rtol_0, rtol_max, threshold < 1, 0 < gamma <= 1, 1 < alpha <= 2");
+  c->ew_version = version;
+  if (version == 2) { c->ew_rtol0 = rtol_0; c->ew_rtol_max = rtol_max; c->ew_gamma = gamma; c->ew_alpha = alpha; c->ew_threshold = threshold; }
+  return 0;
+}
+
+int cfdh_get_newton_history(cfdh_ctx *c, int32_t *n, double *fnorm, double *ksp_rtol, int32_t *ksp_its, double *ksp_rel_res) {
+  if (!c || !n) return CFDH_E_ARG;
+  const size_t m = c->hist_fnorm.size();
+  *n = (int32_t)m;
+  for (size_t k = 0; k < m; k++) {
+    if (fnorm) fnorm[k] = c->hist_fnorm[k];
+    if (ksp_rtol) ksp_rtol[k] = c->hist_rtol[k];
+    if (ksp_its) ksp_its[k] = c->hist_its[k];
+    if (ksp_rel_res) ksp_rel_res[k] = c->hist_relres[k];
+  }
+  return 0;
+}
+
+int cfdh_get_pcd_operator(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *mass_diag) {
+  if (!c || !nnz) return CFDH_E_ARG;
+  ENTER(c);
+  *nnz = c->nnzv;
+  if (!rowptr && !col && !vals && !mass_diag) return 0;
+  if (!rowptr || !col || !vals) return cfdh_fail(c, CFDH_E_ARG, "pass all of rowptr/col/vals or none");
+  if (c->gen || c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_pcd_operator: P1 contexts on one GPU only");
+  if (!c->pcd_set) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_pcd_operator: cfdh_set_schur_pcd was not called");
+  if (!c->params_set || !c->state_set) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_pcd_operator: parameters and state are needed");
+  CHK(k_pcd_assemble(c, c->x.p));
+  std::vector<double> K(c->pcd_K.n);
+  std::vector<int> sptr(c->pcd_sptr.n);
+  HIPCHK(c, hipMemcpyAsync(K.data(), c->pcd_K.p, sizeof(double) * K.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(sptr.data(), c->pcd_sptr.p, sizeof(int) * sptr.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const int nvo = c->nvo;
+  int64_t pos = 0;
+  std::vector<std::pair<int, int>> ord;
+  for (int vu = 0; vu < nvo; vu++) {
+    const int r = c->perm[vu];
+    ord.clear();
+    for (int k = c->h_vptr[r]; k < c->h_vptr[r + 1]; k++) ord.push_back({c->iperm[c->h_vcol[k]], k - c->h_vptr[r]});
+    std::sort(ord.begin(), ord.end());
+    rowptr[vu] = (int32_t)pos;
+    const size_t base = (size_t)sptr[r >> 6] + (r & 63);
+    for (auto &e : ord) { col[pos] = e.first; vals[pos] = K[base + 64 * (size_t)e.second]; pos++; }
+  }
+  rowptr[nvo] = (int32_t)pos;
+  if (mass_diag) for (int vu = 0; vu < nvo; vu++) mass_diag[vu] = c->h_pcd_md[c->perm[vu]];
+  return 0;
+}
+
+int cfdh_apply_preconditioner(cfdh_ctx *c, const double *r, double *z) {
+  if (!c || !r || !z) return CFDH_E_ARG;
+  ENTER(c);
+  if (!c->jac_valid) return cfdh_fail(c, CFDH_E_STATE, "no Jacobian assembled yet");
+  CHK(cfdh_pc_update(c, false));
+  std::vector<double> h;
+  pack_vec(c, r, r + (size_t)c->dim * c->nv, h, nullptr);
+  CHK(upload_vec(c, h, c->xt.p));
+  CHK(cfdh_pc_apply(c, c->xt.p, c->dvec.p));
+  std::vector<double> o;
+  CHK(download_vec(c, c->dvec.p, o));
+  for (int k = 0; k < c->nvo; k++) {
+    const int v = c->iperm[k], d = c->dim;
+    for (int i = 0; i < d; i++) z[(size_t)d * v + i] = o[(size_t)d * k + i];
+    z[(size_t)d * c->nv + v] = o[(size_t)d * c->nvo + k];
+  }
+  return 0;
 }
 
 int cfdh_set_previous2(cfdh_ctx *c, const double *u_prev2) {
@@ -804,9 +893,9 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 1: return c->nv;
     case 2: return c->nc;
     case 3: return c->nnzv;
-    case 4: return c->opt.pc_type == 1 ? c->hL.fine_nnz : c->hS.fine_nnz;
+    case 4: return c->opt.pc_type >= 1 ? c->hL.fine_nnz : c->hS.fine_nnz;
     case 5: return c->ninc;
-    case 6: return (int64_t)(c->opt.pc_type == 1 ? c->hL.lev.size() : c->hS.lev.size());
+    case 6: return (int64_t)(c->opt.pc_type >= 1 ? c->hL.lev.size() : c->hS.lev.size());
     case 7: return c->nblk;
     case 8: return c->hA.fine_nnz;
     case 9: return c->gp_allgather ? c->gp_maxcnt : 0;
@@ -824,7 +913,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 40: case 41: case 42: case 43: case 44: case 45: case 46: case 47: case 48: case 49:
     case 50: case 51: case 52: case 53: case 54: case 55: case 56: case 57: case 58: case 59:
     case 60: case 61: case 62: case 63: case 64: case 65: case 66: case 67: case 68: case 69: {
-      const AmgHier &h = what < 50 ? c->hA : (c->opt.pc_type == 1 ? c->hL : c->hS);
+      const AmgHier &h = what < 50 ? c->hA : (c->opt.pc_type >= 1 ? c->hL : c->hS);
       const size_t l = (size_t)(what % 10);
       if (l >= h.lev.size()) return 0;
       return ((what / 10) & 1) ? (int64_t)h.lev[l]->n : (int64_t)h.lev[l]->A.nnz;
@@ -838,15 +927,17 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 75: return c->pc_valid ? 1 : 0;
     case 76: return c->singular;
     case 77: return c->form;
+    case 78: return c->opt.pc_type;   // Schur approximation in use: 0 SELFP, 1 Cahouet-Chabard, 2 PCD
+    case 79: return c->ew_version;    // Eisenstat-Walker forcing version (0: off)
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
-    case 19: return c->opt.pc_type == 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;
+    case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;
     case 20: return c->hA.nnz_S0;
-    case 21: return c->opt.pc_type == 1 ? c->hL.nnz_G0 : c->hS.nnz_G0;
+    case 21: return c->opt.pc_type >= 1 ? c->hL.nnz_G0 : c->hS.nnz_G0;
     case 22: return c->hA.nnz_G0;
-    case 23: { const AmgHier &h = c->opt.pc_type == 1 ? c->hL : c->hS; return h.lev.size() > 1 ? h.lev[1]->n : 0; }
+    case 23: { const AmgHier &h = c->opt.pc_type >= 1 ? c->hL : c->hS; return h.lev.size() > 1 ? h.lev[1]->n : 0; }
     case 24: return c->hA.lev.size() > 1 ? c->hA.lev[1]->n : 0;
-    case 25: { const AmgHier &h = c->opt.pc_type == 1 ? c->hL : c->hS; return h.fused ? 1 : 0; }
+    case 25: { const AmgHier &h = c->opt.pc_type >= 1 ? c->hL : c->hS; return h.fused ? 1 : 0; }
     default: return -1;
   }
 }

@@ -397,6 +397,24 @@ struct cfdh_ctx {
   long long n_allreduce = 0, n_halo = 0, n_host_sync = 0, n_krylov = 0, n_allgather = 0;
   long long n_attainable_stops = 0;  // FGMRES solves ended by the attainable-accuracy rule (cfdh_info 72), cumulative over the context's life
   long long n_pc_builds = 0;         // preconditioner (re)builds since cfdh_create (cfdh_info 74)
+
+  // pressure convection-diffusion Schur approximation (pc_type 2, cfdh_set_schur_pcd, cfdh_pcd.hip)
+  bool pcd_set = false, pcd_ready = false;  // operator data given / device structures built for the current markers
+  int pcd_in = -1, pcd_out = -1, pcd_time = 0;
+  double pcd_ct = 0;                         // time coefficient of K (rho a0 / (theta dt) or 0)
+  dbuf<int> pcd_iptr, pcd_inc, pcd_fptr, pcd_fac;  // row -> (cell, local) incidences / inlet facets (cfdh_pcd_setup)
+  dbuf<unsigned> pcd_islot, pcd_fslot;       // their row positions of the cell's vertices, 8 bits each
+  dbuf<int> pcd_sptr, pcd_scol, pcd_rlen;    // SELL-64 layout of the vertex graph (owned rows)
+  dbuf<double> pcd_K, pcd_mdinv, pcd_t, pcd_q;  // K (fp64, SELL), 1 / diag(M), t = r / m_d, epilogue values of the A_p Dirichlet rows
+  dbuf<float> pcd_Kf;                        // fp32 K M_d^-1 (columns scaled by 1 / m_d) streamed by the apply pass
+  dbuf<unsigned char> pcd_flag;              // bit 0: Dirichlet row of A_p, bit 1: pressure-Dirichlet row of the Jacobian
+  std::vector<double> h_pcd_md;              // diag(M), owned rows (internal numbering)
+  // Eisenstat-Walker forcing of the linear tolerance (cfdh_set_ksp_forcing) and the per-Newton-iteration record of the last step
+  int ew_version = 0;
+  double ew_rtol0 = 0.3, ew_rtol_max = 0.9, ew_gamma = 1.0, ew_alpha = 1.6180339887498949, ew_threshold = 0.1;
+  std::vector<double> hist_fnorm, hist_rtol, hist_relres;
+  std::vector<int> hist_its;
+  double ksp_last_relres = 0;                // true |r| / |b| at the end of the last cfdh_fgmres
 };
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
@@ -465,6 +483,11 @@ int cfdh_facet_nodes3(const cfdh_ctx *c, int f, int out[8]);  // local nodes of 
 int kg3_assemble(cfdh_ctx *c, const double *xstate, int mode);
 int kg3_functional_partials(cfdh_ctx *c, int kind, int marker, int nb);
 int kg3_wss(cfdh_ctx *c, double *out);
+
+// ---- pressure convection-diffusion Schur approximation (cfdh_pcd.hip) -----------------------------------
+int cfdh_pcd_setup(cfdh_ctx *c);                       // incidences, inlet facets, SELL layout, 1 / diag(M)
+int k_pcd_assemble(cfdh_ctx *c, const double *xstate);  // K at the iterate xstate
+int k_pcd_apply(cfdh_ctx *c, const double *r, double *s);  // t = r / m_d, s = K t, q
 
 // ---- kernels (cfdh_kernels.hip) ----------------------------------------------------
 void prof_begin(cfdh_ctx *c, int kind);

@@ -109,6 +109,27 @@ static void mark_outflow_nodes(const cfdh_ctx *c, std::vector<unsigned char> &pb
   }
 }
 
+// pc_type 2: the Dirichlet rows of the PCD operator's A_p -- every vertex of a facet marked as the outlet (bcs_pcd of
+// stabilized_pcd.py:215-218, PCDPC_vY) -- as bit 1, next to the pressure-Dirichlet bit 0.  The same array gives the flags of the
+// apply pass (bit 0: Dirichlet row of A_p, bit 1: pressure-Dirichlet row of the Jacobian).
+static void mark_pcd_outlet(const cfdh_ctx *c, std::vector<unsigned char> &pbc) {
+  const int n1 = c->dim + 1;
+  for (int k = 0; k < c->nfac; k++) {
+    if (c->fac_marker[k] != c->pcd_out) continue;
+    const int e = c->fac_cell[k], fl = c->fac_local[k];
+    for (int q = 0; q < n1; q++) {
+      const int v = c->h_cells[(size_t)n1 * e + q];
+      if (q != fl && v < c->nvo) pbc[v] |= 2;
+    }
+  }
+}
+static int upload_pcd_flags(cfdh_ctx *c, const std::vector<unsigned char> &pbc) {
+  std::vector<unsigned char> fl(pbc.size());
+  for (size_t i = 0; i < pbc.size(); i++) fl[i] = (unsigned char)((pbc[i] ? 1u : 0u) | ((pbc[i] & 1u) ? 2u : 0u));
+  HIPCHK(c, c->pcd_flag.upload(fl, c->stream));
+  return 0;
+}
+
 // pc_type 1 -- host side of the Cahouet-Chabard-type preconditioner (all rank-local, owned x owned):
 //   * hA : SA hierarchy of the scalar proxy (A00_xx + A00_yy)/2 of the velocity block, applied to both
 //          components at once (the xy coupling of the symmetric-gradient term is dropped: Korn-equivalent);
@@ -289,7 +310,10 @@ static int build_cc_host(cfdh_ctx *c) {
   std::vector<unsigned char> pbc(nvo);
   const unsigned pbit = 1u << c->dim;  // bits 0..dim-1: velocity components, bit dim: pressure
   for (int i = 0; i < nvo; i++) pbc[i] = (c->h_bcflag[i] & pbit) ? 1 : 0;
-  if (!c->ds_terms || c->form == CFDH_FORM_ROTATIONAL) mark_outflow_nodes(c, pbc);
+  const bool pcd = c->opt.pc_type == 2;  // PCD: the same velocity and pressure-Laplacian hierarchies, A_p's own Dirichlet set, no H
+  if (pcd) mark_pcd_outlet(c, pbc);
+  else if (!c->ds_terms || c->form == CFDH_FORM_ROTATIONAL) mark_outflow_nodes(c, pbc);
+  if (pcd) CHK(upload_pcd_flags(c, pbc));
   if (!c->hL.valid || c->hL_pbc != pbc || c->hL_singular != c->singular) {
     CsrHost Lh;
     Lh.n = Lh.m = nvo;
@@ -316,6 +340,7 @@ static int build_cc_host(cfdh_ctx *c) {
     HIPCHK(c, c->ccPbc.upload(pbc, c->stream));
   }
   CHK(build_global_pressure(c));
+  if (pcd) { HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
   // --- H
   c->cc_alpha = c->rho * c->ts_a[0] / (c->ts_theta * c->dt);  // = 2 rho/dt for the midpoint scheme
   c->cc_beta = c->mu;
@@ -407,7 +432,10 @@ static int build_cc_dev(cfdh_ctx *c) {
   std::vector<unsigned char> pbc(nvo);
   const unsigned pbit = 1u << c->dim;
   for (int i = 0; i < nvo; i++) pbc[i] = (c->h_bcflag[i] & pbit) ? 1 : 0;
-  if (!c->ds_terms || c->form == CFDH_FORM_ROTATIONAL) mark_outflow_nodes(c, pbc);
+  const bool pcd = c->opt.pc_type == 2;
+  if (pcd) mark_pcd_outlet(c, pbc);
+  else if (!c->ds_terms || c->form == CFDH_FORM_ROTATIONAL) mark_outflow_nodes(c, pbc);
+  if (pcd) CHK(upload_pcd_flags(c, pbc));
   if (!c->hL.valid || c->hL_pbc != pbc || c->hL_singular != c->singular) {
     CsrHost Lh;
     Lh.n = Lh.m = nvo;
@@ -441,6 +469,11 @@ static int build_cc_dev(cfdh_ctx *c) {
   }
   if (multi) CHK(build_global_pressure(c));
   const double t2 = wall_ms();
+  if (pcd) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ms_pc_build_dev = wall_ms() - t0;
+    return 0;
+  }
   c->cc_alpha = c->rho * c->ts_a[0] / (c->ts_theta * c->dt);
   c->cc_beta = c->mu;
   {
@@ -475,8 +508,14 @@ static int build_cc(cfdh_ctx *c) {
 // hierarchy only when asked (lagged preconditioner)
 int cfdh_pc_update(cfdh_ctx *c, bool refresh_amg) {
   const int nu = c->dim * c->nvo;
-  if (c->dim == 3 && c->opt.pc_type != 1) return cfdh_fail(c, CFDH_E_ARG, "tetrahedral contexts support pc_type 1 only");
-  if (c->opt.pc_type == 1) {
+  if (c->opt.pc_type == 2) {
+    if (c->gen) return cfdh_fail(c, CFDH_E_ARG, "pc_type 2 (PCD) exists for P1 triangles and tetrahedra on the closed-form kernels only");
+    if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "pc_type 2 (PCD) is not available in partitioned runs");
+    if (!c->pcd_set) return cfdh_fail(c, CFDH_E_STATE, "pc_type 2 (PCD) needs cfdh_set_schur_pcd");
+  } else if (c->dim == 3 && c->opt.pc_type != 1) {
+    return cfdh_fail(c, CFDH_E_ARG, "tetrahedral contexts support pc_type 1 and 2 only");
+  }
+  if (c->opt.pc_type == 1 || c->opt.pc_type == 2) {
     if (refresh_amg || !c->pc_valid) {
       c->pc_graph_valid = false;
       CHK(build_cc(c));
@@ -486,6 +525,8 @@ int cfdh_pc_update(cfdh_ctx *c, bool refresh_amg) {
       c->last_stats.pc_refreshes++;
     c->n_pc_builds++;
     }
+    // PCD: K follows the iterate -- assembled once per Newton iteration (fenicsx_pctools reassembles K_p in every PC set-up)
+    if (c->opt.pc_type == 2) CHK(k_pcd_assemble(c, c->x.p));
     return 0;
   }
   CHK(k_extract_diag(c));
@@ -532,12 +573,63 @@ static bool ras_ghost_rhs() {
 //   stage 2: t = V(L) y ; z_p = a' t + b' zH                      | halo(z_p)
 //   stage 3: z_u = V(A00~)(r_u - A01 z_p)
 // With one rank (no exchanges) all stages run back to back; each stage is graph-capturable.
+// pc_type 2 (one rank): the stages of pc_type 1 with the PCD action in place of the Cahouet-Chabard one
+//   stage 1: t = M_d^-1 t_p, s = K t (0 on the Dirichlet rows of A_p)
+//   stage 2: y = V(A_p) s ; z_p = mu t + y (epilogue of the cycle's last kernel; r_p on pressure-Dirichlet rows, mu t on the outlet rows)
+static int pcd_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
+  const int nvo = c->nvo, nu = c->dim * nvo;
+  const double *ru = r, *rp = r + nu;
+  double *zu = z, *zp = z + nu;
+  const bool upper = c->opt.schur_full == 2;
+  switch (stage) {
+    case 0:
+      if (!upper) CHK(k_amg_vcycle(c, c->hA, ru, c->pu0.p));
+      return 0;
+    case 1:
+      if (!upper) CHK(k_spmv_block(c, 3, c->pu0.p, c->pp0.p, rp, 0));   // t_p = r_p - A10 y_u
+      return k_pcd_apply(c, upper ? rp : c->pp0.p, c->pu1.p);
+    case 2: {
+      // CFDH_L_CYCLES = k > 1: k V-cycles on A_p (stationary iteration), as for pc_type 1 -- the converged A_p solve of the tests
+      static const int lcycles = getenv("CFDH_L_CYCLES") ? atoi(getenv("CFDH_L_CYCLES")) : 1;
+      if (lcycles > 1 && c->hL.lev.size() >= 1 && c->hL.lev[0]->A.val.p) {
+        AmgLevel *L0 = c->hL.lev[0];
+        CHK(k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p));
+        for (int cyc = 1; cyc < lcycles; cyc++) {
+          CHK(k_csr_spmv(c, L0->A, c->pu2.p, L0->r.p, 1, c->pu1.p));
+          CHK(k_amg_vcycle(c, c->hL, L0->r.p, L0->d0.p));
+          CHK(v_axpy(c, nvo, 1.0, L0->d0.p, c->pu2.p));
+        }
+        return k_cc_combine(c, nvo, 1.0, c->mu, c->pu2.p, c->pcd_t.p, c->pcd_q.p, c->pcd_flag.p, zp);
+      }
+      c->epi.on = true; c->epi.done = false;
+      c->epi.alpha = 1.0; c->epi.beta = c->mu; c->epi.zH = c->pcd_t.p; c->epi.r = c->pcd_q.p;
+      c->epi.pbc = c->pcd_flag.p; c->epi.out = zp;
+      const int rc = k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p);
+      c->epi.on = false;
+      CHK(rc);
+      if (c->epi.done) { c->epi.done = false; return 0; }
+      return k_cc_combine(c, nvo, 1.0, c->mu, c->pu2.p, c->pcd_t.p, c->pcd_q.p, c->pcd_flag.p, zp);
+    }
+    case 3:
+      if (c->opt.schur_full) {
+        CHK(k_spmv_block(c, 2, zp, c->pu0.p, ru, 0));   // t_u = r_u - A01 z_p
+        CHK(k_amg_vcycle(c, c->hA, c->pu0.p, zu));
+      } else {
+        CHK(v_copy(c, nu, c->pu0.p, zu));
+      }
+      return 0;
+    default:
+      return 0;
+  }
+}
+
 static int pc_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
   const int nvo = c->nvo, nu = c->dim * nvo;
   const double *ru = r, *rp = r + nu;
   double *zu = z, *zp = z + nu;
   const bool multi = c->nranks > 1;
   const bool global_p = c->gp_n > 0 && multi;
+  if (c->opt.pc_type == 2) return pcd_stage(c, r, z, stage);
   if (c->opt.pc_type == 1) {
     const bool upper = c->opt.schur_full == 2;  // block upper-triangular: z_p = S^-1 r_p, z_u = A^-1 (r_u - A01 z_p)
     // logical stages: 0 first velocity cycle, 1 H solve, 2 pressure cycle, 3 coupling product, 4 overlapping velocity
@@ -918,6 +1010,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
   CHK(v_zero(c, c->NL, x));
   if (!(bn >= 0.0)) CHK(v_norm2(c, n, b, &bn));
   int its = 0, reason = 0;
+  c->ksp_last_relres = bn == 0.0 ? 0.0 : 1.0;
   if (!std::isfinite(bn)) { *its_out = 0; *reason_out = -9; return 0; }
   if (bn == 0.0) { *its_out = 0; *reason_out = 2; return 0; }
   const double tol = std::max(o.ksp_rtol * bn, o.ksp_atol);
@@ -966,6 +1059,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
         if (!(diff <= 1e-10 * bn)) return cfdh_fail(c, CFDH_E_STATE, "projected guess: |(b - J x0) - (b - W y)| = %.3e |b|", diff / bn);
       }
       CHK(v_norm2(c, n, V, &beta));
+      c->ksp_last_relres = beta / bn;
       if (guessed && its == 0 && j_prev == 0) {
         c->n_guess_solves++; c->guess_reduction_sum += beta / bn;
         if (o.verbose) fprintf(stderr, "[cfdh]     projected guess (newton %d, %d vectors): |r0| / |b| = %.3e\n", c->guess_slot, c->guess_cnt[c->guess_slot], beta / bn);
@@ -1013,6 +1107,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
       }
       beta_start = beta;
     }
+    c->ksp_last_relres = beta / bn;  // true residual (r0 = b on the first pass)
     if (beta <= tol) { reason = 2; break; }
     if (its >= o.ksp_max_it) { reason = -3; break; }
     if (!std::isfinite(beta)) { reason = -9; break; }
@@ -1280,6 +1375,11 @@ int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st) {
   bool jac_current = true;
   double fn_before = 0.0;
   CHK(guess_ensure(c));
+  c->hist_fnorm.clear(); c->hist_rtol.clear(); c->hist_its.clear(); c->hist_relres.clear();
+  // Eisenstat-Walker forcing (cfdh_set_ksp_forcing): the tolerance of each solve is set here and handed to cfdh_fgmres through
+  // c->opt.ksp_rtol, which is restored on every way out of the step
+  struct RtolGuard { cfdh_options &o; double v; ~RtolGuard() { o.ksp_rtol = v; } } rtol_guard{c->opt, c->opt.ksp_rtol};
+  double ew_rtol_prev = 0.0, ew_fn_prev = 0.0;
   for (int it = 0;; it++) {
     if (o.verbose) fprintf(stderr, "[cfdh]   newton %d |F| = %.6e\n", it, fn);
     if (!std::isfinite(fn)) { reason = CFDH_DIVERGED_FNORM_NAN; break; }
@@ -1300,19 +1400,37 @@ int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st) {
     st->ms_pc_setup += wall_ms() - t0;
     t0 = wall_ms();
     int kits = 0, kreason = 0;
+    if (c->ew_version == 2) {
+      // PETSc's SNESKSPEW version 2: rtol_0 first; then gamma (|F_k| / |F_k-1|)^alpha, raised to gamma rtol_k-1^alpha when that
+      // exceeds the threshold; capped at rtol_max
+      double rt = c->ew_rtol0;
+      if (it > 0) {
+        rt = c->ew_gamma * std::pow(fn / ew_fn_prev, c->ew_alpha);
+        const double stol = c->ew_gamma * std::pow(ew_rtol_prev, c->ew_alpha);
+        if (stol > c->ew_threshold) rt = std::max(rt, stol);
+        rt = std::min(rt, c->ew_rtol_max);
+      }
+      c->opt.ksp_rtol = rt;
+      ew_rtol_prev = rt;
+      ew_fn_prev = fn;
+    }
     c->guess_slot = it;
     if (it < cfdh_ctx::GUESS_NEWTON) {
       c->guess_stored[it] = false;
       if (c->guessX.p) CHK(v_copy(c, n, x, c->guessX.p + (size_t)it * (((size_t)c->NL + 1) & ~(size_t)1)));
     }
     CHK(cfdh_fgmres(c, c->F.p, d, &kits, &kreason, fn));
+    int kits_failed = 0;
     if (kreason < 0 && c->pc_its_ref > 0) {
       // a lagged hierarchy that stopped working: rebuild once and retry
       CHK(cfdh_pc_update(c, true));
       st->krylov_its += kits;
+      kits_failed = kits;
       CHK(cfdh_fgmres(c, c->F.p, d, &kits, &kreason, fn));
     }
     c->guess_slot = -1;
+    c->hist_fnorm.push_back(fn); c->hist_rtol.push_back(c->opt.ksp_rtol); c->hist_its.push_back(kits_failed + kits);
+    c->hist_relres.push_back(c->ksp_last_relres);
     st->krylov_its += kits;
     st->ms_solve += wall_ms() - t0;
     if (kreason < 0) { reason = CFDH_DIVERGED_LINEAR_SOLVE; cfdh_fail(c, CFDH_E_DIVERGED, "FGMRES failed (reason %d) after %d iterations", kreason, kits); break; }

@@ -30,7 +30,7 @@
  * Dimension: gdim = 2 (triangles) or 3 (tetrahedra,
  * /root/reference/src/scenarios/simple_bifurcation.py, scenario_factory.py:47-49)
  * is fixed at cfdh_create; "d" below stands for it.  Tetrahedral contexts are
- * single-GPU in this version (cfdh_set_halo returns CFDH_E_ARG) and use pc_type 1.
+ * single-GPU in this version (cfdh_set_halo returns CFDH_E_ARG) and use pc_type 1 or 2.
  */
 #ifndef CFDH_H
 #define CFDH_H
@@ -99,7 +99,8 @@ typedef struct cfdh_options {
   int32_t remove_p_mean;    /* nullsp.remove(x_n), stabilized_schur.py:319 */
   int32_t verbose;
   int32_t pc_type;          /* 0: SELFP Schur matrix + Chebyshev(A00) (the reference's SELFP, :235);
-                             * 1: Cahouet-Chabard Schur approximation + AMG(A00) (mesh-independent) */
+                             * 1: Cahouet-Chabard Schur approximation + AMG(A00) (mesh-independent);
+                             * 2: pressure convection-diffusion (PCD) Schur approximation + AMG(A00), cfdh_set_schur_pcd */
   int32_t cc_smooth_degree; /* pc_type 1: Chebyshev steps on the mass-like operator H (default 2) */
   int32_t ksp_guess;        /* initial guess of the linear solves (PETSc: KSPGuess, -ksp_guess_type fischer): for each Newton index the
                              * corrections of the last ksp_guess time steps are kept (at the end of a step: iterate minus converged
@@ -246,6 +247,40 @@ int cfdh_set_formulation(cfdh_ctx *ctx, int form);
  * takes Dirichlet rows on every exterior facet that is not fully velocity-constrained, the pressure boundaries among them. */
 int cfdh_set_pressure_boundaries(cfdh_ctx *ctx, int n, const int32_t *markers, const double *values, double beta_nitsche);
 
+/* ---- pressure convection-diffusion preconditioner and forcing (the `stabilized_pcd` variant) ---------------- */
+
+/* Data of the PCD Schur approximation selected by cfdh_options.pc_type = 2 (fenicsx_pctools.pc.PCDPC_vY of
+ * /root/reference/src/solvers/stabilized_pcd.py:204-276, restated -- DESIGN.md section 9).  With theta, a0 of cfdh_set_time_scheme,
+ * w = theta u + (1 - theta) u_prev at the current Newton iterate and the P1 pressure basis phi:
+ *   M_d = diagonal of the consistent P1 mass matrix (the reference's Jacobi on M_p, :273-274);
+ *   K   = rho N(w) - rho R_in(w) + c_t M,  N_ij = int phi_i (w . grad phi_j) dx,  R_in,ij = int_{inlet} (w . n) phi_i phi_j ds over the
+ *         exterior facets whose marker is inlet_marker (ds_in, :220-231), M the consistent mass, c_t = rho a0 / (theta dt) when
+ *         time_term = 1, 0 when time_term = 0 (the reference's literal operator);
+ *   A_p = the P1 pressure Laplacian with Dirichlet rows on every vertex of a facet marked outlet_marker (bcs_pcd, :215-218) and on
+ *         the pressure-Dirichlet vertices, applied as one AMG V-cycle (the reference: CG + hypre, :275-276);
+ *   z_p = mu t + y,  t = M_d^-1 r_p,  s = K t (0 on the Dirichlet rows of A_p),  y = A_p^-1 s (0 on those rows);  z_p = r_p on the
+ *         pressure-Dirichlet rows of the Jacobian.
+ * In this library's convention S = A11 - A10 A00^-1 A01 is positive; the reference's -(I + A_p^-1 K_p) M_p^-1 with K_p = K / mu (no
+ * time term) differs by the factor -1/mu.  K is assembled from the current iterate in every preconditioner update, once per Newton
+ * iteration.  P1 triangles and tetrahedra on one GPU (cfdh_create): CFDH_E_ARG on generic-element contexts (CFDH_ELEM_P2*, Q1*,
+ * P1_GENERIC) and on parts of a partitioned run; pc_type 2 without this call fails with CFDH_E_STATE at the solve. */
+int cfdh_set_schur_pcd(cfdh_ctx *ctx, int inlet_marker, int outlet_marker, int time_term);
+/* Eisenstat-Walker forcing of the linear tolerance (snes_ksp_ew, stabilized_pcd.py:249).  version 0: off (default; ksp_rtol of
+ * cfdh_options for every solve).  version 2 (PETSc's default variant; its defaults 0.3, 0.9, 1.0, (1 + sqrt 5)/2, 0.1): the first
+ * solve of a step uses rtol_0; after that rtol_k = gamma (|F_k| / |F_k-1|)^alpha, raised to gamma rtol_k-1^alpha when that exceeds
+ * threshold, then capped at rtol_max.  ksp_atol and ksp_max_it keep their meaning. */
+int cfdh_set_ksp_forcing(cfdh_ctx *ctx, int version, double rtol_0, double rtol_max, double gamma, double alpha, double threshold);
+/* Per Newton iteration of the last cfdh_solve_step: |F| at the iterate, the linear tolerance used, the FGMRES iterations (a solve
+ * retried after a hierarchy rebuild counts both attempts) and the achieved true |r| / |b| of the accepted solve.  *n receives the count; arrays may be NULL (query) or hold *n entries. */
+int cfdh_get_newton_history(cfdh_ctx *ctx, int32_t *n, double *fnorm, double *ksp_rtol, int32_t *ksp_its, double *ksp_rel_res);
+/* K of cfdh_set_schur_pcd, assembled from the current state (cfdh_set_state), as CSR of the owned rows in user numbering (columns
+ * ascending), and M_d (mass_diag[nv_owned], may be NULL).  Query convention of cfdh_get_csr (nnz first with rowptr = col = vals =
+ * NULL).  Exposed for parity tests, like cfdh_spmv. */
+int cfdh_get_pcd_operator(cfdh_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *mass_diag);
+/* z = P^-1 r with the current preconditioner (built, and for pc_type 2 with K assembled, at the current state when needed) on the
+ * assembled Jacobian; r, z monolithic [gdim*nv | nv] as for cfdh_spmv.  Exposed for parity tests. */
+int cfdh_apply_preconditioner(cfdh_ctx *ctx, const double *r, double *z);
+
 /* u_prev2 (stabilized_schur_bdf2.py:72): upload / download; nv local vertices x gdim */
 int cfdh_set_previous2(cfdh_ctx *ctx, const double *u_prev2);
 int cfdh_get_previous2(cfdh_ctx *ctx, double *u_prev2);
@@ -319,7 +354,7 @@ int cfdh_comm_set_callbacks(cfdh_ctx *ctx, cfdh_allreduce_fn ar, cfdh_exchange_f
 /* ---- measurement ------------------------------------------------------------ */
 
 /* HIP-event timing of the hot kernels on the library's stream.
- * kind 0: fused residual+Jacobian assembly, 1: monolithic SpMV, 2: tau moments,
+ * kind 0: fused residual+Jacobian assembly, 1: monolithic SpMV, 2: tau moments, 10: PCD K assembly, 11: PCD apply pass,
  * 3: A00 SpMV (Chebyshev sweep, pc_type 0), 4: level-0 up-sweep of the pressure hierarchy (x = Sb b + Sc x_c; a
  * Jacobi sweep of the unfused cycle), 5: the same for the velocity hierarchy (two right-hand sides),
  * 8 / 9: level-0 down-sweep (b_c = G b) of the pressure / velocity hierarchy,
@@ -341,7 +376,8 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 30 + l / 40 + l: rows / entries of level l of the velocity hierarchy, 50 + l / 60 + l: of the pressure hierarchy (l < 10, 0 past the end);
  * 70: linear solves that started from a projected initial guess (cfdh_options.ksp_guess), 71: their mean |r0| / |b| in units of 1e-6;
  * 74: preconditioner builds since cfdh_create, 75: 1 while the preconditioner is valid (built, not invalidated since), 76: 1 when the
- * last null-space test of cfdh_solve_step found the constant pressure in the null space of the Jacobian, 77: formulation (CFDH_FORM_*) */
+ * last null-space test of cfdh_solve_step found the constant pressure in the null space of the Jacobian, 77: formulation (CFDH_FORM_*),
+ * 78: Schur approximation in use (cfdh_options.pc_type: 0 SELFP, 1 Cahouet-Chabard, 2 PCD), 79: Eisenstat-Walker forcing version */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
