@@ -36,6 +36,13 @@ class Stats(C.Structure):
     ]
 
 
+class IpcsStats(C.Structure):
+    _fields_ = [
+        ("its", C.c_int32 * 3), ("reason", C.c_int32 * 3), ("rel_res", C.c_double * 3), ("ms_assemble", C.c_double),
+        ("ms_solve", C.c_double * 3), ("ms_total", C.c_double), ("launches", C.c_int32), ("host_syncs", C.c_int32),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, C.c_int, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, dp)
 
@@ -48,6 +55,8 @@ SYMBOLS = [
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner",
+    "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
+    "cfdh_ipcs_apply_pressure_pc",
 ]
 
 
@@ -124,6 +133,13 @@ def lib():
     L.cfdh_get_newton_history.argtypes = [vp, ip, dp, dp, ip, dp]
     L.cfdh_get_pcd_operator.argtypes = [vp, lp, ip, ip, dp, dp]
     L.cfdh_apply_preconditioner.argtypes = [vp, dp, dp]
+    L.cfdh_create_ipcs.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, ip, dp, C.c_int64, ip, ip, ip]
+    L.cfdh_ipcs_set_form.argtypes = [vp, C.c_double, C.c_double]
+    L.cfdh_ipcs_set_tolerances.argtypes = [vp, dp, C.c_double, ip]
+    L.cfdh_ipcs_step.argtypes = [vp, C.POINTER(IpcsStats)]
+    L.cfdh_ipcs_get_operator.argtypes = [vp, C.c_int, lp, ip, ip, dp]
+    L.cfdh_ipcs_get_intermediate.argtypes = [vp, C.c_int, dp]
+    L.cfdh_ipcs_apply_pressure_pc.argtypes = [vp, dp, dp]
     _LIB = L
     return L
 
@@ -430,6 +446,102 @@ class Context:
             raise ValueError("monolithic vector of (gdim + 1) nv entries expected")
         z = np.zeros_like(r)
         self._chk(self.L.cfdh_apply_preconditioner(self.h, _dp(r), _dp(z)))
+        return z
+
+
+class IpcsContext(Context):
+    """Owner of a cfdh_ctx made by cfdh_create_ipcs: the incremental pressure-correction scheme on P2/P1 triangles or tetrahedra.
+    `x`, `cells`: the P2 node mesh (elements.NodeMesh / NodeMesh3D: vertices first), `nvert`: number of vertices (= pressure dofs).
+    Velocity arrays have nn * gdim entries, pressure arrays nvert."""
+
+    def __init__(self, x, cells, nvert, facet_cells, facet_local, facet_marker, device=0):
+        L = lib()
+        self.L = L
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        if cells.ndim != 2 or cells.shape[1] not in (6, 10):
+            raise ValueError("cells must list the 6 nodes of P2 triangles or the 10 nodes of P2 tetrahedra")
+        self.dim = 2 if cells.shape[1] == 6 else 3
+        self.etype = 1
+        self.x = np.ascontiguousarray(np.asarray(x, dtype=np.float64)[:, : self.dim]).copy()
+        self.cells = cells
+        self.nv = self.nvo = len(self.x)
+        self.nvert = int(nvert)
+        fc = np.ascontiguousarray(facet_cells, dtype=np.int32)
+        fl = np.ascontiguousarray(facet_local, dtype=np.int32)
+        fm = np.ascontiguousarray(facet_marker, dtype=np.int32)
+        h = C.c_void_p()
+        rc = L.cfdh_create_ipcs(C.byref(h), int(device), self.dim, self.nv, self.nvert, len(cells), _ip(cells), _dp(self.x), len(fc), _ip(fc), _ip(fl),
+                                _ip(fm))
+        if rc != 0:
+            _raise(rc, "cfdh_create_ipcs failed: " + L.cfdh_last_error(None).decode())
+        self.h = h
+        self._cb = None
+
+    def set_state(self, u_prev=None, p_prev=None, u=None, p=None):
+        a = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (u_prev, p_prev, u, p)]
+        for v, n in zip(a, (self.dim * self.nv, self.nvert, self.dim * self.nv, self.nvert)):
+            if v is not None and v.size != n:
+                raise ValueError("state array has wrong size")
+        self._chk(self.L.cfdh_set_state(self.h, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3])))
+
+    def get_solution(self, u=None, p=None):
+        u = np.empty(self.dim * self.nv) if u is None else u
+        p = np.empty(self.nvert) if p is None else p
+        self._chk(self.L.cfdh_get_solution(self.h, _dp(u), _dp(p)))
+        return u, p
+
+    def get_previous(self, u=None, p=None):
+        u = np.empty(self.dim * self.nv) if u is None else u
+        p = np.empty(self.nvert) if p is None else p
+        self._chk(self.L.cfdh_get_previous(self.h, _dp(u), _dp(p)))
+        return u, p
+
+    def set_form(self, conv_coeff, force_coeff):
+        """Coefficients c (convection) and s_f (force) of the scheme; the context's default is (rho, +rho)."""
+        self._chk(self.L.cfdh_ipcs_set_form(self.h, float(conv_coeff), float(force_coeff)))
+
+    def set_tolerances(self, rtol=(1e-5, 1e-5, 1e-5), atol=1e-50, max_it=(10000, 10000, 10000)):
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rtol, dtype=np.float64), (3,)))
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(max_it, dtype=np.int32), (3,)))
+        self._chk(self.L.cfdh_ipcs_set_tolerances(self.h, _dp(r), float(atol), _ip(m)))
+
+    def step(self):
+        st = IpcsStats()
+        rc = self.L.cfdh_ipcs_step(self.h, C.byref(st))
+        if rc != 0:
+            msg = self.L.cfdh_last_error(self.h).decode()
+            if rc == -4:
+                bad = [r for r in st.reason if r <= 0]
+                raise RuntimeError("Did not converge, reason: %d. (%s)" % (bad[0] if bad else 0, msg))
+            _raise(rc, msg)
+        return st
+
+    def get_operator(self, which):
+        """scipy CSR: 0 A1 (Dirichlet treatment included), 1 L, 2 rho M, 3.. B_d, 3 + gdim.. G_d."""
+        import scipy.sparse as sp
+        nnz = C.c_int64()
+        self._chk(self.L.cfdh_ipcs_get_operator(self.h, int(which), C.byref(nnz), None, None, None))
+        d = self.dim
+        shape = (self.nvert, self.nvert) if which == 1 else (self.nv, self.nv) if which < 3 else (self.nvert, self.nv) if which < 3 + d \
+            else (self.nv, self.nvert)
+        rowptr = np.empty(shape[0] + 1, dtype=np.int32)
+        col = np.empty(nnz.value, dtype=np.int32)
+        val = np.empty(nnz.value)
+        self._chk(self.L.cfdh_ipcs_get_operator(self.h, int(which), C.byref(nnz), _ip(rowptr), _ip(col), _dp(val)))
+        return sp.csr_matrix((val, col, rowptr), shape=shape)
+
+    def get_intermediate(self, which):
+        """0 u*, 1 phi, 2 b1, 3 b2, 4 b3 of the last step / assembly."""
+        out = np.empty(self.nvert if which in (1, 3) else self.dim * self.nv)
+        self._chk(self.L.cfdh_ipcs_get_intermediate(self.h, int(which), _dp(out)))
+        return out
+
+    def apply_pressure_pc(self, r):
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.size != self.nvert:
+            raise ValueError("one value per vertex expected")
+        z = np.zeros_like(r)
+        self._chk(self.L.cfdh_ipcs_apply_pressure_pc(self.h, _dp(r), _dp(z)))
         return z
 
 

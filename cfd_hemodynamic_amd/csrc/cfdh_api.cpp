@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_ipcs.hpp"
 
 std::string g_cfdh_last_error;
 
@@ -17,6 +18,38 @@ int cfdh_prepare_assembly(cfdh_ctx *c);
     if (!(c)) return CFDH_E_ARG;         \
     (void)hipSetDevice((c)->device);     \
   } while (0)
+
+// entry points of the Newton solvers on a context of cfdh_create_ipcs, and the reverse
+#define NOT_IPCS(c, name)                                                                                                    \
+  do {                                                                                                                       \
+    if ((c) && (c)->ipcs) return cfdh_fail((c), CFDH_E_STATE, name ": not available on an incremental pressure-correction context (cfdh_create_ipcs)"); \
+  } while (0)
+#define NEED_IPCS(c, name)                                                                                         \
+  do {                                                                                                             \
+    if (!(c)) return CFDH_E_ARG;                                                                                   \
+    if (!(c)->ipcs) return cfdh_fail((c), CFDH_E_STATE, name ": the context was not created by cfdh_create_ipcs"); \
+    (void)hipSetDevice((c)->device);                                                                               \
+  } while (0)
+
+// whole-field host <-> device copies of an IPCS context (caller's numbering: no permutation); NULL keeps the device copy
+static int ipcs_put(cfdh_ctx *c, dbuf<double> &dst, const double *src) {
+  if (!src) return 0;
+  c->ipcs->n_field_copies++;
+  HIPCHK(c, hipMemcpyAsync(dst.p, src, sizeof(double) * dst.n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+static int ipcs_get(cfdh_ctx *c, const dbuf<double> &src, double *dst) {
+  if (!dst) return 0;
+  c->ipcs->n_field_copies++;
+  HIPCHK(c, hipMemcpyAsync(dst, src.p, sizeof(double) * src.n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+static int ipcs_copy(cfdh_ctx *c, const dbuf<double> &src, dbuf<double> &dst) {
+  HIPCHK(c, hipMemcpyAsync(dst.p, src.p, sizeof(double) * src.n, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
 
 extern "C" {
 
@@ -112,6 +145,7 @@ void cfdh_destroy(cfdh_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  cfdh_ipcs_free(c);
   comm_finalize(c);
   c->hS.clear(); c->hL.clear(); c->hA.clear(); c->hLg.clear();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -135,6 +169,7 @@ int cfdh_set_params(cfdh_ctx *c, double dt, double rho, double mu, double mu_fac
   c->f[0] = f ? f[0] : 0.0; c->f[1] = f ? f[1] : 0.0; c->f[2] = (f && c->dim == 3) ? f[2] : 0.0;
   c->params_set = true;
   if (changed) { c->mom_valid = false; c->pc_valid = false; }
+  if (c->ipcs) c->ipcs->assembled = false;
   return 0;
 }
 
@@ -149,11 +184,13 @@ int cfdh_set_options(cfdh_ctx *c, const cfdh_options *o) {
                           o->schur_full != c->opt.schur_full;  // the velocity hierarchy covers owned + ghost vertices only for schur_full == 2 (ras)
   c->opt = *o;
   if (pc_changed) c->pc_valid = false;
+  if (pc_changed && c->ipcs) c->ipcs->pset_dirty = true;
   c->pc_graph_valid = false;  // degrees / schur_full are baked into the captured graph
   return 0;
 }
 
 int cfdh_clear_dirichlet(cfdh_ctx *c) {
+  if (c && c->ipcs) return cfdh_ipcs_clear_dirichlet(c);
   ENTER(c);
   // only the entries some object wrote (the arrays start out zero): O(#boundary vertices) per step, not O(nv)
   const int st = c->dim + 1;
@@ -171,6 +208,10 @@ int cfdh_clear_dirichlet(cfdh_ctx *c) {
 }
 
 int cfdh_add_dirichlet(cfdh_ctx *c, int field, int64_t n, const int32_t *nodes, const double *values) {
+  if (c && c->ipcs) {
+    if ((field != 0 && field != 1) || n < 0 || (n > 0 && (!nodes || !values))) return cfdh_fail(c, CFDH_E_ARG, "bad Dirichlet arguments");
+    return cfdh_ipcs_add_dirichlet(c, field, n, nodes, values, false);
+  }
   if (!c || (field != 0 && field != 1) || n < 0 || (n > 0 && (!nodes || !values))) return cfdh_fail(c, CFDH_E_ARG, "bad Dirichlet arguments");
   for (int64_t k = 0; k < n; k++)
     if (nodes[k] < 0 || nodes[k] >= c->nv) return cfdh_fail(c, CFDH_E_ARG, "Dirichlet node %d out of range", (int)nodes[k]);
@@ -196,6 +237,10 @@ int cfdh_add_dirichlet(cfdh_ctx *c, int field, int64_t n, const int32_t *nodes, 
 }
 
 int cfdh_update_dirichlet(cfdh_ctx *c, int field, int64_t n, const int32_t *nodes, const double *values) {
+  if (c && c->ipcs) {
+    if ((field != 0 && field != 1) || n < 0 || (n > 0 && (!nodes || !values))) return cfdh_fail(c, CFDH_E_ARG, "bad Dirichlet arguments");
+    return cfdh_ipcs_add_dirichlet(c, field, n, nodes, values, true);
+  }
   if (!c || (field != 0 && field != 1) || n < 0 || (n > 0 && (!nodes || !values))) return cfdh_fail(c, CFDH_E_ARG, "bad Dirichlet arguments");
   const int d = c->dim, st = d + 1;
   const unsigned need = field == 0 ? ((1u << d) - 1u) : (1u << d);
@@ -264,6 +309,13 @@ static int upload_vec(cfdh_ctx *c, const std::vector<double> &h, double *dev) {
 }
 
 int cfdh_set_state(cfdh_ctx *c, const double *u_prev, const double *p_prev, const double *u, const double *p) {
+  if (c && c->ipcs) {
+    ENTER(c);
+    IpcsData *I = c->ipcs;
+    CHK(ipcs_put(c, I->u_prev, u_prev)); CHK(ipcs_put(c, I->p_prev, p_prev)); CHK(ipcs_put(c, I->u_sol, u)); CHK(ipcs_put(c, I->p_sol, p));
+    c->state_set = true; I->assembled = false;
+    return 0;
+  }
   ENTER(c);
   std::vector<double> h, cur;
   if (u_prev || p_prev) {
@@ -284,6 +336,7 @@ int cfdh_set_state(cfdh_ctx *c, const double *u_prev, const double *p_prev, cons
 }
 
 int cfdh_get_solution(cfdh_ctx *c, double *u, double *p) {
+  if (c && c->ipcs) { ENTER(c); CHK(ipcs_get(c, c->ipcs->u_sol, u)); return ipcs_get(c, c->ipcs->p_sol, p); }
   ENTER(c);
   std::vector<double> h;
   CHK(download_vec(c, c->x.p, h));
@@ -292,6 +345,7 @@ int cfdh_get_solution(cfdh_ctx *c, double *u, double *p) {
 }
 
 int cfdh_get_previous(cfdh_ctx *c, double *u, double *p) {
+  if (c && c->ipcs) { ENTER(c); CHK(ipcs_get(c, c->ipcs->u_prev, u)); return ipcs_get(c, c->ipcs->p_prev, p); }
   ENTER(c);
   std::vector<double> h;
   CHK(download_vec(c, c->xprev.p, h));
@@ -300,6 +354,7 @@ int cfdh_get_previous(cfdh_ctx *c, double *u, double *p) {
 }
 
 int cfdh_get_residual(cfdh_ctx *c, double *ru, double *rp) {
+  NOT_IPCS(c, "cfdh_get_residual");
   ENTER(c);
   std::vector<double> h;
   CHK(download_vec(c, c->F.p, h));
@@ -310,6 +365,7 @@ int cfdh_get_residual(cfdh_ctx *c, double *ru, double *rp) {
 }
 
 int cfdh_advance(cfdh_ctx *c) {
+  if (c && c->ipcs) { ENTER(c); CHK(ipcs_copy(c, c->ipcs->u_sol, c->ipcs->u_prev)); return ipcs_copy(c, c->ipcs->p_sol, c->ipcs->p_prev); }
   ENTER(c);
   CHK(v_copy(c, c->NL, c->x.p, c->xprev.p));
   c->mom_valid = false;
@@ -317,6 +373,11 @@ int cfdh_advance(cfdh_ctx *c) {
 }
 
 int cfdh_advance_field(cfdh_ctx *c, int field) {
+  if (c && c->ipcs) {
+    ENTER(c);
+    if (field != 0 && field != 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_advance_field: field must be 0 (velocity) or 1 (pressure)");
+    return field == 0 ? ipcs_copy(c, c->ipcs->u_sol, c->ipcs->u_prev) : ipcs_copy(c, c->ipcs->p_sol, c->ipcs->p_prev);
+  }
   ENTER(c);
   const size_t nu = (size_t)c->dim * c->nvo;
   if (field == 0) {
@@ -331,6 +392,7 @@ int cfdh_advance_field(cfdh_ctx *c, int field) {
 }
 
 int cfdh_set_time_scheme(cfdh_ctx *c, double theta, double a0, double a1, double a2) {
+  NOT_IPCS(c, "cfdh_set_time_scheme");
   ENTER(c);
   if (!(theta > 0) || theta > 1 || !(a0 > 0)) return cfdh_fail(c, CFDH_E_ARG, "time scheme needs 0 < theta <= 1 and a0 > 0");
   if (theta != c->ts_theta || a0 != c->ts_a[0]) c->pc_valid = false;  // a0/(theta dt) scales the preconditioner
@@ -391,6 +453,7 @@ static int upload_cell_facet_flags(cfdh_ctx *c) {
 }
 
 int cfdh_set_boundary_terms(cfdh_ctx *c, int ds_terms, int backflow_marker, double beta) {
+  NOT_IPCS(c, "cfdh_set_boundary_terms");
   ENTER(c);
   if (beta < 0) return cfdh_fail(c, CFDH_E_ARG, "backflow beta must be >= 0");
   if (beta > 0 && c->form == CFDH_FORM_ROTATIONAL)
@@ -403,6 +466,14 @@ int cfdh_set_boundary_terms(cfdh_ctx *c, int ds_terms, int backflow_marker, doub
 }
 
 int cfdh_set_facet_markers(cfdh_ctx *c, int64_t nfacets, const int32_t *markers) {
+  if (c && c->ipcs) {
+    ENTER(c);
+    IpcsData *I = c->ipcs;
+    if (nfacets != (int64_t)I->fmarker.size() || (nfacets > 0 && !markers)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_facet_markers: one marker per exterior facet of cfdh_create_ipcs");
+    I->fmarker.assign(markers, markers + nfacets);
+    if (nfacets > 0) { HIPCHK(c, I->d_fmarker.upload(I->fmarker, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+    return 0;
+  }
   ENTER(c);
   if (nfacets != c->nfac_user) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_facet_markers: %lld markers for the %d exterior facets of cfdh_create", (long long)nfacets, c->nfac_user);
   if (nfacets > 0 && !markers) return cfdh_fail(c, CFDH_E_ARG, "null marker array");
@@ -430,6 +501,7 @@ static int rotational_supported(cfdh_ctx *c, const char *who) {
 }
 
 int cfdh_set_formulation(cfdh_ctx *c, int form) {
+  NOT_IPCS(c, "cfdh_set_formulation");
   ENTER(c);
   if (form != CFDH_FORM_CONVECTIVE && form != CFDH_FORM_ROTATIONAL) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: unknown form %d", form);
   if (form == c->form) return 0;
@@ -447,6 +519,7 @@ int cfdh_set_formulation(cfdh_ctx *c, int form) {
 }
 
 int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, const double *values, double beta_nitsche) {
+  NOT_IPCS(c, "cfdh_set_pressure_boundaries");
   ENTER(c);
   if (n < 0 || n > CFDH_MAX_PBND) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: 0 <= n <= %d", CFDH_MAX_PBND);
   if (n > 0 && (!markers || !values)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: null marker / value array");
@@ -471,6 +544,7 @@ int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, con
 }
 
 int cfdh_set_schur_pcd(cfdh_ctx *c, int inlet_marker, int outlet_marker, int time_term) {
+  NOT_IPCS(c, "cfdh_set_schur_pcd");
   ENTER(c);
   if (c->gen) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: PCD exists for P1 triangles and tetrahedra on the closed-form kernels only");
   if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: PCD is not available in partitioned runs");
@@ -483,6 +557,7 @@ int cfdh_set_schur_pcd(cfdh_ctx *c, int inlet_marker, int outlet_marker, int tim
 }
 
 int cfdh_set_ksp_forcing(cfdh_ctx *c, int version, double rtol_0, double rtol_max, double gamma, double alpha, double threshold) {
+  NOT_IPCS(c, "cfdh_set_ksp_forcing");
   ENTER(c);
   if (version != 0 && version != 2) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_ksp_forcing: version 0 (off) or 2");
   if (version == 2 && !(rtol_0 > 0 && rtol_0 < 1 && rtol_max > 0 && rtol_max < 1 && gamma > 0 && gamma <= 1 && alpha > 1 && alpha <= 2 &&
@@ -494,6 +569,7 @@ int cfdh_set_ksp_forcing(cfdh_ctx *c, int version, double rtol_0, double rtol_ma
 }
 
 int cfdh_get_newton_history(cfdh_ctx *c, int32_t *n, double *fnorm, double *ksp_rtol, int32_t *ksp_its, double *ksp_rel_res) {
+  NOT_IPCS(c, "cfdh_get_newton_history");
   if (!c || !n) return CFDH_E_ARG;
   const size_t m = c->hist_fnorm.size();
   *n = (int32_t)m;
@@ -507,6 +583,7 @@ int cfdh_get_newton_history(cfdh_ctx *c, int32_t *n, double *fnorm, double *ksp_
 }
 
 int cfdh_get_pcd_operator(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *mass_diag) {
+  NOT_IPCS(c, "cfdh_get_pcd_operator");
   if (!c || !nnz) return CFDH_E_ARG;
   ENTER(c);
   *nnz = c->nnzv;
@@ -539,6 +616,7 @@ int cfdh_get_pcd_operator(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *c
 }
 
 int cfdh_apply_preconditioner(cfdh_ctx *c, const double *r, double *z) {
+  NOT_IPCS(c, "cfdh_apply_preconditioner");
   if (!c || !r || !z) return CFDH_E_ARG;
   ENTER(c);
   if (!c->jac_valid) return cfdh_fail(c, CFDH_E_STATE, "no Jacobian assembled yet");
@@ -558,6 +636,7 @@ int cfdh_apply_preconditioner(cfdh_ctx *c, const double *r, double *z) {
 }
 
 int cfdh_set_previous2(cfdh_ctx *c, const double *u_prev2) {
+  if (c && c->ipcs) { ENTER(c); if (!u_prev2) return cfdh_fail(c, CFDH_E_ARG, "u_prev2 is NULL"); return ipcs_put(c, c->ipcs->u_n1, u_prev2); }
   ENTER(c);
   if (!u_prev2) return cfdh_fail(c, CFDH_E_ARG, "u_prev2 is NULL");
   std::vector<double> h;
@@ -567,6 +646,7 @@ int cfdh_set_previous2(cfdh_ctx *c, const double *u_prev2) {
 }
 
 int cfdh_get_previous2(cfdh_ctx *c, double *u_prev2) {
+  if (c && c->ipcs) { ENTER(c); return ipcs_get(c, c->ipcs->u_n1, u_prev2); }
   ENTER(c);
   std::vector<double> h;
   CHK(download_vec(c, c->xprev2.p, h));
@@ -575,12 +655,14 @@ int cfdh_get_previous2(cfdh_ctx *c, double *u_prev2) {
 }
 
 int cfdh_shift_history(cfdh_ctx *c) {
+  NOT_IPCS(c, "cfdh_shift_history");
   ENTER(c);
   CHK(v_copy(c, c->NL, c->xprev.p, c->xprev2.p));
   return 0;
 }
 
 int cfdh_assemble(cfdh_ctx *c, int want_jacobian) {
+  NOT_IPCS(c, "cfdh_assemble");
   ENTER(c);
   if (!c->params_set) return cfdh_fail(c, CFDH_E_STATE, "cfdh_set_params was not called");
   CHK(cfdh_prepare_assembly(c));
@@ -591,6 +673,7 @@ int cfdh_assemble(cfdh_ctx *c, int want_jacobian) {
 }
 
 int cfdh_get_csr(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals) {
+  NOT_IPCS(c, "cfdh_get_csr");
   if (!c || !nnz) return CFDH_E_ARG;
   *nnz = (long long)(c->dim + 1) * (c->dim + 1) * c->nnzv;
   if (!rowptr && !col && !vals) return 0;
@@ -633,6 +716,7 @@ int cfdh_get_csr(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col, doubl
 }
 
 int cfdh_spmv(cfdh_ctx *c, const double *x, double *y) {
+  NOT_IPCS(c, "cfdh_spmv");
   if (!c || !x || !y) return CFDH_E_ARG;
   if (!c->jac_valid) return cfdh_fail(c, CFDH_E_STATE, "no Jacobian assembled yet");
   std::vector<double> h;
@@ -651,6 +735,7 @@ int cfdh_spmv(cfdh_ctx *c, const double *x, double *y) {
 
 int cfdh_set_global_pressure_space(cfdh_ctx *c, int64_t nvg, int64_t ncg, const int32_t *cells, const double *coords,
                                    const int32_t *owned_global, int64_t n_pbc, const int32_t *pbc_nodes) {
+  NOT_IPCS(c, "cfdh_set_global_pressure_space");
   ENTER(c);
   if (nvg <= 0 || ncg <= 0 || !cells || !coords || !owned_global || (n_pbc > 0 && !pbc_nodes))
     return cfdh_fail(c, CFDH_E_ARG, "bad global pressure space arguments");
@@ -827,6 +912,7 @@ int cfdh_set_global_pressure_space(cfdh_ctx *c, int64_t nvg, int64_t ncg, const 
 }
 
 int cfdh_solve_step(cfdh_ctx *c, cfdh_stats *stats) {
+  NOT_IPCS(c, "cfdh_solve_step");
   ENTER(c);
   cfdh_stats st;
   c->err.clear();
@@ -838,10 +924,12 @@ int cfdh_solve_step(cfdh_ctx *c, cfdh_stats *stats) {
 int cfdh_functional(cfdh_ctx *c, int kind, int marker, double *out) {
   if (!out) return CFDH_E_ARG;
   ENTER(c);
+  if (c->ipcs) return cfdh_ipcs_functional(c, kind, marker, out);
   return k_functional(c, kind, marker, out);
 }
 
 int cfdh_wall_shear_stress(cfdh_ctx *c, double *shear) {
+  NOT_IPCS(c, "cfdh_wall_shear_stress");
   ENTER(c);
   const size_t d = (size_t)c->dim;
   if (!c->wss.p) HIPCHK(c, c->wss.alloc(d * (size_t)c->nv));
@@ -859,6 +947,7 @@ int cfdh_wall_shear_stress(cfdh_ctx *c, double *shear) {
 }
 
 int cfdh_profile_enable(cfdh_ctx *c, int on) {
+  NOT_IPCS(c, "cfdh_profile_enable");
   ENTER(c);
   prof_flush(c);
   c->prof_on = on != 0;
@@ -871,6 +960,7 @@ int cfdh_profile_enable(cfdh_ctx *c, int on) {
   return 0;
 }
 int cfdh_profile_get(cfdh_ctx *c, int kind, double *total_ms, int64_t *launches) {
+  NOT_IPCS(c, "cfdh_profile_get");
   if (!c || kind < 0 || kind >= 12) return CFDH_E_ARG;
   prof_flush(c);
   if (total_ms) *total_ms = c->prof[kind].total_ms;
@@ -878,6 +968,7 @@ int cfdh_profile_get(cfdh_ctx *c, int kind, double *total_ms, int64_t *launches)
   return 0;
 }
 int cfdh_profile_reset(cfdh_ctx *c) {
+  NOT_IPCS(c, "cfdh_profile_reset");
   ENTER(c);
   prof_flush(c);
   for (auto &p : c->prof) { p.total_ms = 0; p.launches = 0; }
@@ -888,6 +979,24 @@ int cfdh_profile_reset(cfdh_ctx *c) {
 
 int64_t cfdh_info(const cfdh_ctx *c, int what) {
   if (!c) return -1;
+  if (c->ipcs) {
+    const IpcsData *I = c->ipcs;
+    switch (what) {
+      case 0: case 1: return I->nn;
+      case 2: return I->nc;
+      case 3: return (int64_t)I->hM.col.size();
+      case 6: return (int64_t)I->hLam.lev.size();
+      case 15: return I->last.host_syncs;
+      case 18: return 1;
+      case 26: return I->D;
+      case 29: return I->NL;
+      case 80: return I->last.launches;
+      case 81: return I->nvert;
+      case 82: return I->n_field_copies;
+      case 83: return 1;
+      default: return -1;
+    }
+  }
   switch (what) {
     case 0: return c->nvo;
     case 1: return c->nv;
@@ -940,6 +1049,112 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 25: { const AmgHier &h = c->opt.pc_type >= 1 ? c->hL : c->hS; return h.fused ? 1 : 0; }
     default: return -1;
   }
+}
+
+// ---- incremental pressure correction (cfdh_ipcs.hip) ----------------------------------------------------------------------
+
+int cfdh_create_ipcs(cfdh_ctx **out, int device, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells, const double *node_coords,
+                     int64_t nfacets, const int32_t *facet_cells, const int32_t *facet_local, const int32_t *facet_marker) {
+  if (!out) return cfdh_fail(nullptr, CFDH_E_ARG, "null output pointer");
+  *out = nullptr;
+  if (gdim != 2 && gdim != 3) return cfdh_fail(nullptr, CFDH_E_ARG, "gdim must be 2 (P2/P1 triangles) or 3 (P2/P1 tetrahedra)");
+  if (!cells || !node_coords || nfacets < 0 || (nfacets > 0 && (!facet_cells || !facet_local))) return cfdh_fail(nullptr, CFDH_E_ARG, "null mesh array");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return cfdh_fail(nullptr, CFDH_E_HIP, "no HIP device available: libcfdh has no CPU fallback");
+  if (device < 0 || device >= ndev) return cfdh_fail(nullptr, CFDH_E_ARG, "device %d out of range (%d devices)", device, ndev);
+  cfdh_ctx *c = new (std::nothrow) cfdh_ctx();
+  if (!c) return cfdh_fail(nullptr, CFDH_E_NOMEM, "out of host memory");
+  c->device = device;
+  cfdh_default_options(&c->opt);
+  c->use_graph = false;  // plain stream order
+  memset(&c->last_stats, 0, sizeof c->last_stats);
+  int rc = 0;
+  if (hipSetDevice(device) != hipSuccess) rc = cfdh_fail(nullptr, CFDH_E_HIP, "hipSetDevice(%d) failed", device);
+  else if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = cfdh_fail(nullptr, CFDH_E_HIP, "hipStreamCreate failed");
+  else rc = cfdh_ipcs_create(c, gdim, nn, nvert, nc, cells, node_coords, nfacets, facet_cells, facet_local, facet_marker);
+  if (rc) {
+    g_cfdh_last_error = c->err.empty() ? g_cfdh_last_error : c->err;
+    cfdh_destroy(c);
+    return rc;
+  }
+  *out = c;
+  return 0;
+}
+
+int cfdh_ipcs_set_form(cfdh_ctx *c, double conv_coeff, double force_coeff) {
+  NEED_IPCS(c, "cfdh_ipcs_set_form");
+  if (!(conv_coeff >= 0) || !std::isfinite(conv_coeff) || !std::isfinite(force_coeff)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_set_form: conv_coeff >= 0 and finite coefficients");
+  c->ipcs->conv_coeff = conv_coeff; c->ipcs->force_coeff = force_coeff; c->ipcs->force_default = false;
+  c->ipcs->assembled = false;
+  return 0;
+}
+
+int cfdh_ipcs_set_tolerances(cfdh_ctx *c, const double rtol[3], double atol, const int32_t max_it[3]) {
+  NEED_IPCS(c, "cfdh_ipcs_set_tolerances");
+  if (!rtol || !max_it || !(atol >= 0)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_set_tolerances: bad arguments");
+  for (int k = 0; k < 3; k++)
+    if (!(rtol[k] >= 0) || !(rtol[k] < 1) || max_it[k] < 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_set_tolerances: 0 <= rtol < 1, max_it >= 1");
+  for (int k = 0; k < 3; k++) { c->ipcs->rtol[k] = rtol[k]; c->ipcs->max_it[k] = max_it[k]; }
+  c->ipcs->atol = atol;
+  return 0;
+}
+
+int cfdh_ipcs_step(cfdh_ctx *c, cfdh_ipcs_stats *stats) {
+  NEED_IPCS(c, "cfdh_ipcs_step");
+  c->err.clear();
+  cfdh_ipcs_stats st;
+  const int rc = cfdh_ipcs_step_impl(c, &st);
+  if (stats) *stats = st;
+  return rc;
+}
+
+int cfdh_ipcs_get_operator(cfdh_ctx *c, int which, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals) {
+  NEED_IPCS(c, "cfdh_ipcs_get_operator");
+  IpcsData *I = c->ipcs;
+  const int D = I->D;
+  if (!nnz || which < 0 || which >= 3 + 2 * D) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_operator: which in [0, %d)", 3 + 2 * D);
+  const std::vector<int> &ptr = which == 1 ? I->hL.rowptr : which < 3 ? I->hM.rowptr : which < 3 + D ? I->bptr : I->gptr;
+  const std::vector<int> &cl = which == 1 ? I->hL.col : which < 3 ? I->hM.col : which < 3 + D ? I->bcol : I->gcol;
+  *nnz = (int64_t)cl.size();
+  if (!rowptr && !col && !vals) return 0;
+  if (!rowptr || !col || !vals) return cfdh_fail(c, CFDH_E_ARG, "pass all of rowptr/col/vals or none");
+  std::copy(ptr.begin(), ptr.end(), rowptr);
+  std::copy(cl.begin(), cl.end(), col);
+  if (which >= 3) {
+    const std::vector<double> &v = which < 3 + D ? I->hB : I->hG;
+    const int d = which < 3 + D ? which - 3 : which - 3 - D;
+    for (size_t k = 0; k < cl.size(); k++) vals[k] = v[(size_t)D * k + d];
+    return 0;
+  }
+  if (which == 0) {
+    if (!I->assembled) CHK(cfdh_ipcs_assemble(c));
+  } else {
+    if (!c->params_set) return cfdh_fail(c, CFDH_E_STATE, "cfdh_set_params was not called");
+    I->assembled = false;
+    CHK(cfdh_ipcs_assemble(c));  // brings L and rho M up to date with the Dirichlet data and rho
+  }
+  const double *src = which == 0 ? I->A1v.p : which == 1 ? I->Lv.p : I->RMv.p;
+  HIPCHK(c, hipMemcpyAsync(vals, src, sizeof(double) * cl.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int cfdh_ipcs_get_intermediate(cfdh_ctx *c, int which, double *out) {
+  NEED_IPCS(c, "cfdh_ipcs_get_intermediate");
+  IpcsData *I = c->ipcs;
+  if (!out || which < 0 || which > 4) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_intermediate: which in [0, 4]");
+  const dbuf<double> *src[5] = {&I->us, &I->phi, &I->b1, &I->b2, &I->b3};
+  I->n_field_copies++;
+  HIPCHK(c, hipMemcpyAsync(out, src[which]->p, sizeof(double) * src[which]->n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int cfdh_ipcs_apply_pressure_pc(cfdh_ctx *c, const double *r, double *z) {
+  NEED_IPCS(c, "cfdh_ipcs_apply_pressure_pc");
+  if (!r || !z) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_apply_pressure_pc: null array");
+  return cfdh_ipcs_apply_pc(c, r, z);
 }
 
 }  // extern "C"

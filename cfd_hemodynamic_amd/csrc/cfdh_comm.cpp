@@ -86,6 +86,7 @@ static int global_counts(cfdh_ctx *c) {
 }
 
 extern "C" int cfdh_comm_init(cfdh_ctx *c, const void *id128, int rank, int nranks) {
+  if (c && c->ipcs) return cfdh_fail(c, CFDH_E_STATE, "cfdh_comm_init: not available on an incremental pressure-correction context (cfdh_create_ipcs)");
   if (!c || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return cfdh_fail(c, CFDH_E_ARG, "bad comm arguments");
   std::string why;
   if (!load_nccl(why)) return cfdh_fail(c, CFDH_E_COMM, "%s", why.c_str());
@@ -101,6 +102,7 @@ extern "C" int cfdh_comm_init(cfdh_ctx *c, const void *id128, int rank, int nran
 }
 
 extern "C" int cfdh_comm_set_callbacks(cfdh_ctx *c, cfdh_allreduce_fn ar, cfdh_exchange_fn ex, void *user, int rank, int nranks) {
+  if (c && c->ipcs) return cfdh_fail(c, CFDH_E_STATE, "cfdh_comm_set_callbacks: not available on an incremental pressure-correction context (cfdh_create_ipcs)");
   if (!c || !ar || !ex || nranks < 1) return cfdh_fail(c, CFDH_E_ARG, "bad comm callbacks");
   if (c->nccl_comm) comm_finalize(c);  // the callbacks replace an RCCL communicator
   if (c->gp_allgather) { c->gp_allgather = false; c->pc_graph_valid = false; }  // back to the all-reduce of the padded vector
@@ -185,6 +187,7 @@ int comm_halo(cfdh_ctx *c, double *vec) {
 
 extern "C" int cfdh_set_halo(cfdh_ctx *c, int nnbr, const int32_t *nbr_rank, const int64_t *send_ptr, const int32_t *send_idx,
                              const int64_t *recv_ptr, const int32_t *recv_idx) {
+  if (c && c->ipcs) return cfdh_fail(c, CFDH_E_STATE, "cfdh_set_halo: not available on an incremental pressure-correction context (cfdh_create_ipcs)");
   if (!c || nnbr < 0) return cfdh_fail(c, CFDH_E_ARG, "bad halo arguments");
   c->nnbr = nnbr;
   c->rasp.ready = false;  // the ghost-row pattern follows the halo plan

@@ -143,8 +143,11 @@ struct ProfSlot {
   long long launches = 0;
 };
 
+struct IpcsData;  // incremental pressure-correction context (cfdh_ipcs.hpp)
+
 struct cfdh_ctx {
   int device = 0;
+  IpcsData *ipcs = nullptr;  // set by cfdh_create_ipcs: the context runs the pressure-correction scheme, not the Newton solver
   hipStream_t stream = nullptr;
   std::string err;
 

@@ -1,0 +1,45 @@
+// State of an incremental pressure-correction context (cfdh_create_ipcs; cfdh_ipcs.hip).  Node numbering is the caller's.
+#pragma once
+#include "cfdh_internal.hpp"
+
+struct IpcsData {
+  int D = 2, NL = 6, nn = 0, nvert = 0, nc = 0;
+  // host mesh and constant operators (P2 pattern: hM.rowptr / hM.col, shared by K and A1; P1 pattern: hL.rowptr / hL.col)
+  std::vector<int> cells, fcell, flocal, fmarker;
+  std::vector<double> coords;
+  CsrHost hM, hL;                    // mass on the P2 nodes; unconstrained P1 stiffness
+  std::vector<double> hK, hMp, m1;   // P2 stiffness, P1 mass, int phi_i
+  std::vector<int> gptr, gcol, bptr, bcol;  // patterns [nn x nvert] (G_d, B_d^T) and [nvert x nn] (B_d)
+  std::vector<double> hG, hBT, hB;   // [nnz][D] interleaved
+  // device copies
+  dbuf<int> d_cells, rp2, col2, eptr, elist, d_gptr, d_gcol, d_bptr, d_bcol, rp1, col1, d_fcell, d_flocal, d_fmarker;
+  dbuf<double> d_coords, d_geo, d_T2, Mv, Kv, Gv, BTv, Bv, d_m1, Mpv, Lv, Afree, A1v, RMv, dinv1, dinv3, cw, fout;
+  // state and work vectors: velocity-sized [nn D], pressure-sized [nvert]
+  dbuf<double> u_sol, u_prev, u_n1, us, b1, b3, kr, krh, kp, kv, ks, kt, ky, kz, uval, ucnt;
+  dbuf<double> p_sol, p_prev, phi, b2, pr, pz, pp, pq, lift2, prhs;
+  dbuf<unsigned char> uflag, pflag;
+  dbuf<double> S, P;                 // Krylov scalars, partial sums
+  // Dirichlet data (host master copies)
+  std::vector<unsigned char> h_uflag, h_pflag;
+  std::vector<double> h_ucnt, h_uval, h_pcnt, h_pval;
+  bool ubc_dirty = true, pbc_dirty = true, pset_dirty = true;
+  AmgHier hLam;                      // hierarchy of the pressure Laplacian, rebuilt when the pressure Dirichlet SET changes
+  bool singular = true, assembled = false;
+  double rm_rho = -1.0;              // density RMv / dinv3 were built for
+  double conv_coeff = -1.0, force_coeff = 0.0;  // cfdh_ipcs_set_form; before that call: rho and +rho
+  bool force_default = true;
+  double rtol[3] = {1e-5, 1e-5, 1e-5}, atol = 1e-50;
+  int max_it[3] = {10000, 10000, 10000};
+  long long n_launch = 0, n_sync = 0, n_field_copies = 0;  // of the step in progress; whole-field host copies since creation
+  cfdh_ipcs_stats last = {};
+};
+
+int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells, const double *coords, int64_t nfac,
+                     const int32_t *fcell, const int32_t *flocal, const int32_t *fmarker);
+void cfdh_ipcs_free(cfdh_ctx *c);
+int cfdh_ipcs_clear_dirichlet(cfdh_ctx *c);
+int cfdh_ipcs_add_dirichlet(cfdh_ctx *c, int field, int64_t n, const int32_t *nodes, const double *values, bool update);
+int cfdh_ipcs_assemble(cfdh_ctx *c);   // A1, b1 at the current state
+int cfdh_ipcs_step_impl(cfdh_ctx *c, cfdh_ipcs_stats *st);
+int cfdh_ipcs_apply_pc(cfdh_ctx *c, const double *r, double *z);
+int cfdh_ipcs_functional(cfdh_ctx *c, int kind, int marker, double *out);

@@ -1,0 +1,63 @@
+// Wave64 / workgroup reduction helpers shared by the kernel files (DPP row operations, fixed summation order).
+// Blocks are 256 threads (four wavefronts) wherever block_sum / block_max are used.
+#pragma once
+#include <hip/hip_runtime.h>
+
+// ---------------------------------------------------------------- wave-level helpers
+template <int CTRL>
+__device__ __forceinline__ double dpp_shuffle(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+// sum over aligned groups of 8 lanes (result in every lane of the group)
+__device__ __forceinline__ double group8_sum(double v) {
+  v += dpp_shuffle<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_shuffle<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_shuffle<0x141>(v);  // row_half_mirror
+  return v;
+}
+// sum over aligned groups of 4 lanes
+__device__ __forceinline__ double quad_sum(double v) {
+  v += dpp_shuffle<0xB1>(v);  // quad_perm [1,0,3,2]
+  v += dpp_shuffle<0x4E>(v);  // quad_perm [2,3,0,1]
+  return v;
+}
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+  int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+  int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+// sum over the 64 lanes of the wave (result in every lane)
+__device__ __forceinline__ double wave_sum(double v) {
+  v = group8_sum(v);
+  v += dpp_shuffle<0x140>(v);  // row_mirror -> sums of 16
+  return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
+}
+__device__ __forceinline__ double wave_max(double v) {
+  v = fmax(v, dpp_shuffle<0xB1>(v));
+  v = fmax(v, dpp_shuffle<0x4E>(v));
+  v = fmax(v, dpp_shuffle<0x141>(v));
+  v = fmax(v, dpp_shuffle<0x140>(v));
+  return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)), fmax(readlane_d(v, 32), readlane_d(v, 48)));
+}
+// block (256 threads) sum; result valid in thread 0
+__device__ __forceinline__ double block_sum(double v, double *sh /*[4]*/) {
+  v = wave_sum(v);
+  int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) sh[w] = v;
+  __syncthreads();
+  double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ double block_max(double v, double *sh) {
+  v = wave_max(v);
+  int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) sh[w] = v;
+  __syncthreads();
+  double r = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+  __syncthreads();
+  return r;
+}

@@ -52,7 +52,11 @@ class SolverBase(ABC):
         from .elements import dof_mesh
         dm = dof_mesh(self.mesh, degree)
         if getattr(self, "_dm", None) not in (None, dm):
-            raise ValueError("velocity and pressure must use the same Lagrange degree (equal-order elements)")
+            # the one mixed pair: P2 velocity with P1 pressure on simplices (Taylor-Hood, ipcs_bdf2.py:45-48).  Q lives on the base
+            # mesh, whose vertices are the first nodes of V's node mesh (elements.NodeMesh / NodeMesh3D)
+            if getattr(self._dm, "base", None) is self.mesh and dm is self.mesh and self._V is not None and self._Q is None:
+                return dm
+            raise ValueError("velocity and pressure must use the same Lagrange degree (equal-order elements), or degree 2 / 1 on simplices")
         self._dm = dm
         return dm
 

@@ -281,6 +281,71 @@ int cfdh_get_pcd_operator(cfdh_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t 
  * assembled Jacobian; r, z monolithic [gdim*nv | nv] as for cfdh_spmv.  Exposed for parity tests. */
 int cfdh_apply_preconditioner(cfdh_ctx *ctx, const double *r, double *z);
 
+/* ---- incremental pressure correction on P2/P1 Taylor-Hood elements (the `ipcs_bdf2` solver) -------------------------- */
+
+/* The second solver family of the reference (/root/reference/src/solvers/ipcs_bdf2.py:66-91,127-172): P2 velocity / P1 pressure,
+ * linear, three solves per step.  With the P2 basis phi, the P1 basis psi, w = 1.5 u_prev - 0.5 u_n1, per velocity component
+ * (the d components share ONE scalar matrix on the P2 node graph):
+ *   1. A1 u* = b1,  A1 = rho/dt M + c/2 N(w) + mu/2 K,  b1 = (rho/dt M - c/2 N(w) - mu/2 K) u_prev + B^T p_sol + s_f F,
+ *      N_ij = int phi_i (w . grad phi_j), (B_d)_ij = int psi_i d_d phi_j, F_i = f int phi_i; velocity Dirichlet objects as
+ *      cfdh_add_dirichlet documents them (lifting, identity rows whose diagonal counts the objects, later object wins; the
+ *      right-hand side of such a row is count * value).  BiCGStab + Jacobi on the interleaved d-component vector.
+ *   2. L phi = -rho/dt sum_d B_d u*_d, L the P1 stiffness matrix with the pressure Dirichlet objects applied the same way (the
+ *      object's VALUE goes into phi: right for homogeneous data only, as in the reference); p_sol += phi.  Flexible PCG
+ *      preconditioned by one V-cycle of the smoothed-aggregation hierarchy.  Without a pressure Dirichlet object the problem is
+ *      solved mean-free (right-hand side and phi have zero mean).
+ *   3. rho M u_sol = rho M u* - dt G phi, (G_d)_ij = int phi_i d_d psi_j, no boundary condition.  CG + Jacobi.
+ *   4. u_n1 <- u_prev.
+ * Every solve stops on the true residual, |b - A x| <= max(rtol |b|, atol); phi starts from zero, steps 1 and 3 from the previous
+ * step's u* / u_sol.
+ *
+ * cells [nc][6 | 10] list the P2 nodes in the local order of cfdh_create_elem; the vertices must be the nodes [0, nvert) (the
+ * pressure lives there), the edge nodes the rest; node_coords [nn][gdim]; exterior facets as for cfdh_create.  One GPU.
+ * A context of this kind answers cfdh_set_params, cfdh_clear / add / update_dirichlet (field 0: P2 node ids, field 1: vertex
+ * ids), cfdh_set_state / cfdh_get_solution / cfdh_get_previous (velocity arrays [nn][gdim], pressure arrays [nvert]; cfdh_set_state
+ * with u, p sets u_sol, p_sol), cfdh_set_previous2 / cfdh_get_previous2 (u_n1), cfdh_advance, cfdh_advance_field,
+ * cfdh_set_facet_markers, cfdh_functional (kinds 2-6; 0 / 1 for gdim 2 with P2 velocity gradients and P1 pressure),
+ * cfdh_info (0, 1: nn; 2: nc; 3: entries of A1; 6: levels of the pressure hierarchy; 15: host synchronisations and 80: kernel
+ * launches of the last step; 81: nvert; 82: whole-field host copies since creation; 83: 1 (the context kind)), cfdh_last_error,
+ * cfdh_destroy.  Every other entry point returns CFDH_E_STATE on it, and the cfdh_ipcs_* entry points return CFDH_E_STATE on every
+ * other context. */
+int cfdh_create_ipcs(cfdh_ctx **out, int device, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells,
+                     const double *node_coords, int64_t nfacets, const int32_t *facet_cells, const int32_t *facet_local,
+                     const int32_t *facet_marker);
+/* c = conv_coeff and s_f = force_coeff of the scheme above.  Before this call the context uses the consistent momentum
+ * equation rho u_t + rho (w . grad) u - mu lap u + grad p = rho f, i.e. (rho, +rho) of the current cfdh_set_params; the
+ * reference's literal form is (1, -1). */
+int cfdh_ipcs_set_form(cfdh_ctx *ctx, double conv_coeff, double force_coeff);
+/* per solve (1, 2, 3): relative tolerance and iteration cap; one absolute tolerance.  Defaults 1e-5 (PETSc's), 1e-50, 10000.
+ * The cap bounds the iterations LAUNCHED (BiCGStab / CG iterations go out in batches of up to four ahead of the convergence test,
+ * the last batch cut to what is left), so its[k] <= max_it[k] always; a solve that has not met its tolerance on the true residual
+ * by then ends with CFDH_KSP_DIVERGED_ITS, one that meets a NaN / inf or a breakdown (a zero denominator) with
+ * CFDH_KSP_DIVERGED_NANORINF. */
+int cfdh_ipcs_set_tolerances(cfdh_ctx *ctx, const double rtol[3], double atol, const int32_t max_it[3]);
+typedef struct cfdh_ipcs_stats {
+  int32_t its[3], reason[3];   /* CFDH_KSP_* */
+  double rel_res[3];           /* achieved true |b - A x| / |b| */
+  double ms_assemble, ms_solve[3], ms_total;
+  /* kernels launched and stream synchronisations made by the scheme's own code in the step (assembly, right-hand sides, Krylov
+   * loops).  NOT counted: the kernels inside the V-cycles (one cycle per pressure iteration), memsets and copies.  Two of the
+   * synchronisations only delimit the phase times above. */
+  int32_t launches, host_syncs;
+} cfdh_ipcs_stats;
+/* One step: 1-4 above.  CFDH_E_DIVERGED with a reason <= 0 when a solve hit its cap or met a NaN (the plugin raises
+ * RuntimeError("Did not converge, reason: r.")). */
+int cfdh_ipcs_step(cfdh_ctx *ctx, cfdh_ipcs_stats *stats);
+/* Operators as CSR in the caller's numbering, columns ascending; query convention of cfdh_get_csr (nnz first).  which 0: A1 as
+ * last assembled, Dirichlet treatment included (assembled from the current state when no step has run); 1: L with its Dirichlet
+ * rows; 2: rho M; 3 .. 3 + gdim - 1: B_d; 3 + gdim .. 3 + 2 gdim - 1: G_d.  Exposed for parity tests, like
+ * cfdh_get_pcd_operator. */
+int cfdh_ipcs_get_operator(cfdh_ctx *ctx, int which, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals);
+/* Vectors of the last step (or, for b1, of the assembly cfdh_ipcs_get_operator(0) triggered): which 0: u* [nn][gdim], 1: phi
+ * [nvert], 2: b1 [nn][gdim], 3: b2 [nvert], 4: b3 [nn][gdim]. */
+int cfdh_ipcs_get_intermediate(cfdh_ctx *ctx, int which, double *out);
+/* z = V r, one V-cycle of the pressure hierarchy for the current pressure Dirichlet set ([nvert] host arrays).  Exposed so that
+ * a test can measure how symmetric the cycle is (it decides between PCG and flexible PCG). */
+int cfdh_ipcs_apply_pressure_pc(cfdh_ctx *ctx, const double *r, double *z);
+
 /* u_prev2 (stabilized_schur_bdf2.py:72): upload / download; nv local vertices x gdim */
 int cfdh_set_previous2(cfdh_ctx *ctx, const double *u_prev2);
 int cfdh_get_previous2(cfdh_ctx *ctx, double *u_prev2);

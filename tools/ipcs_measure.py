@@ -1,0 +1,107 @@
+#!/usr/bin/env python
+"""Time steps of `ipcs_bdf2` (P2/P1 pressure correction) next to `stabilized_schur_backflow` with p_grade = 2 (the existing
+second-order path) on the same mesh, in one process, alternating blocks of steps.  Writes profiles/ipcs_measure.json.
+
+    python tools/ipcs_measure.py [--cases tg288,dfg110,bifurcation2.5e-4] [--steps 50] [--warmup 5] [--no-compare]
+
+Per case: unknowns, ms/step (host clock around a synchronised step; the step ends with a stream synchronisation), ms per phase
+(assembly, the three solves), iterations per solve, kernel launches and host synchronisations per step -- all from the step
+statistics of cfdh_ipcs_step -- and for the Newton solver (node count the same, one more pressure unknown per edge node) ms/step, Newton
+and FGMRES iterations.  The profiler is off.  The
+comparison is reported, not gated."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _scenario(case, solver, **kw):
+    if case.startswith("tg"):
+        from cfd_hemodynamic_amd.scenarios.taylor_green import TaylorGreenSimulation
+
+        class VelocityOnly(TaylorGreenSimulation):
+            bcp = property(lambda self: [])
+
+        return VelocityOnly(solver, 0.0005, 1.0, nx=int(case[2:]), quiet=True, **kw)
+    if case.startswith("dfg"):
+        from cfd_hemodynamic_amd.scenarios.dfg_1 import DFG1Benchmark
+        return DFG1Benchmark(solver, 0.001, 1.0, m=int(case[3:] or 110), quiet=True, **kw)
+    if case.startswith("bifurcation"):
+        from cfd_hemodynamic_amd.scenarios.simple_bifurcation import SimpleBifurcationSimulation as S
+        return S(solver, 1e-4, 1.0, res=float(case[11:] or 2.5e-4), quiet=True, **kw)
+    raise SystemExit("unknown case " + case)
+
+
+def _steps(sim, n, rec):
+    s = sim.solver
+    for _ in range(n):
+        t0 = time.perf_counter()
+        s.solveStep()
+        s.advance()
+        s.functional(4)  # a scalar read-back: the step is complete on the device
+        rec.append((1e3 * (time.perf_counter() - t0), s.last_stats))
+
+
+def _summary(rec, ipcs):
+    out = {"ms_per_step": float(np.median([r[0] for r in rec])), "ms_per_step_mean": float(np.mean([r[0] for r in rec]))}
+    st = [r[1] for r in rec]
+    if ipcs:
+        out.update(ms_assemble=float(np.mean([x.ms_assemble for x in st])), ms_solve=[float(np.mean([x.ms_solve[k] for x in st])) for k in range(3)],
+                   iterations=[float(np.mean([x.its[k] for x in st])) for k in range(3)], launches=float(np.mean([x.launches for x in st])),
+                   host_syncs=float(np.mean([x.host_syncs for x in st])))
+    else:
+        out.update(newton_its=float(np.mean([x.newton_its for x in st])), krylov_its=float(np.mean([x.krylov_its for x in st])))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="tg288,dfg110")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-compare", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ipcs_measure.json"))
+    a = ap.parse_args()
+    res = {}
+    block = 5
+    for case in a.cases.split(","):
+        sim = _scenario(case, "ipcs_bdf2")
+        V, Q = sim.solver.V, sim.solver.Q
+        r = {"velocity_dofs": V.num_dofs, "pressure_dofs": Q.num_dofs, "unknowns": V.num_dofs + Q.num_dofs}
+        ref, why = None, None
+        if not a.no_compare:
+            try:
+                ref = _scenario(case, "stabilized_schur_backflow", p_grade=2)
+            except Exception as exc:
+                why = "%s: %s" % (type(exc).__name__, exc)
+        rec, rec_ref = [], []
+        _steps(sim, a.warmup, [])
+        for _ in range(0, a.steps, block):  # alternate blocks of steps of the two solvers
+            _steps(sim, block, rec)
+            if ref is not None:
+                try:
+                    _steps(ref, a.warmup if not rec_ref else 0, [])
+                    _steps(ref, block, rec_ref)
+                except Exception as exc:  # the P2/P2 path does not converge everywhere: report it
+                    ref, why = None, "%s: %s" % (type(exc).__name__, exc)
+        r["ipcs_bdf2"] = _summary(rec, True)
+        if rec_ref:
+            r["stabilized_schur_backflow_p2"] = dict(_summary(rec_ref, False), steps=len(rec_ref))
+        if why:
+            r.setdefault("stabilized_schur_backflow_p2", {})["failed"] = why
+        del sim, ref
+        res[case] = r
+        print(case, json.dumps(r), flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
