@@ -55,6 +55,7 @@ SYMBOLS = [
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner",
+    "cfdh_get_amg_operator", "cfdh_get_amg_vectors",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
     "cfdh_ipcs_apply_pressure_pc",
 ]
@@ -133,6 +134,8 @@ def lib():
     L.cfdh_get_newton_history.argtypes = [vp, ip, dp, dp, ip, dp]
     L.cfdh_get_pcd_operator.argtypes = [vp, lp, ip, ip, dp, dp]
     L.cfdh_apply_preconditioner.argtypes = [vp, dp, dp]
+    L.cfdh_get_amg_operator.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, lp, lp, ip, ip, dp]
+    L.cfdh_get_amg_vectors.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, dp]
     L.cfdh_create_ipcs.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, ip, dp, C.c_int64, ip, ip, ip]
     L.cfdh_ipcs_set_form.argtypes = [vp, C.c_double, C.c_double]
     L.cfdh_ipcs_set_tolerances.argtypes = [vp, dp, C.c_double, ip]
@@ -170,6 +173,10 @@ def _raise(code, msg):
 
 FORM_CONVECTIVE, FORM_ROTATIONAL = 0, 1  # cfdh_set_formulation
 PC_SELFP, PC_CAHOUET_CHABARD, PC_PCD = 0, 1, 2  # cfdh_options.pc_type
+AMG_HIER_A, AMG_HIER_P, AMG_HIER_H = 0, 1, 2  # cfdh_get_amg_operator / cfdh_get_amg_vectors
+AMG_OP_A, AMG_OP_P, AMG_OP_G, AMG_OP_SB, AMG_OP_SC = 0, 1, 2, 3, 4
+(AMG_VEC_DINV, AMG_VEC_WDINV, AMG_VEC_AGG, AMG_VEC_COARSE_INV, AMG_VEC_D, AMG_VEC_LAMBDA, AMG_VEC_CC_SCALARS, AMG_VEC_CC_ML,
+ AMG_VEC_CC_PBC, AMG_VEC_SPGEMM_ROWS, AMG_VEC_SHAPE, AMG_VEC_ORDER, AMG_VEC_A00_LMAX, AMG_VEC_A00_DINV) = range(14)
 # Eisenstat-Walker version 2 with PETSc's defaults: rtol_0, rtol_max, gamma, alpha, threshold (cfdh_set_ksp_forcing)
 EW_DEFAULTS = (0.3, 0.9, 1.0, (1.0 + 5.0 ** 0.5) / 2.0, 0.1)
 
@@ -447,6 +454,29 @@ class Context:
         z = np.zeros_like(r)
         self._chk(self.L.cfdh_apply_preconditioner(self.h, _dp(r), _dp(z)))
         return z
+
+    def get_amg_operator(self, hier, level, which, raw=False):
+        """One operator of a built hierarchy as scipy CSR (AMG_HIER_*, AMG_OP_*); level-0 indices in the caller's numbering.
+        raw: the (rowptr, col, vals, shape) arrays as downloaded, unchecked (scipy would sum duplicates and sort)."""
+        import scipy.sparse as sp
+        nr, nc, nnz = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.L.cfdh_get_amg_operator(self.h, int(hier), int(level), int(which), C.byref(nr), C.byref(nc), C.byref(nnz), None, None, None))
+        rowptr = np.empty(nr.value + 1, dtype=np.int32)
+        col = np.empty(nnz.value, dtype=np.int32)
+        val = np.empty(nnz.value)
+        self._chk(self.L.cfdh_get_amg_operator(self.h, int(hier), int(level), int(which), C.byref(nr), C.byref(nc), C.byref(nnz), _ip(rowptr),
+                                               _ip(col), _dp(val)))
+        if raw:
+            return rowptr, col, val, (nr.value, nc.value), nnz.value
+        return sp.csr_matrix((val, col, rowptr), shape=(nr.value, nc.value))
+
+    def get_amg_vectors(self, hier, level, which):
+        """Vectors / scalars of a built hierarchy as float64 (AMG_VEC_*)."""
+        n = C.c_int64()
+        self._chk(self.L.cfdh_get_amg_vectors(self.h, int(hier), int(level), int(which), C.byref(n), None))
+        out = np.empty(n.value)
+        self._chk(self.L.cfdh_get_amg_vectors(self.h, int(hier), int(level), int(which), C.byref(n), _dp(out)))
+        return out
 
 
 class IpcsContext(Context):

@@ -91,6 +91,7 @@ struct Dev {
   hipStream_t s;
   dbuf<int> scan_sums;
   int rc = 0;
+  long long *path_rows = nullptr;  // [3] rows per product kernel family (hash, small, dense), counted on the host
   explicit Dev(cfdh_ctx *c_) : c(c_), s(c_->stream) {}
   // inclusive scan in place
   int scan(int *a, int n) {
@@ -775,6 +776,7 @@ struct Spgemm {
       hipLaunchKernelGGL(bin_rows_kernel, gr, bl, 0, s, n, tmp.p, pass, lists.p, cnt);
       HIPCHK(c, hipMemcpyAsync(hc, cnt, sizeof(int) * 16, hipMemcpyDeviceToHost, s));
       HIPCHK(c, hipStreamSynchronize(s));
+      if (dv.path_rows) { dv.path_rows[0] += (long long)hc[1] + hc[2] + hc[3] + hc[4]; dv.path_rows[1] += hc[0]; dv.path_rows[2] += hc[5]; }
 #define HASH_LAUNCH(TS, NUM, b)                                                                                                  \
   if (hc[b] > 0)                                                                                                                 \
     hipLaunchKernelGGL((spgemm_hash_kernel<TS, NUM, AOp, BOp>), dim3(hc[b]), dim3(64), 0, s, lists.p + (size_t)(b) * n, cnt + (b), A, B, \
@@ -1091,6 +1093,11 @@ int cfdh_amg_setup_dev(cfdh_ctx *c, AmgHier &H, CsrDev &A0, bool singular, int n
   static const double theta_env = getenv("CFDH_AMG_THETA") ? atof(getenv("CFDH_AMG_THETA")) : -1.0;
   const double theta = o.amg_theta >= 0 ? o.amg_theta : (theta_env >= 0 ? theta_env : (c->dim == 3 ? 0.02 : 0.07));
   const bool host_agg = getenv("CFDH_AMG_AGG") && !strcmp(getenv("CFDH_AMG_AGG"), "host");
+  // CFDH_AMG_KEEP=1 (tests, cfdh_get_amg_operator / cfdh_get_amg_vectors): P and the aggregate ids stay in their level instead of
+  // being released -- buffers that exist anyway change owner, nothing is allocated or launched for it
+  const bool keep = getenv("CFDH_AMG_KEEP") && getenv("CFDH_AMG_KEEP")[0] == '1';
+  for (long long &q : H.spgemm_rows) q = 0;
+  B.dv.path_rows = H.spgemm_rows;
   // secondary roots (section 6 of DESIGN.md): CFDH_AGG_GAP for both hierarchies, CFDH_AGG_GAP_A / _L for the velocity proxy / the pressure Laplacian
   // Defaults: 4 for the velocity proxy, off for the Laplacian -- on the cut-cell tree mesh of config 5 secondary roots in the
   // PRESSURE hierarchy cost 30 % more iterations (52.7 instead of 40.0 per step at 8 M DOF) and gain <= 4 % elsewhere.
@@ -1205,6 +1212,7 @@ int cfdh_amg_setup_dev(cfdh_ctx *c, AmgHier &H, CsrDev &A0, bool singular, int n
     // a partitioned run also uses the sweep-by-sweep cycle (distributed finest pressure level, overlapping velocity block): it
     // needs the plain transfer operators
     if (c->nranks > 1) { move_csr(L->P, P); move_csr(L->R, R); }
+    else if (keep) { move_csr(L->P, P); L->agg.adopt(agg); }
     move_csr(L->A, A);
     lastL = L;
     move_csr(A, Ac);

@@ -635,6 +635,191 @@ int cfdh_apply_preconditioner(cfdh_ctx *c, const double *r, double *z) {
   return 0;
 }
 
+// ---- read-only view of the built hierarchies (cfdh_get_amg_operator / cfdh_get_amg_vectors)
+static int amg_pick(cfdh_ctx *c, const char *name, int hier, int level, AmgHier **H, AmgLevel **L) {
+  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_STATE, "%s: one GPU only", name);
+  if (!c->pc_valid) return cfdh_fail(c, CFDH_E_STATE, "%s: no preconditioner built yet (cfdh_apply_preconditioner or cfdh_solve_step first)", name);
+  *H = nullptr;
+  if (hier == CFDH_AMG_HIER_H) {
+    if (c->opt.pc_type != 1 || c->Hlev.n <= 0) return cfdh_fail(c, CFDH_E_STATE, "%s: H exists for pc_type 1 only", name);
+    *L = &c->Hlev;
+    return 0;
+  }
+  if (hier != CFDH_AMG_HIER_A && hier != CFDH_AMG_HIER_P) return cfdh_fail(c, CFDH_E_ARG, "%s: unknown hierarchy %d", name, hier);
+  if (hier == CFDH_AMG_HIER_A && c->opt.pc_type == 0) return cfdh_fail(c, CFDH_E_STATE, "%s: pc_type 0 has no velocity hierarchy", name);
+  AmgHier *h = hier == CFDH_AMG_HIER_A ? &c->hA : (c->opt.pc_type == 0 ? &c->hS : &c->hL);
+  if (!h->valid) return cfdh_fail(c, CFDH_E_STATE, "%s: hierarchy %d is not built", name, hier);
+  if (level < 0 || level >= (int)h->lev.size()) return cfdh_fail(c, CFDH_E_ARG, "%s: level %d of %d", name, level, (int)h->lev.size());
+  *H = h;
+  *L = h->lev[level];
+  return 0;
+}
+
+int cfdh_get_amg_operator(cfdh_ctx *c, int hier, int level, int which, int64_t *nrow, int64_t *ncol, int64_t *nnz, int32_t *rowptr,
+                          int32_t *col, double *vals) {
+  NOT_IPCS(c, "cfdh_get_amg_operator");
+  if (!c || !nrow || !ncol || !nnz) return CFDH_E_ARG;
+  ENTER(c);
+  AmgHier *H = nullptr;
+  AmgLevel *L = nullptr;
+  CHK(amg_pick(c, "cfdh_get_amg_operator", hier, level, &H, &L));
+  if (which < CFDH_AMG_OP_A || which > CFDH_AMG_OP_SC) return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_operator: unknown operator %d", which);
+  if (!H) level = 0;
+  const CsrDev &M = which == CFDH_AMG_OP_A ? L->A : which == CFDH_AMG_OP_P ? L->P : which == CFDH_AMG_OP_G ? L->G : which == CFDH_AMG_OP_SB ? L->Sb : L->Sc;
+  if (M.n <= 0 || !M.rowptr.p || !M.col.p || !M.val.p)
+    return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_operator: operator %d of level %d is not kept in fp64 CSR (P: CFDH_AMG_KEEP=1 before the build)", which, level);
+  *nrow = M.n; *ncol = M.m; *nnz = M.nnz;
+  if (!rowptr && !col && !vals) return 0;
+  if (!rowptr || !col || !vals) return cfdh_fail(c, CFDH_E_ARG, "pass all of rowptr/col/vals or none");
+  std::vector<int> rp((size_t)M.n + 1), cl((size_t)M.nnz);
+  std::vector<double> vl((size_t)M.nnz);
+  HIPCHK(c, hipMemcpyAsync(rp.data(), M.rowptr.p, sizeof(int) * rp.size(), hipMemcpyDeviceToHost, c->stream));
+  if (M.nnz > 0) {
+    HIPCHK(c, hipMemcpyAsync(cl.data(), M.col.p, sizeof(int) * cl.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(vl.data(), M.val.p, sizeof(double) * vl.size(), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (rp[M.n] != M.nnz) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_operator: rowptr ends at %d, the operator holds %d entries", rp[M.n], M.nnz);
+  // level 0 lives in the internal numbering: rows / columns that number it go back to the caller's
+  const bool rows0 = level == 0 && which != CFDH_AMG_OP_G && (int)c->perm.size() == M.n;
+  const bool cols0 = level == 0 && (which == CFDH_AMG_OP_A || which == CFDH_AMG_OP_SB || which == CFDH_AMG_OP_G) && (int)c->iperm.size() == M.m;
+  int64_t pos = 0;
+  std::vector<std::pair<int, double>> row;
+  for (int ru = 0; ru < M.n; ru++) {
+    const int r = rows0 ? c->perm[ru] : ru;
+    rowptr[ru] = (int32_t)pos;
+    row.clear();
+    for (int k = rp[r]; k < rp[r + 1]; k++) row.push_back({cols0 ? c->iperm[cl[k]] : cl[k], vl[k]});
+    // a stable sort by column only: the order in which the build stored equal or descending columns stays visible to the caller
+    if (cols0) std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
+    for (auto &e : row) { col[pos] = e.first; vals[pos] = e.second; pos++; }
+  }
+  rowptr[M.n] = (int32_t)pos;
+  return 0;
+}
+
+int cfdh_get_amg_vectors(cfdh_ctx *c, int hier, int level, int which, int64_t *n, double *out) {
+  NOT_IPCS(c, "cfdh_get_amg_vectors");
+  if (!c || !n) return CFDH_E_ARG;
+  ENTER(c);
+  AmgHier *H = nullptr;
+  AmgLevel *L = nullptr;
+  CHK(amg_pick(c, "cfdh_get_amg_vectors", hier, level, &H, &L));
+  if (!H) level = 0;
+  const bool perm0 = level == 0 && (int)c->perm.size() == L->n;
+  auto fetch = [&](const void *src, size_t bytes, void *dst) -> int {
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  };
+  const int nvo = c->nvo;
+  switch (which) {
+    case CFDH_AMG_VEC_DINV:
+    case CFDH_AMG_VEC_WDINV: {
+      const dbuf<double> &v = which == CFDH_AMG_VEC_DINV ? L->dinv : L->wdinv;
+      if (!v.p || (int)v.n < L->n) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: vector %d is not there", which);
+      *n = L->n;
+      if (!out) return 0;
+      std::vector<double> h((size_t)L->n);
+      CHK(fetch(v.p, sizeof(double) * h.size(), h.data()));
+      for (int i = 0; i < L->n; i++) out[i] = h[perm0 ? c->perm[i] : i];
+      return 0;
+    }
+    case CFDH_AMG_VEC_AGG: {
+      if (!L->agg.p || (int)L->agg.n < L->n) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: the aggregate ids were not kept (CFDH_AMG_KEEP=1 before the build)");
+      *n = L->n;
+      if (!out) return 0;
+      std::vector<int> h((size_t)L->n);
+      CHK(fetch(L->agg.p, sizeof(int) * h.size(), h.data()));
+      for (int i = 0; i < L->n; i++) out[i] = (double)h[perm0 ? c->perm[i] : i];
+      return 0;
+    }
+    case CFDH_AMG_VEC_COARSE_INV: {
+      if (!H || H->coarse_n <= 0 || !H->coarse_inv.p) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: no dense coarsest inverse");
+      *n = (int64_t)H->coarse_n * H->coarse_n;
+      if (!out) return 0;
+      return fetch(H->coarse_inv.p, sizeof(double) * (size_t)*n, out);
+    }
+    case CFDH_AMG_VEC_D: {
+      if (L->Dn <= 0 || !L->D.p) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: level %d has no folded dense correction", level);
+      *n = (int64_t)L->n * L->Dn;
+      if (!out) return 0;
+      std::vector<float> h((size_t)*n);
+      CHK(fetch(L->D.p, sizeof(float) * h.size(), h.data()));
+      for (int i = 0; i < L->n; i++) {
+        const size_t r = (size_t)(perm0 ? c->perm[i] : i);
+        for (int j = 0; j < L->Dn; j++) out[(size_t)i * L->Dn + j] = (double)h[r * L->Dn + j];
+      }
+      return 0;
+    }
+    case CFDH_AMG_VEC_LAMBDA:
+      *n = 2;
+      if (out) { out[0] = L->lmax; out[1] = L->lmin; }
+      return 0;
+    case CFDH_AMG_VEC_CC_SCALARS:
+      *n = 2;
+      if (out) { out[0] = c->cc_alpha; out[1] = c->cc_beta; }
+      return 0;
+    case CFDH_AMG_VEC_CC_ML: {
+      if (!c->ccMl.p || (int)c->ccMl.n < nvo) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: no lumped mass (pc_type 1, 2)");
+      *n = nvo;
+      if (!out) return 0;
+      std::vector<double> h((size_t)nvo);
+      CHK(fetch(c->ccMl.p, sizeof(double) * h.size(), h.data()));
+      for (int i = 0; i < nvo; i++) out[i] = h[c->perm[i]];
+      return 0;
+    }
+    case CFDH_AMG_VEC_CC_PBC: {
+      if (!c->ccPbc.p || (int)c->ccPbc.n < nvo) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: no pressure flags (pc_type 1, 2)");
+      *n = nvo;
+      if (!out) return 0;
+      std::vector<unsigned char> h((size_t)nvo);
+      CHK(fetch(c->ccPbc.p, h.size(), h.data()));
+      for (int i = 0; i < nvo; i++) out[i] = (double)h[c->perm[i]];
+      return 0;
+    }
+    case CFDH_AMG_VEC_SPGEMM_ROWS:
+      if (!H) return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_vectors: H is built without sparse products");
+      *n = 3;
+      if (out) for (int q = 0; q < 3; q++) out[q] = (double)H->spgemm_rows[q];
+      return 0;
+    case CFDH_AMG_VEC_SHAPE: {
+      const int nl = H ? (int)H->lev.size() : 1;
+      *n = 4 + 5 * (int64_t)nl;
+      if (!out) return 0;
+      out[0] = nl; out[1] = H ? H->coarse_n : 0; out[2] = H ? H->ncol : 1; out[3] = H && H->fused ? 1 : 0;
+      for (int l = 0; l < nl; l++) {
+        const AmgLevel *q = H ? H->lev[l] : L;
+        double *o = out + 4 + 5 * l;
+        o[0] = q->n; o[1] = q->Dn; o[2] = q->fine ? 1 : 0; o[3] = q->sell ? 1 : 0; o[4] = q->agg.p ? 1 : 0;
+      }
+      return 0;
+    }
+    case CFDH_AMG_VEC_A00_LMAX:
+      if (c->opt.pc_type != 0) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: the Chebyshev solve on A00 belongs to pc_type 0");
+      *n = 1;
+      if (out) out[0] = c->lmaxA;
+      return 0;
+    case CFDH_AMG_VEC_A00_DINV: {
+      const size_t nu = (size_t)c->dim * nvo;
+      if (c->opt.pc_type != 0 || !c->dinvA.p || c->dinvA.n < nu) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: 1 / diag(A00) belongs to pc_type 0");
+      *n = (int64_t)nu;
+      if (!out) return 0;
+      std::vector<double> h(nu);
+      CHK(fetch(c->dinvA.p, sizeof(double) * nu, h.data()));
+      for (int i = 0; i < nvo; i++)
+        for (int q = 0; q < c->dim; q++) out[(size_t)c->dim * i + q] = h[(size_t)c->dim * c->perm[i] + q];
+      return 0;
+    }
+    case CFDH_AMG_VEC_ORDER:
+      *n = L->n;
+      if (out) for (int i = 0; i < L->n; i++) out[i] = (double)(perm0 ? c->perm[i] : i);
+      return 0;
+    default:
+      return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_vectors: unknown item %d", which);
+  }
+}
+
 int cfdh_set_previous2(cfdh_ctx *c, const double *u_prev2) {
   if (c && c->ipcs) { ENTER(c); if (!u_prev2) return cfdh_fail(c, CFDH_E_ARG, "u_prev2 is NULL"); return ipcs_put(c, c->ipcs->u_n1, u_prev2); }
   ENTER(c);

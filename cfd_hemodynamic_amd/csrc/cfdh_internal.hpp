@@ -113,6 +113,7 @@ struct AmgLevel {
   int Dn = 0;        // columns of D (= size of the coarsest level); 0: not folded
   bool fine = false; // short regular rows: fp32 values in G (down-sweep)
   bool sell = false; // ... and SELL-64 / fp32 for Sb, Sc (up-sweep); not for three right-hand sides on tetrahedra (measured slower)
+  dbuf<int> agg;     // aggregate ids of the device build (-1: no coarse correction); kept with P only under CFDH_AMG_KEEP=1 (cfdh_get_amg_*)
 };
 
 // One smoothed-aggregation hierarchy.  ncol = 2 applies the same scalar operators to two
@@ -125,6 +126,7 @@ struct AmgHier {
   bool valid = false;
   bool fused = false;  // composite operators present on every level (built for damped-Jacobi smoothing)
   long long nnz_G0 = 0, nnz_S0 = 0;  // entries of G and of Sb + Sc on the finest level (roofline accounting)
+  long long spgemm_rows[3] = {0, 0, 0};  // rows the last device build sent to the hash / small / dense product kernels (both passes)
   // host copies of the finest level (operator, prolongator, Jacobi weights): kept on request so that a
   // partitioned run can cut its rows of the replicated pressure hierarchy out of them
   bool keep_host0 = false;

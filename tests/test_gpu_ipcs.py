@@ -363,6 +363,8 @@ def test_wrong_context_calls_return_state_errors():
     assert L.cfdh_set_time_scheme(ipcs.h, 1.0, 1.0, -1.0, 0.0) == -3
     z = np.zeros(3 * nm.num_vertices)
     assert L.cfdh_apply_preconditioner(ipcs.h, _lib._dp(z), _lib._dp(z)) == -3
+    assert L.cfdh_get_amg_operator(ipcs.h, 1, 0, 0, ctypes.byref(ctypes.c_int64()), ctypes.byref(ctypes.c_int64()), ctypes.byref(ctypes.c_int64()), None, None, None) == -3
+    assert L.cfdh_get_amg_vectors(ipcs.h, 1, 0, 0, ctypes.byref(ctypes.c_int64()), None) == -3
     ist = _lib.IpcsStats()
     assert L.cfdh_ipcs_step(newton.h, ctypes.byref(ist)) == -3
     assert b"cfdh_create_ipcs" in L.cfdh_last_error(newton.h)
