@@ -54,7 +54,7 @@ SYMBOLS = [
     "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_set_formulation", "cfdh_set_pressure_boundaries", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
-    "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner",
+    "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
     "cfdh_get_amg_operator", "cfdh_get_amg_vectors",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
     "cfdh_ipcs_apply_pressure_pc",
@@ -134,6 +134,7 @@ def lib():
     L.cfdh_get_newton_history.argtypes = [vp, ip, dp, dp, ip, dp]
     L.cfdh_get_pcd_operator.argtypes = [vp, lp, ip, ip, dp, dp]
     L.cfdh_apply_preconditioner.argtypes = [vp, dp, dp]
+    L.cfdh_apply_operator.argtypes = [vp, dp, dp, dp]
     L.cfdh_get_amg_operator.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, lp, lp, ip, ip, dp]
     L.cfdh_get_amg_vectors.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, dp]
     L.cfdh_create_ipcs.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, ip, dp, C.c_int64, ip, ip, ip]
@@ -454,6 +455,16 @@ class Context:
         z = np.zeros_like(r)
         self._chk(self.L.cfdh_apply_preconditioner(self.h, _dp(r), _dp(z)))
         return z
+
+    def apply_operator(self, r):
+        """(z, w) = (P^-1 r, J z) launched as one FGMRES iteration launches them (test entry; one GPU)."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.size != (self.dim + 1) * self.nv:
+            raise ValueError("monolithic vector of (gdim + 1) nv entries expected")
+        z = np.zeros_like(r)
+        w = np.zeros((self.dim + 1) * self.nvo)
+        self._chk(self.L.cfdh_apply_operator(self.h, _dp(r), _dp(z), _dp(w)))
+        return z, w
 
     def get_amg_operator(self, hier, level, which, raw=False):
         """One operator of a built hierarchy as scipy CSR (AMG_HIER_*, AMG_OP_*); level-0 indices in the caller's numbering.

@@ -87,6 +87,7 @@ static int create_ctx(cfdh_ctx **out, int device, int gdim, int etype, int64_t n
   c->device = device;
   cfdh_default_options(&c->opt);
   { const char *e = getenv("CFDH_NO_GRAPH"); c->use_graph = !(e && e[0] == '1'); }
+  { const char *e = getenv("CFDH_SOLVE_LEAN"); c->lean = !(e && e[0] == '0'); }  // 0: the solve paths without the lean prologue / epilogue / kept coupling product (A/B runs, tests)
   // No hipGraph replay under a rocprofiler-sdk tool on a HIP runtime >= 7.2.  That runtime submits the kernel packets of a graph
   // launch with ONE doorbell; ROCr's intercepted queue hands such a batch to the profiler's queue interceptor as (pointer into
   // the ring, packet count) without splitting it at the ring's wrap-around, and the interceptor walks `count` packets linearly:
@@ -635,6 +636,29 @@ int cfdh_apply_preconditioner(cfdh_ctx *c, const double *r, double *z) {
   return 0;
 }
 
+int cfdh_apply_operator(cfdh_ctx *c, const double *r, double *z, double *w) {
+  NOT_IPCS(c, "cfdh_apply_operator");
+  if (!c || !r || !z || !w) return CFDH_E_ARG;
+  ENTER(c);
+  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_STATE, "cfdh_apply_operator: one GPU only");
+  if (!c->jac_valid) return cfdh_fail(c, CFDH_E_STATE, "no Jacobian assembled yet");
+  CHK(cfdh_pc_update(c, false));
+  std::vector<double> h;
+  pack_vec(c, r, r + (size_t)c->dim * c->nv, h, nullptr);
+  CHK(upload_vec(c, h, c->xt.p));
+  CHK(cfdh_apply_operator_dev(c, c->xt.p, c->dvec.p));  // w lands in the Krylov work vector
+  std::vector<double> oz, ow;
+  CHK(download_vec(c, c->dvec.p, oz));
+  CHK(download_vec(c, c->kw.p, ow));
+  for (int k = 0; k < c->nvo; k++) {
+    const int v = c->iperm[k], d = c->dim;
+    for (int i = 0; i < d; i++) { z[(size_t)d * v + i] = oz[(size_t)d * k + i]; w[(size_t)d * v + i] = ow[(size_t)d * k + i]; }
+    z[(size_t)d * c->nv + v] = oz[(size_t)d * c->nvo + k];
+    w[(size_t)d * c->nvo + v] = ow[(size_t)d * c->nvo + k];
+  }
+  return 0;
+}
+
 // ---- read-only view of the built hierarchies (cfdh_get_amg_operator / cfdh_get_amg_vectors)
 static int amg_pick(cfdh_ctx *c, const char *name, int hier, int level, AmgHier **H, AmgLevel **L) {
   if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_STATE, "%s: one GPU only", name);
@@ -1158,6 +1182,7 @@ int cfdh_profile_reset(cfdh_ctx *c) {
   prof_flush(c);
   for (auto &p : c->prof) { p.total_ms = 0; p.launches = 0; }
   c->n_allreduce = c->n_halo = c->n_host_sync = c->n_krylov = c->n_allgather = 0;
+  c->n_cycles = c->n_guess_projections = c->n_iter_sync = 0;
   c->n_krylov_discarded = 0;
   return 0;
 }
@@ -1218,6 +1243,12 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 29: return c->nloc;
     case 73: return c->n_krylov_discarded;  // FGMRES iterations launched ahead of the host's convergence test and discarded (not in krylov_its)
     case 74: return c->n_pc_builds;
+    case 84: return c->n_cycles;      // FGMRES cycles whose true residual was read back (reset with 13..17)
+    case 86: return c->n_guess_projections;  // linear solves whose prologue projected a guess, used or not (reset with 13..17)
+    case 87: return c->n_iter_sync;   // host synchronisations inside the FGMRES cycles (batches of iterations, re-orthogonalisations; reset with 13..17)
+    case 88: return c->guess_last_rank;  // rank the pivoted Cholesky found in the last Gram system of a projected guess (-1: none yet)
+    case 89: return c->guess_last_k;     // ... and the number of kept vectors it had
+    case 85: return c->lean ? 1 : 0;  // lean solve path switched on (CFDH_SOLVE_LEAN)
     case 75: return c->pc_valid ? 1 : 0;
     case 76: return c->singular;
     case 77: return c->form;

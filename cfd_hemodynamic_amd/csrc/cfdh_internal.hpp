@@ -420,6 +420,15 @@ struct cfdh_ctx {
   std::vector<double> hist_fnorm, hist_rtol, hist_relres;
   std::vector<int> hist_its;
   double ksp_last_relres = 0;                // true |r| / |b| at the end of the last cfdh_fgmres
+  // Lean solve path (CFDH_SOLVE_LEAN, default on; read by cfdh_create): one rank, P1 triangles, pc_type 1 / 2.  The coupling
+  // product of the preconditioner keeps q_u = A01 z_p for the Krylov product that follows it, the prologue and epilogue of a
+  // linear solve and the norms of a Newton iteration come back in one read each (cfdh_solver.cpp).
+  bool lean = true;
+  dbuf<double> qu;                           // [2 nvo] A01 z_p of the last preconditioner application; its address is baked into the captured graphs
+  long long n_guess_projections = 0;         // linear solves whose prologue projected a guess, used or not (cfdh_info 86), reset likewise
+  int guess_last_rank = -1, guess_last_k = 0;  // rank and size of the last Gram system of a projected guess (cfdh_info 88, 89)
+  long long n_iter_sync = 0;                 // host synchronisations inside the FGMRES cycles: batches of iterations, re-orthogonalisations (cfdh_info 87), reset likewise
+  long long n_cycles = 0;                    // FGMRES cycles whose true residual was read back (cfdh_info 84), reset with the counters 13..17
 };
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
@@ -524,6 +533,16 @@ int k_scatter_global(cfdh_ctx *c, int n, const int *l2g, const double *loc, doub
 int k_gather_global(cfdh_ctx *c, int n, const int *l2g, const double *glob, double *loc);
 int k_cc_combine(cfdh_ctx *c, int n, double alpha, double beta, const double *t, const double *z, const double *r, const unsigned char *pbc, double *out, double *out2 = nullptr);
 int k_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm);
+// lean solve path (one rank, P1 triangles)
+int k_spmv_a01_keep(cfdh_ctx *c, const double *x, double *y, const double *b, double *q);  // y = b - A01 x and q = A01 x
+int k_spmv_full_kept(cfdh_ctx *c, const double *x, double *y, const double *q);            // y = J x with q = A01 x_p given
+int k_resid_norm(cfdh_ctx *c, const double *x, const double *b, double *r, double *nrm, bool *done);  // r = b - J x, |r|: one read-back
+int k_fnorm_nulltest(cfdh_ctx *c, int n, const double *F, double *fn, double *nrm, double *absnrm);  // one read-back
+int v_guess_combine(cfdh_ctx *c, int n, const double *U, const double *W, int ld, int k, const double *hd, const double *b, double *x, double *r);
+int v_guess_read(cfdh_ctx *c, int k, double *beta, bool *used, int *rank, double *y);
+int v_scale_inv_lean(cfdh_ctx *c, int n, double *x);
+int v_lincomb_keep(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const double *y_dev, double *x, double *x2);  // x += sum y_k Z_k, x2 = x
+int v_norm2_triple(cfdh_ctx *c, int n, const double *a, const double *b, const double *cc, double *out);  // three norms, one read-back
 int k_bc_scatter(cfdh_ctx *c, int n, int ncomp, const int *idx, const unsigned char *flag, const double *val, const double *mult);
 
 // vector ops on [0,n)
@@ -565,6 +584,7 @@ int comm_finalize(cfdh_ctx *c);
 // ---- solver (cfdh_solver.cpp) ------------------------------------------------------
 int cfdh_pc_update(cfdh_ctx *c, bool force_refresh);
 int cfdh_pc_apply(cfdh_ctx *c, const double *r, double *z);
+int cfdh_apply_operator_dev(cfdh_ctx *c, const double *r, double *z);  // z = P^-1 r, kw = J z: the pair of one FGMRES iteration
 int cfdh_host_threads();  // cfdh_setup.cpp: thread count of the host loops (CFDH_HOST_THREADS, default 8)
 int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its, int *reason, double bnorm = -1.0);
 int v_norm2_pair(cfdh_ctx *c, int n, const double *x, const double *y, double *nx, double *ny);

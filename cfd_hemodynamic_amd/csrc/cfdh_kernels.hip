@@ -762,9 +762,13 @@ __global__ __launch_bounds__(TPB) void spmv_blk_kernel(int nvo, const int *__res
 // lanes per row and the first two entries of every lane requested together: 16 B of matrix per entry is too little per
 // load for the 8-lane scheme, which left this kernel at 3.6 TB/s (16.1 us for 58 MB; this form: 12.2 us.  The same
 // change does nothing for the full product, whose lanes already carry 72 B of matrix per entry: 37.3 vs 36.6 us)
+// KEEP: the product itself, q = A01 x_p, is stored as well (16 B per row from the lane that holds the sums): the Krylov product
+// that follows the preconditioner reuses it instead of reading the A01 block again (spmv_full_lean_kernel<true, false>)
+template <bool KEEP>
 __global__ __launch_bounds__(TPB) void spmv_a01_resid_kernel(int nvo, const int *__restrict__ vptr, const int *__restrict__ vcol,
                                                              const double *__restrict__ A, const double *__restrict__ x,
-                                                             double *__restrict__ y, const double *__restrict__ bvec) {
+                                                             double *__restrict__ y, const double *__restrict__ bvec,
+                                                             double *__restrict__ q) {
   const int gid = blockIdx.x * TPB + threadIdx.x;
   const int row = gid >> 2, l = gid & 3;
   double a0 = 0, a1 = 0;
@@ -789,7 +793,10 @@ __global__ __launch_bounds__(TPB) void spmv_a01_resid_kernel(int nvo, const int 
     }
   }
   a0 = quad_sum(a0); a1 = quad_sum(a1);
-  if (row < nvo && l == 0) *(double2 *)(y + 2 * (size_t)row) = make_double2(bb.x - a0, bb.y - a1);
+  if (row < nvo && l == 0) {
+    *(double2 *)(y + 2 * (size_t)row) = make_double2(bb.x - a0, bb.y - a1);
+    if (KEEP) *(double2 *)(q + 2 * (size_t)row) = make_double2(a0, a1);
+  }
 }
 
 // coupling blocks INCLUDING ghost columns: xv is a full vector in the [u | p | ghost triplets] layout whose
@@ -846,8 +853,8 @@ int k_spmv_block(cfdh_ctx *c, int blk, const double *x, double *y, const double 
   else if (blk == 2) {
     if (mode) {
       const long long n4 = 4ll * c->nvo;
-      hipLaunchKernelGGL(spmv_a01_resid_kernel, dim3((unsigned)((n4 + TPB - 1) / TPB)), block, 0, c->stream, c->nvo, c->vptr.p,
-                         c->vcol.p, c->A01.p, x, y, b);
+      hipLaunchKernelGGL(spmv_a01_resid_kernel<false>, dim3((unsigned)((n4 + TPB - 1) / TPB)), block, 0, c->stream, c->nvo, c->vptr.p,
+                         c->vcol.p, c->A01.p, x, y, b, (double *)nullptr);
     } else {
       LAUNCH_BLK(2, 0, c->A01.p);
     }
@@ -855,6 +862,78 @@ int k_spmv_block(cfdh_ctx *c, int blk, const double *x, double *y, const double 
   else if (blk == 3) { if (mode) LAUNCH_BLK(3, 1, c->A10.p); else LAUNCH_BLK(3, 0, c->A10.p); }
   else { if (mode) LAUNCH_BLK(4, 1, c->A11.p); else LAUNCH_BLK(4, 0, c->A11.p); }
 #undef LAUNCH_BLK
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// ---- products of the lean solve path (CFDH_SOLVE_LEAN, one rank, P1 triangles; cfdh_solver.cpp).  Kernels of their own: the
+// plain product above stays as it is.
+//   KEPT : y = J x for the x the preconditioner has just written, with q = A01 x_p taken from the coupling product of that
+//          application (spmv_a01_resid_kernel<true>): y_u = A00 x_u + q, y_p = A10 x_u + A11 x_p -- 60 instead of 76 B per entry
+//   RESID: y = b - J x and the block partials of |y|^2 (the true residual after a cycle: product, waxpy and the first
+//          reduction pass in one kernel)
+template <bool KEPT, bool RESID>
+__global__ __launch_bounds__(TPB) void spmv_full_lean_kernel(int nvo, const int *__restrict__ vptr, const int *__restrict__ vcol,
+                                                             const double *__restrict__ A00, const double *__restrict__ A01,
+                                                             const double *__restrict__ A10, const double *__restrict__ A11,
+                                                             const double *__restrict__ x, double *__restrict__ y,
+                                                             const double *__restrict__ q, const double *__restrict__ b,
+                                                             double *__restrict__ partial) {
+  __shared__ double sh[4];
+  const int gid = blockIdx.x * TPB + threadIdx.x;
+  const int row = gid >> 3, l = gid & 7;
+  double a0 = 0, a1 = 0, a2 = 0;
+  if (row < nvo) {
+    const int ks = vptr[row], ke = vptr[row + 1];
+    for (int k = ks + l; k < ke; k += 8) {
+      const int w = vcol[k];
+      const int uo = uoff(w, nvo), po = poff(w, nvo);
+      const double xu0 = x[uo], xu1 = x[uo + 1], xp = x[po];
+      const double2 b0 = *(const double2 *)(A00 + 4 * (size_t)k), b1 = *(const double2 *)(A00 + 4 * (size_t)k + 2);
+      const double2 c10 = *(const double2 *)(A10 + 2 * (size_t)k);
+      const double c11 = A11[k];
+      if (KEPT) {
+        a0 += b0.x * xu0 + b0.y * xu1;
+        a1 += b1.x * xu0 + b1.y * xu1;
+      } else {
+        const double2 c01 = *(const double2 *)(A01 + 2 * (size_t)k);
+        a0 += b0.x * xu0 + b0.y * xu1 + c01.x * xp;
+        a1 += b1.x * xu0 + b1.y * xu1 + c01.y * xp;
+      }
+      a2 += c10.x * xu0 + c10.y * xu1 + c11 * xp;
+    }
+  }
+  a0 = group8_sum(a0); a1 = group8_sum(a1); a2 = group8_sum(a2);
+  double ss = 0.0;
+  if (row < nvo && l == 0) {
+    if (KEPT) { const double2 qq = *(const double2 *)(q + 2 * (size_t)row); a0 += qq.x; a1 += qq.y; }
+    if (RESID) {
+      const double2 bu = *(const double2 *)(b + 2 * (size_t)row);
+      a0 = bu.x - a0; a1 = bu.y - a1; a2 = b[2 * (size_t)nvo + row] - a2;
+      ss = a0 * a0 + a1 * a1 + a2 * a2;
+    }
+    *(double2 *)(y + 2 * (size_t)row) = make_double2(a0, a1);
+    y[2 * (size_t)nvo + row] = a2;
+  }
+  if (RESID) {
+    ss = block_sum(ss, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = ss;
+  }
+}
+
+// t_u = r_u - A01 x_p as k_spmv_block(c, 2, ...) forms it, and q = A01 x_p kept for the product that follows
+int k_spmv_a01_keep(cfdh_ctx *c, const double *x, double *y, const double *b, double *q) {
+  const long long n4 = 4ll * c->nvo;
+  hipLaunchKernelGGL(spmv_a01_resid_kernel<true>, dim3((unsigned)((n4 + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p,
+                     c->vcol.p, c->A01.p, x, y, b, q);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+// y = J x with the kept coupling product q = A01 x_p
+int k_spmv_full_kept(cfdh_ctx *c, const double *x, double *y, const double *q) {
+  const long long nthreads = 8ll * c->nvo;
+  hipLaunchKernelGGL((spmv_full_lean_kernel<true, false>), dim3((unsigned)((nthreads + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->nvo,
+                     c->vptr.p, c->vcol.p, c->A00.p, c->A01.p, c->A10.p, c->A11.p, x, y, q, (const double *)nullptr, (double *)nullptr);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -2302,6 +2381,197 @@ int v_lincomb(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const doubl
   HIPCHK(c, hipGetLastError());
   return 0;
 }
+
+// ---- lean solve path: prologue and epilogue of a linear solve with one read-back each (cfdh_solver.cpp) ----------------------
+// Host-mapped words behind CFDH_MIRROR_OFF: [0] squared norm of the residual, [1] 1 when the projected guess is used, [2] rank
+// of the Gram system, [3 .. 3 + k) the coefficients y.
+// The k x k Gram system of the projected guess (k <= 8), solved by one lane with the pivoted Cholesky and the two drop tests of
+// the host code in guess_project: hd[8 i + q] = W_q . W_i (i < k), hd[8 k + q] = W_q . b.  Rank 0 or a non-finite y: y = 0, not used.
+__global__ void gram_solve_kernel(int k, const double *__restrict__ hd, double *__restrict__ y, double *__restrict__ info) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double G[64], Lc[64], dg[8], g[8], yy[8], t[8];
+  int piv[8];
+  bool taken[8];
+  for (int i = 0; i < k; i++) {
+    for (int q = 0; q < k; q++) { G[q * k + i] = hd[i * 8 + q]; Lc[q * k + i] = 0.0; }
+    g[i] = hd[k * 8 + i]; yy[i] = 0.0; taken[i] = false;
+  }
+  double dmax0 = 0.0;
+  bool ok = true;
+  for (int i = 0; i < k; i++) {
+    dg[i] = G[i * k + i];
+    if (!isfinite(dg[i])) ok = false;
+    if (i == 0 || dg[i] > dmax0) dmax0 = dg[i];
+  }
+  ok = ok && dmax0 > 0.0 && isfinite(dmax0);
+  int r = 0;
+  if (ok) {
+    for (int it = 0; it < k; it++) {
+      int p = -1;
+      for (int i = 0; i < k; i++) if (!taken[i] && (p < 0 || dg[i] > dg[p])) p = i;
+      if (p < 0 || !(dg[p] > 1e-10 * G[p * k + p]) || !(dg[p] > 1e-14 * dmax0)) break;
+      taken[p] = true;
+      const int rr = r;
+      piv[r++] = p;
+      const double lpp = sqrt(dg[p]);
+      Lc[p * k + rr] = lpp;
+      for (int i = 0; i < k; i++) {
+        if (taken[i]) continue;
+        double sacc = G[i * k + p];
+        for (int q = 0; q < rr; q++) sacc -= Lc[i * k + q] * Lc[p * k + q];
+        Lc[i * k + rr] = sacc / lpp;
+        dg[i] -= Lc[i * k + rr] * Lc[i * k + rr];
+      }
+    }
+    for (int a = 0; a < r; a++) {
+      double sacc = g[piv[a]];
+      for (int q = 0; q < a; q++) sacc -= Lc[piv[a] * k + q] * t[q];
+      t[a] = sacc / Lc[piv[a] * k + a];
+    }
+    for (int a = r - 1; a >= 0; a--) {
+      double sacc = t[a];
+      for (int q = a + 1; q < r; q++) sacc -= Lc[piv[q] * k + a] * yy[piv[q]];
+      yy[piv[a]] = sacc / Lc[piv[a] * k + a];
+    }
+  }
+  bool used = ok && r > 0;
+  for (int i = 0; i < k; i++) if (!isfinite(yy[i])) used = false;
+  for (int i = 0; i < k; i++) { const double v = used ? yy[i] : 0.0; y[i] = v; info[3 + i] = v; }
+  info[1] = used ? 1.0 : 0.0;
+  info[2] = (double)r;
+}
+// x = U y, r = b - W y and the block partials of |r|^2 in one pass over U, W and b.  Entry by entry the arithmetic of
+// multiaxpy_kernel (on a zeroed x, and on a copy of b), block by block the partial sums of reduce_partial_kernel<0>.
+__global__ __launch_bounds__(TPB) void guess_combine_kernel(int n, const double *__restrict__ U, const double *__restrict__ W, size_t ld,
+                                                            int nvec, const double *__restrict__ y, const double *__restrict__ b,
+                                                            double *__restrict__ x, double *__restrict__ r, double *__restrict__ partial) {
+  __shared__ double sh[4];
+  double ss = 0.0;
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, c0 = b[i], c1 = 0.0, c2 = 0.0, c3 = 0.0;
+    int v = 0;
+    for (; v + 4 <= nvec; v += 4) {
+      const double y0 = y[v], y1 = y[v + 1], y2 = y[v + 2], y3 = y[v + 3];
+      const double u0 = U[(size_t)v * ld + i], u1 = U[(size_t)(v + 1) * ld + i], u2 = U[(size_t)(v + 2) * ld + i], u3 = U[(size_t)(v + 3) * ld + i];
+      const double w0 = W[(size_t)v * ld + i], w1 = W[(size_t)(v + 1) * ld + i], w2 = W[(size_t)(v + 2) * ld + i], w3 = W[(size_t)(v + 3) * ld + i];
+      a0 += y0 * u0; a1 += y1 * u1; a2 += y2 * u2; a3 += y3 * u3;
+      c0 -= y0 * w0; c1 -= y1 * w1; c2 -= y2 * w2; c3 -= y3 * w3;
+    }
+    for (; v < nvec; v++) { a0 += y[v] * U[(size_t)v * ld + i]; c0 -= y[v] * W[(size_t)v * ld + i]; }
+    const double ri = (c0 + c1) + (c2 + c3);
+    x[i] = (a0 + a1) + (a2 + a3);
+    r[i] = ri;
+    ss += ri * ri;
+  }
+  ss = block_sum(ss, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = ss;
+}
+// x *= 1 / sqrt(s2[0]) with the squared norm read on the device (0 when it is not positive)
+__global__ __launch_bounds__(TPB) void scale_inv_sqrt_kernel(int n, double *__restrict__ x, const double *__restrict__ s2) {
+  const double beta = sqrt(s2[0]);
+  const double a = beta > 0.0 ? 1.0 / beta : 0.0;
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) x[i] *= a;
+}
+// x += sum_i y_i Z_i as v_lincomb, and the result stored a second time in x2 (the kept copy of a converged solve)
+__global__ __launch_bounds__(TPB) void lincomb_keep_kernel(int n, const double *__restrict__ V, size_t ld, int nvec,
+                                                           const double *__restrict__ h, double *__restrict__ w, double *__restrict__ w2) {
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
+    double a0 = w[i], a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int v = 0;
+    for (; v + 4 <= nvec; v += 4) {
+      const double x0 = V[(size_t)v * ld + i], x1 = V[(size_t)(v + 1) * ld + i], x2 = V[(size_t)(v + 2) * ld + i],
+                   x3 = V[(size_t)(v + 3) * ld + i];
+      a0 += h[v] * x0; a1 += h[v + 1] * x1; a2 += h[v + 2] * x2; a3 += h[v + 3] * x3;
+    }
+    for (; v < nvec; v++) a0 += h[v] * V[(size_t)v * ld + i];
+    const double o = (a0 + a1) + (a2 + a3);
+    w[i] = o;
+    w2[i] = o;
+  }
+}
+// block partials of a.a, b.b and c.c in one pass (each sum in the order of reduce_partial_kernel<0>)
+__global__ __launch_bounds__(TPB) void norm3_partial_kernel(int n, const double *__restrict__ a, const double *__restrict__ b,
+                                                            const double *__restrict__ cc, double *__restrict__ partial) {
+  __shared__ double sh[4];
+  double s0 = 0, s1 = 0, s2 = 0;
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
+    const double ai = a[i], bi = b[i], ci = cc[i];
+    s0 += ai * ai; s1 += bi * bi; s2 += ci * ci;
+  }
+  s0 = block_sum(s0, sh);
+  s1 = block_sum(s1, sh);
+  s2 = block_sum(s2, sh);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; partial[2 * gridDim.x + blockIdx.x] = s2; }
+}
+static double *lean_mirror(cfdh_ctx *c) { c->mirror_src = nullptr; return c->h_pinned_dev + CFDH_MIRROR_OFF; }
+static int lean_sync(cfdh_ctx *c) {
+  c->n_host_sync++;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+#define CFDH_LEAN_S2 12  // red_out word that holds the squared residual norm of the lean prologue / epilogue
+// Prologue of a solve with k kept vectors, hd = Gram system from v_gram: y on the device (ky), x = U y, r = b - W y, |r|^2 and the
+// "used" flag in the host-mapped words.  Nothing is read back here.
+int v_guess_combine(cfdh_ctx *c, int n, const double *U, const double *W, int ld, int k, const double *hd, const double *b, double *x, double *r) {
+  if (k < 1 || k > 8) return cfdh_fail(c, CFDH_E_STATE, "projected guess: %d kept vectors", k);
+  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
+  double *mir = lean_mirror(c);
+  hipLaunchKernelGGL(gram_solve_kernel, dim3(1), dim3(64), 0, c->stream, k, hd, c->ky.p, mir);
+  hipLaunchKernelGGL(guess_combine_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, U, W, (size_t)ld, k, (const double *)c->ky.p, b, x, r, c->red_partial.p);
+  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p + CFDH_LEAN_S2, mir);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+// the one read-back of the prologue: |r0|, whether the guess is used, the rank and the coefficients
+int v_guess_read(cfdh_ctx *c, int k, double *beta, bool *used, int *rank, double *y) {
+  CHK(lean_sync(c));
+  const double *m = c->h_pinned + CFDH_MIRROR_OFF;
+  *beta = sqrt(m[0]);
+  *used = m[1] != 0.0;
+  *rank = (int)m[2];
+  for (int i = 0; i < k; i++) y[i] = m[3 + i];
+  return 0;
+}
+// x /= the norm the last lean prologue / epilogue left on the device
+int v_scale_inv_lean(cfdh_ctx *c, int n, double *x) {
+  hipLaunchKernelGGL(scale_inv_sqrt_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, x, (const double *)(c->red_out.p + CFDH_LEAN_S2));
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+// true residual r = b - J x and its norm with one kernel over the matrix and ONE read-back; false in *done when the partial
+// sums of this mesh do not fit the reduction workspace (the caller then takes the three-kernel path)
+int k_resid_norm(cfdh_ctx *c, const double *x, const double *b, double *r, double *nrm, bool *done) {
+  const long long nthreads = 8ll * c->nvo;
+  const long long nb = (nthreads + TPB - 1) / TPB;
+  *done = false;
+  if (c->dim != 2 || (size_t)nb > c->red_partial.n) return 0;
+  double *mir = lean_mirror(c);
+  hipLaunchKernelGGL((spmv_full_lean_kernel<false, true>), dim3((unsigned)nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->vcol.p, c->A00.p,
+                     c->A01.p, c->A10.p, c->A11.p, x, r, (const double *)nullptr, b, c->red_partial.p);
+  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, (int)nb, (int)nb, c->red_partial.p, c->red_out.p + CFDH_LEAN_S2, mir);
+  HIPCHK(c, hipGetLastError());
+  CHK(lean_sync(c));
+  *nrm = sqrt(c->h_pinned[CFDH_MIRROR_OFF]);
+  *done = true;
+  return 0;
+}
+int v_lincomb_keep(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const double *y_dev, double *x, double *x2) {
+  hipLaunchKernelGGL(lincomb_keep_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, Z, (size_t)ld, nvec, y_dev, x, x2);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+// |a|, |b|, |cc| with one pass and one read-back (one rank)
+int v_norm2_triple(cfdh_ctx *c, int n, const double *a, const double *b, const double *cc, double *out) {
+  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
+  if ((size_t)3 * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "reduction workspace too small");
+  double *mir = lean_mirror(c);
+  hipLaunchKernelGGL(norm3_partial_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, a, b, cc, c->red_partial.p);
+  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(3), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p, mir);
+  HIPCHK(c, hipGetLastError());
+  CHK(lean_sync(c));
+  for (int i = 0; i < 3; i++) out[i] = sqrt(c->h_pinned[CFDH_MIRROR_OFF + i]);
+  return 0;
+}
 __global__ void sqrt_kernel(double *s) { s[0] = sqrt(s[0]); }
 int v_norm_to_dev(cfdh_ctx *c, int n, const double *w, double *out_dev) {
   CHK(reduce_dev(c, 0, n, w, w, out_dev));
@@ -2361,6 +2631,23 @@ int k_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm) {
   CHK(read_scalars(c, c->red_out.p, 2, s));
   *nrm = sqrt(s[0]);
   *absnrm = sqrt(s[1]);
+  return 0;
+}
+// |F| and the two numbers of the null-space test with ONE read-back (one rank, triangles): each value is reduced exactly as
+// v_norm2 / k_nullspace_test reduce it
+int k_fnorm_nulltest(cfdh_ctx *c, int n, const double *F, double *fn, double *nrm, double *absnrm) {
+  const int nbf = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
+  const int nb = vgrid(c->nvo) > c->red_blocks ? c->red_blocks : vgrid(c->nvo);
+  if ((size_t)nbf + 2 * (size_t)nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "reduction workspace too small");
+  double *mir = lean_mirror(c), *pn = c->red_partial.p + nbf;
+  hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nbf), dim3(TPB), 0, c->stream, n, F, F, c->red_partial.p);
+  hipLaunchKernelGGL(nulltest_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->A01.p, c->A11.p, pn);
+  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nbf, nbf, c->red_partial.p, c->red_out.p, mir);
+  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(2), dim3(TPB), 0, c->stream, nb, nb, pn, c->red_out.p + 1, mir + 1);
+  HIPCHK(c, hipGetLastError());
+  CHK(lean_sync(c));
+  const double *m = c->h_pinned + CFDH_MIRROR_OFF;
+  *fn = sqrt(m[0]); *nrm = sqrt(m[1]); *absnrm = sqrt(m[2]);
   return 0;
 }
 

@@ -576,6 +576,18 @@ static bool ras_ghost_rhs() {
 // pc_type 2 (one rank): the stages of pc_type 1 with the PCD action in place of the Cahouet-Chabard one
 //   stage 1: t = M_d^-1 t_p, s = K t (0 on the Dirichlet rows of A_p)
 //   stage 2: y = V(A_p) s ; z_p = mu t + y (epilogue of the cycle's last kernel; r_p on pressure-Dirichlet rows, mu t on the outlet rows)
+// Lean solve path: the scope in which the solver takes it at all -- one rank, the closed-form P1 triangle kernels, the
+// Cahouet-Chabard or PCD preconditioner.  Everything else keeps the general code paths.
+static bool lean_newton(const cfdh_ctx *c) {  // merged read-backs of the Newton iteration: whatever the preconditioner
+  return c->lean && c->nranks == 1 && c->nv == c->nvo && c->dim == 2 && !c->gen;
+}
+static bool lean_scope(const cfdh_ctx *c) { return lean_newton(c) && (c->opt.pc_type == 1 || c->opt.pc_type == 2); }
+// The coupling product of the preconditioner also stores q_u = A01 z_p (for the Krylov product that follows, see pc_then_product)
+// unless z_p changes after the stages: the mean of a singular system is removed from it behind the graph.  The choice is baked
+// into the captured graphs; every input of it invalidates them when it changes (hierarchy rebuild on a change of `singular` or of
+// the options).
+static bool lean_keep_qu(const cfdh_ctx *c) { return lean_scope(c) && c->opt.schur_full != 0 && !c->singular && c->qu.p != nullptr; }
+
 static int pcd_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
   const int nvo = c->nvo, nu = c->dim * nvo;
   const double *ru = r, *rp = r + nu;
@@ -612,7 +624,8 @@ static int pcd_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
     }
     case 3:
       if (c->opt.schur_full) {
-        CHK(k_spmv_block(c, 2, zp, c->pu0.p, ru, 0));   // t_u = r_u - A01 z_p
+        if (lean_keep_qu(c)) CHK(k_spmv_a01_keep(c, zp, c->pu0.p, ru, c->qu.p));
+        else CHK(k_spmv_block(c, 2, zp, c->pu0.p, ru, 0));   // t_u = r_u - A01 z_p
         CHK(k_amg_vcycle(c, c->hA, c->pu0.p, zu));
       } else {
         CHK(v_copy(c, nu, c->pu0.p, zu));
@@ -709,6 +722,7 @@ static int pc_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
           // t_u = r_u - A01 z_p (with ghosts); for the overlapping cycle straight into the velocity slots of the halo scratch vector
           // (the kernel reads the pressure slots and ghost records of that vector and writes its owned velocity slots: disjoint)
           if (multi) CHK(k_spmv_block_ghost(c, 2, c->pcw.p, c->ras ? c->pcw.p : c->pu0.p, ru));
+          else if (lean_keep_qu(c)) CHK(k_spmv_a01_keep(c, zp, c->pu0.p, ru, c->qu.p));
           else CHK(k_spmv_block(c, 2, zp, c->pu0.p, ru, 0));
           if (multi && c->ras) {
             // experiment (CFDH_RAS_GHOST_RHS=0): no exchange of the overlap residual -- the right-hand side of the overlapping
@@ -793,6 +807,10 @@ int cfdh_pc_apply(cfdh_ctx *c, const double *r, double *z) {
   const bool graph = c->use_graph && !c->prof_on;
   const bool multi = c->nranks > 1 && c->opt.pc_type == 1;
   if (multi && !c->pcw.p) { HIPCHK(c, c->pcw.alloc(c->NL)); HIPCHK(c, c->pcw.zero(c->stream)); }
+  if (lean_scope(c) && c->opt.schur_full != 0 && !c->qu.p) {  // before any capture: the graphs hold its address
+    HIPCHK(c, c->qu.alloc(2 * (size_t)c->nvo));
+    c->pc_graph_valid = false;
+  }
   if (!graph) {
     for (int st = 0; st < 6; st++) { CHK(pc_stage(c, r, z, st)); CHK(pc_exchange(c, st)); }
   } else {
@@ -832,6 +850,22 @@ int cfdh_pc_apply(cfdh_ctx *c, const double *r, double *z) {
   }
   if (c->singular) CHK(v_sub_mean(c, nvo, z + (size_t)c->dim * nvo));
   return 0;
+}
+
+// One FGMRES iteration's operator: z = P^-1 r, then w = J z.  On the lean path the product takes A01 z_p from the buffer the
+// preconditioner application has just filled on the same stream instead of reading the A01 block again.  While the kernel
+// timers run the plain product is launched (its byte count is the one the timers' callers know).
+static int pc_then_product(cfdh_ctx *c, const double *r, double *z, double *w) {
+  CHK(cfdh_pc_apply(c, r, z));
+  CHK(comm_halo(c, z));
+  if (lean_keep_qu(c) && !c->prof_on) return k_spmv_full_kept(c, z, w, c->qu.p);
+  return k_spmv_full(c, z, w);
+}
+
+static int ensure_krylov(cfdh_ctx *c);
+int cfdh_apply_operator_dev(cfdh_ctx *c, const double *r, double *z) {
+  CHK(ensure_krylov(c));
+  return pc_then_product(c, r, z, c->kw.p);
 }
 
 static int ensure_krylov(cfdh_ctx *c) {
@@ -904,6 +938,7 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
   HIPCHK(c, hipMemcpyAsync(c->h_pinned, hd, sizeof(double) * 8 * (size_t)(k + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->n_host_sync++;
+  c->n_guess_projections++;
   for (int i = 0; i <= k; i++)
     for (int q = 0; q < k; q++) (i < k ? G[(size_t)q * k + i] : g[q]) = c->h_pinned[(size_t)i * 8 + q];
   if (c->opt.verbose > 1) {
@@ -921,6 +956,7 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
   std::vector<char> taken(k, 0);
   for (int i = 0; i < k; i++) dg[i] = G[(size_t)i * k + i];
   const double dmax0 = *std::max_element(dg.begin(), dg.end());
+  c->guess_last_rank = 0; c->guess_last_k = k;
   if (!(dmax0 > 0.0) || !std::isfinite(dmax0)) return 0;
   for (int r = 0; r < k; r++) {
     int p = -1;
@@ -940,6 +976,7 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
     }
   }
   const int r = (int)piv.size();
+  c->guess_last_rank = r; c->guess_last_k = k;
   if (r == 0) return 0;
   std::vector<double> t(r);
   for (int a = 0; a < r; a++) {
@@ -953,7 +990,11 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
     y[piv[a]] = sacc / Lc[(size_t)piv[a] * k + a];
   }
   for (int i = 0; i < k; i++) if (!std::isfinite(y[i])) return 0;
-  HIPCHK(c, hipMemcpyAsync(c->ky.p, y.data(), sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
+  // y travels through the pinned slot behind the read-back ring, as at the end of a cycle: no drain of the stream for a host
+  // temporary (the slot is next written at the end of the first cycle, behind events recorded after this copy)
+  double *ystage = c->h_ring + c->h_ring_stride * cfdh_ctx::KRING;
+  for (int i = 0; i < k; i++) ystage[i] = y[i];
+  HIPCHK(c, hipMemcpyAsync(c->ky.p, ystage, sizeof(double) * k, hipMemcpyHostToDevice, c->stream));
   CHK(v_lincomb(c, n, U, (int)ld, k, c->ky.p, x));  // x (zeroed by the caller) += U y
   // singular system: the guess, like every preconditioned vector, carries no constant-pressure component (the Krylov vectors
   // cannot remove one, and through the kept corrections it would feed back from step to step)
@@ -961,18 +1002,49 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
   // r0 = b - J x0 = b - W y without another product (the true residual is formed after every cycle anyway)
   CHK(v_copy(c, n, b, V));
   CHK(v_multiaxpy(c, n, Z, (int)ld, k, c->ky.p, V));
-  HIPCHK(c, hipStreamSynchronize(c->stream));        // y is a host temporary
   *used = true;
   return 0;
 }
 
-// keep the solution of a converged solve for the guesses of later time steps
-static int guess_store(cfdh_ctx *c, const double *x) {
+// The same projection on the lean path (one rank): the Gram system is solved on the device, ONE kernel then reads U, W and b once
+// and writes x0 = U y, r0 = b - W y (into V_0) and the partial sums of |r0|^2 -- no zero-fill of x, no copy of b, two passes less
+// over the kept vectors, and nothing is read back here: the caller reads |r0| and the "used" flag in one go (v_guess_read).
+// *ran: the kernels were launched (x and V_0 are fully written, with y = 0 when the guess turns out unusable).
+// Singular system: as on the general path, the mean pressure is removed from x0 after the combination and r0 stays b - W y.
+static int guess_project_lean(cfdh_ctx *c, const double *b, double *x, bool *ran) {
+  *ran = false;
+  CHK(guess_ensure(c));
+  const int slot = c->guess_slot, m = c->guess_m;
+  if (m <= 0 || slot < 0 || slot >= cfdh_ctx::GUESS_NEWTON || c->guess_cnt[slot] == 0 || c->kry_m < m + 1) return 0;
+  const int k = c->guess_cnt[slot], n = c->NO;
+  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
+  double *U = c->guessU.p + ld * (size_t)m * slot;
+  CHK(k_spmv_full_multi(c, U, c->kZ.p, (int)ld, k));
+  CHK(v_gram(c, n, c->kZ.p, (int)ld, k, b, c->kh.p));  // every word the solve reads is written: no memset
+  CHK(v_guess_combine(c, n, U, c->kZ.p, (int)ld, k, c->kh.p, b, x, c->kV.p));
+  if (c->singular) CHK(v_sub_mean(c, c->nvo, x + (size_t)c->dim * c->nvo));
+  c->n_guess_projections++;
+  *ran = true;
+  return 0;
+}
+
+// where guess_store would put the solution of the solve in progress (nullptr: nothing is kept)
+// only while the ring of this Newton index is not full: then the slot is free, and a solve that fails after all has overwritten
+// nothing.  In a full ring the slot holds the oldest live vector, which must survive a failed solve: guess_store copies.
+static double *guess_store_target(cfdh_ctx *c) {
+  const int slot = c->guess_slot, m = c->guess_m;
+  if (m <= 0 || slot < 0 || slot >= cfdh_ctx::GUESS_NEWTON || !c->guessU.p || c->guess_cnt[slot] >= m) return nullptr;
+  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
+  return c->guessU.p + ld * (size_t)m * slot + (size_t)c->guess_head[slot] * ld;
+}
+
+// keep the solution of a converged solve for the guesses of later time steps (in_place: the last update of x wrote the copy already)
+static int guess_store(cfdh_ctx *c, const double *x, bool in_place = false) {
   const int slot = c->guess_slot, m = c->guess_m;
   if (m <= 0 || slot < 0 || slot >= cfdh_ctx::GUESS_NEWTON) return 0;
   const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
   double *U = c->guessU.p + ld * (size_t)m * slot;
-  CHK(v_copy(c, c->NO, x, U + (size_t)c->guess_head[slot] * ld));
+  if (!in_place) CHK(v_copy(c, c->NO, x, U + (size_t)c->guess_head[slot] * ld));
   c->guess_stored[slot] = true;
   c->guess_head[slot] = (c->guess_head[slot] + 1) % m;
   if (c->guess_cnt[slot] < m) c->guess_cnt[slot]++;
@@ -1007,18 +1079,6 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
   const cfdh_options &o = c->opt;
   std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m), hh(2 * (size_t)(m + 1) + 8);
   double bn = bnorm;  // the caller may know |b| already (Newton: |F| of the accepted iterate)
-  CHK(v_zero(c, c->NL, x));
-  if (!(bn >= 0.0)) CHK(v_norm2(c, n, b, &bn));
-  int its = 0, reason = 0;
-  c->ksp_last_relres = bn == 0.0 ? 0.0 : 1.0;
-  if (!std::isfinite(bn)) { *its_out = 0; *reason_out = -9; return 0; }
-  if (bn == 0.0) { *its_out = 0; *reason_out = 2; return 0; }
-  const double tol = std::max(o.ksp_rtol * bn, o.ksp_atol);
-  double *V = c->kV.p, *Z = c->kZ.p, *w = c->kw.p, *hd = c->kh.p;
-  bool first = true;
-  bool guessed = false;
-  CHK(guess_project(c, b, x, &guessed));
-  if (guessed) first = false;  // the cycle starts from the true residual of x0, as after a restart
   // Long cycles at the default tolerance orthogonalise against an fp32 COPY of the basis (half the traffic of the two passes over
   // V, which are ~40 % of an iteration at depth 25).  Chosen per solve from the length of the last solve with the same Newton
   // index; never for tolerances below 1e-6 (parity runs), never again on a context whose watchdog tripped with the copy in use.
@@ -1030,6 +1090,37 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
   // saves on one GPU: taken only where a rank still holds >= 2 M unknowns (decided from the GLOBAL count: the same on every rank).
   const bool worth32 = c->nranks <= 1 || (c->nvo_global / c->nranks) * (c->dim + 1) >= 2.0e6;
   bool use32 = fp32_env > 0 && o.ksp_rtol >= 1e-6 && c->krylov_fp32_ok && ((expect_long && worth32) || fp32_env >= 2);
+  // Lean prologue and epilogue (not with the fp32 copy of the basis, which keeps the general path)
+  const bool lean_solve = lean_scope(c) && !use32;
+  // prologue on the lean path: launched whole before anything is read back; needs |b| from the caller (Newton passes it)
+  bool pro = false, pro_pending = false;
+  double beta_pro = 0.0;
+  const bool guess_check = getenv("CFDH_GUESS_CHECK") != nullptr;
+  if (lean_solve && bn > 0.0 && std::isfinite(bn)) CHK(guess_project_lean(c, b, x, &pro));
+  if (!pro) CHK(v_zero(c, c->NL, x));
+  if (!(bn >= 0.0)) CHK(v_norm2(c, n, b, &bn));
+  int its = 0, reason = 0;
+  c->ksp_last_relres = bn == 0.0 ? 0.0 : 1.0;
+  if (!std::isfinite(bn)) { *its_out = 0; *reason_out = -9; return 0; }
+  if (bn == 0.0) { *its_out = 0; *reason_out = 2; return 0; }
+  const double tol = std::max(o.ksp_rtol * bn, o.ksp_atol);
+  double *V = c->kV.p, *Z = c->kZ.p, *w = c->kw.p, *hd = c->kh.p;
+  bool first = true;
+  bool guessed = false;
+  bool kept_copy = false;  // the copy guess_store makes is current (written by the last update of x)
+  if (pro) {
+    // V_0 is normalised by a kernel that reads |r0|^2 on the device: it is queued BEFORE the read-back, so the device does not
+    // idle while the host wakes up (the check hook below wants the unscaled vector: it scales afterwards)
+    if (!guess_check) CHK(v_scale_inv_lean(c, n, V));
+    int rank = 0;
+    CHK(v_guess_read(c, c->guess_cnt[c->guess_slot], &beta_pro, &guessed, &rank, y.data()));
+    c->guess_last_rank = rank; c->guess_last_k = c->guess_cnt[c->guess_slot];
+    if (guessed) pro_pending = true;
+    else CHK(v_zero(c, c->NL, x));  // rank 0 or non-finite coefficients: zero guess (the kernel wrote 0 U; a NaN in U must not survive)
+  } else {
+    CHK(guess_project(c, b, x, &guessed));
+  }
+  if (guessed) first = false;  // the cycle starts from the true residual of x0, as after a restart
   float *V32 = nullptr;
   const size_t ld32 = (ld + 3) & ~(size_t)3;  // columns of the copy start on 16-B boundaries (float4 loads)
   if (use32) {
@@ -1044,11 +1135,18 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
     if (first) {
       beta = bn;  // r0 = b: v_0 = b / |b| is formed below straight from b
     } else {
+      bool have_beta = false;
       if (!(guessed && its == 0 && j_prev == 0)) {  // (after a projected guess V_0 already holds r0 = b - W y)
         CHK(comm_halo(c, x));
-        CHK(k_spmv_full(c, x, w));
-        CHK(v_waxpy(c, n, -1.0, w, b, V));
-      } else if (getenv("CFDH_GUESS_CHECK")) {
+        // lean path: product, b - J x and the first pass of the norm in one kernel, one read-back (not while the kernel timers run:
+        // they count the plain product)
+        if (lean_solve && !c->prof_on) CHK(k_resid_norm(c, x, b, V, &beta, &have_beta));
+        if (!have_beta) {
+          CHK(k_spmv_full(c, x, w));
+          CHK(v_waxpy(c, n, -1.0, w, b, V));
+        }
+        c->n_cycles++;
+      } else if (guess_check) {
         // test hook: the residual assembled from the multi-vector product must be the true residual of x0
         double diff = 0.0;
         CHK(comm_halo(c, x));
@@ -1058,7 +1156,8 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
         CHK(v_norm2(c, n, w, &diff));
         if (!(diff <= 1e-10 * bn)) return cfdh_fail(c, CFDH_E_STATE, "projected guess: |(b - J x0) - (b - W y)| = %.3e |b|", diff / bn);
       }
-      CHK(v_norm2(c, n, V, &beta));
+      if (pro_pending) { beta = beta_pro; have_beta = true; }  // read back with the "used" flag
+      if (!have_beta) CHK(v_norm2(c, n, V, &beta));
       c->ksp_last_relres = beta / bn;
       if (guessed && its == 0 && j_prev == 0) {
         c->n_guess_solves++; c->guess_reduction_sum += beta / bn;
@@ -1079,6 +1178,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
           for (int i = 0; i < j_prev; i++) y[i] = -y[i];
           HIPCHK(c, hipMemcpyAsync(c->ky.p, y.data(), sizeof(double) * j_prev, hipMemcpyHostToDevice, c->stream));
           CHK(v_lincomb(c, n, Z, (int)ld, j_prev, c->ky.p, x));
+          kept_copy = false;
           HIPCHK(c, hipStreamSynchronize(c->stream));
           est_prev = beta_start;  // do not trip again on the restored iterate
           continue;
@@ -1112,7 +1212,9 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
     if (its >= o.ksp_max_it) { reason = -3; break; }
     if (!std::isfinite(beta)) { reason = -9; break; }
     if (first) CHK(v_scale_to(c, n, 1.0 / beta, b, V));
+    else if (pro_pending && !guess_check) { /* scaled on the device, queued ahead of the read-back */ }
     else CHK(v_scale(c, n, 1.0 / beta, V));
+    pro_pending = false;
     if (use32) CHK(v_store32(c, n, V, V32));
     first = false;
     std::fill(g.begin(), g.end(), 0.0);
@@ -1147,9 +1249,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
     auto launch = [&](int jj) -> int {
       double *vj = V + (size_t)jj * ld, *zj = Z + (size_t)jj * ld, *vn = V + (size_t)(jj + 1) * ld;
       double *slot = c->h_ring_dev + (size_t)(jj % cfdh_ctx::KRING) * rs;
-      CHK(cfdh_pc_apply(c, vj, zj));
-      CHK(comm_halo(c, zj));
-      CHK(k_spmv_full(c, zj, w));
+      CHK(pc_then_product(c, vj, zj, w));
       // classical Gram-Schmidt (PETSc's default for (F)GMRES): h = [V^T w ; w.w] comes from ONE fused multi-dot
       if (use32) {
         // the same Gram-Schmidt step against the fp32 copy: h = V32^T w, v_{j+1} = (w - V32 h) / |w - V32 h| with the norm
@@ -1180,7 +1280,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
       // process: everything launched if that may finish the solve / the cycle, otherwise all but the newest
       int upto = jl;
       if (!sync_now && jl - j > 1 && jl < maxl && need > jl - j) upto = jl - 1;
-      c->n_host_sync++;
+      c->n_host_sync++; c->n_iter_sync++;
       HIPCHK(c, hipEventSynchronize(c->ev_ring[(upto - 1) % cfdh_ctx::KRING]));
       for (; j < upto && !done; ) {
         const double *hs = c->h_ring + (size_t)(j % cfdh_ctx::KRING) * rs;
@@ -1208,12 +1308,13 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
           // in terms of w: h += s h2, |w''| = s |vn|.  The coefficients and the squared norm of the corrected vector travel
           // in ONE reduction over the ranks: [h2 ; vn.vn] from one fused multi-dot, |vn - V h2|^2 = vn.vn - |h2|^2 (the basis is
           // orthonormal to round-off here -- the fp32 copy measures its norm instead)
-          if (jl > j + 1) { c->n_krylov_discarded += jl - (j + 1); jl = j + 1; }  // what ran ahead used the unrefined vector
+          // what ran ahead used the unrefined vector: it is launched again, and its ring slots are not consumed by this batch
+          if (jl > j + 1) { c->n_krylov_discarded += jl - (j + 1); jl = j + 1; upto = jl; }
           CHK(v_multidot(c, n, V, (int)ld, j + 1, vn, hd + (m + 2), true));
           CHK(v_multiaxpy(c, n, V, (int)ld, j + 1, hd + (m + 2), vn));
           if (use32) CHK(v_norm_to_dev(c, n, vn, hd + 2 * (m + 2)));
           HIPCHK(c, hipMemcpyAsync(c->h_pinned, hd + (m + 2), sizeof(double) * (m + 4), hipMemcpyDeviceToHost, c->stream));
-          c->n_host_sync++;
+          c->n_host_sync++; c->n_iter_sync++;
           HIPCHK(c, hipStreamSynchronize(c->stream));
           // scale of the first pass, formed exactly as gs_update_normalize_kernel forms it (the device word s_dev may belong to
           // an iteration that ran ahead by now); the fp32 path measured it: slot word j + 2
@@ -1273,7 +1374,12 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
     double *ystage = c->h_ring + c->h_ring_stride * cfdh_ctx::KRING;
     for (int i = 0; i < j; i++) ystage[i] = y[i];
     HIPCHK(c, hipMemcpyAsync(c->ky.p, ystage, sizeof(double) * j, hipMemcpyHostToDevice, c->stream));
-    CHK(v_lincomb(c, n, Z, (int)ld, j, c->ky.p, x));
+    // lean path: the update of a cycle that converged by the recurrence also writes the copy guess_store would make (a second
+    // store instead of a pass over x) where that slot is free; any other update of x leaves the copy to guess_store
+    double *keep = (lean_solve && done && reason == 0 && its < o.ksp_max_it) ? guess_store_target(c) : nullptr;
+    if (keep) CHK(v_lincomb_keep(c, n, Z, (int)ld, j, c->ky.p, x, keep));
+    else CHK(v_lincomb(c, n, Z, (int)ld, j, c->ky.p, x));
+    kept_copy = keep != nullptr;
     est_prev = std::fabs(g[j]);
     j_prev = j;
     (void)done;
@@ -1282,7 +1388,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
   *its_out = its;
   *reason_out = reason;
   if (gslot >= 0 && gslot < cfdh_ctx::GUESS_NEWTON) c->guess_last_its[gslot] = its;
-  if (reason > 0) CHK(guess_store(c, x));
+  if (reason > 0) CHK(guess_store(c, x, kept_copy));
   return 0;
 }
 
@@ -1351,8 +1457,10 @@ int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st) {
   CHK(comm_halo(c, c->x.p));
   double t0 = wall_ms();
   CHK(k_assemble(c, c->x.p, 1));
-  double fn;
-  CHK(v_norm2(c, n, c->F.p, &fn));
+  const bool lean = lean_newton(c);
+  double fn, ns_nrm = 0.0, ns_abs = 0.0;
+  if (lean) CHK(k_fnorm_nulltest(c, n, c->F.p, &fn, &ns_nrm, &ns_abs));  // |F| and the null-space numbers below: one read-back
+  else CHK(v_norm2(c, n, c->F.p, &fn));
   st->ms_assemble += wall_ms() - t0;
   st->fnorm0 = fn;
   // constant-pressure null space (MatNullSpaceTest: |J n| < 1e-7 for the unit vector n).  PETSc's bound is absolute; on a
@@ -1360,8 +1468,8 @@ int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st) {
   // do-nothing outlets: the pressure level is fixed, yet the test says singular and the projected solve stagnates at 2e-2).
   // The vector is therefore accepted only if it is also small relative to |J| n.
   {
-    double nrm, absnrm;
-    CHK(k_nullspace_test(c, &nrm, &absnrm));
+    double nrm = ns_nrm, absnrm = ns_abs;
+    if (!lean) CHK(k_nullspace_test(c, &nrm, &absnrm));
     const double np = c->nranks > 1 ? c->nvo_global : (double)nvo;
     const int sing = ((nrm / std::sqrt(np)) < 1e-7 && nrm <= 1e-6 * absnrm) ? 1 : 0;
     if (sing != c->singular) { c->singular = sing; c->pc_valid = false; }
@@ -1443,13 +1551,15 @@ int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st) {
     else if (o.pc_refresh == 0 && kits > (3 * c->pc_its_ref) / 2 + 5) force_refresh = true;
     // backtracking line search on 1/2 |F|^2 (Dennis-Schnabel, alpha = 1e-4)
     t0 = wall_ms();
-    double lam = 1.0, fnew = 0.0;
+    double lam = 1.0, fnew = 0.0, dn = 0.0, xn = 0.0;
     bool ok = false;
     for (int ls = 0; ls < 40; ls++) {
       CHK(v_waxpy(c, n, -lam, d, x, xt));
       CHK(comm_halo(c, xt));
       CHK(k_assemble(c, xt, expect_converged ? 2 : 1));  // residual (and Jacobian) at the trial point in one pass
-      CHK(v_norm2(c, n, c->F.p, &fnew));
+      // lean path: |F(x_t)|, |d| and |x_t| in one reduction and one read-back
+      if (lean) { double t3[3]; CHK(v_norm2_triple(c, n, c->F.p, d, xt, t3)); fnew = t3[0]; dn = t3[1]; xn = t3[2]; }
+      else CHK(v_norm2(c, n, c->F.p, &fnew));
       if (std::isfinite(fnew) && (fnew * fnew <= fn * fn * (1.0 - 2.0e-4 * lam) || fnew < o.snes_atol)) { ok = true; break; }
       double l2 = std::isfinite(fnew) ? fn * fn * lam * lam / (2.0 * (0.5 * fnew * fnew - 0.5 * fn * fn + fn * fn * lam)) : 0.0;
       if (!(l2 > 0.1 * lam)) l2 = 0.1 * lam;
@@ -1458,8 +1568,7 @@ int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st) {
     }
     st->ms_assemble += wall_ms() - t0;
     if (!ok) { reason = CFDH_DIVERGED_LINE_SEARCH; break; }
-    double dn, xn;
-    CHK(v_norm2_pair(c, n, d, xt, &dn, &xn));
+    if (!lean) CHK(v_norm2_pair(c, n, d, xt, &dn, &xn));
     if (o.verbose) fprintf(stderr, "[cfdh]     step length %.3e, |dx| = %.3e, |x| = %.3e, %d FGMRES iterations\n", lam, dn, xn, kits);
     std::swap(c->x.p, c->xt.p);
     x = c->x.p; xt = c->xt.p;

@@ -280,6 +280,11 @@ int cfdh_get_pcd_operator(cfdh_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t 
 /* z = P^-1 r with the current preconditioner (built, and for pc_type 2 with K assembled, at the current state when needed) on the
  * assembled Jacobian; r, z monolithic [gdim*nv | nv] as for cfdh_spmv.  Exposed for parity tests. */
 int cfdh_apply_preconditioner(cfdh_ctx *ctx, const double *r, double *z);
+/* The operator of one FGMRES iteration, launched exactly as the solver launches it: z = P^-1 r, then w = J z on the solver's
+ * stream (r, z as for cfdh_apply_preconditioner, w as y of cfdh_spmv).  On the lean solve path (environment CFDH_SOLVE_LEAN, default
+ * on, read by cfdh_create; 0 selects the general paths) the product reuses A01 z_p from the preconditioner application instead of
+ * reading that block again.  Exposed for tests. */
+int cfdh_apply_operator(cfdh_ctx *ctx, const double *r, double *z, double *w);
 
 /* ---- read-only view of the built preconditioner (parity tests) ---------------------------------------------------------
  * hier: which hierarchy; level: 0 = finest (ignored for CFDH_AMG_HIER_H, which has one level). */
@@ -477,6 +482,10 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 29: nodes per cell;
  * 30 + l / 40 + l: rows / entries of level l of the velocity hierarchy, 50 + l / 60 + l: of the pressure hierarchy (l < 10, 0 past the end);
  * 70: linear solves that started from a projected initial guess (cfdh_options.ksp_guess), 71: their mean |r0| / |b| in units of 1e-6;
+ * 84: FGMRES cycles whose true residual was read back, 86: linear solves whose prologue projected an initial guess (used or not) -- both
+ * reset with 13..17, like 87: the host synchronisations inside the FGMRES cycles (one per batch of iterations the host processes, one
+ * per re-orthogonalised vector); 85: 1 when the lean solve path is switched on (CFDH_SOLVE_LEAN);
+ * 88 / 89: rank found in, and size of, the Gram system of the last projected initial guess (-1 / 0: none yet);
  * 74: preconditioner builds since cfdh_create, 75: 1 while the preconditioner is valid (built, not invalidated since), 76: 1 when the
  * last null-space test of cfdh_solve_step found the constant pressure in the null space of the Jacobian, 77: formulation (CFDH_FORM_*),
  * 78: Schur approximation in use (cfdh_options.pc_type: 0 SELFP, 1 Cahouet-Chabard, 2 PCD), 79: Eisenstat-Walker forcing version */
