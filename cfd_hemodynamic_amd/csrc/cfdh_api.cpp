@@ -88,6 +88,18 @@ static int create_ctx(cfdh_ctx **out, int device, int gdim, int etype, int64_t n
   cfdh_default_options(&c->opt);
   { const char *e = getenv("CFDH_NO_GRAPH"); c->use_graph = !(e && e[0] == '1'); }
   { const char *e = getenv("CFDH_SOLVE_LEAN"); c->lean = !(e && e[0] == '0'); }  // 0: the solve paths without the lean prologue / epilogue / kept coupling product (A/B runs, tests)
+  {
+    cfdh_ctx::SolveEnv &v = c->env;
+    const char *e;
+    if ((e = getenv("CFDH_KRYLOV_FP32"))) v.krylov_fp32 = atoi(e);
+    v.guess_check = getenv("CFDH_GUESS_CHECK") != nullptr;
+    e = getenv("CFDH_NO_ATTAINABLE_STOP"); v.no_attainable_stop = e && e[0] == '1';
+    if ((e = getenv("CFDH_GS_REFINE_FROM"))) v.gs_refine_from = atoi(e);
+    if ((e = getenv("CFDH_KSP_LAG"))) v.ksp_lag = atoi(e);
+    if ((e = getenv("CFDH_GS_ETA2"))) v.gs_eta2 = atof(e);
+    if ((e = getenv("CFDH_L_CYCLES"))) v.l_cycles = atoi(e);
+    if ((e = getenv("CFDH_A_CYCLES"))) v.a_cycles = atoi(e);
+  }
   // No hipGraph replay under a rocprofiler-sdk tool on a HIP runtime >= 7.2.  That runtime submits the kernel packets of a graph
   // launch with ONE doorbell; ROCr's intercepted queue hands such a batch to the profiler's queue interceptor as (pointer into
   // the ring, packet count) without splitting it at the ring's wrap-around, and the interceptor walks `count` packets linearly:

@@ -424,6 +424,17 @@ struct cfdh_ctx {
   // product of the preconditioner keeps q_u = A01 z_p for the Krylov product that follows it, the prologue and epilogue of a
   // linear solve and the norms of a Newton iteration come back in one read each (cfdh_solver.cpp).
   bool lean = true;
+  // What the solve and the preconditioner application take from the environment, read once by cfdh_create next to
+  // CFDH_SOLVE_LEAN and CFDH_NO_GRAPH (table in INTEGRATION.md): set them before the context they are meant for is created.
+  struct SolveEnv {
+    int krylov_fp32 = 1;              // CFDH_KRYLOV_FP32: fp32 copy of the basis -- 0 never, 1 long cycles, 2 always
+    bool guess_check = false;         // CFDH_GUESS_CHECK: test hook on the residual of the projected guess
+    bool no_attainable_stop = false;  // CFDH_NO_ATTAINABLE_STOP=1
+    int gs_refine_from = -1;          // CFDH_GS_REFINE_FROM: second Gram-Schmidt pass from this vector on (< 0: the watchdog decides)
+    int ksp_lag = KRING - 3;          // CFDH_KSP_LAG: iterations launched ahead of the host at most
+    double gs_eta2 = 1e-6;            // CFDH_GS_ETA2: refine when |w'|^2 <= eta2 |w|^2
+    int l_cycles = 1, a_cycles = 1;   // CFDH_L_CYCLES, CFDH_A_CYCLES: V-cycles per pressure / velocity solve of the preconditioner
+  } env;
   dbuf<double> qu;                           // [2 nvo] A01 z_p of the last preconditioner application; its address is baked into the captured graphs
   long long n_guess_projections = 0;         // linear solves whose prologue projected a guess, used or not (cfdh_info 86), reset likewise
   int guess_last_rank = -1, guess_last_k = 0;  // rank and size of the last Gram system of a projected guess (cfdh_info 88, 89)

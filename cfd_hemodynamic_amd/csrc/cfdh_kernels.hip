@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_krylov_host.hpp"
 #include "cfdh_quad_tri.h"
 
 #define TPB 256
@@ -2221,8 +2222,7 @@ __global__ __launch_bounds__(TPB) void gs_update_normalize_kernel(int n, const d
   const double ww = h[nvec];
   double hh2 = 0.0;
   for (int v = 0; v < nvec; v++) hh2 += h[v] * h[v];
-  const double nrm2 = ww - hh2;
-  const double s = (nrm2 > 0.0 && nrm2 <= ww) ? sqrt(nrm2) : sqrt(ww);  // cancellation: any positive scale, the caller re-orthogonalises
+  const double s = cfdh_krylov::gs_scale(ww, hh2);  // cancellation: any positive scale, the caller re-orthogonalises
   const double inv = s > 0.0 ? 1.0 / s : 0.0;
   if (blockIdx.x == 0 && threadIdx.x == 0) *s_out = s;
   // two consecutive entries per lane (16-B loads: ld is even and all vectors are 16-B aligned); same summation order per entry
@@ -2385,58 +2385,13 @@ int v_lincomb(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const doubl
 // ---- lean solve path: prologue and epilogue of a linear solve with one read-back each (cfdh_solver.cpp) ----------------------
 // Host-mapped words behind CFDH_MIRROR_OFF: [0] squared norm of the residual, [1] 1 when the projected guess is used, [2] rank
 // of the Gram system, [3 .. 3 + k) the coefficients y.
-// The k x k Gram system of the projected guess (k <= 8), solved by one lane with the pivoted Cholesky and the two drop tests of
-// the host code in guess_project: hd[8 i + q] = W_q . W_i (i < k), hd[8 k + q] = W_q . b.  Rank 0 or a non-finite y: y = 0, not used.
+// The k x k Gram system of the projected guess (k <= 8), solved by one lane: cfdh_krylov::gram_solve, the same function the
+// general path calls on the host.
 __global__ void gram_solve_kernel(int k, const double *__restrict__ hd, double *__restrict__ y, double *__restrict__ info) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double G[64], Lc[64], dg[8], g[8], yy[8], t[8];
-  int piv[8];
-  bool taken[8];
-  for (int i = 0; i < k; i++) {
-    for (int q = 0; q < k; q++) { G[q * k + i] = hd[i * 8 + q]; Lc[q * k + i] = 0.0; }
-    g[i] = hd[k * 8 + i]; yy[i] = 0.0; taken[i] = false;
-  }
-  double dmax0 = 0.0;
-  bool ok = true;
-  for (int i = 0; i < k; i++) {
-    dg[i] = G[i * k + i];
-    if (!isfinite(dg[i])) ok = false;
-    if (i == 0 || dg[i] > dmax0) dmax0 = dg[i];
-  }
-  ok = ok && dmax0 > 0.0 && isfinite(dmax0);
   int r = 0;
-  if (ok) {
-    for (int it = 0; it < k; it++) {
-      int p = -1;
-      for (int i = 0; i < k; i++) if (!taken[i] && (p < 0 || dg[i] > dg[p])) p = i;
-      if (p < 0 || !(dg[p] > 1e-10 * G[p * k + p]) || !(dg[p] > 1e-14 * dmax0)) break;
-      taken[p] = true;
-      const int rr = r;
-      piv[r++] = p;
-      const double lpp = sqrt(dg[p]);
-      Lc[p * k + rr] = lpp;
-      for (int i = 0; i < k; i++) {
-        if (taken[i]) continue;
-        double sacc = G[i * k + p];
-        for (int q = 0; q < rr; q++) sacc -= Lc[i * k + q] * Lc[p * k + q];
-        Lc[i * k + rr] = sacc / lpp;
-        dg[i] -= Lc[i * k + rr] * Lc[i * k + rr];
-      }
-    }
-    for (int a = 0; a < r; a++) {
-      double sacc = g[piv[a]];
-      for (int q = 0; q < a; q++) sacc -= Lc[piv[a] * k + q] * t[q];
-      t[a] = sacc / Lc[piv[a] * k + a];
-    }
-    for (int a = r - 1; a >= 0; a--) {
-      double sacc = t[a];
-      for (int q = a + 1; q < r; q++) sacc -= Lc[piv[q] * k + a] * yy[piv[q]];
-      yy[piv[a]] = sacc / Lc[piv[a] * k + a];
-    }
-  }
-  bool used = ok && r > 0;
-  for (int i = 0; i < k; i++) if (!isfinite(yy[i])) used = false;
-  for (int i = 0; i < k; i++) { const double v = used ? yy[i] : 0.0; y[i] = v; info[3 + i] = v; }
+  const bool used = cfdh_krylov::gram_solve(k, hd, y, &r);
+  for (int i = 0; i < k; i++) info[3 + i] = y[i];
   info[1] = used ? 1.0 : 0.0;
   info[2] = (double)r;
 }

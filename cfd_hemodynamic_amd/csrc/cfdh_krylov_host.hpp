@@ -1,0 +1,157 @@
+// The arithmetic of the linear solve that needs no device: the Gram system of the projected guess, the least-squares problem of
+// the Arnoldi recurrence, the scale of a Gram-Schmidt pass and the launch-ahead policy.  Plain C++17 without HIP and without the
+// context, so that the CPU tests compile it with the host compiler (tests/krylov_host_shim.cpp); gram_solve and gs_scale are also
+// called from kernels (cfdh_kernels.hip), which is what keeps the host and the device to ONE copy of each.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#ifdef __HIPCC__
+#define CFDH_HD __host__ __device__
+#else
+#define CFDH_HD
+#endif
+
+namespace cfdh_krylov {
+
+// The k x k Gram system of the projected guess (k <= 8): y = argmin |b - W y| from the normal equations, by a pivoted Cholesky
+// that drops directions which have become numerically dependent -- a pivot whose remaining diagonal is not above 1e-10 of its
+// own G_pp, or not above 1e-14 of the largest diagonal entry.  Device layout: hd[8 i + q] = W_q . W_i (i < k), hd[8 k + q] = W_q . b.
+// Dropped directions get y = 0.  Rank 0, a non-finite diagonal or a non-finite y: y = 0 and the guess is not used.
+CFDH_HD inline bool gram_solve(int k, const double *hd, double *y, int *rank) {
+  double G[64], Lc[64], dg[8], g[8], yy[8], t[8];
+  int piv[8];
+  bool taken[8];
+  for (int i = 0; i < k; i++) {
+    for (int q = 0; q < k; q++) { G[q * k + i] = hd[i * 8 + q]; Lc[q * k + i] = 0.0; }
+    g[i] = hd[k * 8 + i]; yy[i] = 0.0; taken[i] = false;
+  }
+  double dmax0 = 0.0;
+  bool ok = true;
+  for (int i = 0; i < k; i++) {
+    dg[i] = G[i * k + i];
+    if (!std::isfinite(dg[i])) ok = false;
+    if (i == 0 || dg[i] > dmax0) dmax0 = dg[i];
+  }
+  ok = ok && dmax0 > 0.0 && std::isfinite(dmax0);
+  int r = 0;
+  if (ok) {
+    for (int it = 0; it < k; it++) {
+      int p = -1;
+      for (int i = 0; i < k; i++) if (!taken[i] && (p < 0 || dg[i] > dg[p])) p = i;
+      if (p < 0 || !(dg[p] > 1e-10 * G[p * k + p]) || !(dg[p] > 1e-14 * dmax0)) break;
+      taken[p] = true;
+      const int rr = r;
+      piv[r++] = p;
+      const double lpp = std::sqrt(dg[p]);
+      Lc[p * k + rr] = lpp;
+      for (int i = 0; i < k; i++) {
+        if (taken[i]) continue;
+        double sacc = G[i * k + p];
+        for (int q = 0; q < rr; q++) sacc -= Lc[i * k + q] * Lc[p * k + q];
+        Lc[i * k + rr] = sacc / lpp;
+        dg[i] -= Lc[i * k + rr] * Lc[i * k + rr];
+      }
+    }
+    for (int a = 0; a < r; a++) {
+      double sacc = g[piv[a]];
+      for (int q = 0; q < a; q++) sacc -= Lc[piv[a] * k + q] * t[q];
+      t[a] = sacc / Lc[piv[a] * k + a];
+    }
+    for (int a = r - 1; a >= 0; a--) {
+      double sacc = t[a];
+      for (int q = a + 1; q < r; q++) sacc -= Lc[piv[q] * k + a] * yy[piv[q]];
+      yy[piv[a]] = sacc / Lc[piv[a] * k + a];
+    }
+  }
+  bool used = ok && r > 0;
+  for (int i = 0; i < k; i++) if (!std::isfinite(yy[i])) used = false;
+  for (int i = 0; i < k; i++) y[i] = used ? yy[i] : 0.0;
+  *rank = r;
+  return used;
+}
+
+// Scale of the first Gram-Schmidt pass from the reduced coefficients: s = sqrt(w.w - |h|^2), or, when that difference has
+// cancelled (not positive, or above w.w), any positive scale -- the caller re-orthogonalises such a vector.
+CFDH_HD inline double gs_scale(double ww, double hh2) {
+  const double nrm2 = ww - hh2;
+  return (nrm2 > 0.0 && nrm2 <= ww) ? std::sqrt(nrm2) : std::sqrt(ww);
+}
+
+// min |beta e_1 - H y| of the Arnoldi recurrence, column by column with Givens rotations (host only: it owns its storage).
+// Column j of H sits at H[j (m + 1) ..], already rotated.
+struct ArnoldiLsq {
+  int m;
+  std::vector<double> H, cs, sn, g, y;
+  explicit ArnoldiLsq(int m_) : m(m_), H((size_t)(m_ + 1) * m_, 0.0), cs(m_), sn(m_), g(m_ + 1), y(m_) {}
+  void start(double beta) {
+    std::fill(g.begin(), g.end(), 0.0);
+    g[0] = beta;
+  }
+  // column j = [h_0 .. h_j ; hnorm].  False on breakdown: the new diagonal entry is not positive or not finite.
+  bool add_column(int j, const double *h, double hnorm) {
+    double *Hj = &H[(size_t)j * (m + 1)];
+    for (int i = 0; i <= j; i++) Hj[i] = h[i];
+    Hj[j + 1] = hnorm;
+    for (int i = 0; i < j; i++) {
+      const double t = cs[i] * Hj[i] + sn[i] * Hj[i + 1];
+      Hj[i + 1] = -sn[i] * Hj[i] + cs[i] * Hj[i + 1];
+      Hj[i] = t;
+    }
+    const double d = std::hypot(Hj[j], Hj[j + 1]);
+    if (!(d > 0) || !std::isfinite(d)) return false;
+    cs[j] = Hj[j] / d; sn[j] = Hj[j + 1] / d;
+    Hj[j] = d; Hj[j + 1] = 0.0;
+    g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
+    return true;
+  }
+  // residual norm of the recurrence after j columns
+  double residual(int j) const { return std::fabs(g[j]); }
+  // y = H_j^-1 g for the first j columns
+  const double *solve(int j) {
+    for (int i = j - 1; i >= 0; i--) {
+      double s = g[i];
+      for (int k = i + 1; k < j; k++) s -= H[(size_t)k * (m + 1) + i] * y[k];
+      y[i] = s / H[(size_t)i * (m + 1) + i];
+    }
+    return y.data();
+  }
+};
+
+// How far the iterations of a cycle are launched ahead of the host's bookkeeping.  `need` is the number of iterations still
+// expected, counted from the last one the host has processed: from the history alone (e_its, the length of the last solve with
+// the same Newton index; 0: unknown) before any residual of this cycle is known, afterwards the smaller of the rate-based
+// prediction and what the history leaves.
+struct LaunchAhead {
+  int need = 1;
+  double res_hist[4] = {0, 0, 0, 0};
+  int nhist = 0;
+  int e_its = 0;
+  CFDH_HD void start(double beta, int e_its_, int its) {
+    e_its = e_its_;
+    need = std::max(1, std::min(e_its - its - 2, 3));
+    res_hist[0] = beta; res_hist[1] = res_hist[2] = res_hist[3] = 0.0;
+    nhist = 1;
+  }
+  // iterations wanted in flight (one short of the prediction when it is long: the last predicted iteration is confirmed before
+  // anything follows it)
+  CFDH_HD int in_flight(bool sync_now, int lagmax) const {
+    return sync_now ? 1 : std::max(1, std::min(need - (need >= 4 ? 1 : 0), lagmax + 1));
+  }
+  // the host processes everything launched if that may finish the solve / the cycle, otherwise all but the newest
+  CFDH_HD int process_upto(int j, int jl, int maxl, bool sync_now) const {
+    return (!sync_now && jl - j > 1 && jl < maxl && need > jl - j) ? jl - 1 : jl;
+  }
+  // iterations the tolerance is away at the contraction factor of the last (up to three) iterations
+  CFDH_HD void observe(double res, double tol, int its) {
+    if (nhist < 4) res_hist[nhist++] = res;
+    else { res_hist[0] = res_hist[1]; res_hist[1] = res_hist[2]; res_hist[2] = res_hist[3]; res_hist[3] = res; }
+    const double rho = std::pow(res / res_hist[0], 1.0 / (nhist - 1));
+    int n_rem = (rho > 0.0 && rho < 0.97) ? (int)std::ceil(std::log(tol / res) / std::log(rho)) : (1 << 20);
+    if (nhist == 2) n_rem = std::min(n_rem, 3);  // one sample of the rate: a short look ahead only
+    need = std::max(1, e_its > 0 ? std::min(n_rem, std::max(e_its - its, 1) + 2) : n_rem);
+  }
+};
+
+}  // namespace cfdh_krylov

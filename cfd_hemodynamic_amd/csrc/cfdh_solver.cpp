@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_krylov_host.hpp"
 
 int cfdh_host_threads();
 
@@ -588,6 +589,35 @@ static bool lean_scope(const cfdh_ctx *c) { return lean_newton(c) && (c->opt.pc_
 // the options).
 static bool lean_keep_qu(const cfdh_ctx *c) { return lean_scope(c) && c->opt.schur_full != 0 && !c->singular && c->qu.p != nullptr; }
 
+// Rank-local pressure cycle t = V(L) y (y in pu1, t in pu2) and the combination out = alpha t + beta zH (r on the flagged rows;
+// out2, if given, receives a second copy).  The combination runs in the epilogue of the cycle's last kernel when the fused cycle
+// is used, as a kernel of its own otherwise.  CFDH_L_CYCLES = k > 1 (experiments, tests): k V-cycles as the stationary iteration
+// t += V(y - L t).
+static int pressure_cycle_combine(cfdh_ctx *c, double alpha, double beta, const double *zH, const double *r, const unsigned char *flag,
+                                  double *out, double *out2) {
+  const int nvo = c->nvo;
+  if (c->env.l_cycles > 1 && c->hL.lev.size() >= 1 && c->hL.lev[0]->A.val.p) {
+    AmgLevel *L0 = c->hL.lev[0];
+    CHK(k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p));
+    for (int cyc = 1; cyc < c->env.l_cycles; cyc++) {
+      CHK(k_csr_spmv(c, L0->A, c->pu2.p, L0->r.p, 1, c->pu1.p));   // r = y - L t
+      CHK(k_amg_vcycle(c, c->hL, L0->r.p, L0->d0.p));
+      CHK(v_axpy(c, nvo, 1.0, L0->d0.p, c->pu2.p));
+    }
+    CHK(k_cc_combine(c, nvo, alpha, beta, c->pu2.p, zH, r, flag, out));
+    return out2 ? v_copy(c, nvo, out, out2) : 0;
+  }
+  c->epi.on = true; c->epi.done = false;
+  c->epi.alpha = alpha; c->epi.beta = beta; c->epi.zH = zH; c->epi.r = r;
+  c->epi.pbc = flag; c->epi.out = out;
+  const int rc = k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p);
+  c->epi.on = false;
+  CHK(rc);
+  if (!c->epi.done) return k_cc_combine(c, nvo, alpha, beta, c->pu2.p, zH, r, flag, out, out2);
+  c->epi.done = false;
+  return out2 ? v_copy(c, nvo, out, out2) : 0;
+}
+
 static int pcd_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
   const int nvo = c->nvo, nu = c->dim * nvo;
   const double *ru = r, *rp = r + nu;
@@ -600,28 +630,8 @@ static int pcd_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
     case 1:
       if (!upper) CHK(k_spmv_block(c, 3, c->pu0.p, c->pp0.p, rp, 0));   // t_p = r_p - A10 y_u
       return k_pcd_apply(c, upper ? rp : c->pp0.p, c->pu1.p);
-    case 2: {
-      // CFDH_L_CYCLES = k > 1: k V-cycles on A_p (stationary iteration), as for pc_type 1 -- the converged A_p solve of the tests
-      static const int lcycles = getenv("CFDH_L_CYCLES") ? atoi(getenv("CFDH_L_CYCLES")) : 1;
-      if (lcycles > 1 && c->hL.lev.size() >= 1 && c->hL.lev[0]->A.val.p) {
-        AmgLevel *L0 = c->hL.lev[0];
-        CHK(k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p));
-        for (int cyc = 1; cyc < lcycles; cyc++) {
-          CHK(k_csr_spmv(c, L0->A, c->pu2.p, L0->r.p, 1, c->pu1.p));
-          CHK(k_amg_vcycle(c, c->hL, L0->r.p, L0->d0.p));
-          CHK(v_axpy(c, nvo, 1.0, L0->d0.p, c->pu2.p));
-        }
-        return k_cc_combine(c, nvo, 1.0, c->mu, c->pu2.p, c->pcd_t.p, c->pcd_q.p, c->pcd_flag.p, zp);
-      }
-      c->epi.on = true; c->epi.done = false;
-      c->epi.alpha = 1.0; c->epi.beta = c->mu; c->epi.zH = c->pcd_t.p; c->epi.r = c->pcd_q.p;
-      c->epi.pbc = c->pcd_flag.p; c->epi.out = zp;
-      const int rc = k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p);
-      c->epi.on = false;
-      CHK(rc);
-      if (c->epi.done) { c->epi.done = false; return 0; }
-      return k_cc_combine(c, nvo, 1.0, c->mu, c->pu2.p, c->pcd_t.p, c->pcd_q.p, c->pcd_flag.p, zp);
-    }
+    case 2:  // CFDH_L_CYCLES > 1: the converged A_p solve of the tests
+      return pressure_cycle_combine(c, 1.0, c->mu, c->pcd_t.p, c->pcd_q.p, c->pcd_flag.p, zp, nullptr);
     case 3:
       if (c->opt.schur_full) {
         if (lean_keep_qu(c)) CHK(k_spmv_a01_keep(c, zp, c->pu0.p, ru, c->qu.p));
@@ -679,7 +689,9 @@ static int pc_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
         return 0;
       case 10:
         return k_dl0_down(c, c->pcw.p);  // pre-smoothing of the owned rows, owned part of the coarse right-hand side
-      case 2:
+      case 2: {
+        double *zp_halo = (multi && c->opt.schur_full) ? c->pcw.p + nu : nullptr;  // z_p also into the halo scratch vector
+        const double *tp = upper ? rp : c->pp0.p;
         if (dist) {
           CHK(k_dl0_up(c, c->pu2.p));    // replicated coarse cycle, prolongation, post-smoothing of the owned rows
         } else if (global_p) {
@@ -687,36 +699,10 @@ static int pc_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
           CHK(k_amg_vcycle(c, c->hLg, c->gp_rhs.p, c->gp_sol.p));  // the same global V-cycle on every rank
           CHK(k_gather_global(c, nvo, c->gp_l2g.p, c->gp_sol.p, c->pu2.p));
         } else {
-          // rank-local cycle: the combination below runs in the epilogue of its last kernel when the fused cycle is used
-          static const int lcycles = getenv("CFDH_L_CYCLES") ? atoi(getenv("CFDH_L_CYCLES")) : 1;
-          if (lcycles > 1 && c->hL.lev.size() >= 1 && c->hL.lev[0]->A.val.p) {
-            // experiment: k V-cycles on the pressure Laplacian (stationary iteration x += V(b - L x))
-            AmgLevel *L0 = c->hL.lev[0];
-            CHK(k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p));
-            for (int cyc = 1; cyc < lcycles; cyc++) {
-              CHK(k_csr_spmv(c, L0->A, c->pu2.p, L0->r.p, 1, c->pu1.p));   // r = y - L t
-              CHK(k_amg_vcycle(c, c->hL, L0->r.p, L0->d0.p));
-              CHK(v_axpy(c, nvo, 1.0, L0->d0.p, c->pu2.p));
-            }
-            CHK(k_cc_combine(c, nvo, c->cc_alpha, c->cc_beta, c->pu2.p, c->pp1.p, upper ? rp : c->pp0.p, c->ccPbc.p, zp));
-            if (multi && c->opt.schur_full) CHK(v_copy(c, nvo, zp, c->pcw.p + nu));
-            return 0;
-          }
-          c->epi.on = true; c->epi.done = false;
-          c->epi.alpha = c->cc_alpha; c->epi.beta = c->cc_beta; c->epi.zH = c->pp1.p; c->epi.r = upper ? rp : c->pp0.p;
-          c->epi.pbc = c->ccPbc.p; c->epi.out = zp;
-          const int rc = k_amg_vcycle(c, c->hL, c->pu1.p, c->pu2.p);
-          c->epi.on = false;
-          CHK(rc);
+          return pressure_cycle_combine(c, c->cc_alpha, c->cc_beta, c->pp1.p, tp, c->ccPbc.p, zp, zp_halo);
         }
-        if (c->epi.done) {
-          c->epi.done = false;
-          if (multi && c->opt.schur_full) CHK(v_copy(c, nvo, zp, c->pcw.p + nu));  // z_p into the halo scratch vector
-        } else {
-          CHK(k_cc_combine(c, nvo, c->cc_alpha, c->cc_beta, c->pu2.p, c->pp1.p, upper ? rp : c->pp0.p, c->ccPbc.p, zp,
-                           (multi && c->opt.schur_full) ? c->pcw.p + nu : nullptr));
-        }
-        return 0;
+        return k_cc_combine(c, nvo, c->cc_alpha, c->cc_beta, c->pu2.p, c->pp1.p, tp, c->ccPbc.p, zp, zp_halo);
+      }
       case 3:
         if (c->opt.schur_full) {
           // t_u = r_u - A01 z_p (with ghosts); for the overlapping cycle straight into the velocity slots of the halo scratch vector
@@ -731,11 +717,10 @@ static int pc_stage(cfdh_ctx *c, const double *r, double *z, int stage) {
           }
           else {
             CHK(k_amg_vcycle(c, c->hA, c->pu0.p, zu));
-            static const int acycles = getenv("CFDH_A_CYCLES") ? atoi(getenv("CFDH_A_CYCLES")) : 1;
-            if (acycles > 1 && !multi && c->hA.lev[0]->A.val.p) {
+            if (c->env.a_cycles > 1 && !multi && c->hA.lev[0]->A.val.p) {
               // experiment: further V-cycles on the velocity proxy (stationary iteration)
               AmgLevel *L0 = c->hA.lev[0];
-              for (int cyc = 1; cyc < acycles; cyc++) {
+              for (int cyc = 1; cyc < c->env.a_cycles; cyc++) {
                 CHK(k_csr_spmv_ncol(c, L0->A, zu, L0->r.p, 1, c->pu0.p, c->dim));
                 CHK(k_amg_vcycle(c, c->hA, L0->r.p, L0->d0.p));
                 CHK(v_axpy(c, nu, 1.0, L0->d0.p, zu));
@@ -862,6 +847,9 @@ static int pc_then_product(cfdh_ctx *c, const double *r, double *z, double *w) {
   return k_spmv_full(c, z, w);
 }
 
+// leading dimension of the Krylov and guess vectors: even, so that every V_j / Z_j / U_j stays 16-B aligned
+static size_t krylov_ld(const cfdh_ctx *c) { return ((size_t)c->NL + 1) & ~(size_t)1; }
+
 static int ensure_krylov(cfdh_ctx *c);
 int cfdh_apply_operator_dev(cfdh_ctx *c, const double *r, double *z) {
   CHK(ensure_krylov(c));
@@ -871,7 +859,7 @@ int cfdh_apply_operator_dev(cfdh_ctx *c, const double *r, double *z) {
 static int ensure_krylov(cfdh_ctx *c) {
   const int m = c->opt.ksp_restart;
   if (c->kry_m == m && c->kV.p) return 0;
-  const size_t NL = ((size_t)c->NL + 1) & ~(size_t)1;  // even leading dimension: every V_j / Z_j stays 16-B aligned
+  const size_t NL = krylov_ld(c);
   c->pc_graph_valid = false;  // captured graphs hold pointers into V / Z
   HIPCHK(c, c->kV.alloc(NL * (m + 1)));
   HIPCHK(c, c->kZ.alloc(NL * m));
@@ -900,7 +888,7 @@ static int ensure_krylov(cfdh_ctx *c) {
 // cost the SpMVs.  The Krylov workspace is free before the first cycle: V_1.. hold the halo-extended copies, Z_0.. hold W.
 static int guess_ensure(cfdh_ctx *c) {
   const int m = c->opt.ksp_guess;
-  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
+  const size_t ld = krylov_ld(c);
   if (m == c->guess_m && (m == 0 || c->guessU.p)) return 0;
   c->guess_m = m;
   for (int k = 0; k < cfdh_ctx::GUESS_NEWTON; k++) c->guess_cnt[k] = c->guess_head[k] = 0;
@@ -911,14 +899,26 @@ static int guess_ensure(cfdh_ctx *c) {
   return 0;
 }
 
+// the solve in progress belongs to a ring of kept solutions (a Newton index below GUESS_NEWTON, with ksp_guess on)
+static bool guess_ring_valid(const cfdh_ctx *c) {
+  return c->guess_m > 0 && c->guess_slot >= 0 && c->guess_slot < cfdh_ctx::GUESS_NEWTON;
+}
+// kept vectors the projection of this solve can use (0: none, or the Krylov workspace is too small to hold their products)
+static int guess_usable(const cfdh_ctx *c) {
+  return (guess_ring_valid(c) && c->kry_m >= c->guess_m + 1) ? c->guess_cnt[c->guess_slot] : 0;
+}
+// iterations of the last solve with the same Newton index: the expected length of this one (0: unknown)
+static int guess_expected_its(const cfdh_ctx *c) {
+  return (c->guess_slot >= 0 && c->guess_slot < cfdh_ctx::GUESS_NEWTON) ? c->guess_last_its[c->guess_slot] : 0;
+}
+
 static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
   *used = false;
   CHK(guess_ensure(c));
-  const int slot = c->guess_slot, m = c->guess_m;
-  if (m <= 0 || slot < 0 || slot >= cfdh_ctx::GUESS_NEWTON || c->guess_cnt[slot] == 0 || c->kry_m < m + 1) return 0;
-  const int k = c->guess_cnt[slot], n = c->NO;
-  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
-  double *U = c->guessU.p + ld * (size_t)m * slot;  // the ring of this Newton index (order is irrelevant to the projection)
+  const int k = guess_usable(c), n = c->NO;
+  if (k == 0) return 0;
+  const size_t ld = krylov_ld(c);
+  double *U = c->guessU.p + ld * (size_t)c->guess_m * c->guess_slot;  // the ring of this Newton index (order is irrelevant to the projection)
   double *V = c->kV.p, *Z = c->kZ.p, *hd = c->kh.p;
   if (c->nranks > 1) {  // halo-extended copies in V_1.. (the kept vectors hold owned entries only)
     for (int i = 0; i < k; i++) {
@@ -930,8 +930,7 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
   } else {
     CHK(k_spmv_full_multi(c, U, Z, (int)ld, k));  // one pass over the Jacobian for all kept vectors
   }
-  // Gram matrix G = W^T W (column by column) and g = W^T b
-  std::vector<double> G((size_t)k * k), g(k), y(k, 0.0);
+  // Gram system: hd[8 i + q] = W_q . W_i, hd[8 k + q] = W_q . b
   HIPCHK(c, hipMemsetAsync(hd, 0, sizeof(double) * 8 * (size_t)(k + 1), c->stream));
   CHK(v_gram(c, n, Z, (int)ld, k, b, hd));  // one pass over W and b, ONE read-back
   CHK(comm_allreduce_dev(c, hd, 8 * (k + 1), 0));  // ONE reduction over the ranks for the whole Gram system
@@ -939,57 +938,22 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->n_host_sync++;
   c->n_guess_projections++;
-  for (int i = 0; i <= k; i++)
-    for (int q = 0; q < k; q++) (i < k ? G[(size_t)q * k + i] : g[q]) = c->h_pinned[(size_t)i * 8 + q];
+  double gram[8 * 9];  // a copy: the pinned words are reused by the next read-back
+  std::copy(c->h_pinned, c->h_pinned + 8 * (size_t)(k + 1), gram);
   if (c->opt.verbose > 1) {
     double bb = 0.0;
     CHK(v_norm2(c, n, b, &bb));
-    fprintf(stderr, "[cfdh]     guess diag (newton %d): cos(W_i, b) =", slot);
-    for (int i = 0; i < k; i++) fprintf(stderr, " %.6f", g[i] / (std::sqrt(G[(size_t)i * k + i]) * bb));
+    fprintf(stderr, "[cfdh]     guess diag (newton %d): cos(W_i, b) =", c->guess_slot);
+    for (int i = 0; i < k; i++) fprintf(stderr, " %.6f", gram[8 * k + i] / (std::sqrt(gram[9 * i]) * bb));
     fprintf(stderr, "; |W_i|/|b| =");
-    for (int i = 0; i < k; i++) fprintf(stderr, " %.4f", std::sqrt(G[(size_t)i * k + i]) / bb);
+    for (int i = 0; i < k; i++) fprintf(stderr, " %.4f", std::sqrt(gram[9 * i]) / bb);
     fprintf(stderr, "\n");
   }
-  // pivoted Cholesky of G with a relative drop tolerance, then the two triangular solves
-  std::vector<int> piv;
-  std::vector<double> Lc((size_t)k * k, 0.0), dg(k);
-  std::vector<char> taken(k, 0);
-  for (int i = 0; i < k; i++) dg[i] = G[(size_t)i * k + i];
-  const double dmax0 = *std::max_element(dg.begin(), dg.end());
-  c->guess_last_rank = 0; c->guess_last_k = k;
-  if (!(dmax0 > 0.0) || !std::isfinite(dmax0)) return 0;
-  for (int r = 0; r < k; r++) {
-    int p = -1;
-    for (int i = 0; i < k; i++) if (!taken[i] && (p < 0 || dg[i] > dg[p])) p = i;
-    if (p < 0 || !(dg[p] > 1e-10 * G[(size_t)p * k + p]) || !(dg[p] > 1e-14 * dmax0)) break;
-    taken[p] = 1;
-    const int rr = (int)piv.size();
-    piv.push_back(p);
-    const double lpp = std::sqrt(dg[p]);
-    Lc[(size_t)p * k + rr] = lpp;
-    for (int i = 0; i < k; i++) {
-      if (taken[i]) continue;
-      double sacc = G[(size_t)i * k + p];
-      for (int q = 0; q < rr; q++) sacc -= Lc[(size_t)i * k + q] * Lc[(size_t)p * k + q];
-      Lc[(size_t)i * k + rr] = sacc / lpp;
-      dg[i] -= Lc[(size_t)i * k + rr] * Lc[(size_t)i * k + rr];
-    }
-  }
-  const int r = (int)piv.size();
-  c->guess_last_rank = r; c->guess_last_k = k;
-  if (r == 0) return 0;
-  std::vector<double> t(r);
-  for (int a = 0; a < r; a++) {
-    double sacc = g[piv[a]];
-    for (int q = 0; q < a; q++) sacc -= Lc[(size_t)piv[a] * k + q] * t[q];
-    t[a] = sacc / Lc[(size_t)piv[a] * k + a];
-  }
-  for (int a = r - 1; a >= 0; a--) {
-    double sacc = t[a];
-    for (int q = a + 1; q < r; q++) sacc -= Lc[(size_t)piv[q] * k + a] * y[piv[q]];
-    y[piv[a]] = sacc / Lc[(size_t)piv[a] * k + a];
-  }
-  for (int i = 0; i < k; i++) if (!std::isfinite(y[i])) return 0;
+  double y[8];
+  int rank = 0;
+  const bool ok = cfdh_krylov::gram_solve(k, gram, y, &rank);
+  c->guess_last_rank = rank; c->guess_last_k = k;
+  if (!ok) return 0;
   // y travels through the pinned slot behind the read-back ring, as at the end of a cycle: no drain of the stream for a host
   // temporary (the slot is next written at the end of the first cycle, behind events recorded after this copy)
   double *ystage = c->h_ring + c->h_ring_stride * cfdh_ctx::KRING;
@@ -1014,11 +978,10 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
 static int guess_project_lean(cfdh_ctx *c, const double *b, double *x, bool *ran) {
   *ran = false;
   CHK(guess_ensure(c));
-  const int slot = c->guess_slot, m = c->guess_m;
-  if (m <= 0 || slot < 0 || slot >= cfdh_ctx::GUESS_NEWTON || c->guess_cnt[slot] == 0 || c->kry_m < m + 1) return 0;
-  const int k = c->guess_cnt[slot], n = c->NO;
-  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
-  double *U = c->guessU.p + ld * (size_t)m * slot;
+  const int k = guess_usable(c), n = c->NO;
+  if (k == 0) return 0;
+  const size_t ld = krylov_ld(c);
+  double *U = c->guessU.p + ld * (size_t)c->guess_m * c->guess_slot;
   CHK(k_spmv_full_multi(c, U, c->kZ.p, (int)ld, k));
   CHK(v_gram(c, n, c->kZ.p, (int)ld, k, b, c->kh.p));  // every word the solve reads is written: no memset
   CHK(v_guess_combine(c, n, U, c->kZ.p, (int)ld, k, c->kh.p, b, x, c->kV.p));
@@ -1033,16 +996,16 @@ static int guess_project_lean(cfdh_ctx *c, const double *b, double *x, bool *ran
 // nothing.  In a full ring the slot holds the oldest live vector, which must survive a failed solve: guess_store copies.
 static double *guess_store_target(cfdh_ctx *c) {
   const int slot = c->guess_slot, m = c->guess_m;
-  if (m <= 0 || slot < 0 || slot >= cfdh_ctx::GUESS_NEWTON || !c->guessU.p || c->guess_cnt[slot] >= m) return nullptr;
-  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
+  if (!guess_ring_valid(c) || !c->guessU.p || c->guess_cnt[slot] >= m) return nullptr;
+  const size_t ld = krylov_ld(c);
   return c->guessU.p + ld * (size_t)m * slot + (size_t)c->guess_head[slot] * ld;
 }
 
 // keep the solution of a converged solve for the guesses of later time steps (in_place: the last update of x wrote the copy already)
 static int guess_store(cfdh_ctx *c, const double *x, bool in_place = false) {
   const int slot = c->guess_slot, m = c->guess_m;
-  if (m <= 0 || slot < 0 || slot >= cfdh_ctx::GUESS_NEWTON) return 0;
-  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
+  if (!guess_ring_valid(c)) return 0;
+  const size_t ld = krylov_ld(c);
   double *U = c->guessU.p + ld * (size_t)m * slot;
   if (!in_place) CHK(v_copy(c, c->NO, x, U + (size_t)c->guess_head[slot] * ld));
   c->guess_stored[slot] = true;
@@ -1058,7 +1021,7 @@ static int guess_store(cfdh_ctx *c, const double *x, bool in_place = false) {
 static int guess_refine(cfdh_ctx *c, int newton_its, const double *x_final) {
   const int m = c->guess_m;
   if (m <= 0 || !c->guessX.p) return 0;
-  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
+  const size_t ld = krylov_ld(c);
   for (int k = 0; k < newton_its && k < cfdh_ctx::GUESS_NEWTON; k++) {
     if (!c->guess_stored[k]) continue;
     double *U = c->guessU.p + ld * (size_t)m * k;
@@ -1068,327 +1031,373 @@ static int guess_refine(cfdh_ctx *c, int newton_its, const double *x_final) {
   return 0;
 }
 
+// ---- FGMRES ----------------------------------------------------------------------------------------------------------------
+// Where V_0 of the next cycle comes from.
+enum class V0From {
+  rhs,           // zero guess: r0 = b, v_0 = b / |b| is formed straight from b
+  guess,         // projected guess, general path: V_0 holds r0 = b - W y, unscaled
+  guess_scaled,  // projected guess, lean path: V_0 = r0 / |r0| already, scaled on the device ahead of the read-back
+  residual       // after a cycle: the true residual b - J x is formed and its norm read back
+};
+enum class Between { proceed, retry, stop };  // what the checks between two cycles decide
+
+// State of one solve.
+struct Fgmres {
+  cfdh_ctx *c;
+  const double *b;
+  double *x;
+  int n, m;
+  size_t ld, ld32;
+  double bn = 0.0, tol = 0.0;  // |b|, absolute tolerance
+  // Long cycles at the default tolerance orthogonalise against an fp32 COPY of the basis (half the traffic of the two passes over
+  // V, which are ~40 % of an iteration at depth 25).  Chosen per solve from the length of the last solve with the same Newton
+  // index; never for tolerances below 1e-6 (parity runs), never again on a context whose watchdog tripped with the copy in use.
+  // CFDH_KRYLOV_FP32 = 0: never, 2: always (where the tolerance allows).
+  bool use32 = false;
+  bool lean = false;  // lean prologue and epilogue (not with the fp32 copy of the basis, which keeps the general path)
+  float *V32 = nullptr;
+  int e_its = 0;  // expected length of this solve: the last solve with the same Newton index took that many iterations (0: unknown)
+  cfdh_krylov::ArnoldiLsq lsq;
+  std::vector<double> hh;  // Gram-Schmidt coefficients of the iteration being processed
+  int its = 0, reason = 0;
+  int j_prev = 0;             // length of the last cycle
+  bool converged = false;     // the last cycle ended with the recurrence below the tolerance
+  double est_prev = 0.0;      // residual estimate at the end of the last cycle
+  double beta_start = 0.0;    // true residual at its start
+  double last_true = -1.0;    // true residual at the last disagreement between recurrence and true residual
+  bool kept_copy = false;     // the copy guess_store makes is current (written by the last update of x)
+  Fgmres(cfdh_ctx *c_, const double *b_, double *x_)
+      : c(c_), b(b_), x(x_), n(c_->NO), m(c_->kry_m), ld(krylov_ld(c_)), ld32((ld + 3) & ~(size_t)3),  // columns of the copy start on 16-B boundaries (float4 loads)
+        lsq(c_->kry_m), hh(2 * (size_t)(c_->kry_m + 1) + 8) {}
+};
+
+// Start of a solve on both paths: x0 (zero or the projected guess), |b|, the tolerance, and V_0 = r0 with its norm *beta when a
+// guess is used.  s.reason != 0 on return: |b| is zero or not finite, nothing to iterate.
+static int fgmres_start(Fgmres &s, double bnorm, V0From *src, double *beta) {
+  cfdh_ctx *c = s.c;
+  const cfdh_options &o = c->opt;
+  const int n = s.n;
+  double *V = c->kV.p;
+  s.e_its = guess_expected_its(c);
+  // In a partitioned run the copy costs one more all-reduce per iteration (the measured norm) and saves 1/nranks of the traffic it
+  // saves on one GPU: taken only where a rank still holds >= 2 M unknowns (decided from the GLOBAL count: the same on every rank).
+  const bool worth32 = c->nranks <= 1 || (c->nvo_global / c->nranks) * (c->dim + 1) >= 2.0e6;
+  const int fp32_env = c->env.krylov_fp32;
+  s.use32 = fp32_env > 0 && o.ksp_rtol >= 1e-6 && c->krylov_fp32_ok && ((s.e_its >= 20 && worth32) || fp32_env >= 2);
+  s.lean = lean_scope(c) && !s.use32;
+  double bn = bnorm;  // the caller may know |b| already (Newton: |F| of the accepted iterate)
+  // prologue on the lean path: launched whole before anything is read back; needs |b| from the caller (Newton passes it)
+  bool pro = false;
+  if (s.lean && bn > 0.0 && std::isfinite(bn)) CHK(guess_project_lean(c, s.b, s.x, &pro));
+  if (!pro) CHK(v_zero(c, c->NL, s.x));
+  if (!(bn >= 0.0)) CHK(v_norm2(c, n, s.b, &bn));
+  s.bn = bn;
+  c->ksp_last_relres = bn == 0.0 ? 0.0 : 1.0;
+  if (!std::isfinite(bn)) { s.reason = -9; return 0; }
+  if (bn == 0.0) { s.reason = 2; return 0; }
+  s.tol = std::max(o.ksp_rtol * bn, o.ksp_atol);
+  const bool check = c->env.guess_check;
+  bool guessed = false;
+  *src = V0From::guess;
+  if (pro) {
+    // V_0 is normalised by a kernel that reads |r0|^2 on the device: it is queued BEFORE the read-back, so the device does not
+    // idle while the host wakes up (the check hook below wants the unscaled vector: it scales afterwards)
+    if (!check) { CHK(v_scale_inv_lean(c, n, V)); *src = V0From::guess_scaled; }
+    int rank = 0;
+    double y[8];
+    CHK(v_guess_read(c, c->guess_cnt[c->guess_slot], beta, &guessed, &rank, y));
+    c->guess_last_rank = rank; c->guess_last_k = c->guess_cnt[c->guess_slot];
+    if (!guessed) CHK(v_zero(c, c->NL, s.x));  // rank 0 or non-finite coefficients: zero guess (the kernel wrote 0 U; a NaN in U must not survive)
+  } else {
+    CHK(guess_project(c, s.b, s.x, &guessed));
+  }
+  if (s.use32) {
+    if (c->kV32.n < s.ld32 * (size_t)(s.m + 1)) HIPCHK(c, c->kV32.alloc(s.ld32 * (size_t)(s.m + 1)));
+    s.V32 = c->kV32.p;
+  }
+  if (!guessed) { *src = V0From::rhs; *beta = bn; s.beta_start = bn; return 0; }
+  // the cycle starts from the true residual of x0, as after a restart
+  if (check) {
+    // test hook: the residual assembled from the multi-vector product must be the true residual of x0
+    double diff = 0.0, *w = c->kw.p;
+    CHK(comm_halo(c, s.x));
+    CHK(k_spmv_full(c, s.x, w));
+    CHK(v_waxpy(c, n, -1.0, w, s.b, w));   // w = b - J x0
+    CHK(v_waxpy(c, n, -1.0, V, w, w));     // w -= V_0
+    CHK(v_norm2(c, n, w, &diff));
+    if (!(diff <= 1e-10 * bn)) return cfdh_fail(c, CFDH_E_STATE, "projected guess: |(b - J x0) - (b - W y)| = %.3e |b|", diff / bn);
+  }
+  if (!pro) CHK(v_norm2(c, n, V, beta));  // (the lean path read it back with the "used" flag)
+  c->n_guess_solves++; c->guess_reduction_sum += *beta / bn;
+  if (o.verbose) fprintf(stderr, "[cfdh]     projected guess (newton %d, %d vectors): |r0| / |b| = %.3e\n", c->guess_slot, c->guess_cnt[c->guess_slot], *beta / bn);
+  s.beta_start = *beta;
+  return 0;
+}
+
+// True residual at a restart: V_0 = b - J x and its norm.
+static int fgmres_true_residual(Fgmres &s, double *beta) {
+  cfdh_ctx *c = s.c;
+  double *V = c->kV.p, *w = c->kw.p;
+  bool have_beta = false;
+  CHK(comm_halo(c, s.x));
+  // lean path: product, b - J x and the first pass of the norm in one kernel, one read-back (not while the kernel timers run:
+  // they count the plain product)
+  if (s.lean && !c->prof_on) CHK(k_resid_norm(c, s.x, s.b, V, beta, &have_beta));
+  if (!have_beta) {
+    CHK(k_spmv_full(c, s.x, w));
+    CHK(v_waxpy(c, s.n, -1.0, w, s.b, V));
+    CHK(v_norm2(c, s.n, V, beta));
+  }
+  c->n_cycles++;
+  c->ksp_last_relres = *beta / s.bn;
+  return 0;
+}
+
+// The checks between two cycles, on the true residual beta formed after the last one.
+static int fgmres_between_cycles(Fgmres &s, double beta, Between *next) {
+  cfdh_ctx *c = s.c;
+  const cfdh_options &o = c->opt;
+  const double tol = s.tol, est_prev = s.est_prev;
+  const int j_prev = s.j_prev;
+  *next = Between::proceed;
+  // Orthogonality watchdog.  Unrefined classical Gram-Schmidt (PETSc's default) can lose the basis in a long cycle:
+  // the recurrence then reports convergence while the true residual, formed here after every cycle anyway, does not
+  // follow.  Once that is seen on a context, long cycles are re-orthogonalised (DGKS) from then on, and a cycle that
+  // made the residual worse is taken back.
+  const bool lost = j_prev > 0 && beta > 10.0 * std::max(est_prev, tol);
+  if (s.use32 && lost) {
+    // the fp32 copy is the first suspect: this solve and all later ones of the context go back to the fp64 basis
+    s.use32 = false; c->krylov_fp32_ok = false;
+    if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e vs recurrence %.3e after a %d-vector cycle with the fp32 basis copy: switched off\n", beta, est_prev, j_prev);
+  } else if (!c->gs_refine_long && lost) {
+    c->gs_refine_long = true;
+    if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e vs recurrence %.3e after a %d-vector cycle: re-orthogonalising long cycles from now on\n", beta, est_prev, j_prev);
+    if (beta > s.beta_start) {
+      std::vector<double> &y = s.lsq.y;
+      for (int i = 0; i < j_prev; i++) y[i] = -y[i];
+      HIPCHK(c, hipMemcpyAsync(c->ky.p, y.data(), sizeof(double) * j_prev, hipMemcpyHostToDevice, c->stream));
+      CHK(v_lincomb(c, s.n, c->kZ.p, (int)s.ld, j_prev, c->ky.p, s.x));
+      s.kept_copy = false;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      s.est_prev = s.beta_start;  // do not trip again on the restored iterate
+      *next = Between::retry;
+      return 0;
+    }
+  }
+  // Attainable accuracy.  The convergence test of a cycle is the recurrence norm (as in PETSc, which never looks further);
+  // here the true residual is formed after every cycle and another cycle follows if it disagrees.  When a second cycle
+  // in a row ends "converged" by the recurrence without halving the true residual, that residual is the floor of this
+  // system (rounding level of J x, or the component of b outside the range of a singular Jacobian: lid cavity at
+  // ksp_rtol 1e-10) and the iteration stops instead of spending ksp_max_it on it.
+  // The stop is bounded and reported as what it is: it applies only within 10x the tolerance or once the residual is six
+  // orders below |b| (beyond what the reference's rtol = 1e-5 ever asks for); anything else runs on to ksp_max_it and fails
+  // like PETSc's DIVERGED_ITS.  It returns its own reason code (CFDH_KSP_CONVERGED_ATTAINABLE) and is counted
+  // (cfdh_info 72).  CFDH_NO_ATTAINABLE_STOP=1 disables it.
+  if (j_prev > 0 && est_prev <= tol && beta > tol && !c->env.no_attainable_stop) {
+    if (s.last_true > 0.0 && beta > 0.5 * s.last_true && (beta <= 10.0 * tol || beta <= 1e-6 * s.bn)) {
+      if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e stays above the tolerance %.3e although the recurrence converged twice: attainable accuracy, stopping\n", beta, tol);
+      s.reason = CFDH_KSP_CONVERGED_ATTAINABLE;
+      c->n_attainable_stops++;
+      *next = Between::stop;
+      return 0;
+    }
+    s.last_true = beta;
+  } else {
+    s.last_true = -1.0;  // a cycle that ended without recurrence convergence (restart): the floor has to be seen twice IN A ROW
+  }
+  s.beta_start = beta;
+  return 0;
+}
+
+// Launch of iteration jj: z_jj = P^-1 v_jj, w = J z_jj, one Gram-Schmidt pass against V_0..V_jj into V_jj+1; the coefficients
+// [h_0 .. h_jj, w.w, (measured norm)] land in the iteration's slot of the host-mapped ring, behind its event.
+static int fgmres_launch(Fgmres &s, int jj) {
+  cfdh_ctx *c = s.c;
+  const int n = s.n, m = s.m;
+  const size_t ld = s.ld, ld32 = s.ld32;
+  double *V = c->kV.p, *w = c->kw.p, *hd = c->kh.p, *s_dev = hd + 2 * (m + 2) + 1;
+  double *vj = V + (size_t)jj * ld, *zj = c->kZ.p + (size_t)jj * ld, *vn = V + (size_t)(jj + 1) * ld;
+  double *slot = c->h_ring_dev + (size_t)(jj % cfdh_ctx::KRING) * c->h_ring_stride;
+  CHK(pc_then_product(c, vj, zj, w));
+  // classical Gram-Schmidt (PETSc's default for (F)GMRES): h = [V^T w ; w.w] comes from ONE fused multi-dot
+  if (s.use32) {
+    // the same Gram-Schmidt step against the fp32 copy: h = V32^T w, v_{j+1} = (w - V32 h) / |w - V32 h| with the norm
+    // MEASURED (the identity below needs columns that are orthonormal to round-off); both the fp64 vector (input of the
+    // next preconditioner application) and its fp32 copy are written
+    CHK(v_multidot32(c, n, s.V32, (int)ld32, jj + 1, w, hd, slot));
+    CHK(v_gs_update32(c, n, s.V32, (int)ld32, jj + 1, hd, w, vn, s.V32 + (size_t)(jj + 1) * ld32, s_dev, slot + (jj + 2)));
+    HIPCHK(c, hipEventRecord(c->ev_ring[jj % cfdh_ctx::KRING], c->stream));
+  } else {
+    CHK(v_multidot(c, n, V, (int)ld, jj + 1, w, hd, true, slot));
+    // h (all-reduced in a partitioned run) sits in the host-mapped slot: the event marks THAT; the update of w below
+    // overlaps with the host's Hessenberg bookkeeping and the next launches
+    HIPCHK(c, hipEventRecord(c->ev_ring[jj % cfdh_ctx::KRING], c->stream));
+    // v_{j+1} = (w - V h) / s with s = sqrt(w.w - |h|^2) formed on the device from the reduced coefficients: update and
+    // normalisation in one pass (the host forms the same norm for the Hessenberg matrix from its copy of h)
+    CHK(v_gs_update_normalize(c, n, V, (int)ld, jj + 1, hd, w, vn, s_dev));
+  }
+  return 0;
+}
+
+// Second Gram-Schmidt pass on the (already scaled) vector of iteration j: vn = w'/s  ->  h2 = V^T vn, vn -= V h2, vn /= |vn|;
+// in terms of w: h += s h2 (into s.hh), |w''| = s |vn| (into *hnorm).  The coefficients and the squared norm of the corrected vector
+// travel in ONE reduction over the ranks: [h2 ; vn.vn] from one fused multi-dot, |vn - V h2|^2 = vn.vn - |h2|^2 (the basis is
+// orthonormal to round-off here -- the fp32 copy measures its norm instead).  hs: the iteration's ring slot.
+static int fgmres_second_pass(Fgmres &s, int j, const double *hs, double ww, double hh2, double *hnorm) {
+  cfdh_ctx *c = s.c;
+  const int n = s.n, m = s.m;
+  double *V = c->kV.p, *hd = c->kh.p, *vn = V + (size_t)(j + 1) * s.ld;
+  CHK(v_multidot(c, n, V, (int)s.ld, j + 1, vn, hd + (m + 2), true));
+  CHK(v_multiaxpy(c, n, V, (int)s.ld, j + 1, hd + (m + 2), vn));
+  if (s.use32) CHK(v_norm_to_dev(c, n, vn, hd + 2 * (m + 2)));
+  HIPCHK(c, hipMemcpyAsync(c->h_pinned, hd + (m + 2), sizeof(double) * (m + 4), hipMemcpyDeviceToHost, c->stream));
+  c->n_host_sync++; c->n_iter_sync++;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // scale of the first pass, formed by the function gs_update_normalize_kernel forms it with (the device word s_dev may belong to
+  // an iteration that ran ahead by now); the fp32 path measured it: slot word j + 2
+  const double sc = s.use32 ? hs[j + 2] : cfdh_krylov::gs_scale(ww, hh2);
+  double h22 = 0.0;
+  for (int i = 0; i <= j; i++) { s.hh[i] += sc * c->h_pinned[i]; h22 += c->h_pinned[i] * c->h_pinned[i]; }
+  double vnorm;
+  if (s.use32) vnorm = c->h_pinned[m + 2];
+  else {
+    const double d2 = c->h_pinned[j + 1] - h22;
+    vnorm = d2 > 0.0 ? std::sqrt(d2) : 0.0;
+  }
+  *hnorm = sc * vnorm;
+  if (s.use32) { CHK(v_scale_inv_dev(c, n, vn, hd + 2 * (m + 2), vn)); CHK(v_store32(c, n, vn, s.V32 + (size_t)(j + 1) * s.ld32)); }
+  else CHK(v_scale(c, n, vnorm > 0.0 ? 1.0 / vnorm : 0.0, vn));
+  return 0;
+}
+
+// One cycle from V_0 of norm beta.  The device needs nothing from the host to go from one iteration to the next (the Gram-Schmidt
+// update forms its own scale from the reduced coefficients), so iterations are LAUNCHED ahead of the host's bookkeeping: every
+// iteration in flight publishes [h_0..h_j, w.w, (measured norm)] into its own slot of a host-mapped ring behind an event, and the
+// host catches up -- Hessenberg column, Givens rotation, convergence test -- in batches, always leaving one iteration running so
+// that the GPU never waits for the host.  How far to run ahead follows from the convergence rate seen so far (iterations the
+// tolerance is still away at the current contraction factor, at most KRING - 3): an iteration launched beyond the one that
+// converges is discarded (x uses the columns up to convergence only) and counted (cfdh_info 73).  Solves that decide a second
+// Gram-Schmidt pass per vector (ksp_rtol < 1e-7, long cycles after the watchdog tripped) stay synchronous; the rare
+// cancellation case (|w'|^2 < 1e-2 |w|^2) refines the vector when the host sees it and re-launches what ran ahead of it.
+// On return s.j_prev is the number of columns of this cycle; s.reason = -9 on breakdown.
+static int fgmres_cycle(Fgmres &s, double beta) {
+  cfdh_ctx *c = s.c;
+  const cfdh_options &o = c->opt;
+  const int refine_from = c->env.gs_refine_from >= 0 ? c->env.gs_refine_from : (c->gs_refine_long ? 24 : (1 << 30));
+  const int lagmax = (o.ksp_rtol < 1e-7 || c->prof_on) ? 0 : std::max(0, std::min(c->env.ksp_lag, cfdh_ctx::KRING - 3));
+  const int maxl = std::min(s.m, o.ksp_max_it - s.its);  // iterations this cycle may run
+  int j = 0;    // iterations processed by the host (complete Hessenberg columns)
+  int jl = 0;   // iterations launched
+  cfdh_krylov::LaunchAhead ahead;
+  ahead.start(beta, s.e_its, s.its);
+  s.lsq.start(beta);
+  s.converged = false;
+  double *hh = s.hh.data();
+  while (!s.converged && s.reason == 0) {
+    // launch: one iteration beyond the batch the host will process next stays in flight, unless the batch is predicted to
+    // contain the converging iteration
+    const bool sync_now = lagmax == 0 || j >= refine_from;
+    const int want = ahead.in_flight(sync_now, lagmax);
+    while (jl < maxl && jl - j < want) { CHK(fgmres_launch(s, jl)); jl++; }
+    if (jl == j) break;  // cycle full (restart) or iteration cap
+    int upto = ahead.process_upto(j, jl, maxl, sync_now);
+    c->n_host_sync++; c->n_iter_sync++;
+    HIPCHK(c, hipEventSynchronize(c->ev_ring[(upto - 1) % cfdh_ctx::KRING]));
+    while (j < upto) {
+      const double *hs = c->h_ring + (size_t)(j % cfdh_ctx::KRING) * c->h_ring_stride;
+      double ww = hs[j + 1], hh2 = 0.0;
+      for (int i = 0; i <= j; i++) { hh[i] = hs[i]; hh2 += hh[i] * hh[i]; }
+      const double nrm2 = s.use32 ? hs[j + 2] * hs[j + 2] : ww - hh2;
+      // PETSc's default never refines.  Here: tolerances down to ~1e-7 refine only when two digits
+      // cancel; tighter solves (parity runs at 1e-10) use the DGKS criterion (|w'| < |w|/sqrt(2)),
+      // because classical Gram-Schmidt then loses the orthogonality the deep convergence needs
+      // ... and so can a long Krylov cycle: beyond ~two dozen vectors the unrefined basis may drift far enough from
+      // orthogonality that the least-squares solution picks up huge spurious components (Newton corrections ten times
+      // the size of the iterate on the tree domain, config 5) although the residual norm looks converged.  Paying the
+      // second pass on every long cycle costs 14 % of a 3-D step whose 47-vector cycles never need it, so it is switched
+      // on by the watchdog (CFDH_GS_REFINE_FROM=<j> forces it from vector j on)
+      // (at the reference's tolerance: only when three digits cancel -- one classical pass then leaves an orthogonality
+      // error of ~1e3 eps, far below rtol 1e-5.  With a good preconditioner w = J M^-1 v_j is close to v_j, so a threshold of
+      // 1e-2 -- rounds 2 and 3 -- sent a third of all iterations of the headline run through the second pass for nothing.)
+      const double eta2 = (o.ksp_rtol < 1e-7 || j >= refine_from) ? 0.5 : c->env.gs_eta2;
+      double hnorm = std::sqrt(nrm2);
+      if (!(nrm2 > eta2 * ww)) {
+        // what ran ahead used the unrefined vector: it is launched again, and its ring slots are not consumed by this batch
+        if (jl > j + 1) { c->n_krylov_discarded += jl - (j + 1); jl = j + 1; upto = jl; }
+        CHK(fgmres_second_pass(s, j, hs, ww, hh2, &hnorm));
+      }
+      const bool ok = s.lsq.add_column(j, hh, hnorm);
+      j++;
+      if (!ok) { s.reason = -9; break; }
+      s.its++;
+      const double res = s.lsq.residual(j);
+      if (o.verbose > 1) fprintf(stderr, "[cfdh]     fgmres %3d  |r|/|b| = %.3e\n", s.its, res / s.bn);
+      if (res <= s.tol) { s.converged = true; break; }
+      ahead.observe(res, s.tol, s.its);
+    }
+  }
+  if (jl > j) c->n_krylov_discarded += jl - j;  // launched ahead of the converging iteration: not part of the solution
+  s.j_prev = j;
+  return 0;
+}
+
+// x += Z y with y = H^-1 g of the cycle that has just ended.
+static int fgmres_update_x(Fgmres &s) {
+  cfdh_ctx *c = s.c;
+  const int j = s.j_prev;
+  const double *y = s.lsq.solve(j);
+  // y travels through a pinned slot behind the ring (no stream synchronisation: the slot is rewritten at the end of the next
+  // cycle at the earliest, after events recorded behind this copy have been waited for)
+  double *ystage = c->h_ring + c->h_ring_stride * cfdh_ctx::KRING;
+  for (int i = 0; i < j; i++) ystage[i] = y[i];
+  HIPCHK(c, hipMemcpyAsync(c->ky.p, ystage, sizeof(double) * j, hipMemcpyHostToDevice, c->stream));
+  // lean path: the update of a cycle that converged by the recurrence also writes the copy guess_store would make (a second
+  // store instead of a pass over x) where that slot is free; any other update of x leaves the copy to guess_store
+  double *keep = (s.lean && s.converged && s.its < c->opt.ksp_max_it) ? guess_store_target(c) : nullptr;
+  if (keep) CHK(v_lincomb_keep(c, s.n, c->kZ.p, (int)s.ld, j, c->ky.p, s.x, keep));
+  else CHK(v_lincomb(c, s.n, c->kZ.p, (int)s.ld, j, c->ky.p, s.x));
+  s.kept_copy = keep != nullptr;
+  s.est_prev = s.lsq.residual(j);
+  return 0;
+}
+
 // Solve J x = b, x0 = 0 or the projected guess.  Right preconditioning, convergence on the true
 // residual norm relative to |b| (KSP defaults: rtol, atol; KSP_NORM_UNPRECONDITIONED
 // for FGMRES).  Classical Gram-Schmidt with one re-orthogonalisation pass; the
 // 2j+3 scalars of an iteration come back in a single read.
 int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reason_out, double bnorm) {
   CHK(ensure_krylov(c));
-  const int n = c->NO, m = c->kry_m;
-  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;
-  const cfdh_options &o = c->opt;
-  std::vector<double> H((size_t)(m + 1) * m, 0.0), cs(m), sn(m), g(m + 1), y(m), hh(2 * (size_t)(m + 1) + 8);
-  double bn = bnorm;  // the caller may know |b| already (Newton: |F| of the accepted iterate)
-  // Long cycles at the default tolerance orthogonalise against an fp32 COPY of the basis (half the traffic of the two passes over
-  // V, which are ~40 % of an iteration at depth 25).  Chosen per solve from the length of the last solve with the same Newton
-  // index; never for tolerances below 1e-6 (parity runs), never again on a context whose watchdog tripped with the copy in use.
-  // CFDH_KRYLOV_FP32 = 0: never, 2: always (where the tolerance allows).
-  const int fp32_env = getenv("CFDH_KRYLOV_FP32") ? atoi(getenv("CFDH_KRYLOV_FP32")) : 1;
-  const int gslot = c->guess_slot;
-  const bool expect_long = gslot >= 0 && gslot < cfdh_ctx::GUESS_NEWTON && c->guess_last_its[gslot] >= 20;
-  // In a partitioned run the copy costs one more all-reduce per iteration (the measured norm) and saves 1/nranks of the traffic it
-  // saves on one GPU: taken only where a rank still holds >= 2 M unknowns (decided from the GLOBAL count: the same on every rank).
-  const bool worth32 = c->nranks <= 1 || (c->nvo_global / c->nranks) * (c->dim + 1) >= 2.0e6;
-  bool use32 = fp32_env > 0 && o.ksp_rtol >= 1e-6 && c->krylov_fp32_ok && ((expect_long && worth32) || fp32_env >= 2);
-  // Lean prologue and epilogue (not with the fp32 copy of the basis, which keeps the general path)
-  const bool lean_solve = lean_scope(c) && !use32;
-  // prologue on the lean path: launched whole before anything is read back; needs |b| from the caller (Newton passes it)
-  bool pro = false, pro_pending = false;
-  double beta_pro = 0.0;
-  const bool guess_check = getenv("CFDH_GUESS_CHECK") != nullptr;
-  if (lean_solve && bn > 0.0 && std::isfinite(bn)) CHK(guess_project_lean(c, b, x, &pro));
-  if (!pro) CHK(v_zero(c, c->NL, x));
-  if (!(bn >= 0.0)) CHK(v_norm2(c, n, b, &bn));
-  int its = 0, reason = 0;
-  c->ksp_last_relres = bn == 0.0 ? 0.0 : 1.0;
-  if (!std::isfinite(bn)) { *its_out = 0; *reason_out = -9; return 0; }
-  if (bn == 0.0) { *its_out = 0; *reason_out = 2; return 0; }
-  const double tol = std::max(o.ksp_rtol * bn, o.ksp_atol);
-  double *V = c->kV.p, *Z = c->kZ.p, *w = c->kw.p, *hd = c->kh.p;
-  bool first = true;
-  bool guessed = false;
-  bool kept_copy = false;  // the copy guess_store makes is current (written by the last update of x)
-  if (pro) {
-    // V_0 is normalised by a kernel that reads |r0|^2 on the device: it is queued BEFORE the read-back, so the device does not
-    // idle while the host wakes up (the check hook below wants the unscaled vector: it scales afterwards)
-    if (!guess_check) CHK(v_scale_inv_lean(c, n, V));
-    int rank = 0;
-    CHK(v_guess_read(c, c->guess_cnt[c->guess_slot], &beta_pro, &guessed, &rank, y.data()));
-    c->guess_last_rank = rank; c->guess_last_k = c->guess_cnt[c->guess_slot];
-    if (guessed) pro_pending = true;
-    else CHK(v_zero(c, c->NL, x));  // rank 0 or non-finite coefficients: zero guess (the kernel wrote 0 U; a NaN in U must not survive)
-  } else {
-    CHK(guess_project(c, b, x, &guessed));
-  }
-  if (guessed) first = false;  // the cycle starts from the true residual of x0, as after a restart
-  float *V32 = nullptr;
-  const size_t ld32 = (ld + 3) & ~(size_t)3;  // columns of the copy start on 16-B boundaries (float4 loads)
-  if (use32) {
-    if (c->kV32.n < ld32 * (size_t)(m + 1)) HIPCHK(c, c->kV32.alloc(ld32 * (size_t)(m + 1)));
-    V32 = c->kV32.p;
-  }
-  double last_true = -1.0;  // true residual at the last disagreement between recurrence and true residual
-  double est_prev = 0.0, beta_start = bn;  // residual estimate at the end / true residual at the start of the last cycle
-  int j_prev = 0;
+  Fgmres s(c, b, x);
+  V0From src = V0From::rhs;
+  double beta = 0.0;
+  CHK(fgmres_start(s, bnorm, &src, &beta));
+  if (s.reason != 0) { *its_out = 0; *reason_out = s.reason; return 0; }
+  double *V = c->kV.p;
   for (;;) {
-    double beta;
-    if (first) {
-      beta = bn;  // r0 = b: v_0 = b / |b| is formed below straight from b
-    } else {
-      bool have_beta = false;
-      if (!(guessed && its == 0 && j_prev == 0)) {  // (after a projected guess V_0 already holds r0 = b - W y)
-        CHK(comm_halo(c, x));
-        // lean path: product, b - J x and the first pass of the norm in one kernel, one read-back (not while the kernel timers run:
-        // they count the plain product)
-        if (lean_solve && !c->prof_on) CHK(k_resid_norm(c, x, b, V, &beta, &have_beta));
-        if (!have_beta) {
-          CHK(k_spmv_full(c, x, w));
-          CHK(v_waxpy(c, n, -1.0, w, b, V));
-        }
-        c->n_cycles++;
-      } else if (guess_check) {
-        // test hook: the residual assembled from the multi-vector product must be the true residual of x0
-        double diff = 0.0;
-        CHK(comm_halo(c, x));
-        CHK(k_spmv_full(c, x, w));
-        CHK(v_waxpy(c, n, -1.0, w, b, w));   // w = b - J x0
-        CHK(v_waxpy(c, n, -1.0, V, w, w));   // w -= V_0
-        CHK(v_norm2(c, n, w, &diff));
-        if (!(diff <= 1e-10 * bn)) return cfdh_fail(c, CFDH_E_STATE, "projected guess: |(b - J x0) - (b - W y)| = %.3e |b|", diff / bn);
-      }
-      if (pro_pending) { beta = beta_pro; have_beta = true; }  // read back with the "used" flag
-      if (!have_beta) CHK(v_norm2(c, n, V, &beta));
-      c->ksp_last_relres = beta / bn;
-      if (guessed && its == 0 && j_prev == 0) {
-        c->n_guess_solves++; c->guess_reduction_sum += beta / bn;
-        if (o.verbose) fprintf(stderr, "[cfdh]     projected guess (newton %d, %d vectors): |r0| / |b| = %.3e\n", c->guess_slot, c->guess_cnt[c->guess_slot], beta / bn);
-      }
-      // Orthogonality watchdog.  Unrefined classical Gram-Schmidt (PETSc's default) can lose the basis in a long cycle:
-      // the recurrence then reports convergence while the true residual, formed here after every cycle anyway, does not
-      // follow.  Once that is seen on a context, long cycles are re-orthogonalised (DGKS) from then on, and a cycle that
-      // made the residual worse is taken back.
-      if (use32 && j_prev > 0 && beta > 10.0 * std::max(est_prev, tol)) {
-        // the fp32 copy is the first suspect: this solve and all later ones of the context go back to the fp64 basis
-        use32 = false; c->krylov_fp32_ok = false;
-        if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e vs recurrence %.3e after a %d-vector cycle with the fp32 basis copy: switched off\n", beta, est_prev, j_prev);
-      } else if (!c->gs_refine_long && j_prev > 0 && beta > 10.0 * std::max(est_prev, tol)) {
-        c->gs_refine_long = true;
-        if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e vs recurrence %.3e after a %d-vector cycle: re-orthogonalising long cycles from now on\n", beta, est_prev, j_prev);
-        if (beta > beta_start && j_prev > 0) {
-          for (int i = 0; i < j_prev; i++) y[i] = -y[i];
-          HIPCHK(c, hipMemcpyAsync(c->ky.p, y.data(), sizeof(double) * j_prev, hipMemcpyHostToDevice, c->stream));
-          CHK(v_lincomb(c, n, Z, (int)ld, j_prev, c->ky.p, x));
-          kept_copy = false;
-          HIPCHK(c, hipStreamSynchronize(c->stream));
-          est_prev = beta_start;  // do not trip again on the restored iterate
-          continue;
-        }
-      }
-      // Attainable accuracy.  The convergence test of a cycle is the recurrence norm (as in PETSc, which never looks further);
-      // here the true residual is formed after every cycle and another cycle follows if it disagrees.  When a second cycle
-      // in a row ends "converged" by the recurrence without halving the true residual, that residual is the floor of this
-      // system (rounding level of J x, or the component of b outside the range of a singular Jacobian: lid cavity at
-      // ksp_rtol 1e-10) and the iteration stops instead of spending ksp_max_it on it.
-      // The stop is bounded and reported as what it is: it applies only within 10x the tolerance or once the residual is six
-      // orders below |b| (beyond what the reference's rtol = 1e-5 ever asks for); anything else runs on to ksp_max_it and fails
-      // like PETSc's DIVERGED_ITS.  It returns its own reason code (CFDH_KSP_CONVERGED_ATTAINABLE) and is counted
-      // (cfdh_info 72).  CFDH_NO_ATTAINABLE_STOP=1 disables it.
-      static const bool no_attainable = getenv("CFDH_NO_ATTAINABLE_STOP") && getenv("CFDH_NO_ATTAINABLE_STOP")[0] == '1';
-      if (j_prev > 0 && est_prev <= tol && beta > tol && !no_attainable) {
-        if (last_true > 0.0 && beta > 0.5 * last_true && (beta <= 10.0 * tol || beta <= 1e-6 * bn)) {
-          if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e stays above the tolerance %.3e although the recurrence converged twice: attainable accuracy, stopping\n", beta, tol);
-          reason = CFDH_KSP_CONVERGED_ATTAINABLE;
-          c->n_attainable_stops++;
-          break;
-        }
-        last_true = beta;
-      } else {
-        last_true = -1.0;  // a cycle that ended without recurrence convergence (restart): the floor has to be seen twice IN A ROW
-      }
-      beta_start = beta;
+    if (src == V0From::residual) {
+      Between next;
+      CHK(fgmres_true_residual(s, &beta));
+      CHK(fgmres_between_cycles(s, beta, &next));
+      if (next == Between::retry) continue;  // from the iterate before the last cycle
+      if (next == Between::stop) break;
     }
-    c->ksp_last_relres = beta / bn;  // true residual (r0 = b on the first pass)
-    if (beta <= tol) { reason = 2; break; }
-    if (its >= o.ksp_max_it) { reason = -3; break; }
-    if (!std::isfinite(beta)) { reason = -9; break; }
-    if (first) CHK(v_scale_to(c, n, 1.0 / beta, b, V));
-    else if (pro_pending && !guess_check) { /* scaled on the device, queued ahead of the read-back */ }
-    else CHK(v_scale(c, n, 1.0 / beta, V));
-    pro_pending = false;
-    if (use32) CHK(v_store32(c, n, V, V32));
-    first = false;
-    std::fill(g.begin(), g.end(), 0.0);
-    g[0] = beta;
-    // ---- one cycle.  The device needs nothing from the host to go from one iteration to the next (the Gram-Schmidt update forms
-    // its own scale from the reduced coefficients), so iterations are LAUNCHED ahead of the host's bookkeeping: every iteration in
-    // flight publishes [h_0..h_j, w.w, (measured norm)] into its own slot of a host-mapped ring behind an event, and the host
-    // catches up -- Hessenberg column, Givens rotation, convergence test -- in batches, always leaving one iteration running so
-    // that the GPU never waits for the host.  How far to run ahead follows from the convergence rate seen so far (iterations the
-    // tolerance is still away at the current contraction factor, at most KRING - 3): an iteration launched beyond the one that
-    // converges is discarded (x uses the columns up to convergence only) and counted (cfdh_info 73).  Solves that decide a second
-    // Gram-Schmidt pass per vector (ksp_rtol < 1e-7, long cycles after the watchdog tripped) stay synchronous; the rare
-    // cancellation case (|w'|^2 < 1e-2 |w|^2) refines the vector when the host sees it and re-launches what ran ahead of it.
-    static const int refine_env = getenv("CFDH_GS_REFINE_FROM") ? atoi(getenv("CFDH_GS_REFINE_FROM")) : -1;
-    static const int lag_env = getenv("CFDH_KSP_LAG") ? atoi(getenv("CFDH_KSP_LAG")) : cfdh_ctx::KRING - 3;
-    const int refine_from = refine_env >= 0 ? refine_env : (c->gs_refine_long ? 24 : (1 << 30));
-    const int lagmax = (o.ksp_rtol < 1e-7 || c->prof_on) ? 0 : std::max(0, std::min(lag_env, cfdh_ctx::KRING - 3));
-    const int its_base = its;
-    const int maxl = std::min(m, o.ksp_max_it - its_base);  // iterations this cycle may run
-    int j = 0;    // iterations processed by the host (complete Hessenberg columns)
-    int jl = 0;   // iterations launched
-    // expected length of this solve: the last solve with the same Newton index took guess_last_its iterations (0: unknown)
-    const int e_its = (gslot >= 0 && gslot < cfdh_ctx::GUESS_NEWTON) ? c->guess_last_its[gslot] : 0;
-    // iterations still needed, counted from iteration j: from the history alone before any residual of this cycle is known,
-    // afterwards the smaller of the rate-based prediction and what the history leaves
-    int need = std::max(1, std::min(e_its - its - 2, 3));
-    double res_hist[4] = {beta, 0, 0, 0};
-    int nhist = 1;
-    bool done = false;
-    double *s_dev = hd + 2 * (m + 2) + 1;
-    const size_t rs = c->h_ring_stride;
-    auto launch = [&](int jj) -> int {
-      double *vj = V + (size_t)jj * ld, *zj = Z + (size_t)jj * ld, *vn = V + (size_t)(jj + 1) * ld;
-      double *slot = c->h_ring_dev + (size_t)(jj % cfdh_ctx::KRING) * rs;
-      CHK(pc_then_product(c, vj, zj, w));
-      // classical Gram-Schmidt (PETSc's default for (F)GMRES): h = [V^T w ; w.w] comes from ONE fused multi-dot
-      if (use32) {
-        // the same Gram-Schmidt step against the fp32 copy: h = V32^T w, v_{j+1} = (w - V32 h) / |w - V32 h| with the norm
-        // MEASURED (the identity below needs columns that are orthonormal to round-off); both the fp64 vector (input of the
-        // next preconditioner application) and its fp32 copy are written
-        CHK(v_multidot32(c, n, V32, (int)ld32, jj + 1, w, hd, slot));
-        CHK(v_gs_update32(c, n, V32, (int)ld32, jj + 1, hd, w, vn, V32 + (size_t)(jj + 1) * ld32, s_dev, slot + (jj + 2)));
-        HIPCHK(c, hipEventRecord(c->ev_ring[jj % cfdh_ctx::KRING], c->stream));
-      } else {
-        CHK(v_multidot(c, n, V, (int)ld, jj + 1, w, hd, true, slot));
-        // h (all-reduced in a partitioned run) sits in the host-mapped slot: the event marks THAT; the update of w below
-        // overlaps with the host's Hessenberg bookkeeping and the next launches
-        HIPCHK(c, hipEventRecord(c->ev_ring[jj % cfdh_ctx::KRING], c->stream));
-        // v_{j+1} = (w - V h) / s with s = sqrt(w.w - |h|^2) formed on the device from the reduced coefficients: update and
-        // normalisation in one pass (the host forms the same norm for the Hessenberg matrix from its copy of h)
-        CHK(v_gs_update_normalize(c, n, V, (int)ld, jj + 1, hd, w, vn, s_dev));
-      }
-      return 0;
-    };
-    while (!done && reason == 0) {
-      // launch: one iteration beyond the batch the host will process next stays in flight, unless the batch is predicted to
-      // contain the converging iteration
-      const bool sync_now = lagmax == 0 || j >= refine_from;
-      // (one short of the prediction when it is long: the last predicted iteration is confirmed before anything follows it)
-      const int ahead = sync_now ? 1 : std::max(1, std::min(need - (need >= 4 ? 1 : 0), lagmax + 1));   // iterations wanted in flight
-      while (jl < maxl && jl - j < ahead) { CHK(launch(jl)); jl++; }
-      if (jl == j) break;  // cycle full (restart) or iteration cap
-      // process: everything launched if that may finish the solve / the cycle, otherwise all but the newest
-      int upto = jl;
-      if (!sync_now && jl - j > 1 && jl < maxl && need > jl - j) upto = jl - 1;
-      c->n_host_sync++; c->n_iter_sync++;
-      HIPCHK(c, hipEventSynchronize(c->ev_ring[(upto - 1) % cfdh_ctx::KRING]));
-      for (; j < upto && !done; ) {
-        const double *hs = c->h_ring + (size_t)(j % cfdh_ctx::KRING) * rs;
-        double *vn = V + (size_t)(j + 1) * ld;
-        double ww = hs[j + 1], hh2 = 0.0;
-        for (int i = 0; i <= j; i++) { hh[i] = hs[i]; hh2 += hh[i] * hh[i]; }
-        double nrm2 = use32 ? hs[j + 2] * hs[j + 2] : ww - hh2;
-        // PETSc's default never refines.  Here: tolerances down to ~1e-7 refine only when two digits
-        // cancel; tighter solves (parity runs at 1e-10) use the DGKS criterion (|w'| < |w|/sqrt(2)),
-        // because classical Gram-Schmidt then loses the orthogonality the deep convergence needs
-        // ... and so can a long Krylov cycle: beyond ~two dozen vectors the unrefined basis may drift far enough from
-        // orthogonality that the least-squares solution picks up huge spurious components (Newton corrections ten times
-        // the size of the iterate on the tree domain, config 5) although the residual norm looks converged.  Paying the
-        // second pass on every long cycle costs 14 % of a 3-D step whose 47-vector cycles never need it, so it is switched
-        // on by the watchdog above (CFDH_GS_REFINE_FROM=<j> forces it from vector j on)
-        // (at the reference's tolerance: only when three digits cancel -- one classical pass then leaves an orthogonality
-        // error of ~1e3 eps, far below rtol 1e-5.  With a good preconditioner w = J M^-1 v_j is close to v_j, so a threshold of
-        // 1e-2 -- rounds 2 and 3 -- sent a third of all iterations of the headline run through the second pass for nothing.)
-        static const double eta2_env = getenv("CFDH_GS_ETA2") ? atof(getenv("CFDH_GS_ETA2")) : 1e-6;
-        const double eta2 = (o.ksp_rtol < 1e-7 || j >= refine_from) ? 0.5 : eta2_env;
-        const bool refine = !(nrm2 > eta2 * ww);
-        double hnorm;
-        if (refine) {
-          // second Gram-Schmidt pass on the (already scaled) vector: vn = w'/s  ->  h2 = V^T vn, vn -= V h2, vn /= |vn|;
-          // in terms of w: h += s h2, |w''| = s |vn|.  The coefficients and the squared norm of the corrected vector travel
-          // in ONE reduction over the ranks: [h2 ; vn.vn] from one fused multi-dot, |vn - V h2|^2 = vn.vn - |h2|^2 (the basis is
-          // orthonormal to round-off here -- the fp32 copy measures its norm instead)
-          // what ran ahead used the unrefined vector: it is launched again, and its ring slots are not consumed by this batch
-          if (jl > j + 1) { c->n_krylov_discarded += jl - (j + 1); jl = j + 1; upto = jl; }
-          CHK(v_multidot(c, n, V, (int)ld, j + 1, vn, hd + (m + 2), true));
-          CHK(v_multiaxpy(c, n, V, (int)ld, j + 1, hd + (m + 2), vn));
-          if (use32) CHK(v_norm_to_dev(c, n, vn, hd + 2 * (m + 2)));
-          HIPCHK(c, hipMemcpyAsync(c->h_pinned, hd + (m + 2), sizeof(double) * (m + 4), hipMemcpyDeviceToHost, c->stream));
-          c->n_host_sync++; c->n_iter_sync++;
-          HIPCHK(c, hipStreamSynchronize(c->stream));
-          // scale of the first pass, formed exactly as gs_update_normalize_kernel forms it (the device word s_dev may belong to
-          // an iteration that ran ahead by now); the fp32 path measured it: slot word j + 2
-          const double s = use32 ? hs[j + 2] : ((nrm2 > 0.0 && nrm2 <= ww) ? std::sqrt(nrm2) : std::sqrt(ww));
-          double h22 = 0.0;
-          for (int i = 0; i <= j; i++) { hh[i] += s * c->h_pinned[i]; h22 += c->h_pinned[i] * c->h_pinned[i]; }
-          double vnorm;
-          if (use32) vnorm = c->h_pinned[m + 2];
-          else {
-            const double d2 = c->h_pinned[j + 1] - h22;
-            vnorm = d2 > 0.0 ? std::sqrt(d2) : 0.0;
-          }
-          hnorm = s * vnorm;
-          if (use32) { CHK(v_scale_inv_dev(c, n, vn, hd + 2 * (m + 2), vn)); CHK(v_store32(c, n, vn, V32 + (size_t)(j + 1) * ld32)); }
-          else CHK(v_scale(c, n, vnorm > 0.0 ? 1.0 / vnorm : 0.0, vn));
-        } else {
-          hnorm = std::sqrt(nrm2);
-        }
-        double *Hj = &H[(size_t)j * (m + 1)];
-        for (int i = 0; i <= j; i++) Hj[i] = hh[i];
-        Hj[j + 1] = hnorm;
-        for (int i = 0; i < j; i++) {
-          const double t = cs[i] * Hj[i] + sn[i] * Hj[i + 1];
-          Hj[i + 1] = -sn[i] * Hj[i] + cs[i] * Hj[i + 1];
-          Hj[i] = t;
-        }
-        const double d = std::hypot(Hj[j], Hj[j + 1]);
-        if (!(d > 0) || !std::isfinite(d)) { reason = -9; j++; break; }
-        cs[j] = Hj[j] / d; sn[j] = Hj[j + 1] / d;
-        Hj[j] = d; Hj[j + 1] = 0.0;
-        g[j + 1] = -sn[j] * g[j]; g[j] = cs[j] * g[j];
-        its++;
-        j++;
-        const double res = std::fabs(g[j]);
-        if (o.verbose > 1) fprintf(stderr, "[cfdh]     fgmres %3d  |r|/|b| = %.3e\n", its, res / bn);
-        if (res <= tol) { done = true; break; }
-        // iterations the tolerance is away at the contraction factor of the last (up to three) iterations
-        if (nhist < 4) res_hist[nhist++] = res;
-        else { res_hist[0] = res_hist[1]; res_hist[1] = res_hist[2]; res_hist[2] = res_hist[3]; res_hist[3] = res; }
-        const double rho = std::pow(res / res_hist[0], 1.0 / (nhist - 1));
-        int n_rem = (rho > 0.0 && rho < 0.97) ? (int)std::ceil(std::log(tol / res) / std::log(rho)) : (1 << 20);
-        if (nhist == 2) n_rem = std::min(n_rem, 3);  // one sample of the rate: a short look ahead only
-        need = std::max(1, e_its > 0 ? std::min(n_rem, std::max(e_its - its, 1) + 2) : n_rem);
-      }
-      if (done || reason != 0) break;
-    }
-    if (jl > j) c->n_krylov_discarded += jl - j;  // launched ahead of the converging iteration: not part of the solution
-    if (reason == -9) break;
-    // y = H^-1 g ; x += Z y
-    for (int i = j - 1; i >= 0; i--) {
-      double s = g[i];
-      for (int k = i + 1; k < j; k++) s -= H[(size_t)k * (m + 1) + i] * y[k];
-      y[i] = s / H[(size_t)i * (m + 1) + i];
-    }
-    // y travels through a pinned slot behind the ring (no stream synchronisation: the slot is rewritten at the end of the next
-    // cycle at the earliest, after events recorded behind this copy have been waited for)
-    double *ystage = c->h_ring + c->h_ring_stride * cfdh_ctx::KRING;
-    for (int i = 0; i < j; i++) ystage[i] = y[i];
-    HIPCHK(c, hipMemcpyAsync(c->ky.p, ystage, sizeof(double) * j, hipMemcpyHostToDevice, c->stream));
-    // lean path: the update of a cycle that converged by the recurrence also writes the copy guess_store would make (a second
-    // store instead of a pass over x) where that slot is free; any other update of x leaves the copy to guess_store
-    double *keep = (lean_solve && done && reason == 0 && its < o.ksp_max_it) ? guess_store_target(c) : nullptr;
-    if (keep) CHK(v_lincomb_keep(c, n, Z, (int)ld, j, c->ky.p, x, keep));
-    else CHK(v_lincomb(c, n, Z, (int)ld, j, c->ky.p, x));
-    kept_copy = keep != nullptr;
-    est_prev = std::fabs(g[j]);
-    j_prev = j;
-    (void)done;
+    c->ksp_last_relres = beta / s.bn;  // true residual (r0 = b on the first pass)
+    if (beta <= s.tol) { s.reason = 2; break; }
+    if (s.its >= c->opt.ksp_max_it) { s.reason = -3; break; }
+    if (!std::isfinite(beta)) { s.reason = -9; break; }
+    if (src == V0From::rhs) CHK(v_scale_to(c, s.n, 1.0 / beta, b, V));
+    else if (src != V0From::guess_scaled) CHK(v_scale(c, s.n, 1.0 / beta, V));
+    if (s.use32) CHK(v_store32(c, s.n, V, s.V32));
+    src = V0From::residual;
+    CHK(fgmres_cycle(s, beta));
+    if (s.reason == -9) break;
+    CHK(fgmres_update_x(s));
   }
-  c->n_krylov += its;
-  *its_out = its;
-  *reason_out = reason;
-  if (gslot >= 0 && gslot < cfdh_ctx::GUESS_NEWTON) c->guess_last_its[gslot] = its;
-  if (reason > 0) CHK(guess_store(c, x, kept_copy));
+  c->n_krylov += s.its;
+  *its_out = s.its;
+  *reason_out = s.reason;
+  if (c->guess_slot >= 0 && c->guess_slot < cfdh_ctx::GUESS_NEWTON) c->guess_last_its[c->guess_slot] = s.its;
+  if (s.reason > 0) CHK(guess_store(c, x, s.kept_copy));
   return 0;
 }
 
@@ -1525,7 +1534,7 @@ int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st) {
     c->guess_slot = it;
     if (it < cfdh_ctx::GUESS_NEWTON) {
       c->guess_stored[it] = false;
-      if (c->guessX.p) CHK(v_copy(c, n, x, c->guessX.p + (size_t)it * (((size_t)c->NL + 1) & ~(size_t)1)));
+      if (c->guessX.p) CHK(v_copy(c, n, x, c->guessX.p + (size_t)it * krylov_ld(c)));
     }
     CHK(cfdh_fgmres(c, c->F.p, d, &kits, &kreason, fn));
     int kits_failed = 0;

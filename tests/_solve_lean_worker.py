@@ -1,5 +1,5 @@
-"""Worker of tests/test_gpu_solve_lean.py: runs time steps in a process of its own, because the library reads CFDH_KSP_LAG and
-CFDH_GS_ETA2 once per process.  Usage: _solve_lean_worker.py <case> <nsteps> <ksp_rtol> <out.npz>"""
+"""Worker of tests/test_gpu_solve_lean.py: runs time steps in a process of its own, started with the environment it is meant to
+see: the library reads CFDH_KSP_LAG and CFDH_GS_ETA2 at context creation.  Usage: _solve_lean_worker.py <case> <nsteps> <ksp_rtol> <out.npz>"""
 import os
 import sys
 
