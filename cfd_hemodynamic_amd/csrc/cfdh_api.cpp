@@ -524,6 +524,8 @@ int cfdh_set_formulation(cfdh_ctx *c, int form) {
       return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: the rotational formulation cannot be combined with the backflow term (beta > 0)");
   } else if (!c->pb_markers.empty()) {
     return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: pressure boundaries are set (they belong to the rotational formulation)");
+  } else if (c->gen && c->pcd_set) {
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: the PCD operator is set (on the generic element kernels it belongs to the rotational formulation)");
   }
   c->form = form;
   c->jac_valid = false;
@@ -559,8 +561,7 @@ int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, con
 int cfdh_set_schur_pcd(cfdh_ctx *c, int inlet_marker, int outlet_marker, int time_term) {
   NOT_IPCS(c, "cfdh_set_schur_pcd");
   ENTER(c);
-  if (c->gen) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: PCD exists for P1 triangles and tetrahedra on the closed-form kernels only");
-  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: PCD is not available in partitioned runs");
+  CHK(cfdh_pcd_supported(c, "cfdh_set_schur_pcd"));
   if (time_term != 0 && time_term != 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_schur_pcd: time_term must be 0 or 1");
   const bool markers_changed = !c->pcd_set || inlet_marker != c->pcd_in || outlet_marker != c->pcd_out;
   c->pcd_in = inlet_marker; c->pcd_out = outlet_marker; c->pcd_time = time_term;
@@ -602,7 +603,7 @@ int cfdh_get_pcd_operator(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *c
   *nnz = c->nnzv;
   if (!rowptr && !col && !vals && !mass_diag) return 0;
   if (!rowptr || !col || !vals) return cfdh_fail(c, CFDH_E_ARG, "pass all of rowptr/col/vals or none");
-  if (c->gen || c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_pcd_operator: P1 contexts on one GPU only");
+  CHK(cfdh_pcd_supported(c, "cfdh_get_pcd_operator"));
   if (!c->pcd_set) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_pcd_operator: cfdh_set_schur_pcd was not called");
   if (!c->params_set || !c->state_set) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_pcd_operator: parameters and state are needed");
   CHK(k_pcd_assemble(c, c->x.p));

@@ -510,6 +510,7 @@ int kg3_functional_partials(cfdh_ctx *c, int kind, int marker, int nb);
 int kg3_wss(cfdh_ctx *c, double *out);
 
 // ---- pressure convection-diffusion Schur approximation (cfdh_pcd.hip) -----------------------------------
+int cfdh_pcd_supported(cfdh_ctx *c, const char *who);  // 0, or CFDH_E_ARG with the reason on a context pc_type 2 does not exist for
 int cfdh_pcd_setup(cfdh_ctx *c);                       // incidences, inlet facets, SELL layout, 1 / diag(M)
 int k_pcd_assemble(cfdh_ctx *c, const double *xstate);  // K at the iterate xstate
 int k_pcd_apply(cfdh_ctx *c, const double *r, double *s);  // t = r / m_d, s = K t, q

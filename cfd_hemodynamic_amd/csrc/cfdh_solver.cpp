@@ -114,13 +114,15 @@ static void mark_outflow_nodes(const cfdh_ctx *c, std::vector<unsigned char> &pb
 // stabilized_pcd.py:215-218, PCDPC_vY) -- as bit 1, next to the pressure-Dirichlet bit 0.  The same array gives the flags of the
 // apply pass (bit 0: Dirichlet row of A_p, bit 1: pressure-Dirichlet row of the Jacobian).
 static void mark_pcd_outlet(const cfdh_ctx *c, std::vector<unsigned char> &pbc) {
-  const int n1 = c->dim + 1;
   for (int k = 0; k < c->nfac; k++) {
     if (c->fac_marker[k] != c->pcd_out) continue;
     const int e = c->fac_cell[k], fl = c->fac_local[k];
-    for (int q = 0; q < n1; q++) {
-      const int v = c->h_cells[(size_t)n1 * e + q];
-      if (q != fl && v < c->nvo) pbc[v] |= 2;
+    int loc[8], nn = 0;
+    if (c->gen) nn = c->dim == 3 ? cfdh_facet_nodes3(c, fl, loc) : cfdh_facet_nodes(c, fl, loc);
+    else for (int q = 0; q <= c->dim; q++) if (q != fl) loc[nn++] = q;
+    for (int q = 0; q < nn; q++) {
+      const int v = c->h_cells[(size_t)c->nloc * e + loc[q]];
+      if (v < c->nvo) pbc[v] |= 2;
     }
   }
 }
@@ -510,8 +512,7 @@ static int build_cc(cfdh_ctx *c) {
 int cfdh_pc_update(cfdh_ctx *c, bool refresh_amg) {
   const int nu = c->dim * c->nvo;
   if (c->opt.pc_type == 2) {
-    if (c->gen) return cfdh_fail(c, CFDH_E_ARG, "pc_type 2 (PCD) exists for P1 triangles and tetrahedra on the closed-form kernels only");
-    if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "pc_type 2 (PCD) is not available in partitioned runs");
+    CHK(cfdh_pcd_supported(c, "pc_type 2"));
     if (!c->pcd_set) return cfdh_fail(c, CFDH_E_STATE, "pc_type 2 (PCD) needs cfdh_set_schur_pcd");
   } else if (c->dim == 3 && c->opt.pc_type != 1) {
     return cfdh_fail(c, CFDH_E_ARG, "tetrahedral contexts support pc_type 1 and 2 only");

@@ -30,7 +30,8 @@
  * Dimension: gdim = 2 (triangles) or 3 (tetrahedra,
  * /root/reference/src/scenarios/simple_bifurcation.py, scenario_factory.py:47-49)
  * is fixed at cfdh_create; "d" below stands for it.  Tetrahedral contexts are
- * single-GPU in this version (cfdh_set_halo returns CFDH_E_ARG) and use pc_type 1 or 2.
+ * single-GPU in this version (cfdh_set_halo returns CFDH_E_ARG) and use pc_type 1 or 2
+ * (pc_type 2 also on the degree-1 generic contexts of the rotational form, cfdh_set_schur_pcd).
  */
 #ifndef CFDH_H
 #define CFDH_H
@@ -262,8 +263,12 @@ int cfdh_set_pressure_boundaries(cfdh_ctx *ctx, int n, const int32_t *markers, c
  *         pressure-Dirichlet rows of the Jacobian.
  * In this library's convention S = A11 - A10 A00^-1 A01 is positive; the reference's -(I + A_p^-1 K_p) M_p^-1 with K_p = K / mu (no
  * time term) differs by the factor -1/mu.  K is assembled from the current iterate in every preconditioner update, once per Newton
- * iteration.  P1 triangles and tetrahedra on one GPU (cfdh_create): CFDH_E_ARG on generic-element contexts (CFDH_ELEM_P2*, Q1*,
- * P1_GENERIC) and on parts of a partitioned run; pc_type 2 without this call fails with CFDH_E_STATE at the solve. */
+ * iteration.  One GPU.  Contexts: P1 triangles and tetrahedra on the closed-form kernels (cfdh_create), and the degree-1 cells of the
+ * rotational form on the generic element kernels -- CFDH_ELEM_P1_GENERIC triangles, CFDH_ELEM_Q1 parallelograms (gdim 2) and
+ * parallelepipeds (gdim 3) -- once cfdh_set_formulation(CFDH_FORM_ROTATIONAL) has been called; there "P1" above reads "the element's
+ * own", the vertices are the nodes, and cfdh_set_formulation refuses to go back to the convective form while this data is set.
+ * CFDH_E_ARG on generic-element contexts in the convective form, on P2 contexts and on parts of a partitioned run; pc_type 2
+ * without this call fails with CFDH_E_STATE at the solve. */
 int cfdh_set_schur_pcd(cfdh_ctx *ctx, int inlet_marker, int outlet_marker, int time_term);
 /* Eisenstat-Walker forcing of the linear tolerance (snes_ksp_ew, stabilized_pcd.py:249).  version 0: off (default; ksp_rtol of
  * cfdh_options for every solve).  version 2 (PETSc's default variant; its defaults 0.3, 0.9, 1.0, (1 + sqrt 5)/2, 0.1): the first
@@ -275,7 +280,7 @@ int cfdh_set_ksp_forcing(cfdh_ctx *ctx, int version, double rtol_0, double rtol_
 int cfdh_get_newton_history(cfdh_ctx *ctx, int32_t *n, double *fnorm, double *ksp_rtol, int32_t *ksp_its, double *ksp_rel_res);
 /* K of cfdh_set_schur_pcd, assembled from the current state (cfdh_set_state), as CSR of the owned rows in user numbering (columns
  * ascending), and M_d (mass_diag[nv_owned], may be NULL).  Query convention of cfdh_get_csr (nnz first with rowptr = col = vals =
- * NULL).  Exposed for parity tests, like cfdh_spmv. */
+ * NULL).  The contexts of cfdh_set_schur_pcd, CFDH_E_ARG elsewhere.  Exposed for parity tests, like cfdh_spmv. */
 int cfdh_get_pcd_operator(cfdh_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *mass_diag);
 /* z = P^-1 r with the current preconditioner (built, and for pc_type 2 with K assembled, at the current state when needed) on the
  * assembled Jacobian; r, z monolithic [gdim*nv | nv] as for cfdh_spmv.  Exposed for parity tests. */
