@@ -7,77 +7,37 @@
 #include <numeric>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_mesh_host.hpp"
 
-static inline uint64_t spread3(uint64_t x) {  // 21 bits -> every third bit
-  x &= 0x1fffff;
-  x = (x | x << 32) & 0x1f00000000ffffull;
-  x = (x | x << 16) & 0x1f0000ff0000ffull;
-  x = (x | x << 8) & 0x100f00f00f00f00full;
-  x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-  x = (x | x << 2) & 0x1249249249249249ull;
-  return x;
-}
+static const cfdh_mesh::Wording W_CLOSED3 = {"bad mesh sizes", "mesh too large for int32 indexing", "vertex", "vertex %d has no cell",
+                                             "facet (cell, local) out of range"};
 
 int cfdh_build_mesh3(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, const int32_t *cells, const double *coords,
                      int64_t nfac64, const int32_t *fcell, const int32_t *flocal, const int32_t *fmarker) {
   const int nv = (int)nv64, nvo = (int)nvo64, ncu = (int)nc64, nfac = (int)nfac64;
-  if (nv <= 0 || nvo <= 0 || nvo > nv || ncu <= 0) return cfdh_fail(c, CFDH_E_ARG, "bad mesh sizes");
-  if (nv64 > (1ll << 28) || nc64 > (1ll << 29)) return cfdh_fail(c, CFDH_E_ARG, "mesh too large for int32 indexing");
-  for (int64_t k = 0; k < 4 * nc64; k++)
-    if (cells[k] < 0 || cells[k] >= nv) return cfdh_fail(c, CFDH_E_ARG, "cell vertex index out of range");
-  for (int k = 0; k < nfac; k++)
-    if (fcell[k] < 0 || fcell[k] >= ncu || flocal[k] < 0 || flocal[k] > 3) return cfdh_fail(c, CFDH_E_ARG, "facet (cell, local) out of range");
+  std::string why;
+  if (!cfdh_mesh::check_sizes(nv64, nvo64, nc64, 4, cells, 1ll << 28, 1ll << 29, W_CLOSED3, why) ||
+      !cfdh_mesh::check_facets(nfac64, fcell, flocal, nc64, 4, W_CLOSED3, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   c->dim = 3; c->nloc = 4;
   // a part of a partitioned mesh: owned vertices first, ghosts after (as in 2-D); vectors [u owned 3 nvo | p owned nvo |
   // ghosts (ux, uy, uz, p) ng]
   c->nv = nv; c->nvo = nvo; c->ng = nv - nvo;
   c->NO = 4 * nvo; c->NL = 4 * nvo + 4 * c->ng;
   // ---- Morton numbering of the owned vertices (ghosts keep their order: grouped by owner)
-  c->perm.resize(nv); c->iperm.resize(nv);
-  {
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (int v = 0; v < nv; v++)
-      for (int i = 0; i < 3; i++) { lo[i] = std::min(lo[i], coords[3 * v + i]); hi[i] = std::max(hi[i], coords[3 * v + i]); }
-    const double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
-    if (!(ext > 0)) return cfdh_fail(c, CFDH_E_ARG, "degenerate coordinates");
-    std::vector<uint64_t> key(nvo);
-    for (int v = 0; v < nvo; v++) {
-      uint64_t q[3];
-      for (int i = 0; i < 3; i++) q[i] = (uint64_t)std::min(2097151.0, (coords[3 * v + i] - lo[i]) / ext * 2097151.0);
-      key[v] = spread3(q[0]) | (spread3(q[1]) << 1) | (spread3(q[2]) << 2);
-    }
-    std::vector<int> order(nvo);
-    std::iota(order.begin(), order.end(), 0);
-    const char *nr = getenv("CFDH_NO_RENUMBER");
-    if (!(nr && nr[0] == '1')) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-    for (int k = 0; k < nvo; k++) { c->iperm[k] = order[k]; c->perm[order[k]] = k; }
-    for (int v = nvo; v < nv; v++) { c->iperm[v] = v; c->perm[v] = v; }
-  }
-  c->h_coords.resize(3 * (size_t)nv);
-  for (int k = 0; k < nv; k++)
-    for (int i = 0; i < 3; i++) c->h_coords[3 * (size_t)k + i] = coords[3 * (size_t)c->iperm[k] + i];
+  c->perm.resize(nv); c->iperm.resize(nv); c->h_coords.resize(3 * (size_t)nv);
+  if (!cfdh_mesh::morton_numbering(3, 21, cfdh_renumber_enabled(), nv, nvo, coords, c->perm.data(), c->iperm.data(), c->h_coords.data(), why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   // ---- cells in internal ids, sorted by smallest vertex, positively oriented
   {
-    std::vector<std::pair<int, int>> keyed;
-    keyed.reserve(ncu);
-    for (int e = 0; e < ncu; e++) {
-      int mn = nv;
-      for (int a = 0; a < 4; a++) mn = std::min(mn, c->perm[cells[4 * e + a]]);
-      if (mn < nvo) keyed.push_back({mn, e});  // cells touching an owned vertex
-    }
-    std::stable_sort(keyed.begin(), keyed.end());
-    const int nck = (int)keyed.size();
-    c->nc = nck;
-    c->h_cells.resize(4 * (size_t)nck);
-    c->cell_user.resize(nck);
-    std::vector<int> cmap(ncu, -1);
+    std::vector<int> cmap;
+    cfdh_mesh::select_cells(4, ncu, nvo, cells, c->perm.data(), c->h_cells, c->cell_user, cmap);
+    const int nck = c->nc = (int)c->cell_user.size();
     std::vector<unsigned char> flipped(nck, 0);
     const double *X = c->h_coords.data();
     for (int k = 0; k < nck; k++) {
-      const int e = keyed[k].second;
-      cmap[e] = k; c->cell_user[k] = e;
+      const int e = c->cell_user[k];
       int *v = &c->h_cells[4 * (size_t)k];
-      for (int a = 0; a < 4; a++) v[a] = c->perm[cells[4 * e + a]];
       for (int a = 0; a < 4; a++)
         for (int b = a + 1; b < 4; b++)
           if (v[a] == v[b]) return cfdh_fail(c, CFDH_E_ARG, "degenerate cell %d", e);
@@ -103,34 +63,15 @@ int cfdh_build_mesh3(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, con
     c->nfac = (int)c->fac_cell.size();
   }
   const int nc = c->nc;
-  // ---- vertex -> incident (cell, local); vertex graph
-  std::vector<int> vcptr(nvo + 1, 0);
-  for (size_t k = 0; k < 4 * (size_t)nc; k++) if (c->h_cells[k] < nvo) vcptr[c->h_cells[k] + 1]++;
-  for (int v = 0; v < nvo; v++) vcptr[v + 1] += vcptr[v];
+  // ---- vertex -> incident (cell, local) (vcell = 4 cell + local); vertex graph
+  std::vector<int> vcptr, vcell;
+  if (!cfdh_mesh::node_graph(4, nc, nvo, c->h_cells.data(), c->iperm.data(), vcptr, vcell, c->h_vptr, c->h_vcol, c->h_vdiag, W_CLOSED3, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
+  for (int v = 0; v < nvo; v++) {
+    const int deg = c->h_vptr[v + 1] - c->h_vptr[v];
+    if (deg > CFDH3_MAX_SLOTS) return cfdh_fail(c, CFDH_E_ARG, "vertex valence %d exceeds %d", deg, CFDH3_MAX_SLOTS);
+  }
   const int ninc = vcptr[nvo];
-  std::vector<int> vcell(ninc);
-  {
-    std::vector<int> fill(nvo, 0);
-    for (int e = 0; e < nc; e++)
-      for (int a = 0; a < 4; a++) { const int v = c->h_cells[4 * (size_t)e + a]; if (v < nvo) vcell[vcptr[v] + fill[v]++] = 4 * e + a; }
-  }
-  c->h_vptr.assign(nvo + 1, 0);
-  c->h_vcol.clear(); c->h_vcol.reserve((size_t)16 * nvo);
-  c->h_vdiag.resize(nvo);
-  {
-    std::vector<int> tmp;
-    for (int v = 0; v < nvo; v++) {
-      if (vcptr[v + 1] == vcptr[v]) return cfdh_fail(c, CFDH_E_ARG, "vertex %d has no cell", c->iperm[v]);
-      tmp.clear();
-      for (int k = vcptr[v]; k < vcptr[v + 1]; k++) { const int e = vcell[k] >> 2; for (int a = 0; a < 4; a++) tmp.push_back(c->h_cells[4 * (size_t)e + a]); }
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-      if ((int)tmp.size() > CFDH3_MAX_SLOTS) return cfdh_fail(c, CFDH_E_ARG, "vertex valence %d exceeds %d", (int)tmp.size(), CFDH3_MAX_SLOTS);
-      c->h_vdiag[v] = (int)c->h_vcol.size() + (int)(std::lower_bound(tmp.begin(), tmp.end(), v) - tmp.begin());
-      c->h_vcol.insert(c->h_vcol.end(), tmp.begin(), tmp.end());
-      c->h_vptr[v + 1] = (int)c->h_vcol.size();
-    }
-  }
   c->nnzv = (int)c->h_vcol.size();
   c->ninc = ninc;
   // ---- P1 stiffness and lumped mass (geometry only)
@@ -223,13 +164,7 @@ int cfdh_build_mesh3(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, con
   HIPCHK(c, c->cells.upload(c->h_cells, s));
   HIPCHK(c, c->cflag.upload(cflag, s));
   HIPCHK(c, c->mom.alloc(12 * (size_t)nc));
-  HIPCHK(c, c->vptr.upload(c->h_vptr, s));
-  HIPCHK(c, c->vcol.upload(c->h_vcol, s));
-  HIPCHK(c, c->vdiag.upload(c->h_vdiag, s));
-  HIPCHK(c, c->A00.alloc(9 * (size_t)c->nnzv));
-  HIPCHK(c, c->A01.alloc(3 * (size_t)c->nnzv));
-  HIPCHK(c, c->A10.alloc(3 * (size_t)c->nnzv));
-  HIPCHK(c, c->A11.alloc((size_t)c->nnzv));
+  CHK(cfdh_upload_graph(c));
   HIPCHK(c, c->a3_blk_row.upload(blk_row, s));
   HIPCHK(c, c->a3_blk_iptr.upload(blk_iptr, s));
   HIPCHK(c, c->a3_inc_cell.upload(inc_cell, s));
@@ -239,31 +174,11 @@ int cfdh_build_mesh3(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, con
   std::vector<unsigned char> cown(nc, 1);  // lives until the stream synchronisation at the end of this function
   for (int k = 0; k < nc; k++) cown[k] = cells[4 * (size_t)c->cell_user[k]] < nvo ? 1 : 0;
   HIPCHK(c, c->cell_owned.upload(cown, s));
-  if (c->nfac) {
-    HIPCHK(c, c->d_fac_cell.upload(c->fac_cell, s));
-    HIPCHK(c, c->d_fac_local.upload(c->fac_local, s));
-    HIPCHK(c, c->d_fac_marker.upload(c->fac_marker, s));
-  }
-  c->h_bcflag.assign(nv, 0);
-  c->h_bcval.assign(4 * (size_t)nv, 0.0);
-  c->h_bcmult.assign(4 * (size_t)nv, 0.0);
-  HIPCHK(c, c->bcflag.alloc(nv));
-  HIPCHK(c, c->bcval.alloc(4 * (size_t)nv));
-  HIPCHK(c, c->bcmult.alloc(4 * (size_t)nv));
-  c->bc_dirty = true;
-  const size_t NL = c->NL;
-  HIPCHK(c, c->x.alloc(NL)); HIPCHK(c, c->xt.alloc(NL)); HIPCHK(c, c->xprev.alloc(NL)); HIPCHK(c, c->xprev2.alloc(NL));
-  HIPCHK(c, c->F.alloc(NL)); HIPCHK(c, c->dvec.alloc(NL));
-  HIPCHK(c, c->x.zero(s)); HIPCHK(c, c->xt.zero(s)); HIPCHK(c, c->xprev.zero(s)); HIPCHK(c, c->xprev2.zero(s)); HIPCHK(c, c->F.zero(s)); HIPCHK(c, c->dvec.zero(s));
-  c->red_blocks = 1024;
-  HIPCHK(c, c->red_partial.alloc((size_t)c->red_blocks * 260));
-  HIPCHK(c, c->red_out.alloc(1024));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, 1024 * sizeof(double)));
-  HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinned_dev, c->h_pinned, 0));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_h, hipEventDisableTiming));
-  HIPCHK(c, c->pu0.alloc(3 * (size_t)nvo)); HIPCHK(c, c->pu1.alloc(3 * (size_t)nvo)); HIPCHK(c, c->pu2.alloc(3 * (size_t)nvo));
-  HIPCHK(c, c->pr.alloc(3 * (size_t)nvo));
-  HIPCHK(c, c->pp0.alloc(nvo)); HIPCHK(c, c->pp1.alloc(nvo));
+  CHK(cfdh_upload_facets(c));
+  CHK(cfdh_alloc_dirichlet(c));
+  CHK(cfdh_alloc_state(c));
+  CHK(cfdh_alloc_reduction(c, true));
+  CHK(cfdh_alloc_precond_work(c, nvo, false));  // this builder has neither dinvA nor prand
   HIPCHK(c, hipStreamSynchronize(s));
   return 0;
 }

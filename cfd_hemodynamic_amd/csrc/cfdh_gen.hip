@@ -27,8 +27,10 @@
 #include <numeric>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_mesh_host.hpp"
 #include "cfdh_quad_gl.h"
 #include "cfdh_quad_tri.h"
+#include "cfdh_wave.hpp"
 
 #define TPB 256
 #define GEN_MAXL 6
@@ -434,7 +436,7 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
   }
   // constrained rows / columns contribute zeros (their rows are written by gen_bc_rows_kernel)
   const int fd = P.fdst[(size_t)cell * NL + a];
-  if (fd < 0) return;  // row of a ghost node: assembled by its owner (one-cell overlap of the partition)
+  if (fd < 0) return;  // row of a ghost node: assembled by its owner
   {
     double *ef = P.EF + 3 * (size_t)fd;
     ef[0] = (bca & 1u) ? 0.0 : Fa[0];
@@ -506,19 +508,6 @@ __global__ __launch_bounds__(TPB) void gen_bc_rows_kernel(int nvo, int mode, con
   }
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ double block_sum_d(double v, double *sh) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // int u.u and int p^2 with the element's own mass matrix (scenario.py:315-324)
 template <int ET>
 __global__ __launch_bounds__(TPB) void gen_l2_kernel(int nc, int nvo, const int *__restrict__ cells, const unsigned char *__restrict__ cell_owned,
@@ -543,8 +532,8 @@ __global__ __launch_bounds__(TPB) void gen_l2_kernel(int nc, int nvo, const int 
       ap += adet * T.w[q] * pq * pq;
     }
   }
-  au = block_sum_d(au, sh);
-  ap = block_sum_d(ap, sh);
+  au = block_sum_xor(au, sh);
+  ap = block_sum_xor(ap, sh);
   if (threadIdx.x == 0) { partial[blockIdx.x] = au; partial[gridDim.x + blockIdx.x] = ap; }
 }
 
@@ -600,8 +589,8 @@ __global__ __launch_bounds__(TPB) void gen_facet_functional_kernel(int nfac, int
       }
     }
   }
-  a0 = block_sum_d(a0, sh);
-  a1 = block_sum_d(a1, sh);
+  a0 = block_sum_xor(a0, sh);
+  a1 = block_sum_xor(a1, sh);
   if (threadIdx.x == 0) { partial[blockIdx.x] = a0; partial[gridDim.x + blockIdx.x] = a1; }
 }
 
@@ -654,21 +643,18 @@ __global__ __launch_bounds__(TPB) void gen_wss_kernel(int nfac, int nvo, const i
     if (acc[a][0] != 0.0 || acc[a][1] != 0.0) { atomicAdd(out + 2 * (size_t)vs[a], acc[a][0]); atomicAdd(out + 2 * (size_t)vs[a] + 1, acc[a][1]); }
 }
 
-inline uint32_t part1by1(uint32_t x) {
-  x &= 0x0000ffff;
-  x = (x ^ (x << 8)) & 0x00ff00ff;
-  x = (x ^ (x << 4)) & 0x0f0f0f0f;
-  x = (x ^ (x << 2)) & 0x33333333;
-  x = (x ^ (x << 1)) & 0x55555555;
-  return x;
+// the reference tables on the host, filled on first use
+const GenTab &host_tab(int et) {
+  static GenTab T[3];
+  static bool init = false;
+  if (!init) { fill_tab<0>(T[0]); fill_tab<1>(T[1]); fill_tab<2>(T[2]); init = true; }
+  return T[et];
 }
 
 }  // namespace
 
 int kg_upload_tables(cfdh_ctx *c) {
-  static GenTab tab[3];
-  fill_tab<0>(tab[0]); fill_tab<1>(tab[1]); fill_tab<2>(tab[2]);
-  HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(d_tab), tab, sizeof tab));
+  HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(d_tab), &host_tab(0), sizeof(GenTab[3])));
   double g2[2][2], g4[2][4];
   for (int q = 0; q < 2; q++) { g2[0][q] = CFDH_GL2_X[q]; g2[1][q] = CFDH_GL2_W[q]; }
   for (int q = 0; q < 4; q++) { g4[0][q] = CFDH_GL4_X[q]; g4[1][q] = CFDH_GL4_W[q]; }
@@ -686,185 +672,72 @@ int cfdh_facet_nodes(const cfdh_ctx *c, int f, int out[3]) {
   return 2;
 }
 
-// Mesh upload for the generic element path: Morton numbering of the nodes, node graph, value slots of every local node pair,
-// stiffness / diagonal mass of the element on the graph (Cahouet-Chabard preconditioner), state and work vectors.
+// Mesh upload for the generic element path: the shared steps of cfdh_mesh_host.hpp (Morton numbering of the nodes, node graph,
+// slots and staging order of every local node pair, stiffness / diagonal mass of the element on the graph for the
+// Cahouet-Chabard preconditioner), then the state and work vectors.  CFDH_NO_RENUMBER is not read here.
 int cfdh_build_mesh_gen(cfdh_ctx *c, int etype, int64_t nv64, int64_t nvo64, int64_t nc64, const int32_t *cells, const double *coords, int64_t nfac64,
                         const int32_t *fcell, const int32_t *flocal, const int32_t *fmarker) {
   const int nv = (int)nv64, nvo = (int)nvo64, nc = (int)nc64, nfac = (int)nfac64;
-  if (nvo <= 0 || nvo > nv) return cfdh_fail(c, CFDH_E_ARG, "bad owned node count");
   const int et = etype == 3 ? 0 : etype;  // 3: P1 triangles through the generic kernels (cross-check of the closed-form path)
   const int NL = gen_nloc(et), NF = et == 2 ? 4 : 3;
-  if (nv <= 0 || nc <= 0) return cfdh_fail(c, CFDH_E_ARG, "bad mesh sizes");
-  if (nv64 > (1ll << 29) || nc64 > (1ll << 27)) return cfdh_fail(c, CFDH_E_ARG, "mesh too large for int32 indexing");
-  for (int64_t k = 0; k < (int64_t)NL * nc; k++)
-    if (cells[k] < 0 || cells[k] >= nv) return cfdh_fail(c, CFDH_E_ARG, "cell node index out of range");
-  for (int k = 0; k < nfac; k++)
-    if (fcell[k] < 0 || fcell[k] >= nc || flocal[k] < 0 || flocal[k] >= NF) return cfdh_fail(c, CFDH_E_ARG, "facet (cell, local) out of range");
+  const cfdh_mesh::Wording W;
+  std::string why;
+  if (!cfdh_mesh::check_sizes(nv64, nvo64, nc64, NL, cells, 1ll << 29, 1ll << 27, W, why) || !cfdh_mesh::check_facets(nfac64, fcell, flocal, nc64, NF, W, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   c->etype = et; c->nloc = NL; c->gen = true;
-  // partitioned runs (round 4): nodes [0, nvo) are owned, the rest are the ghost nodes of the one-cell overlap in the order of the
-  // halo plan; rows are assembled for owned nodes only; vectors carry the ghost tail [(u_x, u_y, p) per ghost]
+  // vectors carry the ghost tail [(u_x, u_y, p) per ghost]
   c->nv = nv; c->nvo = nvo; c->ng = nv - nvo;
   c->NO = 3 * nvo; c->NL = 3 * nvo + 3 * c->ng;
   // ---- node numbering: owned nodes along a Morton curve, ghosts unchanged
-  c->perm.resize(nv); c->iperm.resize(nv);
-  {
-    std::vector<int> order(nvo);
-    std::iota(order.begin(), order.end(), 0);
-    double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
-    for (int v = 0; v < nv; v++)
-      for (int i = 0; i < 2; i++) { lo[i] = std::min(lo[i], coords[2 * v + i]); hi[i] = std::max(hi[i], coords[2 * v + i]); }
-    const double ext = std::max(hi[0] - lo[0], hi[1] - lo[1]);
-    if (!(ext > 0)) return cfdh_fail(c, CFDH_E_ARG, "degenerate coordinates");
-    std::vector<uint32_t> key(nvo);
-    for (int v = 0; v < nvo; v++) {
-      const uint32_t qx = (uint32_t)std::min(65535.0, (coords[2 * v] - lo[0]) / ext * 65535.0), qy = (uint32_t)std::min(65535.0, (coords[2 * v + 1] - lo[1]) / ext * 65535.0);
-      key[v] = part1by1(qx) | (part1by1(qy) << 1);
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-    for (int k = 0; k < nvo; k++) { c->iperm[k] = order[k]; c->perm[order[k]] = k; }
-    for (int v = nvo; v < nv; v++) { c->iperm[v] = v; c->perm[v] = v; }
-  }
-  c->h_coords.resize(2 * (size_t)nv);
-  for (int k = 0; k < nv; k++) { c->h_coords[2 * k] = coords[2 * c->iperm[k]]; c->h_coords[2 * k + 1] = coords[2 * c->iperm[k] + 1]; }
+  c->perm.resize(nv); c->iperm.resize(nv); c->h_coords.resize(2 * (size_t)nv);
+  if (!cfdh_mesh::morton_numbering(2, 16, true, nv, nvo, coords, c->perm.data(), c->iperm.data(), c->h_coords.data(), why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   // ---- cells (user order kept: no fan structure to build), facets
   c->nc = nc;
   c->h_cells.resize((size_t)NL * nc);
   c->cell_user.resize(nc);
+  const double *X = c->h_coords.data();
+  const int ed[3][2] = {{1, 2}, {0, 2}, {0, 1}};  // the edge of P2 node 3 + q
   for (int e = 0; e < nc; e++) {
     c->cell_user[e] = e;
     for (int a = 0; a < NL; a++) c->h_cells[(size_t)NL * e + a] = c->perm[cells[(size_t)NL * e + a]];
-    const double *X = c->h_coords.data();
     const int *v = &c->h_cells[(size_t)NL * e];
-    const double det = (X[2 * v[1]] - X[2 * v[0]]) * (X[2 * v[2] + 1] - X[2 * v[0] + 1]) - (X[2 * v[1] + 1] - X[2 * v[0] + 1]) * (X[2 * v[2]] - X[2 * v[0]]);
+    const double det = cfdh_mesh::tri_det(X, v);
     if (!(std::fabs(det) > 0)) return cfdh_fail(c, CFDH_E_ARG, "zero-area cell %d", e);
-    if (et == 2) {
-      // Q1 cells must be parallelograms (affine map): x3 = x1 + x2 - x0
-      const double ex = X[2 * v[3]] - (X[2 * v[1]] + X[2 * v[2]] - X[2 * v[0]]), ey = X[2 * v[3] + 1] - (X[2 * v[1] + 1] + X[2 * v[2] + 1] - X[2 * v[0] + 1]);
-      if (std::hypot(ex, ey) > 1e-9 * std::sqrt(std::fabs(det))) return cfdh_fail(c, CFDH_E_ARG, "quadrilateral %d is not a parallelogram: only affine Q1 cells are supported", e);
-    }
-    if (et == 1) {
-      // P2 on a straight-sided triangulation: edge nodes at the edge midpoints
-      const int ed[3][2] = {{1, 2}, {0, 2}, {0, 1}};
-      for (int q = 0; q < 3; q++) {
-        const double mx = 0.5 * (X[2 * v[ed[q][0]]] + X[2 * v[ed[q][1]]]) - X[2 * v[3 + q]], my = 0.5 * (X[2 * v[ed[q][0]] + 1] + X[2 * v[ed[q][1]] + 1]) - X[2 * v[3 + q] + 1];
-        if (std::hypot(mx, my) > 1e-9 * std::sqrt(std::fabs(det))) return cfdh_fail(c, CFDH_E_ARG, "P2 cell %d: edge node %d is not the edge midpoint (curved cells are not supported)", e, q);
-      }
-    }
+    if (et == 2 && !cfdh_mesh::is_parallelogram(X, v, std::fabs(det)))  // affine map
+      return cfdh_fail(c, CFDH_E_ARG, "quadrilateral %d is not a parallelogram: only affine Q1 cells are supported", e);
+    const int bent = et == 1 ? cfdh_mesh::p2_bent_edge(2, ed, X, v, std::fabs(det)) : -1;  // straight-sided triangulation
+    if (bent >= 0) return cfdh_fail(c, CFDH_E_ARG, "P2 cell %d: edge node %d is not the edge midpoint (curved cells are not supported)", e, bent);
   }
   c->fac_cell.assign(fcell, fcell + nfac); c->fac_local.assign(flocal, flocal + nfac);
   c->fac_marker.resize(nfac); c->fac_user.resize(nfac);
   for (int k = 0; k < nfac; k++) { c->fac_marker[k] = fmarker ? fmarker[k] : 0; c->fac_user[k] = k; }
   c->nfac = c->nfac_user = nfac;
   // ---- node graph
-  std::vector<int> ncptr(nv + 1, 0);
-  for (size_t k = 0; k < c->h_cells.size(); k++) ncptr[c->h_cells[k] + 1]++;
-  for (int v = 0; v < nv; v++) ncptr[v + 1] += ncptr[v];
-  std::vector<int> ncell(ncptr[nv]);
-  {
-    std::vector<int> fill(nv, 0);
-    for (int e = 0; e < nc; e++)
-      for (int a = 0; a < NL; a++) { const int v = c->h_cells[(size_t)NL * e + a]; ncell[ncptr[v] + fill[v]++] = e; }
-  }
-  c->h_vptr.assign(nvo + 1, 0);
-  c->h_vcol.clear(); c->h_vcol.reserve((size_t)14 * nvo);
-  c->h_vdiag.resize(nvo);
-  {
-    std::vector<int> tmp;
-    for (int v = 0; v < nvo; v++) {
-      if (ncptr[v + 1] == ncptr[v]) return cfdh_fail(c, CFDH_E_ARG, "node %d belongs to no cell", c->iperm[v]);
-      tmp.clear();
-      for (int k = ncptr[v]; k < ncptr[v + 1]; k++)
-        for (int a = 0; a < NL; a++) tmp.push_back(c->h_cells[(size_t)NL * ncell[k] + a]);
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-      c->h_vdiag[v] = (int)c->h_vcol.size() + (int)(std::lower_bound(tmp.begin(), tmp.end(), v) - tmp.begin());
-      c->h_vcol.insert(c->h_vcol.end(), tmp.begin(), tmp.end());
-      c->h_vptr[v + 1] = (int)c->h_vcol.size();
-    }
-  }
+  std::vector<int> iptr, inc;
+  if (!cfdh_mesh::node_graph(NL, nc, nvo, c->h_cells.data(), c->iperm.data(), iptr, inc, c->h_vptr, c->h_vcol, c->h_vdiag, W, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   c->nnzv = (int)c->h_vcol.size();
   c->ninc = (int)c->h_cells.size();
-  // ---- slots, stiffness and diagonal mass on the graph
-  std::vector<int> slot((size_t)nc * NL * NL);
-  c->h_Lval.assign(c->nnzv, 0.0);
-  c->h_Ml.assign(nv, 0.0);
-  GenTab T;
-  if (et == 0) fill_tab<0>(T); else if (et == 1) fill_tab<1>(T); else fill_tab<2>(T);
-  double msum = 0.0, dsum = 0.0;
-  std::vector<double> mdiag(nv, 0.0);
-  for (int e = 0; e < nc; e++) {
+  // ---- slots, stiffness and diagonal mass on the graph, staging order of the assembly (see the header)
+  std::vector<int> slot, eptr, fptr, fdst;
+  cfdh_mesh::graph_slots(NL, nc, nvo, c->h_cells.data(), c->h_vptr.data(), c->h_vcol.data(), slot);
+  const GenTab &T = host_tab(et);
+  cfdh_mesh::scatter_stiffness_mass(NL, nc, nv, c->h_cells.data(), slot, c->nnzv, [&](int e, double *K, double *Md) {
     const int *v = &c->h_cells[(size_t)NL * e];
-    const double *X = c->h_coords.data();
-    const double J00 = X[2 * v[1]] - X[2 * v[0]], J01 = X[2 * v[2]] - X[2 * v[0]], J10 = X[2 * v[1] + 1] - X[2 * v[0] + 1], J11 = X[2 * v[2] + 1] - X[2 * v[0] + 1];
-    const double det = J00 * J11 - J01 * J10, adet = std::fabs(det);
-    const double Ji[2][2] = {{J11 / det, -J01 / det}, {-J10 / det, J00 / det}};
-    double K[GEN_MAXL][GEN_MAXL] = {{0}}, Md[GEN_MAXL] = {0};
-    for (int q = 0; q < GEN_NQ; q++) {
-      double g[GEN_MAXL][2];
-      for (int a = 0; a < NL; a++)
-        for (int i = 0; i < 2; i++) g[a][i] = T.dphi[q][a][0] * Ji[0][i] + T.dphi[q][a][1] * Ji[1][i];
-      for (int a = 0; a < NL; a++) {
-        Md[a] += adet * T.w[q] * T.phi[q][a] * T.phi[q][a];
-        for (int b = 0; b < NL; b++) K[a][b] += adet * T.w[q] * (g[a][0] * g[b][0] + g[a][1] * g[b][1]);
-      }
-    }
-    msum += adet * (et == 2 ? 1.0 : 0.5);
-    for (int a = 0; a < NL; a++) {
-      mdiag[v[a]] += Md[a];
-      dsum += Md[a];
-      if (v[a] >= nvo) {  // row of a ghost node: assembled by its owner
-        for (int b = 0; b < NL; b++) slot[((size_t)e * NL + a) * NL + b] = -1;
-        continue;
-      }
-      const int *nb = &c->h_vcol[c->h_vptr[v[a]]];
-      const int deg = c->h_vptr[v[a] + 1] - c->h_vptr[v[a]];
-      for (int b = 0; b < NL; b++) {
-        const int k = c->h_vptr[v[a]] + (int)(std::lower_bound(nb, nb + deg, v[b]) - nb);
-        slot[((size_t)e * NL + a) * NL + b] = k;
-        c->h_Lval[k] += K[a][b];
-      }
-    }
-  }
+    cfdh_gen_element_stiffness(c, v, X, K);
+    const double adet = std::fabs(cfdh_mesh::tri_det(X, v));
+    for (int a = 0; a < NL; a++) Md[a] = 0.0;
+    for (int q = 0; q < GEN_NQ; q++)
+      for (int a = 0; a < NL; a++) Md[a] += adet * T.w[q] * T.phi[q][a] * T.phi[q][a];
+    return adet * (et == 2 ? 1.0 : 0.5);
+  }, c->h_Lval, c->h_Ml);
   if (et == 1) {
-    // P1 subspace of the P2 space: vertex nodes (local positions 0..2) numbered in order of first appearance along the node
-    // numbering; an edge node interpolates its two end vertices
-    std::vector<int> vid(nv, -1), ea(nv, -1), eb(nv, -1);
-    for (int e = 0; e < nc; e++) {
-      const int *v = &c->h_cells[(size_t)NL * e];
-      const int ed[3][2] = {{1, 2}, {0, 2}, {0, 1}};
-      for (int q = 0; q < 3; q++) { vid[v[q]] = 0; ea[v[3 + q]] = v[ed[q][0]]; eb[v[3 + q]] = v[ed[q][1]]; }
-    }
-    int nvert = 0;
-    for (int v = 0; v < nv; v++) if (vid[v] == 0) vid[v] = nvert++;
-    CsrHost &P = c->gen_P1;
-    P.n = nv; P.m = nvert;
-    P.rowptr.assign(nv + 1, 0); P.col.clear(); P.val.clear();
-    for (int v = 0; v < nv; v++) {
-      if (vid[v] >= 0) { P.col.push_back(vid[v]); P.val.push_back(1.0); }
-      else {
-        int a = vid[ea[v]], b = vid[eb[v]];
-        if (a > b) std::swap(a, b);
-        P.col.push_back(a); P.val.push_back(0.5); P.col.push_back(b); P.val.push_back(0.5);
-      }
-      P.rowptr[v + 1] = (int)P.col.size();
-    }
+    CsrHost &P = c->gen_P1;  // p-multigrid step: P1 subspace of the P2 space
+    P.n = nv;
+    P.m = cfdh_mesh::p1_subspace(NL, 3, ed, nc, nv, c->h_cells.data(), P.rowptr, P.col, P.val);
   }
-  // staging order of the assembly (see the header): contributions to one block entry / one node adjacent, in cell order
-  std::vector<int> eptr((size_t)c->nnzv + 1, 0), fptr((size_t)nvo + 1, 0), fdst((size_t)nc * NL, -1);
-  for (size_t t = 0; t < slot.size(); t++) if (slot[t] >= 0) eptr[slot[t] + 1]++;
-  for (int k = 0; k < c->nnzv; k++) eptr[k + 1] += eptr[k];
-  {
-    std::vector<int> fill(eptr.begin(), eptr.end() - 1);
-    for (size_t t = 0; t < slot.size(); t++) if (slot[t] >= 0) slot[t] = fill[slot[t]]++;  // (cells ascending: t runs over e first)
-  }
-  for (size_t t = 0; t < (size_t)nc * NL; t++) if (c->h_cells[t] < nvo) fptr[c->h_cells[t] + 1]++;
-  for (int v = 0; v < nvo; v++) fptr[v + 1] += fptr[v];
-  {
-    std::vector<int> fill(fptr.begin(), fptr.end() - 1);
-    for (size_t t = 0; t < (size_t)nc * NL; t++) if (c->h_cells[t] < nvo) fdst[t] = fill[c->h_cells[t]]++;
-  }
-  // diagonal mass scaled to the total measure (HRZ lumping: row sums vanish at P2 vertices); preconditioner only
-  for (int v = 0; v < nv; v++) c->h_Ml[v] = mdiag[v] * (msum / dsum);
+  cfdh_mesh::staging_order(NL, nc, nvo, c->nnzv, c->h_cells.data(), 1, slot, eptr, fptr, fdst);
   // ---- uploads and allocations
   hipStream_t s = c->stream;
   std::vector<unsigned short> gflag(nc, 0);
@@ -875,60 +748,27 @@ int cfdh_build_mesh_gen(cfdh_ctx *c, int etype, int64_t nv64, int64_t nvo64, int
   HIPCHK(c, c->gslot.upload(slot, s));
   HIPCHK(c, c->g_eptr.upload(eptr, s)); HIPCHK(c, c->g_fptr.upload(fptr, s)); HIPCHK(c, c->g_fdst.upload(fdst, s));
   HIPCHK(c, c->gE.alloc(9 * (size_t)nc * NL * NL)); HIPCHK(c, c->gEF.alloc(3 * (size_t)nc * NL));
-  HIPCHK(c, c->vptr.upload(c->h_vptr, s));
-  HIPCHK(c, c->vcol.upload(c->h_vcol, s));
-  HIPCHK(c, c->vdiag.upload(c->h_vdiag, s));
-  HIPCHK(c, c->A00.alloc(4 * (size_t)c->nnzv));
-  HIPCHK(c, c->A01.alloc(2 * (size_t)c->nnzv));
-  HIPCHK(c, c->A10.alloc(2 * (size_t)c->nnzv));
-  HIPCHK(c, c->A11.alloc((size_t)c->nnzv));
+  CHK(cfdh_upload_graph(c));
   std::vector<unsigned char> cown(nc, 1);
   for (int e = 0; e < nc; e++) cown[e] = cells[(size_t)NL * e] < nvo ? 1 : 0;  // the rank that owns a cell's first node integrates it in global functionals
   HIPCHK(c, c->cell_owned.upload(cown, s));
-  std::vector<double> rnd(2 * (size_t)nv);
-  {
-    uint64_t st = 0x2545F4914F6CDD1Dull;
-    for (auto &v : rnd) { st = st * 6364136223846793005ull + 1442695040888963407ull; v = ((st >> 11) * (1.0 / 9007199254740992.0)) - 0.5; }
-    HIPCHK(c, c->prand.upload(rnd, s));
-  }
-  if (nfac) {
-    HIPCHK(c, c->d_fac_cell.upload(c->fac_cell, s));
-    HIPCHK(c, c->d_fac_local.upload(c->fac_local, s));
-    HIPCHK(c, c->d_fac_marker.upload(c->fac_marker, s));
-  }
-  c->h_bcflag.assign(nv, 0);
-  c->h_bcval.assign(3 * (size_t)nv, 0.0);
-  c->h_bcmult.assign(3 * (size_t)nv, 0.0);
-  HIPCHK(c, c->bcflag.alloc(nv));
-  HIPCHK(c, c->bcval.alloc(3 * (size_t)nv));
-  HIPCHK(c, c->bcmult.alloc(3 * (size_t)nv));
-  c->bc_dirty = true;
-  const size_t NLv = c->NL;
-  HIPCHK(c, c->x.alloc(NLv)); HIPCHK(c, c->xt.alloc(NLv)); HIPCHK(c, c->xprev.alloc(NLv)); HIPCHK(c, c->xprev2.alloc(NLv));
-  HIPCHK(c, c->F.alloc(NLv)); HIPCHK(c, c->dvec.alloc(NLv));
-  HIPCHK(c, c->x.zero(s)); HIPCHK(c, c->xt.zero(s)); HIPCHK(c, c->xprev.zero(s)); HIPCHK(c, c->xprev2.zero(s)); HIPCHK(c, c->F.zero(s)); HIPCHK(c, c->dvec.zero(s));
-  c->red_blocks = 1024;
-  HIPCHK(c, c->red_partial.alloc((size_t)c->red_blocks * 260));
-  HIPCHK(c, c->red_out.alloc(1024));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, 1024 * sizeof(double)));
-  HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinned_dev, c->h_pinned, 0));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_h, hipEventDisableTiming));
-  HIPCHK(c, c->dinvA.alloc(2 * (size_t)nv));
-  HIPCHK(c, c->pu0.alloc(2 * (size_t)nv)); HIPCHK(c, c->pu1.alloc(2 * (size_t)nv)); HIPCHK(c, c->pu2.alloc(2 * (size_t)nv));
-  HIPCHK(c, c->pr.alloc(2 * (size_t)nv));
-  HIPCHK(c, c->pp0.alloc(nv)); HIPCHK(c, c->pp1.alloc(nv));
+  const std::vector<double> rnd = cfdh_mesh::lcg_vector(2 * (size_t)nv);
+  HIPCHK(c, c->prand.upload(rnd, s));
+  CHK(cfdh_upload_facets(c));
+  CHK(cfdh_alloc_dirichlet(c));
+  CHK(cfdh_alloc_state(c));
+  CHK(cfdh_alloc_reduction(c, true));
+  CHK(cfdh_alloc_precond_work(c, nv, true));
   c->mom_valid = true;  // no tau-moment pass: tau is evaluated inside the quadrature loop
   HIPCHK(c, hipStreamSynchronize(s));
   return 0;
 }
 
-// stiffness K [nloc][nloc] of one cell of the context's element type (nodes v in the caller's numbering, coordinates [..][2]):
-// the global pressure Laplacian of a partitioned run (cfdh_set_global_pressure_space)
+// stiffness K [nloc][nloc] of one cell of the context's element type (nodes v, coordinates [..][2], both in one numbering): the
+// preconditioner's Laplacian on the graph and the global pressure Laplacian of a partitioned run (cfdh_set_global_pressure_space)
 int cfdh_gen_element_stiffness(const cfdh_ctx *c, const int32_t *v, const double *X, double *K) {
-  static GenTab T[3];
-  static bool init = false;
-  if (!init) { fill_tab<0>(T[0]); fill_tab<1>(T[1]); fill_tab<2>(T[2]); init = true; }
-  const int et = c->etype, NL = c->nloc;
+  const GenTab &T = host_tab(c->etype);
+  const int NL = c->nloc;
   const double J00 = X[2 * v[1]] - X[2 * v[0]], J01 = X[2 * v[2]] - X[2 * v[0]], J10 = X[2 * v[1] + 1] - X[2 * v[0] + 1], J11 = X[2 * v[2] + 1] - X[2 * v[0] + 1];
   const double det = J00 * J11 - J01 * J10, adet = std::fabs(det);
   if (!(adet > 0)) return CFDH_E_ARG;
@@ -937,9 +777,9 @@ int cfdh_gen_element_stiffness(const cfdh_ctx *c, const int32_t *v, const double
   for (int q = 0; q < GEN_NQ; q++) {
     double g[GEN_MAXL][2];
     for (int a = 0; a < NL; a++)
-      for (int i = 0; i < 2; i++) g[a][i] = T[et].dphi[q][a][0] * Ji[0][i] + T[et].dphi[q][a][1] * Ji[1][i];
+      for (int i = 0; i < 2; i++) g[a][i] = T.dphi[q][a][0] * Ji[0][i] + T.dphi[q][a][1] * Ji[1][i];
     for (int a = 0; a < NL; a++)
-      for (int b = 0; b < NL; b++) K[a * NL + b] += adet * T[et].w[q] * (g[a][0] * g[b][0] + g[a][1] * g[b][1]);
+      for (int b = 0; b < NL; b++) K[a * NL + b] += adet * T.w[q] * (g[a][0] * g[b][0] + g[a][1] * g[b][1]);
   }
   return 0;
 }

@@ -23,9 +23,11 @@
 #include <numeric>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_mesh_host.hpp"
 #include "cfdh_quad_gl.h"
 #include "cfdh_quad_tet.h"
 #include "cfdh_quad_tri.h"
+#include "cfdh_wave.hpp"
 
 #define TPB 256
 #define G3_NQ 343  // table size: 7 x 7 x 7 Gauss points on hexahedra; tetrahedra use the first CFDH3_NQ (171) entries
@@ -532,7 +534,7 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
   for (int i = 0; i < 3; i++) Fl[i] = (b == 0 ? Fa[i] : 0.0) + Juu[i][0] * l0 + Juu[i][1] * l1 + Juu[i][2] * l2 + Jup[i] * l3;
   Fl[3] = (b == 0 ? Fa[3] : 0.0) + Jpu[0] * l0 + Jpu[1] * l1 + Jpu[2] * l2 + Jpp * l3;
   const int fd = P.fdst[(size_t)cell * NL * NL + blk];
-  if (fd < 0) return;  // row of a ghost node: assembled by its owner (one-cell overlap of the partition)
+  if (fd < 0) return;  // row of a ghost node: assembled by its owner
   double *ef = P.EF + 4 * (size_t)fd;
   for (int i = 0; i < 4; i++) ef[i] = ((bca >> i) & 1u) ? 0.0 : Fl[i];
   if (P.mode != 1) return;
@@ -764,19 +766,6 @@ __global__ __launch_bounds__(TPB) void gen3_bc_rows_kernel(int nvo, int mode, co
   }
 }
 
-__device__ __forceinline__ double wave_sum3(double v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-__device__ __forceinline__ double block_sum3(double v, double *sh) {
-  v = wave_sum3(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 // int u.u and int p^2 with the element's own mass matrix (scenario.py:315-324)
 template <int ET>
 __global__ __launch_bounds__(TPB) void gen3_l2_kernel(int nc, int nvo, const int *__restrict__ cells, const unsigned char *__restrict__ cell_owned,
@@ -807,8 +796,8 @@ __global__ __launch_bounds__(TPB) void gen3_l2_kernel(int nc, int nvo, const int
       ap += adet * pt[3] * pq * pq;
     }
   }
-  au = block_sum3(au, sh);
-  ap = block_sum3(ap, sh);
+  au = block_sum_xor(au, sh);
+  ap = block_sum_xor(ap, sh);
   if (threadIdx.x == 0) { partial[blockIdx.x] = au; partial[gridDim.x + blockIdx.x] = ap; }
 }
 // kind 7: flux int u.n over the facets with the given marker (outward normal)
@@ -842,7 +831,7 @@ __global__ __launch_bounds__(TPB) void gen3_flux_kernel(int nfac, int marker, in
       a0 += area * w * un;
     }
   }
-  a0 = block_sum3(a0, sh);
+  a0 = block_sum_xor(a0, sh);
   if (threadIdx.x == 0) { partial[blockIdx.x] = a0; partial[gridDim.x + blockIdx.x] = 0.0; }
 }
 // wall shear stress (solverBase.py:163-195): (1/|f|) oint w . (T - (T.n) n), T = -2 mu eps(u) n, per facet node
@@ -892,27 +881,25 @@ __global__ __launch_bounds__(TPB) void gen3_wss_kernel(int nfac, int nvo, const 
       for (int i = 0; i < 3; i++) atomicAdd(out + 3 * (size_t)vs[a] + i, acc[a][i]);
 }
 
-inline uint32_t part1by2(uint32_t x) {
-  x &= 0x000003ff;
-  x = (x ^ (x << 16)) & 0xff0000ff;
-  x = (x ^ (x << 8)) & 0x0300f00f;
-  x = (x ^ (x << 4)) & 0x030c30c3;
-  x = (x ^ (x << 2)) & 0x09249249;
-  return x;
-}
-
-}  // namespace
-
-int kg3_upload_tables(cfdh_ctx *c) {
-  static double pts[2][G3_NQ][4], tri[CFDH_NQ][4], g2[2][2];
+// volume quadrature points (x, y, z, weight times the reference measure): [0] tetrahedron, [1] 7 x 7 x 7 Gauss on the hexahedron
+typedef double Pts3[G3_NQ][4];
+const Pts3 *host_pts3() {
+  static double pts[2][G3_NQ][4];
   for (int q = 0; q < G3_NQ; q++) {
     if (q < CFDH3_NQ) { pts[0][q][0] = CFDH3_QL[q][1]; pts[0][q][1] = CFDH3_QL[q][2]; pts[0][q][2] = CFDH3_QL[q][3]; pts[0][q][3] = CFDH3_QW[q] / 6.0; }
     const int i = q / 49, j = (q / 7) % 7, k = q % 7;
     pts[1][q][0] = CFDH_GL7_X[i]; pts[1][q][1] = CFDH_GL7_X[j]; pts[1][q][2] = CFDH_GL7_X[k]; pts[1][q][3] = CFDH_GL7_W[i] * CFDH_GL7_W[j] * CFDH_GL7_W[k];
   }
+  return pts;
+}
+
+}  // namespace
+
+int kg3_upload_tables(cfdh_ctx *c) {
+  static double tri[CFDH_NQ][4], g2[2][2];
   for (int q = 0; q < CFDH_NQ; q++) { tri[q][0] = CFDH_QL[q][0]; tri[q][1] = CFDH_QL[q][1]; tri[q][2] = CFDH_QL[q][2]; tri[q][3] = CFDH_QW[q]; }
   for (int q = 0; q < 2; q++) { g2[0][q] = CFDH_GL2_X[q]; g2[1][q] = CFDH_GL2_W[q]; }
-  HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(d3_pts), pts, sizeof pts));
+  HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(d3_pts), host_pts3(), sizeof(Pts3[2])));
   HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(d3_tri), tri, sizeof tri));
   HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(d3_gl2), g2, sizeof g2));
   return 0;
@@ -933,215 +920,103 @@ int cfdh_facet_nodes3(const cfdh_ctx *c, int f, int out[8]) {
   return n;
 }
 
-// Mesh upload for the 3-D generic element path (the 3-D counterpart of cfdh_build_mesh_gen): Morton numbering of the nodes,
-// node graph, staging order of the element blocks, stiffness / diagonal mass of the element on the graph (preconditioner),
-// the P1 subspace of a P2 space (p-multigrid step), state and work vectors.
+// Mesh upload for the 3-D generic element path (the 3-D counterpart of cfdh_build_mesh_gen, same shared steps of
+// cfdh_mesh_host.hpp): Morton numbering of the nodes, node graph, staging order of the element blocks, stiffness / diagonal mass
+// of the element on the graph (preconditioner), the P1 subspace of a P2 space (p-multigrid step), state and work vectors.
 int cfdh_build_mesh_gen3(cfdh_ctx *c, int etype, int64_t nv64, int64_t nvo64, int64_t nc64, const int32_t *cells, const double *coords, int64_t nfac64,
                          const int32_t *fcell, const int32_t *flocal, const int32_t *fmarker) {
   const int nv = (int)nv64, nvo = (int)nvo64, nc = (int)nc64, nfac = (int)nfac64;
-  if (nvo <= 0 || nvo > nv) return cfdh_fail(c, CFDH_E_ARG, "bad owned node count");
   const int et = etype == 3 ? 0 : etype;
   const int NL = g3_nloc(et), NF = et == 2 ? 6 : 4, NV = et == 2 ? 8 : 4;
-  if (nv <= 0 || nc <= 0) return cfdh_fail(c, CFDH_E_ARG, "bad mesh sizes");
-  if (nv64 > (1ll << 28) || nc64 > (1ll << 24)) return cfdh_fail(c, CFDH_E_ARG, "mesh too large for int32 indexing of the staged element blocks");
-  for (int64_t k = 0; k < (int64_t)NL * nc; k++)
-    if (cells[k] < 0 || cells[k] >= nv) return cfdh_fail(c, CFDH_E_ARG, "cell node index out of range");
-  for (int k = 0; k < nfac; k++)
-    if (fcell[k] < 0 || fcell[k] >= nc || flocal[k] < 0 || flocal[k] >= NF) return cfdh_fail(c, CFDH_E_ARG, "facet (cell, local) out of range");
+  cfdh_mesh::Wording W;
+  W.too_large = "mesh too large for int32 indexing of the staged element blocks";
+  std::string why;
+  if (!cfdh_mesh::check_sizes(nv64, nvo64, nc64, NL, cells, 1ll << 28, 1ll << 24, W, why) || !cfdh_mesh::check_facets(nfac64, fcell, flocal, nc64, NF, W, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   c->dim = 3;
   c->etype = et; c->nloc = NL; c->gen = true;
-  // partitioned runs: nodes [0, nvo) owned, ghosts after (halo-plan order); rows for owned nodes only; ghost tail of 4 doubles per node
+  // ghost tail of 4 doubles per node
   c->nv = nv; c->nvo = nvo; c->ng = nv - nvo;
   c->NO = 4 * nvo; c->NL = 4 * nvo + 4 * c->ng;
-  c->perm.resize(nv); c->iperm.resize(nv);
-  {
-    std::vector<int> order(nvo);
-    std::iota(order.begin(), order.end(), 0);
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (int v = 0; v < nv; v++)
-      for (int i = 0; i < 3; i++) { lo[i] = std::min(lo[i], coords[3 * v + i]); hi[i] = std::max(hi[i], coords[3 * v + i]); }
-    const double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
-    if (!(ext > 0)) return cfdh_fail(c, CFDH_E_ARG, "degenerate coordinates");
-    std::vector<uint32_t> key(nvo);
-    for (int v = 0; v < nvo; v++) {
-      uint32_t qd[3];
-      for (int i = 0; i < 3; i++) qd[i] = (uint32_t)std::min(1023.0, (coords[3 * v + i] - lo[i]) / ext * 1023.0);
-      key[v] = part1by2(qd[0]) | (part1by2(qd[1]) << 1) | (part1by2(qd[2]) << 2);
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-    for (int k = 0; k < nvo; k++) { c->iperm[k] = order[k]; c->perm[order[k]] = k; }
-    for (int v = nvo; v < nv; v++) { c->iperm[v] = v; c->perm[v] = v; }
-  }
-  c->h_coords.resize(3 * (size_t)nv);
-  for (int k = 0; k < nv; k++) for (int i = 0; i < 3; i++) c->h_coords[3 * (size_t)k + i] = coords[3 * (size_t)c->iperm[k] + i];
+  c->perm.resize(nv); c->iperm.resize(nv); c->h_coords.resize(3 * (size_t)nv);
+  if (!cfdh_mesh::morton_numbering(3, 10, true, nv, nvo, coords, c->perm.data(), c->iperm.data(), c->h_coords.data(), why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   c->nc = nc;
   c->h_cells.resize((size_t)NL * nc);
   c->cell_user.resize(nc);
   const double *X = c->h_coords.data();
-  auto P3 = [&](int v, int i) { return X[3 * (size_t)v + i]; };
+  int ed[6][2];
+  for (int q = 0; q < 6; q++) tet_edge(q, ed[q][0], ed[q][1]);
+  // Ji, |det| of cell e
+  auto geom = [&](int e, double Ji[3][3], double &adet) {
+    const int *v = &c->h_cells[(size_t)NL * e];
+    double Xe[8][3], h;
+    for (int a = 0; a < NV; a++) for (int i = 0; i < 3; i++) Xe[a][i] = X[3 * (size_t)v[a] + i];
+    if (et == 2) geom3<2>(Xe, Ji, adet, h); else geom3<0>(Xe, Ji, adet, h);
+  };
   for (int e = 0; e < nc; e++) {
     c->cell_user[e] = e;
     for (int a = 0; a < NL; a++) c->h_cells[(size_t)NL * e + a] = c->perm[cells[(size_t)NL * e + a]];
     const int *v = &c->h_cells[(size_t)NL * e];
-    double Xe[8][3];
-    for (int a = 0; a < NV; a++) for (int i = 0; i < 3; i++) Xe[a][i] = P3(v[a], i);
-    double Ji[3][3], adet, h;
-    if (et == 2) geom3<2>(Xe, Ji, adet, h); else geom3<0>(Xe, Ji, adet, h);
+    double Ji[3][3], adet;
+    geom(e, Ji, adet);
     if (!(adet > 0) || !std::isfinite(adet)) return cfdh_fail(c, CFDH_E_ARG, "zero-volume cell %d", e);
-    const double tol = 1e-9 * std::cbrt(adet);
-    if (et == 2)  // parallelepipeds only (affine map): x_v = x_0 + i (x_1 - x_0) + j (x_2 - x_0) + k (x_4 - x_0)
-      for (int a = 0; a < 8; a++)
-        for (int i = 0; i < 3; i++) {
-          const double ex = Xe[0][i] + (a & 1) * (Xe[1][i] - Xe[0][i]) + ((a >> 1) & 1) * (Xe[2][i] - Xe[0][i]) + ((a >> 2) & 1) * (Xe[4][i] - Xe[0][i]);
-          if (std::fabs(Xe[a][i] - ex) > tol) return cfdh_fail(c, CFDH_E_ARG, "hexahedron %d is not a parallelepiped: only affine Q1 cells are supported", e);
-        }
-    if (et == 1)  // straight-sided P2: edge nodes at the edge midpoints
-      for (int q = 0; q < 6; q++) {
-        int i, j;
-        tet_edge(q, i, j);
-        for (int d = 0; d < 3; d++)
-          if (std::fabs(0.5 * (P3(v[i], d) + P3(v[j], d)) - P3(v[4 + q], d)) > tol)
-            return cfdh_fail(c, CFDH_E_ARG, "P2 cell %d: edge node %d is not the edge midpoint (curved cells are not supported)", e, q);
-      }
+    if (et == 2 && !cfdh_mesh::is_parallelepiped(X, v, adet))  // affine map
+      return cfdh_fail(c, CFDH_E_ARG, "hexahedron %d is not a parallelepiped: only affine Q1 cells are supported", e);
+    const int bent = et == 1 ? cfdh_mesh::p2_bent_edge(3, ed, X, v, adet) : -1;  // straight-sided P2
+    if (bent >= 0) return cfdh_fail(c, CFDH_E_ARG, "P2 cell %d: edge node %d is not the edge midpoint (curved cells are not supported)", e, bent);
   }
   c->fac_cell.assign(fcell, fcell + nfac); c->fac_local.assign(flocal, flocal + nfac);
   c->fac_marker.resize(nfac); c->fac_user.resize(nfac);
   for (int k = 0; k < nfac; k++) { c->fac_marker[k] = fmarker ? fmarker[k] : 0; c->fac_user[k] = k; }
   c->nfac = c->nfac_user = nfac;
   // ---- node graph
-  std::vector<int> ncptr(nv + 1, 0);
-  for (size_t k = 0; k < c->h_cells.size(); k++) ncptr[c->h_cells[k] + 1]++;
-  for (int v = 0; v < nv; v++) ncptr[v + 1] += ncptr[v];
-  std::vector<int> ncell(ncptr[nv]);
-  {
-    std::vector<int> fill(nv, 0);
-    for (int e = 0; e < nc; e++)
-      for (int a = 0; a < NL; a++) { const int v = c->h_cells[(size_t)NL * e + a]; ncell[ncptr[v] + fill[v]++] = e; }
-  }
-  c->h_vptr.assign(nvo + 1, 0);
-  c->h_vcol.clear(); c->h_vcol.reserve((size_t)30 * nvo);
-  c->h_vdiag.resize(nvo);
-  {
-    std::vector<int> tmp;
-    for (int v = 0; v < nvo; v++) {
-      if (ncptr[v + 1] == ncptr[v]) return cfdh_fail(c, CFDH_E_ARG, "node %d belongs to no cell", c->iperm[v]);
-      tmp.clear();
-      for (int k = ncptr[v]; k < ncptr[v + 1]; k++)
-        for (int a = 0; a < NL; a++) tmp.push_back(c->h_cells[(size_t)NL * ncell[k] + a]);
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-      c->h_vdiag[v] = (int)c->h_vcol.size() + (int)(std::lower_bound(tmp.begin(), tmp.end(), v) - tmp.begin());
-      c->h_vcol.insert(c->h_vcol.end(), tmp.begin(), tmp.end());
-      c->h_vptr[v + 1] = (int)c->h_vcol.size();
-    }
-  }
+  std::vector<int> iptr, inc;
+  if (!cfdh_mesh::node_graph(NL, nc, nvo, c->h_cells.data(), c->iperm.data(), iptr, inc, c->h_vptr, c->h_vcol, c->h_vdiag, W, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   c->nnzv = (int)c->h_vcol.size();
   c->ninc = (int)c->h_cells.size();
-  // ---- staging order, stiffness and diagonal mass on the graph
-  std::vector<int> slot((size_t)nc * NL * NL);
-  c->h_Lval.assign(c->nnzv, 0.0);
-  c->h_Ml.assign(nv, 0.0);
-  double msum = 0.0, dsum = 0.0;
-  std::vector<double> mdiag(nv, 0.0);
-  static double pts[2][G3_NQ][4];
-  for (int q = 0; q < G3_NQ; q++) {
-    if (q < CFDH3_NQ) { pts[0][q][0] = CFDH3_QL[q][1]; pts[0][q][1] = CFDH3_QL[q][2]; pts[0][q][2] = CFDH3_QL[q][3]; pts[0][q][3] = CFDH3_QW[q] / 6.0; }
-    const int i = q / 49, j = (q / 7) % 7, k = q % 7;
-    pts[1][q][0] = CFDH_GL7_X[i]; pts[1][q][1] = CFDH_GL7_X[j]; pts[1][q][2] = CFDH_GL7_X[k]; pts[1][q][3] = CFDH_GL7_W[i] * CFDH_GL7_W[j] * CFDH_GL7_W[k];
-  }
-  // reference stiffness-like integrals are cell dependent only through Ji: K_ab = |det| sum_q w_q (Ji^T dphi_a) . (Ji^T dphi_b)
-  const int nq = g3_nq(et);
-  std::vector<double> rphi((size_t)G3_NQ * NL), rd((size_t)G3_NQ * NL * 3);
-  for (int q = 0; q < nq; q++)
+  // ---- stiffness and diagonal mass on the graph.  The integrals are cell dependent only through Ji:
+  // Mref_a = sum_q w phi_a^2 ; Dref[a][b][k][l] = sum_q w dphi_a[k] dphi_b[l]  ->  K_ab = |det| sum_kl Dref (Ji Ji^T)[k][l]
+  const Pts3 &pts = host_pts3()[et == 2 ? 1 : 0];
+  std::vector<double> Mref(NL, 0.0), Dref((size_t)NL * NL * 9, 0.0), rphi(NL), rd((size_t)NL * 3);
+  for (int q = 0; q < g3_nq(et); q++) {
+    const double w = pts[q][3];
     for (int a = 0; a < NL; a++) {
-      double ph, dr[3];
-      const double *pt = pts[et == 2 ? 1 : 0][q];
-      if (et == 2) basis3<2>(a, pt, ph, dr); else if (et == 1) basis3<1>(a, pt, ph, dr); else basis3<0>(a, pt, ph, dr);
-      rphi[(size_t)q * NL + a] = ph;
-      for (int i = 0; i < 3; i++) rd[((size_t)q * NL + a) * 3 + i] = dr[i];
+      if (et == 2) basis3<2>(a, pts[q], rphi[a], &rd[3 * a]); else if (et == 1) basis3<1>(a, pts[q], rphi[a], &rd[3 * a]); else basis3<0>(a, pts[q], rphi[a], &rd[3 * a]);
     }
-  // reference matrices: Mref_a = sum_q w phi_a^2 ; Dref[a][b][k][l] = sum_q w dphi_a[k] dphi_b[l]  ->  K_ab = |det| sum_kl Dref (Ji Ji^T)[k][l]
-  std::vector<double> Mref(NL, 0.0), Dref((size_t)NL * NL * 9, 0.0);
-  for (int q = 0; q < nq; q++) {
-    const double w = pts[et == 2 ? 1 : 0][q][3];
     for (int a = 0; a < NL; a++) {
-      Mref[a] += w * rphi[(size_t)q * NL + a] * rphi[(size_t)q * NL + a];
+      Mref[a] += w * rphi[a] * rphi[a];
       for (int b = 0; b < NL; b++)
         for (int k = 0; k < 3; k++)
-          for (int l = 0; l < 3; l++) Dref[(((size_t)a * NL + b) * 3 + k) * 3 + l] += w * rd[((size_t)q * NL + a) * 3 + k] * rd[((size_t)q * NL + b) * 3 + l];
+          for (int l = 0; l < 3; l++) Dref[(((size_t)a * NL + b) * 3 + k) * 3 + l] += w * rd[3 * a + k] * rd[3 * b + l];
     }
   }
-  for (int e = 0; e < nc; e++) {
-    const int *v = &c->h_cells[(size_t)NL * e];
-    double Xe[8][3];
-    for (int a = 0; a < NV; a++) for (int i = 0; i < 3; i++) Xe[a][i] = P3(v[a], i);
-    double Ji[3][3], adet, h, M[3][3];
-    if (et == 2) geom3<2>(Xe, Ji, adet, h); else geom3<0>(Xe, Ji, adet, h);
+  std::vector<int> slot, eptr, fptr, fdst;
+  cfdh_mesh::graph_slots(NL, nc, nvo, c->h_cells.data(), c->h_vptr.data(), c->h_vcol.data(), slot);
+  cfdh_mesh::scatter_stiffness_mass(NL, nc, nv, c->h_cells.data(), slot, c->nnzv, [&](int e, double *K, double *Md) {
+    double Ji[3][3], adet, M[3][3];
+    geom(e, Ji, adet);
     for (int k = 0; k < 3; k++)
       for (int l = 0; l < 3; l++) M[k][l] = Ji[k][0] * Ji[l][0] + Ji[k][1] * Ji[l][1] + Ji[k][2] * Ji[l][2];
-    msum += adet * (et == 2 ? 1.0 : 1.0 / 6.0);
     for (int a = 0; a < NL; a++) {
-      mdiag[v[a]] += adet * Mref[a];
-      dsum += adet * Mref[a];
-      if (v[a] >= nvo) {  // row of a ghost node: assembled by its owner
-        for (int b = 0; b < NL; b++) slot[((size_t)e * NL + a) * NL + b] = -1;
-        continue;
-      }
-      const int *nb = &c->h_vcol[c->h_vptr[v[a]]];
-      const int deg = c->h_vptr[v[a] + 1] - c->h_vptr[v[a]];
+      Md[a] = adet * Mref[a];
       for (int b = 0; b < NL; b++) {
-        const int k = c->h_vptr[v[a]] + (int)(std::lower_bound(nb, nb + deg, v[b]) - nb);
-        slot[((size_t)e * NL + a) * NL + b] = k;
         double Kab = 0.0;
         for (int kk = 0; kk < 3; kk++)
           for (int l = 0; l < 3; l++) Kab += Dref[(((size_t)a * NL + b) * 3 + kk) * 3 + l] * M[kk][l];
-        c->h_Lval[k] += adet * Kab;
+        K[a * NL + b] = adet * Kab;
       }
     }
-  }
+    return adet * (et == 2 ? 1.0 : 1.0 / 6.0);
+  }, c->h_Lval, c->h_Ml);
   if (et == 1) {
-    // P1 subspace of the P2 space (first coarse level of both hierarchies): vertex nodes in order of first appearance, an edge
-    // node interpolates its two end vertices
-    std::vector<int> vid(nv, -1), ea(nv, -1), eb(nv, -1);
-    for (int e = 0; e < nc; e++) {
-      const int *v = &c->h_cells[(size_t)NL * e];
-      for (int q = 0; q < 4; q++) vid[v[q]] = 0;
-      for (int q = 0; q < 6; q++) { int i, j; tet_edge(q, i, j); ea[v[4 + q]] = v[i]; eb[v[4 + q]] = v[j]; }
-    }
-    int nvert = 0;
-    for (int v = 0; v < nv; v++) if (vid[v] == 0) vid[v] = nvert++;
-    CsrHost &P = c->gen_P1;
-    P.n = nv; P.m = nvert;
-    P.rowptr.assign(nv + 1, 0); P.col.clear(); P.val.clear();
-    for (int v = 0; v < nv; v++) {
-      if (vid[v] >= 0) { P.col.push_back(vid[v]); P.val.push_back(1.0); }
-      else {
-        int a = vid[ea[v]], b = vid[eb[v]];
-        if (a > b) std::swap(a, b);
-        P.col.push_back(a); P.val.push_back(0.5); P.col.push_back(b); P.val.push_back(0.5);
-      }
-      P.rowptr[v + 1] = (int)P.col.size();
-    }
+    CsrHost &P = c->gen_P1;  // first coarse level of both hierarchies: P1 subspace of the P2 space
+    P.n = nv;
+    P.m = cfdh_mesh::p1_subspace(NL, 4, ed, nc, nv, c->h_cells.data(), P.rowptr, P.col, P.val);
   }
   // staging order of the assembly: contributions to one block entry / one node adjacent, in (cell, lane) order
-  std::vector<int> eptr((size_t)c->nnzv + 1, 0), fptr((size_t)nvo + 1, 0), fdst((size_t)nc * NL * NL, -1);
-  for (size_t t = 0; t < slot.size(); t++) if (slot[t] >= 0) eptr[slot[t] + 1]++;
-  for (int k = 0; k < c->nnzv; k++) eptr[k + 1] += eptr[k];
-  {
-    std::vector<int> fill(eptr.begin(), eptr.end() - 1);
-    for (size_t t = 0; t < slot.size(); t++) if (slot[t] >= 0) slot[t] = fill[slot[t]]++;
-  }
-  for (int e = 0; e < nc; e++)
-    for (int a = 0; a < NL; a++) if (c->h_cells[(size_t)NL * e + a] < nvo) fptr[c->h_cells[(size_t)NL * e + a] + 1] += NL;
-  for (int v = 0; v < nvo; v++) fptr[v + 1] += fptr[v];
-  {
-    std::vector<int> fill(fptr.begin(), fptr.end() - 1);
-    for (int e = 0; e < nc; e++)
-      for (int a = 0; a < NL; a++)
-        if (c->h_cells[(size_t)NL * e + a] < nvo)
-          for (int b = 0; b < NL; b++) fdst[((size_t)e * NL + a) * NL + b] = fill[c->h_cells[(size_t)NL * e + a]]++;
-  }
-  for (int v = 0; v < nv; v++) c->h_Ml[v] = mdiag[v] * (msum / dsum);
+  cfdh_mesh::staging_order(NL, nc, nvo, c->nnzv, c->h_cells.data(), NL, slot, eptr, fptr, fdst);
   // ---- uploads and allocations
   hipStream_t s = c->stream;
   std::vector<unsigned short> gflag(nc, 0);
@@ -1149,57 +1024,24 @@ int cfdh_build_mesh_gen3(cfdh_ctx *c, int etype, int64_t nv64, int64_t nvo64, in
   HIPCHK(c, c->coords.upload(c->h_coords, s));
   HIPCHK(c, c->cells.upload(c->h_cells, s));
   HIPCHK(c, c->gflag.upload(gflag, s));
-  {
-    std::vector<int> fcl;
-    for (int e = 0; e < nc; e++) if (gflag[e]) fcl.push_back(e);
-    c->g3_nfcells = (int)fcl.size();
-    if (c->g3_nfcells) HIPCHK(c, c->g3_fcells.upload(fcl, s));
-  }
+  std::vector<int> fcl;  // the cells with an exterior facet
+  for (int e = 0; e < nc; e++) if (gflag[e]) fcl.push_back(e);
+  c->g3_nfcells = (int)fcl.size();
+  if (c->g3_nfcells) HIPCHK(c, c->g3_fcells.upload(fcl, s));
   HIPCHK(c, c->gslot.upload(slot, s));
   HIPCHK(c, c->g_eptr.upload(eptr, s)); HIPCHK(c, c->g_fptr.upload(fptr, s)); HIPCHK(c, c->g_fdst.upload(fdst, s));
   HIPCHK(c, c->gE.alloc(16 * (size_t)nc * NL * NL)); HIPCHK(c, c->gEF.alloc(4 * (size_t)nc * NL * NL));
-  HIPCHK(c, c->vptr.upload(c->h_vptr, s));
-  HIPCHK(c, c->vcol.upload(c->h_vcol, s));
-  HIPCHK(c, c->vdiag.upload(c->h_vdiag, s));
-  HIPCHK(c, c->A00.alloc(9 * (size_t)c->nnzv));
-  HIPCHK(c, c->A01.alloc(3 * (size_t)c->nnzv));
-  HIPCHK(c, c->A10.alloc(3 * (size_t)c->nnzv));
-  HIPCHK(c, c->A11.alloc((size_t)c->nnzv));
+  CHK(cfdh_upload_graph(c));
   std::vector<unsigned char> cown(nc, 1);
   for (int e = 0; e < nc; e++) cown[e] = cells[(size_t)NL * e] < nvo ? 1 : 0;
   HIPCHK(c, c->cell_owned.upload(cown, s));
-  std::vector<double> rnd(3 * (size_t)nv);
-  {
-    uint64_t st = 0x2545F4914F6CDD1Dull;
-    for (auto &v : rnd) { st = st * 6364136223846793005ull + 1442695040888963407ull; v = ((st >> 11) * (1.0 / 9007199254740992.0)) - 0.5; }
-    HIPCHK(c, c->prand.upload(rnd, s));
-  }
-  if (nfac) {
-    HIPCHK(c, c->d_fac_cell.upload(c->fac_cell, s));
-    HIPCHK(c, c->d_fac_local.upload(c->fac_local, s));
-    HIPCHK(c, c->d_fac_marker.upload(c->fac_marker, s));
-  }
-  c->h_bcflag.assign(nv, 0);
-  c->h_bcval.assign(4 * (size_t)nv, 0.0);
-  c->h_bcmult.assign(4 * (size_t)nv, 0.0);
-  HIPCHK(c, c->bcflag.alloc(nv));
-  HIPCHK(c, c->bcval.alloc(4 * (size_t)nv));
-  HIPCHK(c, c->bcmult.alloc(4 * (size_t)nv));
-  c->bc_dirty = true;
-  const size_t NLv = c->NL;
-  HIPCHK(c, c->x.alloc(NLv)); HIPCHK(c, c->xt.alloc(NLv)); HIPCHK(c, c->xprev.alloc(NLv)); HIPCHK(c, c->xprev2.alloc(NLv));
-  HIPCHK(c, c->F.alloc(NLv)); HIPCHK(c, c->dvec.alloc(NLv));
-  HIPCHK(c, c->x.zero(s)); HIPCHK(c, c->xt.zero(s)); HIPCHK(c, c->xprev.zero(s)); HIPCHK(c, c->xprev2.zero(s)); HIPCHK(c, c->F.zero(s)); HIPCHK(c, c->dvec.zero(s));
-  c->red_blocks = 1024;
-  HIPCHK(c, c->red_partial.alloc((size_t)c->red_blocks * 260));
-  HIPCHK(c, c->red_out.alloc(1024));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, 1024 * sizeof(double)));
-  HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinned_dev, c->h_pinned, 0));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_h, hipEventDisableTiming));
-  HIPCHK(c, c->dinvA.alloc(3 * (size_t)nv));
-  HIPCHK(c, c->pu0.alloc(3 * (size_t)nv)); HIPCHK(c, c->pu1.alloc(3 * (size_t)nv)); HIPCHK(c, c->pu2.alloc(3 * (size_t)nv));
-  HIPCHK(c, c->pr.alloc(3 * (size_t)nv));
-  HIPCHK(c, c->pp0.alloc(nv)); HIPCHK(c, c->pp1.alloc(nv));
+  const std::vector<double> rnd = cfdh_mesh::lcg_vector(3 * (size_t)nv);
+  HIPCHK(c, c->prand.upload(rnd, s));
+  CHK(cfdh_upload_facets(c));
+  CHK(cfdh_alloc_dirichlet(c));
+  CHK(cfdh_alloc_state(c));
+  CHK(cfdh_alloc_reduction(c, true));
+  CHK(cfdh_alloc_precond_work(c, nv, true));
   c->mom_valid = true;  // no tau-moment pass: tau is evaluated inside the quadrature loop
   HIPCHK(c, hipStreamSynchronize(s));
   return 0;
@@ -1213,12 +1055,10 @@ int cfdh_gen3_element_stiffness(const cfdh_ctx *c, const int32_t *v, const doubl
   if (et == 2) geom3<2>(Xe, Ji, adet, h); else geom3<0>(Xe, Ji, adet, h);
   if (!(adet > 0)) return CFDH_E_ARG;
   for (int k = 0; k < NL * NL; k++) K[k] = 0.0;
+  const Pts3 &pts = host_pts3()[et == 2 ? 1 : 0];
   for (int q = 0; q < g3_nq(et); q++) {
-    double pt[3], w, g[10][3];
-    if (et == 2) {
-      const int i = q / 49, j = (q / 7) % 7, k = q % 7;
-      pt[0] = CFDH_GL7_X[i]; pt[1] = CFDH_GL7_X[j]; pt[2] = CFDH_GL7_X[k]; w = CFDH_GL7_W[i] * CFDH_GL7_W[j] * CFDH_GL7_W[k];
-    } else { pt[0] = CFDH3_QL[q][1]; pt[1] = CFDH3_QL[q][2]; pt[2] = CFDH3_QL[q][3]; w = CFDH3_QW[q] / 6.0; }
+    const double *pt = pts[q], w = pt[3];
+    double g[10][3];
     for (int a = 0; a < NL; a++) {
       double ph, dr[3];
       if (et == 2) basis3<2>(a, pt, ph, dr); else if (et == 1) basis3<1>(a, pt, ph, dr); else basis3<0>(a, pt, ph, dr);

@@ -461,6 +461,14 @@ int cfdh_fail(cfdh_ctx *c, int code, const char *fmt, ...);
 // ---- setup (cfdh_setup.cpp) ------------------------------------------------------
 int cfdh_build_mesh(cfdh_ctx *c, int64_t nv, int64_t nvo, int64_t nc, const int32_t *cells, const double *coords,
                     int64_t nfac, const int32_t *fcell, const int32_t *flocal, const int32_t *fmarker);
+bool cfdh_renumber_enabled();  // false with CFDH_NO_RENUMBER=1 (honoured by the two closed-form builders)
+// device-side allocations shared by the context builders (dim, nv, nvo, NL, nnzv, nfac and the host arrays are set by then)
+int cfdh_alloc_reduction(cfdh_ctx *c, bool with_event);  // red_partial, red_out, h_pinned (+ ev_h)
+int cfdh_upload_graph(cfdh_ctx *c);                      // vptr / vcol / vdiag, A00 .. A11
+int cfdh_upload_facets(cfdh_ctx *c);
+int cfdh_alloc_dirichlet(cfdh_ctx *c);                   // bcflag / bcval / bcmult, host and device
+int cfdh_alloc_state(cfdh_ctx *c);                       // x, xt, xprev, xprev2, F, dvec: zeroed
+int cfdh_alloc_precond_work(cfdh_ctx *c, size_t n, bool with_dinvA);  // pu0 .. pr (dim n), pp0, pp1 (n), dinvA (dim n)
 int cfdh_amg_setup(cfdh_ctx *c, AmgHier &H, const CsrHost &A, bool singular, int ncol);
 int cfdh_level_setup(cfdh_ctx *c, AmgLevel &L, const CsrHost &A, double ratio, int ncol, std::vector<double> *w_out = nullptr);
 int cfdh_upload_csr(cfdh_ctx *c, const CsrHost &H, CsrDev &D, const std::vector<double> *colw = nullptr, int parts = CFDH_UP_CSR | CFDH_UP_SELL);

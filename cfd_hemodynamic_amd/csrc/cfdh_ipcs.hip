@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_mesh_host.hpp"
 #include "cfdh_ipcs.hpp"
 #include "cfdh_wave.hpp"
 #include "cfdh_quad_tet.h"
@@ -561,8 +562,10 @@ int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn64, int64_t nvert64, int64
     if (v < 0 || v >= nn || (a < NV && v >= nvert) || (a >= NV && v < nvert))
       return cfdh_fail(c, CFDH_E_ARG, "cfdh_create_ipcs: cell node out of range (vertices must be the nodes [0, nvert), edge nodes the rest)");
   }
-  for (int64_t k = 0; k < nfac; k++)
-    if (fcell[k] < 0 || fcell[k] >= nc || flocal[k] < 0 || flocal[k] >= NV) return cfdh_fail(c, CFDH_E_ARG, "cfdh_create_ipcs: bad exterior facet");
+  cfdh_mesh::Wording W;
+  W.facet = "cfdh_create_ipcs: bad exterior facet";
+  std::string why;
+  if (!cfdh_mesh::check_facets(nfac, fcell, flocal, nc, NV, W, why)) return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   IpcsData *I = new (std::nothrow) IpcsData();
   if (!I) return cfdh_fail(c, CFDH_E_NOMEM, "out of host memory");
   c->ipcs = I;
@@ -576,11 +579,7 @@ int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn64, int64_t nvert64, int64
   if (fmarker) I->fmarker.assign(fmarker, fmarker + nfac);
   hipStream_t s = c->stream;
   // reduction scratch of the shared helpers (AMG set-up uses red_out)
-  c->red_blocks = 1024;
-  HIPCHK(c, c->red_partial.alloc((size_t)c->red_blocks * 260));
-  HIPCHK(c, c->red_out.alloc(1024));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, 1024 * sizeof(double)));
-  HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinned_dev, c->h_pinned, 0));
+  CHK(cfdh_alloc_reduction(c, false));  // no ev_h in this context
   memset(c->h_pinned, 0, 1024 * sizeof(double));
 
   IpRef R;

@@ -11,6 +11,7 @@
 #include <numeric>
 
 #include "cfdh_internal.hpp"
+#include "cfdh_mesh_host.hpp"
 
 int cfdh_fail(cfdh_ctx *c, int code, const char *fmt, ...) {
   char buf[512];
@@ -31,74 +32,98 @@ int cfdh_host_threads() {
   return n < 1 ? 1 : (n > 64 ? 64 : n);
 }
 
-static inline uint32_t part1by1(uint32_t x) {
-  x &= 0x0000ffff;
-  x = (x ^ (x << 8)) & 0x00ff00ff;
-  x = (x ^ (x << 4)) & 0x0f0f0f0f;
-  x = (x ^ (x << 2)) & 0x33333333;
-  x = (x ^ (x << 1)) & 0x55555555;
-  return x;
+// the closed-form builders keep their own wording of the shared refusals
+static const cfdh_mesh::Wording W_CLOSED2 = {"bad mesh sizes", "mesh too large for int32 indexing", "vertex", "owned vertex %d has no cell",
+                                             "facet (cell, local) out of range"};
+
+bool cfdh_renumber_enabled() {
+  const char *nr = getenv("CFDH_NO_RENUMBER");
+  return !(nr && nr[0] == '1');
+}
+
+// ---- device-side allocations that every builder makes (declared in cfdh_internal.hpp) ----
+// reduction scratch; ev_h marks 'Gram-Schmidt coefficients are in h_pinned' (the FGMRES contexts)
+int cfdh_alloc_reduction(cfdh_ctx *c, bool with_event) {
+  c->red_blocks = 1024;
+  HIPCHK(c, c->red_partial.alloc((size_t)c->red_blocks * 260));
+  HIPCHK(c, c->red_out.alloc(1024));
+  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, 1024 * sizeof(double)));
+  HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinned_dev, c->h_pinned, 0));
+  if (with_event) HIPCHK(c, hipEventCreateWithFlags(&c->ev_h, hipEventDisableTiming));
+  return 0;
+}
+// node graph and the Jacobian blocks on it: D*D, D, D, 1 values per entry
+int cfdh_upload_graph(cfdh_ctx *c) {
+  const size_t D = c->dim, nnz = c->nnzv;
+  HIPCHK(c, c->vptr.upload(c->h_vptr, c->stream));
+  HIPCHK(c, c->vcol.upload(c->h_vcol, c->stream));
+  HIPCHK(c, c->vdiag.upload(c->h_vdiag, c->stream));
+  HIPCHK(c, c->A00.alloc(D * D * nnz));
+  HIPCHK(c, c->A01.alloc(D * nnz));
+  HIPCHK(c, c->A10.alloc(D * nnz));
+  HIPCHK(c, c->A11.alloc(nnz));
+  return 0;
+}
+int cfdh_upload_facets(cfdh_ctx *c) {
+  if (!c->nfac) return 0;
+  HIPCHK(c, c->d_fac_cell.upload(c->fac_cell, c->stream));
+  HIPCHK(c, c->d_fac_local.upload(c->fac_local, c->stream));
+  HIPCHK(c, c->d_fac_marker.upload(c->fac_marker, c->stream));
+  return 0;
+}
+// Dirichlet data, D + 1 values per node, on the host and on the device
+int cfdh_alloc_dirichlet(cfdh_ctx *c) {
+  const size_t nv = c->nv, B = c->dim + 1;
+  c->h_bcflag.assign(nv, 0);
+  c->h_bcval.assign(B * nv, 0.0);
+  c->h_bcmult.assign(B * nv, 0.0);
+  HIPCHK(c, c->bcflag.alloc(nv));
+  HIPCHK(c, c->bcval.alloc(B * nv));
+  HIPCHK(c, c->bcmult.alloc(B * nv));
+  c->bc_dirty = true;
+  return 0;
+}
+// state vectors of length NL (owned unknowns and the ghost tail), zeroed
+int cfdh_alloc_state(cfdh_ctx *c) {
+  for (dbuf<double> *b : {&c->x, &c->xt, &c->xprev, &c->xprev2, &c->F, &c->dvec}) {
+    HIPCHK(c, b->alloc((size_t)c->NL));
+    HIPCHK(c, b->zero(c->stream));
+  }
+  return 0;
+}
+// work vectors of the block preconditioner over n nodes (the closed forms: owned nodes, the generic builders: all nodes)
+int cfdh_alloc_precond_work(cfdh_ctx *c, size_t n, bool with_dinvA) {
+  const size_t D = c->dim;
+  if (with_dinvA) HIPCHK(c, c->dinvA.alloc(D * n));
+  for (dbuf<double> *b : {&c->pu0, &c->pu1, &c->pu2, &c->pr}) HIPCHK(c, b->alloc(D * n));
+  HIPCHK(c, c->pp0.alloc(n)); HIPCHK(c, c->pp1.alloc(n));
+  return 0;
 }
 
 int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, const int32_t *cells, const double *coords,
                     int64_t nfac64, const int32_t *fcell, const int32_t *flocal, const int32_t *fmarker) {
   const int nv = (int)nv64, nvo = (int)nvo64, ncu = (int)nc64, nfac = (int)nfac64;
-  if (nv <= 0 || nvo <= 0 || nvo > nv || ncu <= 0) return cfdh_fail(c, CFDH_E_ARG, "bad mesh sizes");
-  if (nv64 > (1ll << 29) || nc64 > (1ll << 29)) return cfdh_fail(c, CFDH_E_ARG, "mesh too large for int32 indexing");
-  for (int64_t k = 0; k < 3 * nc64; k++)
-    if (cells[k] < 0 || cells[k] >= nv) return cfdh_fail(c, CFDH_E_ARG, "cell vertex index out of range");
-  for (int k = 0; k < nfac; k++)
-    if (fcell[k] < 0 || fcell[k] >= ncu || flocal[k] < 0 || flocal[k] > 2)
-      return cfdh_fail(c, CFDH_E_ARG, "facet (cell, local) out of range");
+  std::string why;
+  if (!cfdh_mesh::check_sizes(nv64, nvo64, nc64, 3, cells, 1ll << 29, 1ll << 29, W_CLOSED2, why) ||
+      !cfdh_mesh::check_facets(nfac64, fcell, flocal, nc64, 3, W_CLOSED2, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
   c->nv = nv; c->nvo = nvo; c->ng = nv - nvo;
   c->NO = 3 * nvo; c->NL = 3 * nvo + 3 * c->ng;
 
   // ---- internal numbering: owned vertices along a Morton curve, ghosts unchanged
-  c->perm.resize(nv); c->iperm.resize(nv);
-  {
-    std::vector<int> order(nvo);
-    std::iota(order.begin(), order.end(), 0);
-    const char *nr = getenv("CFDH_NO_RENUMBER");
-    if (!(nr && nr[0] == '1')) {
-      double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
-      for (int v = 0; v < nv; v++)
-        for (int i = 0; i < 2; i++) { lo[i] = std::min(lo[i], coords[2 * v + i]); hi[i] = std::max(hi[i], coords[2 * v + i]); }
-      double ext = std::max(hi[0] - lo[0], hi[1] - lo[1]);
-      if (!(ext > 0)) return cfdh_fail(c, CFDH_E_ARG, "degenerate coordinates");
-      std::vector<uint32_t> key(nvo);
-      for (int v = 0; v < nvo; v++) {
-        uint32_t qx = (uint32_t)std::min(65535.0, (coords[2 * v] - lo[0]) / ext * 65535.0);
-        uint32_t qy = (uint32_t)std::min(65535.0, (coords[2 * v + 1] - lo[1]) / ext * 65535.0);
-        key[v] = part1by1(qx) | (part1by1(qy) << 1);
-      }
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-    }
-    for (int k = 0; k < nvo; k++) { c->iperm[k] = order[k]; c->perm[order[k]] = k; }
-    for (int v = nvo; v < nv; v++) { c->iperm[v] = v; c->perm[v] = v; }
-  }
-  c->h_coords.resize(2 * (size_t)nv);
-  for (int k = 0; k < nv; k++) { c->h_coords[2 * k] = coords[2 * c->iperm[k]]; c->h_coords[2 * k + 1] = coords[2 * c->iperm[k] + 1]; }
+  c->perm.resize(nv); c->iperm.resize(nv); c->h_coords.resize(2 * (size_t)nv);
+  if (!cfdh_mesh::morton_numbering(2, 16, cfdh_renumber_enabled(), nv, nvo, coords, c->perm.data(), c->iperm.data(), c->h_coords.data(), why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
 
   // ---- cells touching an owned vertex, internal ids, sorted by smallest vertex
   {
-    std::vector<std::pair<int, int>> keyed;
-    keyed.reserve(ncu);
     for (int e = 0; e < ncu; e++) {
-      int a = c->perm[cells[3 * e]], b = c->perm[cells[3 * e + 1]], d = c->perm[cells[3 * e + 2]];
+      const int a = cells[3 * e], b = cells[3 * e + 1], d = cells[3 * e + 2];
       if (a == b || b == d || a == d) return cfdh_fail(c, CFDH_E_ARG, "degenerate cell %d", e);
-      int mn = std::min(a, std::min(b, d));
-      if (mn < nvo) keyed.push_back({mn, e});
     }
-    std::stable_sort(keyed.begin(), keyed.end());
-    c->nc = (int)keyed.size();
-    c->h_cells.resize(3 * (size_t)c->nc);
-    c->cell_user.resize(c->nc);
-    std::vector<int> cmap(ncu, -1);
-    for (int k = 0; k < c->nc; k++) {
-      int e = keyed[k].second;
-      cmap[e] = k; c->cell_user[k] = e;
-      for (int a = 0; a < 3; a++) c->h_cells[3 * k + a] = c->perm[cells[3 * e + a]];
-    }
+    std::vector<int> cmap;
+    cfdh_mesh::select_cells(3, ncu, nvo, cells, c->perm.data(), c->h_cells, c->cell_user, cmap);
+    c->nc = (int)c->cell_user.size();
     c->fac_cell.clear(); c->fac_local.clear(); c->fac_marker.clear(); c->fac_user.clear();
     c->nfac_user = nfac;
     for (int k = 0; k < nfac; k++)
@@ -116,8 +141,7 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
     std::vector<unsigned char> flipped(nc, 0);
     for (int e = 0; e < nc; e++) {
       int *v = &c->h_cells[3 * e];
-      const double *X = c->h_coords.data();
-      double det = (X[2 * v[1]] - X[2 * v[0]]) * (X[2 * v[2] + 1] - X[2 * v[0] + 1]) - (X[2 * v[1] + 1] - X[2 * v[0] + 1]) * (X[2 * v[2]] - X[2 * v[0]]);
+      const double det = cfdh_mesh::tri_det(c->h_coords.data(), v);
       if (!(std::fabs(det) > 0)) return cfdh_fail(c, CFDH_E_ARG, "zero-area cell %d", c->cell_user[e]);
       if (det < 0) { std::swap(v[1], v[2]); flipped[e] = 1; }
     }
@@ -125,35 +149,13 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
       if (flipped[c->fac_cell[k]] && c->fac_local[k] != 0) c->fac_local[k] = 3 - c->fac_local[k];
   }
 
-  // ---- vertex -> incident (cell, local) for owned rows; vertex graph
-  std::vector<int> vcptr(nvo + 1, 0);
-  for (int e = 0; e < nc; e++)
-    for (int a = 0; a < 3; a++) { int v = c->h_cells[3 * e + a]; if (v < nvo) vcptr[v + 1]++; }
-  for (int v = 0; v < nvo; v++) vcptr[v + 1] += vcptr[v];
+  // ---- vertex -> incident (cell, local) for owned rows (vcell = 3 cell + local); vertex graph
+  std::vector<int> vcptr, vcell;
+  if (!cfdh_mesh::node_graph(3, nc, nvo, c->h_cells.data(), c->iperm.data(), vcptr, vcell, c->h_vptr, c->h_vcol, c->h_vdiag, W_CLOSED2, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s", why.c_str());
+  for (int v = 0; v < nvo; v++)
+    if (c->h_vptr[v + 1] - c->h_vptr[v] > 255) return cfdh_fail(c, CFDH_E_ARG, "vertex valence > 254 is not supported");
   const int ninc = vcptr[nvo];
-  std::vector<int> vcell(ninc);
-  {
-    std::vector<int> fill(nvo, 0);
-    for (int e = 0; e < nc; e++)
-      for (int a = 0; a < 3; a++) { int v = c->h_cells[3 * e + a]; if (v < nvo) vcell[vcptr[v] + fill[v]++] = 4 * e + a; }
-  }
-  c->h_vptr.assign(nvo + 1, 0);
-  c->h_vcol.clear(); c->h_vcol.reserve((size_t)7 * nvo);
-  c->h_vdiag.resize(nvo);
-  {
-    std::vector<int> tmp;
-    for (int v = 0; v < nvo; v++) {
-      tmp.clear(); tmp.push_back(v);
-      for (int k = vcptr[v]; k < vcptr[v + 1]; k++) { int e = vcell[k] >> 2; for (int a = 0; a < 3; a++) tmp.push_back(c->h_cells[3 * e + a]); }
-      std::sort(tmp.begin(), tmp.end());
-      tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-      if ((int)tmp.size() > 255) return cfdh_fail(c, CFDH_E_ARG, "vertex valence > 254 is not supported");
-      if (vcptr[v + 1] == vcptr[v]) return cfdh_fail(c, CFDH_E_ARG, "owned vertex %d has no cell", c->iperm[v]);
-      c->h_vdiag[v] = (int)c->h_vcol.size() + (int)(std::lower_bound(tmp.begin(), tmp.end(), v) - tmp.begin());
-      c->h_vcol.insert(c->h_vcol.end(), tmp.begin(), tmp.end());
-      c->h_vptr[v + 1] = (int)c->h_vcol.size();
-    }
-  }
   c->nnzv = (int)c->h_vcol.size();
   c->ninc = ninc;
   // P1 stiffness (grad l_a . grad l_b) on the vertex graph and lumped mass of the owned rows: geometry only,
@@ -191,7 +193,7 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
       if (n > 64) return cfdh_fail(c, CFDH_E_ARG, "vertex %d has %d cells: more than one wavefront", c->iperm[v], n);
       v1s.assign(n, 0); v2s.assign(n, 0); used.assign(n, 0); ord.clear();
       for (int q = 0; q < n; q++) {
-        const int e = vcell[k0 + q] >> 2, a = vcell[k0 + q] & 3;
+        const int e = vcell[k0 + q] / 3, a = vcell[k0 + q] % 3;
         v1s[q] = c->h_cells[3 * e + (a + 1) % 3]; v2s[q] = c->h_cells[3 * e + (a + 2) % 3];
       }
       auto find_by_v1 = [&](int w) { for (int q = 0; q < n; q++) if (!used[q] && v1s[q] == w) return q; return -1; };
@@ -214,7 +216,7 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
       for (size_t f = 0; f < fan_len.size(); f++)
         for (int t = 0; t < fan_len[f]; t++) {
           const int pos = fan_first_pos[f] + t, q = ord[pos];
-          const int e = vcell[k0 + q] >> 2, a = vcell[k0 + q] & 3;
+          const int e = vcell[k0 + q] / 3, a = vcell[k0 + q] % 3;
           LaneRec L;
           L.cellslot = vcell[k0 + q]; L.a = (unsigned char)a;
           unsigned slots = 0;
@@ -254,14 +256,14 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
         if (w2 >= CFDH_MAX_INC / 64) break;
         int addv = 0, addc = 0;
         for (int k = vcptr[r1]; k < vcptr[r1 + 1]; k++) {
-          const int e = vcell[k] >> 2;
+          const int e = vcell[k] / 3;
           if (cmark[e] != bid) { cmark[e] = bid; cloc[e] = -1; addc++; }
           for (int q = 0; q < 3; q++) { const int w = c->h_cells[3 * e + q]; if (vmark[w] != bid) { vmark[w] = bid; vloc[w] = -1; addv++; } }
         }
         if (nvl + addv > CFDH_MAX_BV || ncl + addc > CFDH_MAX_BC) {
           if (r1 == r0) return cfdh_fail(c, CFDH_E_ARG, "vertex patch too large for one workgroup");
           for (int k = vcptr[r1]; k < vcptr[r1 + 1]; k++) {
-            const int e = vcell[k] >> 2;
+            const int e = vcell[k] / 3;
             if (cmark[e] == bid && cloc[e] == -1) cmark[e] = -1;
             for (int q = 0; q < 3; q++) { const int w = c->h_cells[3 * e + q]; if (vmark[w] == bid && vloc[w] == -1) vmark[w] = -1; }
           }
@@ -270,7 +272,7 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
         wave = w2; lane = l2;
         for (int k = vcptr[r1]; k < vcptr[r1 + 1]; k++) {
           const LaneRec &L = rowlanes[k];
-          const int e = L.cellslot >> 2, a = L.a;
+          const int e = L.cellslot / 3, a = L.a;
           if (cloc[e] == -1) { cloc[e] = ncl++; blk_clist.push_back(e); }
           for (int q = 0; q < 3; q++) { const int w = c->h_cells[3 * e + q]; if (vloc[w] == -1) { vloc[w] = nvl++; blk_vlist.push_back(w); } }
           unsigned loc = (unsigned)cloc[e];
@@ -305,13 +307,7 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
   HIPCHK(c, c->cells.upload(c->h_cells, s));
   HIPCHK(c, c->cflag.upload(cflag, s));
   HIPCHK(c, c->mom.alloc(8 * (size_t)nc));
-  HIPCHK(c, c->vptr.upload(c->h_vptr, s));
-  HIPCHK(c, c->vcol.upload(c->h_vcol, s));
-  HIPCHK(c, c->vdiag.upload(c->h_vdiag, s));
-  HIPCHK(c, c->A00.alloc(4 * (size_t)c->nnzv));
-  HIPCHK(c, c->A01.alloc(2 * (size_t)c->nnzv));
-  HIPCHK(c, c->A10.alloc(2 * (size_t)c->nnzv));
-  HIPCHK(c, c->A11.alloc((size_t)c->nnzv));
+  CHK(cfdh_upload_graph(c));
   HIPCHK(c, c->inc_slot.upload(inc_slot, s));
   HIPCHK(c, c->inc_rank.upload(inc_rank, s));
   HIPCHK(c, c->blk_row.upload(blk_row, s));
@@ -324,38 +320,13 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
     for (int k = 0; k < nc; k++) cown[k] = cells[3 * c->cell_user[k]] < nvo ? 1 : 0;
     HIPCHK(c, c->cell_owned.upload(cown, s));
   }
-  {
-    std::vector<double> rnd(2 * (size_t)nvo);
-    uint64_t st = 0x2545F4914F6CDD1Dull;
-    for (auto &v : rnd) { st = st * 6364136223846793005ull + 1442695040888963407ull; v = ((st >> 11) * (1.0 / 9007199254740992.0)) - 0.5; }
-    HIPCHK(c, c->prand.upload(rnd, s));
-  }
-  if (c->nfac) {
-    HIPCHK(c, c->d_fac_cell.upload(c->fac_cell, s));
-    HIPCHK(c, c->d_fac_local.upload(c->fac_local, s));
-    HIPCHK(c, c->d_fac_marker.upload(c->fac_marker, s));
-  }
-  c->h_bcflag.assign(nv, 0);
-  c->h_bcval.assign(3 * (size_t)nv, 0.0);
-  c->h_bcmult.assign(3 * (size_t)nv, 0.0);
-  HIPCHK(c, c->bcflag.alloc(nv));
-  HIPCHK(c, c->bcval.alloc(3 * (size_t)nv));
-  HIPCHK(c, c->bcmult.alloc(3 * (size_t)nv));
-  c->bc_dirty = true;
-  const size_t NL = c->NL;
-  HIPCHK(c, c->x.alloc(NL)); HIPCHK(c, c->xt.alloc(NL)); HIPCHK(c, c->xprev.alloc(NL)); HIPCHK(c, c->xprev2.alloc(NL));
-  HIPCHK(c, c->F.alloc(NL)); HIPCHK(c, c->dvec.alloc(NL));
-  HIPCHK(c, c->x.zero(s)); HIPCHK(c, c->xt.zero(s)); HIPCHK(c, c->xprev.zero(s)); HIPCHK(c, c->xprev2.zero(s)); HIPCHK(c, c->F.zero(s)); HIPCHK(c, c->dvec.zero(s));
-  c->red_blocks = 1024;
-  HIPCHK(c, c->red_partial.alloc((size_t)c->red_blocks * 260));
-  HIPCHK(c, c->red_out.alloc(1024));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, 1024 * sizeof(double)));
-  HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinned_dev, c->h_pinned, 0));
-  HIPCHK(c, hipEventCreateWithFlags(&c->ev_h, hipEventDisableTiming));
-  HIPCHK(c, c->dinvA.alloc(2 * (size_t)nvo));
-  HIPCHK(c, c->pu0.alloc(2 * (size_t)nvo)); HIPCHK(c, c->pu1.alloc(2 * (size_t)nvo)); HIPCHK(c, c->pu2.alloc(2 * (size_t)nvo));
-  HIPCHK(c, c->pr.alloc(2 * (size_t)nvo));
-  HIPCHK(c, c->pp0.alloc(nvo)); HIPCHK(c, c->pp1.alloc(nvo));
+  const std::vector<double> rnd = cfdh_mesh::lcg_vector(2 * (size_t)nvo);  // lives until the stream synchronisation below
+  HIPCHK(c, c->prand.upload(rnd, s));
+  CHK(cfdh_upload_facets(c));
+  CHK(cfdh_alloc_dirichlet(c));
+  CHK(cfdh_alloc_state(c));
+  CHK(cfdh_alloc_reduction(c, true));
+  CHK(cfdh_alloc_precond_work(c, nvo, true));
   HIPCHK(c, hipStreamSynchronize(s));
   return 0;
 }

@@ -181,7 +181,7 @@ static int build_global_pressure(cfdh_ctx *c) {
         const int g = c->h_gid[i];
         for (int k = A0.rowptr[g]; k < A0.rowptr[g + 1]; k++) {
           const int loc = c->h_g2l[A0.col[k]];
-          if (loc < 0) { ok = false; break; }  // a neighbour of an owned vertex is always local (one-cell overlap)
+          if (loc < 0) { ok = false; break; }  // a neighbour of an owned vertex is always local (every overlap holds the cells of the owned vertices)
           Al.col.push_back(loc); Al.val.push_back(A0.val[k]);
         }
         Al.rowptr[i + 1] = (int)Al.col.size();

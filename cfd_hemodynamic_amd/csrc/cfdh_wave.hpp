@@ -61,3 +61,19 @@ __device__ __forceinline__ double block_max(double v, double *sh) {
   __syncthreads();
   return r;
 }
+
+// The same two sums by a butterfly of lane exchanges (result in every lane / every thread).  Kept apart from wave_sum / block_sum:
+// those add in another order, and the functionals of the generic elements (L2 norms, fluxes, drag and lift), which have always
+// been reduced this way, would change in their last bits.
+__device__ __forceinline__ double wave_sum_xor(double v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+__device__ __forceinline__ double block_sum_xor(double v, double *sh /*[4]*/) {
+  v = wave_sum_xor(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}

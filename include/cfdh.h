@@ -22,8 +22,8 @@
  * (PETSc.ScalarType = float64, /root/reference/src/solverBase.py:37).
  *
  * Local numbering (multi-GPU): a context holds the vertices [0,nv) of its
- * part, the first nv_owned of them owned, the rest ghosts (one-cell overlap;
- * SURVEY.md 8e).  Velocity arrays are vertex-major/component-minor
+ * part, the first nv_owned of them owned, the rest ghosts (the
+ * ghost contract is stated at cfdh_create_elem_part).  Velocity arrays are vertex-major/component-minor
  * (u[gdim*v+i]), as DOLFINx lays out the blocked P1 space
  * (stabilized_schur.py:55-57).
  *
@@ -147,8 +147,11 @@ int cfdh_create_elem(cfdh_ctx **out, int device, int gdim, int elem, int64_t nn,
                      const double *node_coords, int64_t nfacets, const int32_t *facet_cells, const int32_t *facet_local,
                      const int32_t *facet_marker);
 /* The same for one part of a partitioned run (SURVEY.md 8e for the 8f-4 elements: the reference runs every solver under
- * mpirun, /root/reference/src/simulation_hpc.sh:14-19): nodes [0, nn_owned) are owned, the rest are the ghost nodes of the
- * one-cell overlap, numbered contiguously per neighbour as cfdh_set_halo expects; cells = all cells touching an owned node. */
+ * mpirun, /root/reference/src/simulation_hpc.sh:14-19): nodes [0, nn_owned) are owned, the rest are ghost nodes, numbered
+ * contiguously per neighbour as cfdh_set_halo expects.  Any ghost set that is closed under the halo plan is accepted (one layer
+ * of cells around the owned nodes, or more: PartComm.make_part passes two by default); cells = the cells of the part, of which
+ * those of a deeper layer touch no owned node.  Rows are assembled for owned nodes only, and a cell is integrated in global
+ * functionals by the rank that owns its first node.  This holds for every builder (cfdh_create with nv_owned < nv included). */
 int cfdh_create_elem_part(cfdh_ctx **out, int device, int gdim, int elem, int64_t nn, int64_t nn_owned, int64_t nc, const int32_t *cells,
                           const double *node_coords, int64_t nfacets, const int32_t *facet_cells, const int32_t *facet_local,
                           const int32_t *facet_marker);

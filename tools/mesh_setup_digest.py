@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""sha256 digests of what the context builders produce, for comparing two builds of libcfdh.so byte for byte (the mesh set-up is
+host code: numbering, graph and staging order decide the summation order of the assembly, h_Lval / h_Ml feed the preconditioner).
+
+    python tools/mesh_setup_digest.py --out new.txt [--lib path/to/other/libcfdh.so]
+    python tools/mesh_setup_digest.py --out old.txt --lib ../old-checkout/cfd_hemodynamic_amd/libcfdh.so && cmp old.txt new.txt
+
+One small context of every family: closed-form P1 in 2-D / 3-D (also with CFDH_NO_RENUMBER=1), generic P1 / P2 / Q1 in 2-D / 3-D,
+IPCS in 2-D / 3-D, and one part of a 2-part split (two cell layers) of a closed-form mesh and of a P2 tetrahedral mesh.  Per context:
+Jacobian structure and values, residual, and -- whole meshes -- solution and iteration counts of two time steps."""
+import argparse
+import hashlib
+import os
+import sys
+import types
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--lib", default=None, help="another build of libcfdh.so to load instead of the one in the tree")
+    a = ap.parse_args()
+    from cfd_hemodynamic_amd import _lib
+    if a.lib:
+        _lib._SO = os.path.abspath(a.lib)
+    from cfd_hemodynamic_amd.elements import NodeMesh, NodeMesh3D
+    from cfd_hemodynamic_amd.mesh3d import create_unit_cube
+    from cfd_hemodynamic_amd.parallel import LocalPart, partition_vertices_rcb
+    from gen3_util import LIB_ETYPE3, node_mesh3
+    from gen_util import LIB_ETYPE, node_mesh
+    from util import dfg_case
+
+    lines = []
+
+    def put(case, item, *arrays):
+        lines.append("%s %s %s" % (case, item, sha(*arrays)))
+
+    def part(m, rank):
+        g = types.SimpleNamespace(x=m.x, cells=m.cells, num_vertices=len(m.x), num_cells=len(m.cells), facet_cells=m.facet_cells,
+                                  facet_local=m.facet_local, facet_marker=np.zeros(len(m.facet_cells), np.int32))
+        return LocalPart(g, partition_vertices_rcb(m.x, 2), rank, layers=2)
+
+    def fgmres_context(case, m, etype, nvo=None, steps=2):
+        d = m.x.shape[1]
+        nv = len(m.x)
+        rng = np.random.default_rng(17)
+        ctx = _lib.Context(m.x, m.cells, m.facet_cells, m.facet_local, np.zeros(len(m.facet_cells), np.int32), nv_owned=nvo, etype=etype)
+        ctx.set_params(0.02, 1.3, 0.04, f=(0.2, -0.1, 0.3)[:d])
+        if nvo is None:  # a rotation on the whole boundary (no net flux), pressure free
+            bnd = np.unique(np.asarray(m.facet_vertices)).astype(np.int32)
+            vals = np.zeros((len(bnd), d))
+            vals[:, 0], vals[:, 1] = 0.1 * m.x[bnd, 1], -0.1 * m.x[bnd, 0]
+            ctx.add_dirichlet(0, bnd, vals)
+        un, u, p = 0.05 * rng.standard_normal(d * nv), 0.05 * rng.standard_normal(d * nv), 0.05 * rng.standard_normal(nv)
+        ctx.set_state(u_prev=un, p_prev=np.zeros(nv), u=u, p=p)
+        ctx.assemble(True)
+        J = ctx.get_csr()
+        put(case, "csr-structure", J.indptr, J.indices)
+        put(case, "csr-values", J.data)
+        put(case, "residual", *ctx.get_residual())
+        if nvo is None:  # a part needs its communicator to solve
+            for k in range(steps):
+                try:
+                    st = ctx.solve_step()
+                    lines.append("%s step%d newton %d krylov %d" % (case, k, st.newton_its, st.krylov_its))
+                except RuntimeError as e:
+                    lines.append("%s step%d %s" % (case, k, str(e).split("(")[0].strip()))
+                put(case, "step%d-solution" % k, *ctx.get_solution())
+                ctx.advance()
+        ctx.close()
+
+    def ipcs_context(case, m, nm):
+        d = m.x.shape[1]
+        nn, nvert = len(nm.x), m.num_vertices
+        rng = np.random.default_rng(19)
+        ctx = _lib.IpcsContext(nm.x, nm.cells, nvert, nm.facet_cells, nm.facet_local, np.zeros(len(nm.facet_cells), np.int32))
+        ctx.set_params(0.01, 1.06, 0.05, f=np.asarray((0.3, -0.7, 0.2)[:d]))
+        bnd = np.unique(np.asarray(nm.facet_vertices)).astype(np.int32)
+        vals = np.zeros((len(bnd), d))
+        vals[:, 0], vals[:, 1] = 0.1 * nm.x[bnd, 1], -0.1 * nm.x[bnd, 0]
+        ctx.add_dirichlet(0, bnd, vals)
+        u = 0.05 * rng.standard_normal(d * nn)
+        ctx.set_state(u_prev=u, p_prev=np.zeros(nvert), u=u, p=np.zeros(nvert))
+        ctx.set_previous2(u)
+        for k in range(2):
+            try:
+                st = ctx.step()
+                lines.append("%s step%d its %s" % (case, k, " ".join(str(int(i)) for i in st.its)))
+            except RuntimeError as e:
+                lines.append("%s step%d %s" % (case, k, str(e).split("(")[0].strip()))
+            put(case, "step%d-solution" % k, *ctx.get_solution())
+        for which in range(3 + 2 * d):
+            A = ctx.get_operator(which)
+            put(case, "operator%d" % which, A.indptr, A.indices, A.data)
+        ctx.close()
+
+    tri, tet = dfg_case(6).mesh, create_unit_cube(4)
+    for env in ("", "1"):
+        os.environ["CFDH_NO_RENUMBER"] = env
+        fgmres_context("closed-2d" + ("-norenumber" if env else ""), tri, 0)
+        fgmres_context("closed-3d" + ("-norenumber" if env else ""), tet, 0)
+    os.environ.pop("CFDH_NO_RENUMBER")
+    for kind in ("P1", "P2", "Q1"):
+        fgmres_context("gen-2d-" + kind, node_mesh(kind, 8, 0.05), LIB_ETYPE[kind])
+        fgmres_context("gen-3d-" + kind, node_mesh3(kind, 3 if kind == "P2" else 4, 0.05), LIB_ETYPE3[kind])
+    ipcs_context("ipcs-2d", tri, NodeMesh(tri))
+    ipcs_context("ipcs-3d", tet, NodeMesh3D(tet))
+    for case, m, etype in (("part-closed-2d", tri, 0), ("part-closed-3d", tet, 0), ("part-gen-3d-P2", node_mesh3("P2", 3, 0.05), 1)):
+        lp = part(m, 1)
+        pm = types.SimpleNamespace(x=lp.x, cells=lp.cells, facet_cells=lp.facet_cells, facet_local=lp.facet_local)
+        fgmres_context(case, pm, etype, nvo=lp.nvo)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("%d lines -> %s" % (len(lines), a.out))
+
+
+if __name__ == "__main__":
+    main()
