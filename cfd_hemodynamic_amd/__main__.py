@@ -1,6 +1,8 @@
 """`python -m cfd_hemodynamic_amd simulate --simulation dfg_1 --solver stabilized_schur --T 1.0 --dt 0.01 --name X`
 -- the `simulate` sub-command of the reference's CLI (/root/reference/main.py:87-139,253-254);
-unknown `--key value` pairs are literal-evaluated and passed to the scenario (main.py:12-31)."""
+unknown `--key value` pairs are literal-evaluated and passed to the scenario (main.py:12-31).
+`--wall_indices_from T0 --wall_indices_to T1` (defaults 0 and T; either switches it on) writes the cycle-averaged wall shear
+indices of that window next to the other results (wall_indices.npz / .vtu / .txt)."""
 from __future__ import annotations
 
 import argparse
@@ -39,6 +41,9 @@ def main(argv=None):
     s.add_argument("--dt", type=float, required=True)
     s.add_argument("--name", default="run")
     s.add_argument("--output_dir", default="results")
+    # cycle-averaged wall shear indices (TAWSS, OSI, RRT) over the steps that end in (from, to]; either switch turns them on
+    s.add_argument("--wall_indices_from", type=float, default=None)
+    s.add_argument("--wall_indices_to", type=float, default=None)
     args, extra = ap.parse_known_args(argv)
     kw = _parse_extra(extra)
     try:
@@ -49,7 +54,11 @@ def main(argv=None):
     sim = cls(args.solver, args.dt, args.T, **kw)
     out = os.path.join(args.output_dir, args.simulation, args.name)
     sim.setup()  # the reference calls setup() a second time in Simulation.run (simulation.py:269)
-    sim.solve(out)
+    solve_kw = {}
+    if args.wall_indices_from is not None or args.wall_indices_to is not None:
+        solve_kw["wall_indices"] = (0.0 if args.wall_indices_from is None else args.wall_indices_from,
+                                    args.T if args.wall_indices_to is None else args.wall_indices_to)
+    sim.solve(out, **solve_kw)
     print("results in", out)
     return 0
 

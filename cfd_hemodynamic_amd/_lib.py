@@ -58,6 +58,7 @@ SYMBOLS = [
     "cfdh_get_amg_operator", "cfdh_get_amg_vectors",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
     "cfdh_ipcs_apply_pressure_pc",
+    "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
 ]
 
 
@@ -144,6 +145,9 @@ def lib():
     L.cfdh_ipcs_get_operator.argtypes = [vp, C.c_int, lp, ip, ip, dp]
     L.cfdh_ipcs_get_intermediate.argtypes = [vp, C.c_int, dp]
     L.cfdh_ipcs_apply_pressure_pc.argtypes = [vp, dp, dp]
+    L.cfdh_wall_stats_reset.argtypes = [vp]
+    L.cfdh_wall_stats_accumulate.argtypes = [vp, C.c_double]
+    L.cfdh_wall_stats_get.argtypes = [vp, C.c_int, lp, dp]
     _LIB = L
     return L
 
@@ -180,6 +184,9 @@ AMG_OP_A, AMG_OP_P, AMG_OP_G, AMG_OP_SB, AMG_OP_SC = 0, 1, 2, 3, 4
  AMG_VEC_CC_PBC, AMG_VEC_SPGEMM_ROWS, AMG_VEC_SHAPE, AMG_VEC_ORDER, AMG_VEC_A00_LMAX, AMG_VEC_A00_DINV) = range(14)
 # Eisenstat-Walker version 2 with PETSc's defaults: rtol_0, rtol_max, gamma, alpha, threshold (cfdh_set_ksp_forcing)
 EW_DEFAULTS = (0.3, 0.9, 1.0, (1.0 + 5.0 ** 0.5) / 2.0, 0.1)
+# cfdh_wall_stats_get
+WALL_TAWSS, WALL_OSI, WALL_RRT, WALL_MEAN, WALL_PEAK, WALL_TOTALS = range(6)
+INFO_WALL_STATS_COUNT = 90  # cfdh_info: accumulations since the last cfdh_wall_stats_reset
 
 
 class Context:
@@ -329,6 +336,22 @@ class Context:
         out = np.zeros(self.dim * self.nv)
         self._chk(self.L.cfdh_wall_shear_stress(self.h, _dp(out)))
         return out
+
+    def wall_stats_reset(self):
+        """Zero the accumulators of the cycle-averaged wall shear indices (allocated on first use)."""
+        self._chk(self.L.cfdh_wall_stats_reset(self.h))
+
+    def wall_stats_accumulate(self, weight):
+        """Add the wall shear stress of the current solution with this weight (the step's dt)."""
+        self._chk(self.L.cfdh_wall_stats_accumulate(self.h, float(weight)))
+
+    def wall_stats_get(self, which):
+        """WALL_TAWSS / WALL_OSI / WALL_RRT / WALL_PEAK [nv], WALL_MEAN [nv, gdim], WALL_TOTALS (W, count) as float64."""
+        n = C.c_int64()
+        self._chk(self.L.cfdh_wall_stats_get(self.h, int(which), C.byref(n), None))
+        out = np.empty(n.value)
+        self._chk(self.L.cfdh_wall_stats_get(self.h, int(which), C.byref(n), _dp(out)))
+        return out.reshape(-1, self.dim) if int(which) == WALL_MEAN else out
 
     def set_previous2(self, u_prev2):
         u_prev2 = np.ascontiguousarray(u_prev2, dtype=np.float64).reshape(-1)
@@ -536,6 +559,15 @@ class IpcsContext(Context):
         p = np.empty(self.nvert) if p is None else p
         self._chk(self.L.cfdh_get_previous(self.h, _dp(u), _dp(p)))
         return u, p
+
+    def wall_shear_stress(self, download=True):
+        """Wall shear stress of the P2 u_sol as a P1 field on the vertices, nvert * gdim values."""
+        if not download:
+            self._chk(self.L.cfdh_wall_shear_stress(self.h, None))
+            return None
+        out = np.zeros(self.dim * self.nvert)
+        self._chk(self.L.cfdh_wall_shear_stress(self.h, _dp(out)))
+        return out
 
     def set_form(self, conv_coeff, force_coeff):
         """Coefficients c (convection) and s_f (force) of the scheme; the context's default is (rho, +rho)."""

@@ -1151,8 +1151,19 @@ int cfdh_functional(cfdh_ctx *c, int kind, int marker, double *out) {
 }
 
 int cfdh_wall_shear_stress(cfdh_ctx *c, double *shear) {
-  NOT_IPCS(c, "cfdh_wall_shear_stress");
   ENTER(c);
+  if (c->ipcs) {  // P2 velocity, CG1 field on the vertices (caller's numbering); entries away from the wall stay zero
+    IpcsData *I = c->ipcs;
+    if (!c->params_set) return cfdh_fail(c, CFDH_E_STATE, "cfdh_set_params was not called");
+    const size_t n = (size_t)I->D * (size_t)I->nvert;
+    if (!c->wss.p) { HIPCHK(c, c->wss.alloc(n)); HIPCHK(c, c->wss.zero(c->stream)); }
+    CHK(k_ipcs_wss(c, c->wss.p));
+    if (!shear) return 0;
+    I->n_field_copies++;
+    HIPCHK(c, hipMemcpyAsync(shear, c->wss.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
   const size_t d = (size_t)c->dim;
   if (!c->wss.p) HIPCHK(c, c->wss.alloc(d * (size_t)c->nv));
   CHK(comm_halo(c, c->x.p));
@@ -1164,6 +1175,61 @@ int cfdh_wall_shear_stress(cfdh_ctx *c, double *shear) {
   for (int k = 0; k < c->nv; k++) {
     const int v = c->iperm[k];
     for (size_t i = 0; i < d; i++) shear[d * (size_t)v + i] = h[d * (size_t)k + i];
+  }
+  return 0;
+}
+
+// ---- cycle-averaged wall shear indices (kernels: cfdh_wallstats.hip) ------------------------------------------------------
+static inline size_t ws_nv(const cfdh_ctx *c) { return c->ipcs ? (size_t)c->ipcs->nvert : (size_t)c->nv; }  // vertices of the WSS field
+
+int cfdh_wall_stats_reset(cfdh_ctx *c) {
+  ENTER(c);
+  const size_t d = (size_t)c->dim, n = ws_nv(c);
+  HIPCHK(c, c->ws_S.alloc(d * n)); HIPCHK(c, c->ws_A.alloc(n)); HIPCHK(c, c->ws_M.alloc(n)); HIPCHK(c, c->ws_out.alloc(d * n));
+  HIPCHK(c, c->ws_S.zero(c->stream)); HIPCHK(c, c->ws_A.zero(c->stream)); HIPCHK(c, c->ws_M.zero(c->stream));
+  c->ws_W = 0.0;
+  c->ws_count = 0;
+  c->ws_ready = true;
+  return 0;
+}
+
+int cfdh_wall_stats_accumulate(cfdh_ctx *c, double weight) {
+  ENTER(c);
+  if (!std::isfinite(weight) || !(weight > 0.0)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_wall_stats_accumulate: the weight must be finite and > 0");
+  if (!c->ws_ready) return cfdh_fail(c, CFDH_E_STATE, "cfdh_wall_stats_accumulate: cfdh_wall_stats_reset was not called");
+  CHK(cfdh_wall_shear_stress(c, nullptr));  // always recomputed: facet work only
+  CHK(k_ws_accumulate(c, (int)ws_nv(c), weight, c->wss.p));
+  c->ws_W += weight;
+  c->ws_count++;
+  return 0;
+}
+
+int cfdh_wall_stats_get(cfdh_ctx *c, int which, int64_t *n, double *out) {
+  ENTER(c);
+  if (!n) return cfdh_fail(c, CFDH_E_ARG, "cfdh_wall_stats_get: null count pointer");
+  if (which < 0 || which > 5) return cfdh_fail(c, CFDH_E_ARG, "cfdh_wall_stats_get: which in [0, 5]");
+  if (!c->ws_ready) return cfdh_fail(c, CFDH_E_STATE, "cfdh_wall_stats_get: cfdh_wall_stats_reset was not called");
+  if (which == 5) {
+    *n = 2;
+    if (out) { out[0] = c->ws_W; out[1] = (double)c->ws_count; }
+    return 0;
+  }
+  if (!(c->ws_W > 0.0)) return cfdh_fail(c, CFDH_E_STATE, "cfdh_wall_stats_get: nothing accumulated since the last reset");
+  const size_t nv = ws_nv(c), d = which == 3 ? (size_t)c->dim : 1;
+  *n = (int64_t)(d * nv);
+  if (!out) return 0;
+  CHK(k_ws_derive(c, (int)nv, which, c->ws_out.p));
+  if (c->ipcs) {
+    HIPCHK(c, hipMemcpyAsync(out, c->ws_out.p, sizeof(double) * d * nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  std::vector<double> h(d * nv);
+  HIPCHK(c, hipMemcpyAsync(h.data(), c->ws_out.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < nv; k++) {
+    const size_t v = (size_t)c->iperm[k];
+    for (size_t i = 0; i < d; i++) out[d * v + i] = h[d * k + i];
   }
   return 0;
 }
@@ -1217,6 +1283,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
       case 81: return I->nvert;
       case 82: return I->n_field_copies;
       case 83: return 1;
+      case 84: case 90: return c->ws_count;  // accumulations of the wall shear indices since the last reset
       default: return -1;
     }
   }
@@ -1262,6 +1329,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 88: return c->guess_last_rank;  // rank the pivoted Cholesky found in the last Gram system of a projected guess (-1: none yet)
     case 89: return c->guess_last_k;     // ... and the number of kept vectors it had
     case 85: return c->lean ? 1 : 0;  // lean solve path switched on (CFDH_SOLVE_LEAN)
+    case 90: return c->ws_count;      // accumulations of the wall shear indices since the last cfdh_wall_stats_reset
     case 75: return c->pc_valid ? 1 : 0;
     case 76: return c->singular;
     case 77: return c->form;

@@ -253,6 +253,12 @@ struct cfdh_ctx {
   // state: layout [u owned 2*nvo | p owned nvo | ghosts 3*ng (ux,uy,p)]
   dbuf<double> x, xt, xprev, xprev2, F, dvec;
   dbuf<double> wss;  // [nv][2] wall shear stress of the last cfdh_wall_shear_stress call (allocated on first use)
+  // cycle-averaged wall shear indices (cfdh_wall_stats_*, cfdh_wallstats.hip): per vertex of the WSS field S = sum w tau [dim],
+  // A = sum w |tau|, M = max |tau|; allocated by the first cfdh_wall_stats_reset
+  dbuf<double> ws_S, ws_A, ws_M, ws_out;  // ws_out: the derived field of cfdh_wall_stats_get before its download
+  double ws_W = 0;                        // sum of the weights since the last reset
+  long long ws_count = 0;                 // accumulations since the last reset (cfdh_info 90)
+  bool ws_ready = false;
   double ts_theta = 0.5, ts_a[3] = {1.0, -1.0, 0.0};  // cfdh_set_time_scheme
   bool ds_terms = true;      // cfdh_set_boundary_terms
   double bf_beta = 0.0;
@@ -522,6 +528,11 @@ int cfdh_pcd_supported(cfdh_ctx *c, const char *who);  // 0, or CFDH_E_ARG with 
 int cfdh_pcd_setup(cfdh_ctx *c);                       // incidences, inlet facets, SELL layout, 1 / diag(M)
 int k_pcd_assemble(cfdh_ctx *c, const double *xstate);  // K at the iterate xstate
 int k_pcd_apply(cfdh_ctx *c, const double *r, double *s);  // t = r / m_d, s = K t, q
+
+// ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------
+int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out [nvert][dim]: entries of the wall vertices only
+int k_ws_accumulate(cfdh_ctx *c, int n, double w, const double *tau);     // S += w tau, A += w |tau|, M = max(M, |tau|) on n vertices
+int k_ws_derive(cfdh_ctx *c, int n, int which, double *out);              // the field `which` (0 .. 4) of cfdh_wall_stats_get
 
 // ---- kernels (cfdh_kernels.hip) ----------------------------------------------------
 void prof_begin(cfdh_ctx *c, int kind);

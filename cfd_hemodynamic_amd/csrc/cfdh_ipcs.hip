@@ -698,9 +698,13 @@ int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn64, int64_t nvert64, int64
   HIPCHK(c, I->pflag.alloc(nvert)); HIPCHK(c, I->pflag.zero(s));
   HIPCHK(c, I->S.alloc(IP_NS)); HIPCHK(c, I->S.zero(s));
   HIPCHK(c, I->P.alloc(2 * IP_NB)); HIPCHK(c, I->P.zero(s));
+  std::vector<int> wv, wptr, wfac;  // alive until the synchronisation below
   if (nfac > 0) {
     HIPCHK(c, I->d_fcell.upload(I->fcell, s)); HIPCHK(c, I->d_flocal.upload(I->flocal, s)); HIPCHK(c, I->d_fmarker.upload(I->fmarker, s));
     HIPCHK(c, I->fout.alloc((size_t)nfac));
+    cfdh_mesh::wall_vertex_facets(NL, NV, nfac, I->fcell.data(), I->flocal.data(), I->cells.data(), nvert, wv, wptr, wfac);
+    I->n_wallv = (int)wv.size();
+    HIPCHK(c, I->wv_list.upload(wv, s)); HIPCHK(c, I->wv_ptr.upload(wptr, s)); HIPCHK(c, I->wv_fac.upload(wfac, s));
   }
   I->h_uflag.assign(nn, 0); I->h_ucnt.assign(nn, 0.0); I->h_uval.assign(n1, 0.0);
   I->h_pflag.assign(nvert, 0); I->h_pcnt.assign(nvert, 0.0); I->h_pval.assign(nvert, 0.0);

@@ -14,6 +14,10 @@ struct IpcsData {
   // device copies
   dbuf<int> d_cells, rp2, col2, eptr, elist, d_gptr, d_gcol, d_bptr, d_bcol, rp1, col1, d_fcell, d_flocal, d_fmarker;
   dbuf<double> d_coords, d_geo, d_T2, Mv, Kv, Gv, BTv, Bv, d_m1, Mpv, Lv, Afree, A1v, RMv, dinv1, dinv3, cw, fout;
+  // wall shear stress (cfdh_wallstats.hip): the vertices of the exterior facets and, per wall vertex, its exterior facets in
+  // ascending facet index (cfdh_mesh::wall_vertex_facets)
+  int n_wallv = 0;
+  dbuf<int> wv_list, wv_ptr, wv_fac;
   // state and work vectors: velocity-sized [nn D], pressure-sized [nvert]
   dbuf<double> u_sol, u_prev, u_n1, us, b1, b3, kr, krh, kp, kv, ks, kt, ky, kz, uval, ucnt;
   dbuf<double> p_sol, p_prev, phi, b2, pr, pz, pp, pq, lift2, prhs;

@@ -252,6 +252,27 @@ inline int p1_subspace(int NL, int NV, const int (*edges)[2], int nc, int nv, co
   return nvert;
 }
 
+// ---- wall vertices of a simplex mesh: the vertices (local positions 0 .. NV - 1, all but flocal) of the exterior facets, ascending,
+// and for wall vertex k its exterior facets fac[ptr[k] .. ptr[k + 1]) in ascending facet index -- the gather lists of the wall
+// shear stress on the P2/P1 context (one lane per wall vertex sums its facets in this order)
+inline void wall_vertex_facets(int NL, int NV, int64_t nfac, const int *fcell, const int *flocal, const int *cells, int nvert, std::vector<int> &wv,
+                               std::vector<int> &ptr, std::vector<int> &fac) {
+  std::vector<int> cnt((size_t)nvert + 1, 0);
+  for (int64_t f = 0; f < nfac; f++)
+    for (int a = 0; a < NV; a++)
+      if (a != flocal[f]) cnt[cells[(size_t)NL * fcell[f] + a] + 1]++;
+  wv.clear();
+  ptr.assign(1, 0);
+  std::vector<int> pos((size_t)nvert, -1);
+  for (int v = 0; v < nvert; v++)
+    if (cnt[v + 1] > 0) { pos[v] = (int)wv.size(); wv.push_back(v); ptr.push_back(ptr.back() + cnt[v + 1]); }
+  fac.resize((size_t)ptr.back());
+  std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+  for (int64_t f = 0; f < nfac; f++)
+    for (int a = 0; a < NV; a++)
+      if (a != flocal[f]) fac[fill[pos[cells[(size_t)NL * fcell[f] + a]]]++] = (int)f;
+}
+
 // ---- determinant of the affine map of a 2-D cell from its first three nodes (X: coordinates [..][2], v: the cell's nodes); the
 // builders refuse a cell whose determinant is not different from zero
 inline double tri_det(const double *X, const int *v) {

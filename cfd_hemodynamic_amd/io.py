@@ -14,6 +14,55 @@ import struct
 import numpy as np
 
 
+def write_vtu(fn, mesh, fields) -> None:
+    """One .vtu file of `mesh` with the point-data arrays of the dict `fields` (name -> nv or nv x ncomp values)."""
+    m = mesh
+    nv, nc = m.num_vertices, len(m.cells)
+    pts = np.zeros((nv, 3))
+    pts[:, : m.x.shape[1]] = m.x
+    npc = m.cells.shape[1]  # 3: VTK_TRIANGLE (5), 4: VTK_TETRA (10) / VTK_QUAD (9) in 2-D, 6: VTK_QUADRATIC_TRIANGLE (22)
+    conn, ctype = np.ascontiguousarray(m.cells, dtype=np.int32), (5 if npc == 3 else 10)
+    if npc == 4 and m.x.shape[1] == 2:
+        conn, ctype = conn[:, [0, 1, 3, 2]], 9          # DOLFINx tensor-product order -> VTK's cyclic order
+    elif npc == 6:
+        conn, ctype = conn[:, [0, 1, 2, 5, 3, 4]], 22   # edge nodes: VTK wants (0-1), (1-2), (2-0); ours are opposite vertex 0, 1, 2
+    elif npc == 8:
+        conn, ctype = conn[:, [0, 1, 3, 2, 4, 5, 7, 6]], 12   # VTK_HEXAHEDRON: bottom face cyclic, then the top face
+    elif npc == 10:
+        # VTK_QUADRATIC_TETRA: edges (0-1) (1-2) (0-2) (0-3) (1-3) (2-3); ours (Basix): (2,3) (1,3) (1,2) (0,3) (0,2) (0,1)
+        conn, ctype = conn[:, [0, 1, 2, 3, 9, 6, 8, 7, 5, 4]], 24
+    data = {}
+    for name, vals in fields.items():
+        d = np.asarray(vals, dtype=np.float64).reshape(nv, -1)
+        if d.shape[1] == 2:  # ParaView wants 3-component vectors
+            d = np.concatenate([d, np.zeros((nv, 1))], axis=1)
+        data[name] = d
+    arrays = [pts.ravel(), np.ascontiguousarray(conn).ravel(),
+              (npc * np.arange(1, nc + 1)).astype(np.int32), np.full(nc, ctype, dtype=np.uint8)] + [d.ravel() for d in data.values()]
+    offs, blob = [], bytearray()
+    for a in arrays:
+        offs.append(len(blob))
+        raw = np.ascontiguousarray(a).tobytes()
+        blob += struct.pack("<Q", len(raw)) + raw
+    point_data = "\n".join('<DataArray type="Float64" Name="%s" NumberOfComponents="%d" format="appended" offset="%d"/>' % (name, d.shape[1], off)
+                           for (name, d), off in zip(data.items(), offs[4:]))
+    head = (
+        '<?xml version="1.0"?>\n'
+        '<VTKFile type="UnstructuredGrid" version="1.0" byte_order="LittleEndian" header_type="UInt64">\n'
+        '<UnstructuredGrid><Piece NumberOfPoints="%d" NumberOfCells="%d">\n'
+        '<Points><DataArray type="Float64" NumberOfComponents="3" format="appended" offset="%d"/></Points>\n'
+        '<Cells>\n<DataArray type="Int32" Name="connectivity" format="appended" offset="%d"/>\n'
+        '<DataArray type="Int32" Name="offsets" format="appended" offset="%d"/>\n'
+        '<DataArray type="UInt8" Name="types" format="appended" offset="%d"/>\n</Cells>\n'
+        '<PointData>%s</PointData>\n'
+        '</Piece></UnstructuredGrid>\n<AppendedData encoding="raw">\n_'
+        % (nv, nc, offs[0], offs[1], offs[2], offs[3], point_data))
+    with open(fn, "wb") as f:
+        f.write(head.encode())
+        f.write(bytes(blob))
+        f.write(b"\n</AppendedData>\n</VTKFile>\n")
+
+
 class VTUWriter:
     def __init__(self, comm, filename: str, function, name: str = None):
         self.comm = comm
@@ -30,49 +79,8 @@ class VTUWriter:
         vals = np.array(self.function.x.array, dtype=np.float64, copy=True)  # collective in partitioned runs
         if self.comm.rank != 0:
             return
-        m = self.mesh
-        nv, nc = m.num_vertices, len(m.cells)
-        bs = vals.size // nv
-        pts = np.zeros((nv, 3))
-        pts[:, : m.x.shape[1]] = m.x
-        data = vals.reshape(nv, bs)
-        if bs == 2:  # ParaView wants 3-component vectors
-            data = np.concatenate([data, np.zeros((nv, 1))], axis=1)
-        npc = m.cells.shape[1]  # 3: VTK_TRIANGLE (5), 4: VTK_TETRA (10) / VTK_QUAD (9) in 2-D, 6: VTK_QUADRATIC_TRIANGLE (22)
-        conn, ctype = np.ascontiguousarray(m.cells, dtype=np.int32), (5 if npc == 3 else 10)
-        if npc == 4 and m.x.shape[1] == 2:
-            conn, ctype = conn[:, [0, 1, 3, 2]], 9          # DOLFINx tensor-product order -> VTK's cyclic order
-        elif npc == 6:
-            conn, ctype = conn[:, [0, 1, 2, 5, 3, 4]], 22   # edge nodes: VTK wants (0-1), (1-2), (2-0); ours are opposite vertex 0, 1, 2
-        elif npc == 8:
-            conn, ctype = conn[:, [0, 1, 3, 2, 4, 5, 7, 6]], 12   # VTK_HEXAHEDRON: bottom face cyclic, then the top face
-        elif npc == 10:
-            # VTK_QUADRATIC_TETRA: edges (0-1) (1-2) (0-2) (0-3) (1-3) (2-3); ours (Basix): (2,3) (1,3) (1,2) (0,3) (0,2) (0,1)
-            conn, ctype = conn[:, [0, 1, 2, 3, 9, 6, 8, 7, 5, 4]], 24
-        arrays = [pts.ravel(), np.ascontiguousarray(conn).ravel(),
-                  (npc * np.arange(1, nc + 1)).astype(np.int32), np.full(nc, ctype, dtype=np.uint8), data.ravel()]
-        offs, blob = [], bytearray()
-        for a in arrays:
-            offs.append(len(blob))
-            raw = np.ascontiguousarray(a).tobytes()
-            blob += struct.pack("<Q", len(raw)) + raw
-        ncomp = data.shape[1]
         fn = "%s_%06d.vtu" % (self.base, len(self.steps))
-        head = (
-            '<?xml version="1.0"?>\n'
-            '<VTKFile type="UnstructuredGrid" version="1.0" byte_order="LittleEndian" header_type="UInt64">\n'
-            '<UnstructuredGrid><Piece NumberOfPoints="%d" NumberOfCells="%d">\n'
-            '<Points><DataArray type="Float64" NumberOfComponents="3" format="appended" offset="%d"/></Points>\n'
-            '<Cells>\n<DataArray type="Int32" Name="connectivity" format="appended" offset="%d"/>\n'
-            '<DataArray type="Int32" Name="offsets" format="appended" offset="%d"/>\n'
-            '<DataArray type="UInt8" Name="types" format="appended" offset="%d"/>\n</Cells>\n'
-            '<PointData><DataArray type="Float64" Name="%s" NumberOfComponents="%d" format="appended" offset="%d"/></PointData>\n'
-            '</Piece></UnstructuredGrid>\n<AppendedData encoding="raw">\n_'
-            % (nv, nc, offs[0], offs[1], offs[2], offs[3], self.name, ncomp, offs[4]))
-        with open(fn, "wb") as f:
-            f.write(head.encode())
-            f.write(bytes(blob))
-            f.write(b"\n</AppendedData>\n</VTKFile>\n")
+        write_vtu(fn, self.mesh, {self.name: vals})
         self.steps.append((float(t), os.path.basename(fn)))
         self._write_index()
 

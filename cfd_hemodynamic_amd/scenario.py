@@ -118,8 +118,19 @@ class Scenario(ABC):
             print(f"Suggested cores: {(nV + nQ) / 20000:.1f}")
 
     def solve(self, output_folder: str = None, afterStepCallback: Callable[[float], None] = None,
-              device_resident: bool = True, max_steps: int = None, write_every: int = 1) -> str:
+              device_resident: bool = True, max_steps: int = None, write_every: int = 1, wall_indices=None) -> str:
+        """wall_indices: None (default) -- nothing; True -- the cycle-averaged wall shear indices (TAWSS, OSI, RRT, mean and peak
+        wall shear stress: wall_indices.py) over the whole run; (t0, t1) -- over the steps that end in (t0, t1].  They are accumulated
+        on the device with weight dt right after the step's `assemble_wss()`; afterwards `self.wall_indices` holds the fields, `W` and
+        `steps`, and with an output folder wall_indices.npz / .vtu / .txt are written."""
         mesh, T, solver = self.mesh, self.T, self.solver
+        self.wall_indices = None
+        if wall_indices is not None and wall_indices is not True:
+            wall_indices = (float(wall_indices[0]), float(wall_indices[1]))
+        if wall_indices is not None:
+            from .wall_indices import step_in_window, write_outputs
+            solver.wall_stats_reset()
+        wi_steps = 0
         quiet = getattr(self, "quiet", False)
         if output_folder and mesh.comm.rank == 0:
             os.makedirs(output_folder, exist_ok=True)
@@ -169,6 +180,9 @@ class Scenario(ABC):
                 if error_log:
                     error_log.write("t = %.3f: error = %.3g" % (t, error) + "\n")
             solver.assemble_wss()
+            if wall_indices is not None and step_in_window(t, self.dt, wall_indices):
+                solver.wall_stats_accumulate(self.dt)
+                wi_steps += 1
             if writers and i % write_every == 0:
                 for w in writers:
                     w.write(t)
@@ -219,6 +233,14 @@ class Scenario(ABC):
                     f.write(f"L2 norm of pressure: {norm_p}\n")
                 np.savez(os.path.join(output_folder, "final.npz"), x=mesh.x, cells=mesh.cells, **fields)
             mesh.comm.barrier()
+        if wall_indices is not None:
+            if wi_steps > 0:
+                self.wall_indices = solver.wall_indices()
+                if output_folder and mesh.comm.rank == 0:
+                    fields = self.wall_indices
+                    write_outputs(output_folder, solver.shear_stress.function_space.mesh, fields, fields["W"], fields["steps"])
+            elif mesh.comm.rank == 0:
+                print("wall_indices: no step ended inside the window %s (the run stopped at t=%.6g): nothing written" % (wall_indices, t))
         for w in writers:
             w.close()
         if error_log:

@@ -12,8 +12,10 @@ reason: r.") like the other plugins.  What differs from the reference's configur
   invisible for rho = 1, f = 0 and wrong otherwise;
 * linear solvers: BiCGStab + Jacobi, flexible PCG + one smoothed-aggregation V-cycle (reference: MINRES + BoomerAMG), CG + Jacobi
   (reference: CG + SOR); every solve stops on the true residual at `rtol` (default 1e-5, PETSc's), `atol`, `max_it`;
-* a pressure Dirichlet VALUE goes into phi as in the reference (right for homogeneous data only): one warning when it is non-zero;
-* the wall shear stress is not computed on this context (`shear_stress` stays zero).
+* a pressure Dirichlet VALUE goes into phi as in the reference (right for homogeneous data only): one warning when it is non-zero.
+
+`assemble_wss()` computes the wall shear stress of the P2 velocity on the device as a P1 field on the vertices (`shear_stress`, filled
+when it is read); `wall_stats_reset / wall_stats_accumulate / wall_indices` give the cycle-averaged indices (TAWSS, OSI, RRT).
 
 Keyword arguments: `consistent`, `rtol` (one value or three), `atol`, `max_it`, `device`, `verbose`, `quiet`, `options` (AMG fields
 of cfdh_options).  Quadrilateral / hexahedral meshes and a partitioned `comm` are refused before any device work.
@@ -27,7 +29,7 @@ import numpy as np
 
 from .. import _lib
 from ..boundaryCondition import BoundaryCondition
-from ..fem import Function
+from ..fem import Function, FunctionSpace
 from ..solverBase import SolverBase
 from .stabilized_schur import Solver as _SchurSolver
 
@@ -58,6 +60,7 @@ class Solver(SolverBase):
         self._verbose = int(kwargs.get("verbose", 0))
         self._quiet = bool(kwargs.get("quiet", False))
         self._part = None
+        self._comm = kwargs.get("comm", None)
         self.consistent = bool(kwargs.get("consistent", True))
         dm = self._dm
         self.ctx = _lib.IpcsContext(dm.x, dm.cells, mesh.num_vertices, dm.facet_cells, dm.facet_local, dm.facet_marker,
@@ -78,6 +81,7 @@ class Solver(SolverBase):
         self._warned_p = False
         # lazy host/device synchronisation of the state Functions
         self._sol_dev_newer = False      # u_sol, p_sol
+        self._wss_dev_newer = False      # shear_stress
         self._mid_dev_newer = False      # u_star, phi
         self._prev_dev_newer = False     # u_prev, p_prev, u_n1
         self._prev_host_dirty = True
@@ -94,6 +98,10 @@ class Solver(SolverBase):
 
     _bc_nodes_values = _SchurSolver._bc_nodes_values
     _upload_bcs = _SchurSolver._upload_bcs
+    _wall_stats_one_gpu = _SchurSolver._wall_stats_one_gpu
+    wall_stats_reset = _SchurSolver.wall_stats_reset
+    wall_stats_accumulate = _SchurSolver.wall_stats_accumulate
+    wall_indices = _SchurSolver.wall_indices
 
     # -- lazy sync ---------------------------------------------------------------
     def _sync_solution(self):
@@ -175,9 +183,25 @@ class Solver(SolverBase):
         if self._verbose and not self._quiet:
             print("ipcs_bdf2: iterations %s, |r|/|b| %s" % (list(st.its), ["%.2e" % r for r in st.rel_res]))
 
+    def initStressForm(self):
+        """The stress fields live on the vertex (degree-1) space whatever the velocity degree (solverBase.py:144-162: `vector` is
+        CG1); the base class would put them on the P2 node mesh of V."""
+        self.normal_stress = Function(FunctionSpace(self.mesh, 1), name="normal_stress")
+        self.shear_stress = Function(FunctionSpace(self.mesh, self.mesh.geometry.dim), name="shear_stress")
+
+    def _sync_wss(self):
+        if self._wss_dev_newer:
+            self._wss_dev_newer = False
+            self.shear_stress.x._array[:] = self.ctx.wall_shear_stress(download=True)
+
     def assemble_wss(self):
-        """Not available on this context (wall shear stress on the IPCS context is a follow-up): `shear_stress` stays zero."""
-        return None
+        """solverBase.py:185-195 for the P2 u_sol on the device (cfdh_wall_shear_stress); the host array behind `shear_stress.x.array`
+        is filled when it is read."""
+        if not hasattr(self, "shear_stress"):
+            return
+        self.shear_stress.x._pre_access = self._sync_wss
+        self.ctx.wall_shear_stress(download=False)
+        self._wss_dev_newer = True
 
     # -- device-resident extras ------------------------------------------------------
     def advance(self):

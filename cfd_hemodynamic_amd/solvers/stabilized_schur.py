@@ -150,6 +150,33 @@ class Solver(SolverBase):
         self.ctx.wall_shear_stress(download=False)
         self._dev_newer["wss"] = True
 
+    # -- cycle-averaged wall shear indices (cfdh_wall_stats_*; wall_indices.py) ---------
+    def _wall_stats_one_gpu(self):
+        comm = getattr(self, "_comm", None)
+        if comm is not None and comm.size > 1:
+            raise NotImplementedError("the wall shear indices (TAWSS, OSI, RRT) run on one GPU: the plugin does not gather them over the "
+                                      "parts of a partitioned run")
+
+    def wall_stats_reset(self):
+        """Zero the device accumulators of TAWSS / OSI / RRT (allocated on first use)."""
+        self._wall_stats_one_gpu()
+        self.ctx.wall_stats_reset()
+
+    def wall_stats_accumulate(self, weight):
+        """Add the wall shear stress of the current solution with this weight (the step's dt); nothing crosses the host."""
+        self._wall_stats_one_gpu()
+        self.ctx.wall_stats_accumulate(weight)
+
+    def wall_indices(self):
+        """dict tawss, osi, rrt, wss_mean, wss_peak (wall_indices.indices_from_sums) formed on the device, plus W and steps; arrays in
+        the numbering of `shear_stress`."""
+        self._wall_stats_one_gpu()
+        from ..wall_indices import FIELDS
+        out = {k: self.ctx.wall_stats_get(w) for w, k in enumerate(FIELDS)}
+        W, steps = self.ctx.wall_stats_get(_lib.WALL_TOTALS)
+        out["W"], out["steps"] = float(W), int(steps)
+        return out
+
     def _sync_previous(self):
         if self._prev_dev_newer:
             self._prev_dev_newer = False

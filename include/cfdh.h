@@ -355,9 +355,10 @@ int cfdh_get_amg_vectors(cfdh_ctx *ctx, int hier, int level, int which, int64_t 
  * ids), cfdh_set_state / cfdh_get_solution / cfdh_get_previous (velocity arrays [nn][gdim], pressure arrays [nvert]; cfdh_set_state
  * with u, p sets u_sol, p_sol), cfdh_set_previous2 / cfdh_get_previous2 (u_n1), cfdh_advance, cfdh_advance_field,
  * cfdh_set_facet_markers, cfdh_functional (kinds 2-6; 0 / 1 for gdim 2 with P2 velocity gradients and P1 pressure),
+ * cfdh_wall_shear_stress, cfdh_wall_stats_reset / accumulate / get,
  * cfdh_info (0, 1: nn; 2: nc; 3: entries of A1; 6: levels of the pressure hierarchy; 15: host synchronisations and 80: kernel
- * launches of the last step; 81: nvert; 82: whole-field host copies since creation; 83: 1 (the context kind)), cfdh_last_error,
- * cfdh_destroy.  Every other entry point returns CFDH_E_STATE on it, and the cfdh_ipcs_* entry points return CFDH_E_STATE on every
+ * launches of the last step; 81: nvert; 82: whole-field host copies since creation; 83: 1 (the context kind); 84 and 90:
+ * accumulations of the wall shear indices since the last reset), cfdh_last_error, cfdh_destroy.  Every other entry point returns CFDH_E_STATE on it, and the cfdh_ipcs_* entry points return CFDH_E_STATE on every
  * other context. */
 int cfdh_create_ipcs(cfdh_ctx **out, int device, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells,
                      const double *node_coords, int64_t nfacets, const int32_t *facet_cells, const int32_t *facet_local,
@@ -434,8 +435,28 @@ int cfdh_functional(cfdh_ctx *ctx, int kind, int marker, double *out);
 /* Wall shear stress, the per-step `assemble_wss()` of solverBase.py:163-195,
  * (1/FacetArea) * inner(w, Tt) * ds with T = -sigma(u_sol, p_sol) n, Tt = T - (T.n) n, assembled on
  * the device from the current solution into a P1 vector field (zero away from the boundary).
- * shear: nv x gdim host array, or NULL to compute without downloading. */
+ * shear: nv x gdim host array, or NULL to compute without downloading.
+ * On a context of cfdh_create_ipcs the field is that of the P2 u_sol on the VERTICES (the test space `vector` of
+ * solverBase.py:144-162 is CG1 whatever the velocity degree): shear [nvert][gdim], T = -mu (grad u + grad u^T) n, and per vertex v
+ * the sum over its exterior facets f of (1/|f|) int_f lambda_v Tt ds, integrated exactly (the integrand is quadratic) and gathered
+ * per vertex in ascending facet index without atomics: two calls on one state return the same bytes. */
 int cfdh_wall_shear_stress(cfdh_ctx *ctx, double *shear);
+
+/* Cycle-averaged wall shear indices, accumulated on the device over a window of time steps.  Per vertex of the wall-shear field
+ * (nv vertices; nvert on a context of cfdh_create_ipcs), with tau_k the wall shear stress at accumulation k and w_k its weight:
+ *   S [gdim] = sum w_k tau_k,   A = sum w_k |tau_k|,   M = max_k |tau_k|,   and the scalars W = sum w_k and the count.
+ * cfdh_wall_stats_reset allocates on first use and zeroes.  cfdh_wall_stats_accumulate computes the wall shear stress of the
+ * current solution as cfdh_wall_shear_stress(ctx, NULL) does and updates S, A, M in one pointwise kernel (rank-local on a part of a
+ * partitioned run: owned entries are meaningful); weight must be finite and > 0 (CFDH_E_ARG); CFDH_E_STATE before any reset.
+ * cfdh_wall_stats_get forms the field `which` on the device and downloads it in the caller's numbering; *n receives the number of
+ * doubles, out may be NULL (query):
+ *   0: TAWSS = A / W [nv]                 1: OSI = (1 - |S| / A) / 2, clamped to [0, 1/2], 0 where A == 0 [nv]
+ *   2: RRT = W / |S| (= 1 / ((1 - 2 OSI) TAWSS)), +inf where |S| == 0 < A, 0 where A == 0 [nv]
+ *   3: mean vector S / W [nv][gdim]       4: peak M [nv]       5: {W, count} [2]
+ * which 0 .. 4 with W == 0 and any call before a reset: CFDH_E_STATE; an unknown which: CFDH_E_ARG.  cfdh_info(ctx, 90): the count. */
+int cfdh_wall_stats_reset(cfdh_ctx *ctx);
+int cfdh_wall_stats_accumulate(cfdh_ctx *ctx, double weight);
+int cfdh_wall_stats_get(cfdh_ctx *ctx, int which, int64_t *n, double *out);
 
 /* ---- multi-GPU ---------------------------------------------- */
 
@@ -496,7 +517,8 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 88 / 89: rank found in, and size of, the Gram system of the last projected initial guess (-1 / 0: none yet);
  * 74: preconditioner builds since cfdh_create, 75: 1 while the preconditioner is valid (built, not invalidated since), 76: 1 when the
  * last null-space test of cfdh_solve_step found the constant pressure in the null space of the Jacobian, 77: formulation (CFDH_FORM_*),
- * 78: Schur approximation in use (cfdh_options.pc_type: 0 SELFP, 1 Cahouet-Chabard, 2 PCD), 79: Eisenstat-Walker forcing version */
+ * 78: Schur approximation in use (cfdh_options.pc_type: 0 SELFP, 1 Cahouet-Chabard, 2 PCD), 79: Eisenstat-Walker forcing version;
+ * 90: accumulations of the wall shear indices since the last cfdh_wall_stats_reset (every context kind) */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
