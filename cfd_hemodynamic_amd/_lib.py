@@ -55,7 +55,7 @@ SYMBOLS = [
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
-    "cfdh_get_amg_operator", "cfdh_get_amg_vectors",
+    "cfdh_get_amg_operator", "cfdh_get_amg_vectors", "cfdh_krylov_vec_op",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
     "cfdh_ipcs_apply_pressure_pc",
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
@@ -138,6 +138,8 @@ def lib():
     L.cfdh_apply_operator.argtypes = [vp, dp, dp, dp]
     L.cfdh_get_amg_operator.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, lp, lp, ip, ip, dp]
     L.cfdh_get_amg_vectors.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, dp]
+    L.cfdh_krylov_vec_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int, dp, dp,
+                                     C.POINTER(C.c_float), ip, dp, dp, dp]
     L.cfdh_create_ipcs.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, ip, dp, C.c_int64, ip, ip, ip]
     L.cfdh_ipcs_set_form.argtypes = [vp, C.c_double, C.c_double]
     L.cfdh_ipcs_set_tolerances.argtypes = [vp, dp, C.c_double, ip]
@@ -182,6 +184,11 @@ AMG_HIER_A, AMG_HIER_P, AMG_HIER_H = 0, 1, 2  # cfdh_get_amg_operator / cfdh_get
 AMG_OP_A, AMG_OP_P, AMG_OP_G, AMG_OP_SB, AMG_OP_SC = 0, 1, 2, 3, 4
 (AMG_VEC_DINV, AMG_VEC_WDINV, AMG_VEC_AGG, AMG_VEC_COARSE_INV, AMG_VEC_D, AMG_VEC_LAMBDA, AMG_VEC_CC_SCALARS, AMG_VEC_CC_ML,
  AMG_VEC_CC_PBC, AMG_VEC_SPGEMM_ROWS, AMG_VEC_SHAPE, AMG_VEC_ORDER, AMG_VEC_A00_LMAX, AMG_VEC_A00_DINV) = range(14)
+# cfdh_krylov_vec_op
+(KVOP_DOT, KVOP_NORM2, KVOP_NORM2_PAIR, KVOP_NORM2_TRIPLE, KVOP_NORMINF_DIFF, KVOP_SUB_MEAN, KVOP_NORM_SCALE_INV, KVOP_MULTIDOT,
+ KVOP_MULTIDOT32, KVOP_GRAM, KVOP_MULTIAXPY, KVOP_LINCOMB, KVOP_LINCOMB_KEEP, KVOP_GS_UPDATE_NORMALIZE, KVOP_GS_UPDATE32, KVOP_STORE32,
+ KVOP_GUESS, KVOP_AXPY, KVOP_WAXPY, KVOP_SCALE, KVOP_SCALE_TO, KVOP_PMULT) = range(22)
+KVOP_FLAG_OPTION, KVOP_FLAG_RING = 1, 2  # the op's own switch (with y / with w.w / scale r) ; mirror into a slot of the read-back ring
 # Eisenstat-Walker version 2 with PETSc's defaults: rtol_0, rtol_max, gamma, alpha, threshold (cfdh_set_ksp_forcing)
 EW_DEFAULTS = (0.3, 0.9, 1.0, (1.0 + 5.0 ** 0.5) / 2.0, 0.1)
 # cfdh_wall_stats_get
@@ -488,6 +495,32 @@ class Context:
         w = np.zeros((self.dim + 1) * self.nvo)
         self._chk(self.L.cfdh_apply_operator(self.h, _dp(r), _dp(z), _dp(w)))
         return z, w
+
+    def krylov_vec_op(self, op, n, ld, nvec=1, A=None, B=None, x=None, y=None, coef=None, scalar=0.0, flags=0):
+        """One Krylov vector wrapper (KVOP_*) on caller data, launched as the solver launches it (test entry; one GPU).
+        A, B: column-major blocks flattened to [ld * nvec]; x, y: [n]; coef: the op's coefficients.  Returns a dict with
+        out1, out2 [n], out32 [n] (float32) and the scalars the wrapper returned (host), left on the device (dev) and wrote into
+        the host-mapped words (mirror)."""
+        def arr(a, need, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+            if a.size < need:
+                raise ValueError("%s: %d entries, %d needed" % (what, a.size, need))
+            return a
+        blk = max(n, 0) if op == KVOP_NORM2_TRIPLE else max(ld, 0) * max(nvec, 0)
+        ncoef = {KVOP_GS_UPDATE_NORMALIZE: nvec + 1, KVOP_GUESS: 8 * (nvec + 1)}.get(op, nvec)
+        A, B = arr(A, blk, "A"), arr(B, blk, "B")
+        x, y, coef = arr(x, n, "x"), arr(y, n, "y"), arr(coef, ncoef, "coef")
+        m = max(n, 1)
+        out1, out2, out32 = np.zeros(m), np.zeros(m), np.zeros(m, dtype=np.float32)
+        ns = max(nvec + 2, 72)
+        host, dev, mir = np.zeros(ns), np.zeros(ns), np.zeros(ns)
+        cnt = np.zeros(3, dtype=np.int32)
+        self._chk(self.L.cfdh_krylov_vec_op(self.h, int(op), int(n), int(ld), int(nvec), _dp(A), _dp(B), _dp(x), _dp(y), _dp(coef),
+                                            float(scalar), int(flags), _dp(out1), _dp(out2), out32.ctypes.data_as(C.POINTER(C.c_float)),
+                                            _ip(cnt), _dp(host), _dp(dev), _dp(mir)))
+        return {"out1": out1, "out2": out2, "out32": out32, "host": host[:cnt[0]], "dev": dev[:cnt[1]], "mirror": mir[:cnt[2]]}
 
     def get_amg_operator(self, hier, level, which, raw=False):
         """One operator of a built hierarchy as scipy CSR (AMG_HIER_*, AMG_OP_*); level-0 indices in the caller's numbering.

@@ -51,6 +51,26 @@ static int ipcs_copy(cfdh_ctx *c, const dbuf<double> &src, dbuf<double> &dst) {
   return 0;
 }
 
+namespace {
+// a device allocation that lives for one call of cfdh_krylov_vec_op
+template <class T>
+struct HookBuf {
+  T *p = nullptr;
+  ~HookBuf() { if (p) (void)hipFree(p); }
+  // `count` zeroed entries, the first `filled` of them from src (NULL: none)
+  int put(cfdh_ctx *c, const T *src, size_t count, size_t filled) {
+    HIPCHK(c, hipMalloc((void **)&p, sizeof(T) * count));
+    HIPCHK(c, hipMemsetAsync(p, 0, sizeof(T) * count, c->stream));
+    if (src && filled) HIPCHK(c, hipMemcpyAsync(p, src, sizeof(T) * filled, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  }
+  int get(cfdh_ctx *c, T *dst, size_t count) const {
+    HIPCHK(c, hipMemcpy(dst, p, sizeof(T) * count, hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
+}  // namespace
+
 extern "C" {
 
 int cfdh_abi_version(void) { return CFDH_ABI_VERSION; }
@@ -669,6 +689,141 @@ int cfdh_apply_operator(cfdh_ctx *c, const double *r, double *z, double *w) {
     z[(size_t)d * c->nv + v] = oz[(size_t)d * c->nvo + k];
     w[(size_t)d * c->nvo + v] = ow[(size_t)d * c->nvo + k];
   }
+  return 0;
+}
+
+// ---- test hook: ONE Krylov vector wrapper (v_* of cfdh_kernels.hip) on caller data, launched as the solver launches it ------
+int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const double *A, const double *B, const double *x, const double *y,
+                       const double *coef, double scalar, int flags, double *out1, double *out2, float *out32, int32_t *nscal,
+                       double *scal_host, double *scal_dev, double *scal_mirror) {
+  NOT_IPCS(c, "cfdh_krylov_vec_op");
+  ENTER(c);
+  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_STATE, "cfdh_krylov_vec_op: one GPU only");
+  // ---- everything the production callers guarantee is checked here, before any launch
+  if (op < 0 || op >= CFDH_KVOP_COUNT) return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: unknown op %d", op);
+  if (n < 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: n = %d < 1", n);
+  if (nvec < 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: nvec = %d < 1", nvec);
+  if (ld < n) return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: ld = %d < n = %d", ld, n);
+  if (ld & 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: odd ld = %d (the columns must stay 16-byte aligned)", ld);
+  const bool f32 = op == CFDH_KVOP_MULTIDOT32 || op == CFDH_KVOP_GS_UPDATE32;
+  if (f32 && (ld & 3)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: ld = %d is not a multiple of 4 (fp32 basis copy)", ld);
+  if ((op == CFDH_KVOP_GUESS || op == CFDH_KVOP_GRAM) && nvec > 8)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: k = %d kept vectors outside 1 .. 8", nvec);
+  // which inputs and outputs the op uses
+  bool nA = false, nB = false, nx = true, ny = false, nc = false, o1 = false, o2 = false, o32 = false;
+  switch (op) {
+    case CFDH_KVOP_DOT: case CFDH_KVOP_NORM2_PAIR: ny = true; break;
+    case CFDH_KVOP_NORM2: break;
+    case CFDH_KVOP_NORM2_TRIPLE: ny = nA = true; break;
+    case CFDH_KVOP_NORMINF_DIFF: ny = (flags & 1) != 0; break;
+    case CFDH_KVOP_SUB_MEAN: case CFDH_KVOP_NORM_SCALE_INV: case CFDH_KVOP_SCALE: case CFDH_KVOP_SCALE_TO: o1 = true; break;
+    case CFDH_KVOP_MULTIDOT: case CFDH_KVOP_MULTIDOT32: case CFDH_KVOP_GRAM: nA = true; break;
+    case CFDH_KVOP_MULTIAXPY: case CFDH_KVOP_LINCOMB: case CFDH_KVOP_GS_UPDATE_NORMALIZE: nA = nc = o1 = true; break;
+    case CFDH_KVOP_LINCOMB_KEEP: nA = nc = o1 = o2 = true; break;
+    case CFDH_KVOP_GS_UPDATE32: nA = nc = o1 = o32 = true; break;
+    case CFDH_KVOP_STORE32: o32 = true; break;
+    case CFDH_KVOP_GUESS: nA = nB = nc = o1 = o2 = true; break;
+    case CFDH_KVOP_AXPY: case CFDH_KVOP_WAXPY: case CFDH_KVOP_PMULT: ny = o1 = true; break;
+  }
+  if ((nA && !A) || (nB && !B) || (nx && !x) || (ny && !y) || (nc && !coef) || (o1 && !out1) || (o2 && !out2) || (o32 && !out32) ||
+      !nscal || !scal_host || !scal_dev || !scal_mirror)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: op %d misses an array", op);
+  const bool to_ring = (flags & 2) != 0;
+  const bool mirrored = op == CFDH_KVOP_MULTIDOT || op == CFDH_KVOP_MULTIDOT32 || op == CFDH_KVOP_GS_UPDATE32;
+  CHK(ensure_krylov(c));
+  if ((size_t)(nvec + 2) * 1024 > c->red_partial.n) HIPCHK(c, c->red_partial.alloc((size_t)(nvec + 2) * 1024 + 1024));
+  if (mirrored && (size_t)nvec + 2 > (to_ring ? c->h_ring_stride : (size_t)(1024 - CFDH_MIRROR_OFF)))
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: nvec = %d does not fit the host-mapped words", nvec);
+
+  const size_t N = (size_t)n, LD = (size_t)ld, blk = LD * (size_t)nvec;
+  HookBuf<double> dA, dB, dx, dy, dc, d1, d2, ds;
+  HookBuf<float> dA32, d32;
+  if (nA && !f32) { if (op == CFDH_KVOP_NORM2_TRIPLE) CHK(dA.put(c, A, LD, N)); else CHK(dA.put(c, A, blk, blk)); }
+  std::vector<float> a32;
+  if (nA && f32) {  // the fp32 copy of the basis, as v_store32 rounds it
+    a32.resize(blk);
+    for (size_t i = 0; i < blk; i++) a32[i] = (float)A[i];
+    CHK(dA32.put(c, a32.data(), blk, blk));
+  }
+  if (nB) CHK(dB.put(c, B, blk, blk));
+  if (nx) CHK(dx.put(c, x, LD, N));
+  if (ny) CHK(dy.put(c, y, LD, N));
+  const int ncoef = op == CFDH_KVOP_GS_UPDATE_NORMALIZE ? nvec + 1 : (op == CFDH_KVOP_GUESS ? 8 * (nvec + 1) : nvec);
+  if (nc) CHK(dc.put(c, coef, (size_t)ncoef, (size_t)ncoef));
+  if (o1) CHK(d1.put(c, nullptr, LD, 0));
+  if (o2) CHK(d2.put(c, nullptr, LD, 0));
+  if (o32) CHK(d32.put(c, nullptr, LD, 0));
+  CHK(ds.put(c, nullptr, (size_t)std::max(nvec + 2, 8 * 9), 0));  // device scalars: h, the Gram slots, a norm
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // the host-mapped words the op may write start from a pattern no result has
+  double *mir_host = to_ring && mirrored ? c->h_ring + (size_t)((nvec - 1) % cfdh_ctx::KRING) * c->h_ring_stride : c->h_pinned + CFDH_MIRROR_OFF;
+  double *mir_dev = to_ring && mirrored ? c->h_ring_dev + (size_t)((nvec - 1) % cfdh_ctx::KRING) * c->h_ring_stride : c->h_pinned_dev + CFDH_MIRROR_OFF;
+  const int nmir_max = mirrored ? nvec + 2 : 16;
+  for (int i = 0; i < nmir_max; i++) mir_host[i] = -7.25;
+  int ns = 0, nd = 0, nm = 0;  // scalars returned by the wrapper / left on the device / in the host-mapped words
+  const double *dev_src = ds.p;
+  switch (op) {
+    case CFDH_KVOP_DOT: CHK(v_dot(c, n, dx.p, dy.p, scal_host)); ns = nd = nm = 1; dev_src = c->red_out.p; break;
+    case CFDH_KVOP_NORM2: CHK(v_norm2(c, n, dx.p, scal_host)); ns = nd = nm = 1; dev_src = c->red_out.p; break;
+    case CFDH_KVOP_NORM2_PAIR: CHK(v_norm2_pair(c, n, dx.p, dy.p, scal_host, scal_host + 1)); ns = nd = nm = 2; dev_src = c->red_out.p; break;
+    case CFDH_KVOP_NORM2_TRIPLE: CHK(v_norm2_triple(c, n, dx.p, dy.p, dA.p, scal_host)); ns = nd = nm = 3; dev_src = c->red_out.p; break;
+    case CFDH_KVOP_NORMINF_DIFF: CHK(v_norminf_diff(c, n, dx.p, ny ? dy.p : nullptr, scal_host)); ns = nd = nm = 1; dev_src = c->red_out.p; break;
+    case CFDH_KVOP_SUB_MEAN:
+      HIPCHK(c, hipMemcpyAsync(d1.p, dx.p, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+      CHK(v_sub_mean(c, n, d1.p)); nd = 1; dev_src = c->red_out.p + 8; break;
+    case CFDH_KVOP_NORM_SCALE_INV:
+      CHK(v_norm_to_dev(c, n, dx.p, ds.p));
+      CHK(v_scale_inv_dev(c, n, dx.p, ds.p, d1.p)); nd = 1; break;
+    case CFDH_KVOP_MULTIDOT: {
+      const bool ww = (flags & 1) != 0;
+      CHK(v_multidot(c, n, dA.p, ld, nvec, dx.p, ds.p, ww, mir_dev)); nd = nm = nvec + (ww ? 1 : 0); break;
+    }
+    case CFDH_KVOP_MULTIDOT32: CHK(v_multidot32(c, n, dA32.p, ld, nvec, dx.p, ds.p, mir_dev)); nd = nm = nvec + 1; break;
+    case CFDH_KVOP_GRAM: CHK(v_gram(c, n, dA.p, ld, nvec, dx.p, ds.p)); nd = 8 * (nvec + 1); break;
+    case CFDH_KVOP_MULTIAXPY:
+      HIPCHK(c, hipMemcpyAsync(d1.p, dx.p, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+      CHK(v_multiaxpy(c, n, dA.p, ld, nvec, dc.p, d1.p)); break;
+    case CFDH_KVOP_LINCOMB:
+      HIPCHK(c, hipMemcpyAsync(d1.p, dx.p, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+      CHK(v_lincomb(c, n, dA.p, ld, nvec, dc.p, d1.p)); break;
+    case CFDH_KVOP_LINCOMB_KEEP:
+      HIPCHK(c, hipMemcpyAsync(d1.p, dx.p, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+      CHK(v_lincomb_keep(c, n, dA.p, ld, nvec, dc.p, d1.p, d2.p)); break;
+    case CFDH_KVOP_GS_UPDATE_NORMALIZE: CHK(v_gs_update_normalize(c, n, dA.p, ld, nvec, dc.p, dx.p, d1.p, ds.p)); nd = 1; break;
+    case CFDH_KVOP_GS_UPDATE32:
+      // the slot layout of an iteration: [h_0 .. h_j, w.w, measured norm]; the norm is the only word written here
+      CHK(v_gs_update32(c, n, dA32.p, ld, nvec, dc.p, dx.p, d1.p, d32.p, ds.p, mir_dev + (nvec + 1))); nd = 1; nm = nvec + 2; break;
+    case CFDH_KVOP_STORE32: CHK(v_store32(c, n, dx.p, d32.p)); break;
+    case CFDH_KVOP_GUESS: {
+      CHK(v_guess_combine(c, n, dA.p, dB.p, ld, nvec, dc.p, dx.p, d1.p, d2.p));
+      bool used = false; int rank = 0;
+      CHK(v_guess_read(c, nvec, scal_host, &used, &rank, scal_host + 3));
+      scal_host[1] = used ? 1.0 : 0.0; scal_host[2] = (double)rank;
+      if (flags & 1) CHK(v_scale_inv_lean(c, n, d2.p));
+      ns = nm = 3 + nvec;
+      // device side: the squared norm, then y as guess_combine_kernel read it
+      HIPCHK(c, hipMemcpyAsync(ds.p, c->red_out.p + CFDH_LEAN_S2, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(ds.p + 1, c->ky.p, sizeof(double) * nvec, hipMemcpyDeviceToDevice, c->stream));
+      nd = 1 + nvec; break;
+    }
+    case CFDH_KVOP_AXPY:
+      HIPCHK(c, hipMemcpyAsync(d1.p, dy.p, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+      CHK(v_axpy(c, n, scalar, dx.p, d1.p)); break;
+    case CFDH_KVOP_WAXPY: CHK(v_waxpy(c, n, scalar, dx.p, dy.p, d1.p)); break;
+    case CFDH_KVOP_SCALE:
+      HIPCHK(c, hipMemcpyAsync(d1.p, dx.p, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
+      CHK(v_scale(c, n, scalar, d1.p)); break;
+    case CFDH_KVOP_SCALE_TO: CHK(v_scale_to(c, n, scalar, dx.p, d1.p)); break;
+    case CFDH_KVOP_PMULT: CHK(v_pointwise_mult(c, n, dx.p, dy.p, d1.p)); break;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->mirror_src = nullptr;  // no later read-back may take the words of this call for its own
+  if (nd) HIPCHK(c, hipMemcpy(scal_dev, dev_src, sizeof(double) * nd, hipMemcpyDeviceToHost));
+  for (int i = 0; i < nm; i++) scal_mirror[i] = mir_host[i];
+  nscal[0] = ns; nscal[1] = nd; nscal[2] = nm;
+  if (o1) CHK(d1.get(c, out1, N));
+  if (o2) CHK(d2.get(c, out2, N));
+  if (o32) CHK(d32.get(c, out32, N));
   return 0;
 }
 

@@ -541,6 +541,8 @@ void prof_flush(cfdh_ctx *c);
 
 int k_upload_quadrature(cfdh_ctx *c);
 int k_halo_pack(cfdh_ctx *c, const double *vec);
+#define CFDH_MIRROR_OFF 300  // h_pinned word where the host-mapped copies of reduced scalars start
+#define CFDH_LEAN_S2 12      // red_out word that holds the squared residual norm of the lean prologue / epilogue
 int v_pointwise_mult(cfdh_ctx *c, int n, const double *a, const double *b, double *out);
 int k_moments(cfdh_ctx *c);
 int k_assemble(cfdh_ctx *c, const double *xstate, int mode);  // mode 0: F only, 1: F+J, 2: F with lifting (no J write)
@@ -615,6 +617,7 @@ int comm_finalize(cfdh_ctx *c);
 // ---- solver (cfdh_solver.cpp) ------------------------------------------------------
 int cfdh_pc_update(cfdh_ctx *c, bool force_refresh);
 int cfdh_pc_apply(cfdh_ctx *c, const double *r, double *z);
+int ensure_krylov(cfdh_ctx *c);  // Krylov workspace (kV, kZ, kw, kh, ky, the read-back ring) for the current ksp_restart
 int cfdh_apply_operator_dev(cfdh_ctx *c, const double *r, double *z);  // z = P^-1 r, kw = J z: the pair of one FGMRES iteration
 int cfdh_host_threads();  // cfdh_setup.cpp: thread count of the host loops (CFDH_HOST_THREADS, default 8)
 int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its, int *reason, double bnorm = -1.0);

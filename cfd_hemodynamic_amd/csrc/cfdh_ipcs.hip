@@ -403,11 +403,11 @@ __global__ __launch_bounds__(TPB) void ip_quad_kernel(int n, const int *__restri
   d0 = block_sum(d0, sh);
   if (threadIdx.x == 0) P[blockIdx.x] = d0;
 }
-// P0 = max |x - y| (y may be null)
+// P0 = max |x - y| (y may be null; NaN when an entry is NaN)
 __global__ __launch_bounds__(TPB) void ip_maxdiff_kernel(int n, const double *__restrict__ x, const double *__restrict__ y, double *__restrict__ P) {
   __shared__ double sh[4];
   double a = 0.0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) a = fmax(a, fabs(y ? x[i] - y[i] : x[i]));
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) a = max_nan(a, fabs(y ? x[i] - y[i] : x[i]));
   a = block_max(a, sh);
   if (threadIdx.x == 0) P[blockIdx.x] = a;
 }
@@ -1074,7 +1074,10 @@ static int ip_reduce_host(cfdh_ctx *c, int nb, bool is_max, double *out) {
   HIPCHK(c, hipMemcpyAsync(h.data(), I->P.p, sizeof(double) * nb, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   double a = 0.0;
-  for (int i = 0; i < nb; i++) a = is_max ? std::max(a, h[i]) : a + h[i];
+  for (int i = 0; i < nb; i++) {
+    if (!is_max) a += h[i];
+    else if (h[i] > a || h[i] != h[i]) a = h[i];  // a NaN partial stays (std::max would drop it)
+  }
   *out = a;
   return 0;
 }

@@ -1919,7 +1919,7 @@ int v_scale(cfdh_ctx *c, int n, double a, double *x) {
 }
 
 // ---- reductions: per-block partials (fixed order) -> one final block; deterministic
-// OP 0: sum x*y, 1: max |x - y| (y may be null)
+// OP 0: sum x*y, 1: max |x - y| (y may be null; NaN when an entry is NaN)
 template <int OP>
 __global__ __launch_bounds__(TPB) void reduce_partial_kernel(int n, const double *__restrict__ x, const double *__restrict__ y,
                                                              double *__restrict__ partial) {
@@ -1927,7 +1927,7 @@ __global__ __launch_bounds__(TPB) void reduce_partial_kernel(int n, const double
   double a = 0;
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
     if (OP == 0) a += x[i] * y[i];
-    else a = fmax(a, fabs(y ? x[i] - y[i] : x[i]));
+    else a = max_nan(a, fabs(y ? x[i] - y[i] : x[i]));
   }
   a = (OP == 0) ? block_sum(a, sh) : block_max(a, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = a;
@@ -1939,7 +1939,7 @@ __global__ __launch_bounds__(TPB) void reduce_final_kernel(int nblk, int stride,
   __shared__ double sh[4];
   const double *pp = partial + (size_t)blockIdx.x * stride;
   double a = 0;
-  for (int i = threadIdx.x; i < nblk; i += TPB) a = (OP == 1) ? fmax(a, pp[i]) : a + pp[i];
+  for (int i = threadIdx.x; i < nblk; i += TPB) a = (OP == 1) ? max_nan(a, pp[i]) : a + pp[i];
   a = (OP == 1) ? block_max(a, sh) : block_sum(a, sh);
   if (threadIdx.x == 0) {
     const double v = (OP == 2) ? sqrt(a) : a;
@@ -1950,7 +1950,6 @@ __global__ __launch_bounds__(TPB) void reduce_final_kernel(int nblk, int stride,
 
 // Single rank: the final reduction kernel also stores its results into host-mapped memory (h_pinned + 300),
 // so reading them back costs a stream synchronisation instead of a copy kernel (~11 us each).
-#define CFDH_MIRROR_OFF 300
 static double *scalar_mirror(cfdh_ctx *c, const double *out_dev, int cnt) {
   if (c->nranks > 1 || cnt > 64) { c->mirror_src = nullptr; return nullptr; }
   c->mirror_src = out_dev; c->mirror_cnt = cnt;
@@ -2464,7 +2463,6 @@ static int lean_sync(cfdh_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
-#define CFDH_LEAN_S2 12  // red_out word that holds the squared residual norm of the lean prologue / epilogue
 // Prologue of a solve with k kept vectors, hd = Gram system from v_gram: y on the device (ky), x = U y, r = b - W y, |r|^2 and the
 // "used" flag in the host-mapped words.  Nothing is read back here.
 int v_guess_combine(cfdh_ctx *c, int n, const double *U, const double *W, int ld, int k, const double *hd, const double *b, double *x, double *r) {

@@ -851,13 +851,12 @@ static int pc_then_product(cfdh_ctx *c, const double *r, double *z, double *w) {
 // leading dimension of the Krylov and guess vectors: even, so that every V_j / Z_j / U_j stays 16-B aligned
 static size_t krylov_ld(const cfdh_ctx *c) { return ((size_t)c->NL + 1) & ~(size_t)1; }
 
-static int ensure_krylov(cfdh_ctx *c);
 int cfdh_apply_operator_dev(cfdh_ctx *c, const double *r, double *z) {
   CHK(ensure_krylov(c));
   return pc_then_product(c, r, z, c->kw.p);
 }
 
-static int ensure_krylov(cfdh_ctx *c) {
+int ensure_krylov(cfdh_ctx *c) {
   const int m = c->opt.ksp_restart;
   if (c->kry_m == m && c->kV.p) return 0;
   const size_t NL = krylov_ld(c);

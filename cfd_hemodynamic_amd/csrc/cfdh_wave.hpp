@@ -35,12 +35,15 @@ __device__ __forceinline__ double wave_sum(double v) {
   v += dpp_shuffle<0x140>(v);  // row_mirror -> sums of 16
   return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
 }
+// maximum that keeps a NaN: fmax returns the other operand, which turned the inf-norm of a NaN field into 0.  For two numbers
+// the result is fmax's, bit for bit.
+__device__ __forceinline__ double max_nan(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
 __device__ __forceinline__ double wave_max(double v) {
-  v = fmax(v, dpp_shuffle<0xB1>(v));
-  v = fmax(v, dpp_shuffle<0x4E>(v));
-  v = fmax(v, dpp_shuffle<0x141>(v));
-  v = fmax(v, dpp_shuffle<0x140>(v));
-  return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)), fmax(readlane_d(v, 32), readlane_d(v, 48)));
+  v = max_nan(v, dpp_shuffle<0xB1>(v));
+  v = max_nan(v, dpp_shuffle<0x4E>(v));
+  v = max_nan(v, dpp_shuffle<0x141>(v));
+  v = max_nan(v, dpp_shuffle<0x140>(v));
+  return max_nan(max_nan(readlane_d(v, 0), readlane_d(v, 16)), max_nan(readlane_d(v, 32), readlane_d(v, 48)));
 }
 // block (256 threads) sum; result valid in thread 0
 __device__ __forceinline__ double block_sum(double v, double *sh /*[4]*/) {
@@ -57,7 +60,7 @@ __device__ __forceinline__ double block_max(double v, double *sh) {
   int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) sh[w] = v;
   __syncthreads();
-  double r = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+  double r = max_nan(max_nan(sh[0], sh[1]), max_nan(sh[2], sh[3]));
   __syncthreads();
   return r;
 }

@@ -331,6 +331,46 @@ int cfdh_get_amg_operator(cfdh_ctx *ctx, int hier, int level, int which, int64_t
  * numbering.  Error codes as above. */
 int cfdh_get_amg_vectors(cfdh_ctx *ctx, int hier, int level, int which, int64_t *n, double *out);
 
+/* ---- one Krylov vector kernel at a time (tests) ---------------------------------------------------------------------------
+ * The small vector kernels of the linear solve (dot products, Gram-Schmidt updates, the fp32 basis copy, the prologue of the
+ * projected guess, axpy-style updates) behind the wrapper the solver itself calls, on the context's stream. */
+#define CFDH_KVOP_DOT 0                  /* host[0] = x . y */
+#define CFDH_KVOP_NORM2 1                /* host[0] = |x| */
+#define CFDH_KVOP_NORM2_PAIR 2           /* host = |x|, |y|; dev / mirror hold the squares */
+#define CFDH_KVOP_NORM2_TRIPLE 3         /* host = |x|, |y|, |A_0| */
+#define CFDH_KVOP_NORMINF_DIFF 4         /* host[0] = max |x - y| (flags 1) or max |x| */
+#define CFDH_KVOP_SUB_MEAN 5             /* out1 = x - mean(x); dev[0] = sum(x) */
+#define CFDH_KVOP_NORM_SCALE_INV 6       /* dev[0] = |x| left on the device, out1 = x / dev[0] (zeros for a zero norm) */
+#define CFDH_KVOP_MULTIDOT 7             /* dev[v] = A_v . x for v < nvec, dev[nvec] = x . x with flags 1; mirrored */
+#define CFDH_KVOP_MULTIDOT32 8           /* the same against the fp32 copy of A, x . x always; mirrored */
+#define CFDH_KVOP_GRAM 9                 /* dev[8 i + q] = A_q . A_i (i < nvec), dev[8 nvec + q] = A_q . x; nvec = k in 1 .. 8 */
+#define CFDH_KVOP_MULTIAXPY 10           /* out1 = x - sum coef_v A_v */
+#define CFDH_KVOP_LINCOMB 11             /* out1 = x + sum coef_v A_v */
+#define CFDH_KVOP_LINCOMB_KEEP 12        /* the same, stored in out1 and out2 */
+#define CFDH_KVOP_GS_UPDATE_NORMALIZE 13 /* out1 = (x - sum coef_v A_v) / s, dev[0] = s from coef[nvec] = x . x and |coef|^2 */
+#define CFDH_KVOP_GS_UPDATE32 14         /* the same against the fp32 copy with the measured norm: out1, out32, dev[0] = mirror[nvec + 1] = s */
+#define CFDH_KVOP_STORE32 15             /* out32 = (float)x */
+#define CFDH_KVOP_GUESS 16               /* coef = Gram slots of nvec = k kept vectors: out1 = A y, out2 = x - B y (flags 1: divided by
+                                            its norm on the device); host = |out2|, used, rank, y; dev = |out2|^2, y; mirror = |out2|^2, used, rank, y */
+#define CFDH_KVOP_AXPY 17                /* out1 = y + scalar x */
+#define CFDH_KVOP_WAXPY 18               /* the same through the three-vector kernel */
+#define CFDH_KVOP_SCALE 19               /* out1 = scalar x, in place */
+#define CFDH_KVOP_SCALE_TO 20            /* out1 = scalar x */
+#define CFDH_KVOP_PMULT 21               /* out1 = x y entry by entry */
+#define CFDH_KVOP_COUNT 22
+/* Runs ONE op: A and B are column-major blocks [ld * nvec], x and y vectors [n], coef the op's coefficients; every array the op does
+ * not use may be NULL.  Each array gets a device allocation of its own for the call (ld entries per column, zero behind n), the
+ * wrapper runs on the solver's stream exactly as the solver calls it, and the results come back: out1 / out2 [n], out32 [n],
+ * scal_host (what the wrapper returned to its caller), scal_dev (the scalars it left on the device) and scal_mirror (the
+ * host-mapped words the host reads instead of a copy: behind the context's scalar mirror, or with flags 2 in a slot of the FGMRES
+ * read-back ring), with their counts in nscal[3].  The three scalar arrays hold max(nvec + 2, 72) entries.  Nothing of the call
+ * stays in the context, and no solver state changes.  Arguments the solver never produces are refused with CFDH_E_ARG before
+ * anything is launched: n < 1, nvec < 1, ld < n, an odd ld, an ld that is no multiple of 4 for the fp32 ops, nvec above 8 for
+ * CFDH_KVOP_GRAM and CFDH_KVOP_GUESS.  One GPU only (CFDH_E_STATE on a partitioned or pressure-correction context).  Exposed for tests. */
+int cfdh_krylov_vec_op(cfdh_ctx *ctx, int op, int n, int ld, int nvec, const double *A, const double *B, const double *x, const double *y,
+                       const double *coef, double scalar, int flags, double *out1, double *out2, float *out32, int32_t *nscal,
+                       double *scal_host, double *scal_dev, double *scal_mirror);
+
 /* ---- incremental pressure correction on P2/P1 Taylor-Hood elements (the `ipcs_bdf2` solver) -------------------------- */
 
 /* The second solver family of the reference (/root/reference/src/solvers/ipcs_bdf2.py:66-91,127-172): P2 velocity / P1 pressure,
