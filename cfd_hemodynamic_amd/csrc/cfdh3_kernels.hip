@@ -17,6 +17,7 @@
 
 #include "cfdh_internal.hpp"
 #include "cfdh_quad_tet.h"
+#include "cfdh_wave.hpp"
 
 #define TPB 256
 
@@ -29,13 +30,6 @@ int k3_upload_quadrature(cfdh_ctx *c) {
   return 0;
 }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp3(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
 // quad-local permutation (every source lane lies in the reader's own quad, so no lane ever reads an undefined value and
 // the destination needs no initialisation: one v_mov_b32_dpp per half instead of v_mov + v_mov_b32_dpp)
 template <int CTRL>
@@ -44,27 +38,6 @@ __device__ __forceinline__ double dppq(double v) {
   lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
   hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double g8sum(double v) {
-  v += dpp3<0xB1>(v);
-  v += dpp3<0x4E>(v);
-  v += dpp3<0x141>(v);
-  return v;
-}
-__device__ __forceinline__ double wsum3(double v) {
-  v = g8sum(v);
-  v += dpp3<0x140>(v);
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-__device__ __forceinline__ double bsum3(double v, double *sh) {
-  v = wsum3(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  __syncthreads();
-  return r;
 }
 
 // gradients of the barycentrics, volume, greatest vertex distance of a positively oriented tetrahedron
@@ -548,7 +521,7 @@ __global__ __launch_bounds__(TPB) void spmv3_full_kernel(int nv, const int *__re
       a3 += c10[0] * x0 + c10[1] * x1 + c10[2] * x2 + A11[k] * xp;
     }
   }
-  a0 = g8sum(a0); a1 = g8sum(a1); a2 = g8sum(a2); a3 = g8sum(a3);
+  a0 = group8_sum(a0); a1 = group8_sum(a1); a2 = group8_sum(a2); a3 = group8_sum(a3);
   if (row < nv && l == 0) {
     y[3 * (size_t)row] = a0; y[3 * (size_t)row + 1] = a1; y[3 * (size_t)row + 2] = a2;
     y[3 * (size_t)nv + row] = a3;
@@ -587,7 +560,7 @@ __global__ __launch_bounds__(TPB) void spmv3_full_multi_kernel(int nv, const int
   }
 #pragma unroll
   for (int v = 0; v < NV; v++) {
-    const double s0 = g8sum(a[v][0]), s1 = g8sum(a[v][1]), s2 = g8sum(a[v][2]), s3 = g8sum(a[v][3]);
+    const double s0 = group8_sum(a[v][0]), s1 = group8_sum(a[v][1]), s2 = group8_sum(a[v][2]), s3 = group8_sum(a[v][3]);
     if (row < nv && l == 0) {
       double *y = Y + (size_t)v * ld;
       y[3 * (size_t)row] = s0; y[3 * (size_t)row + 1] = s1; y[3 * (size_t)row + 2] = s2;
@@ -641,8 +614,8 @@ __global__ __launch_bounds__(TPB) void spmv3_blk_kernel(int nv, const int *__res
       }
     }
   }
-  a0 = g8sum(a0);
-  if (BLK == 2) { a1 = g8sum(a1); a2 = g8sum(a2); }
+  a0 = group8_sum(a0);
+  if (BLK == 2) { a1 = group8_sum(a1); a2 = group8_sum(a2); }
   if (row < nv && l == 0) {
     if (BLK == 2) {
       const size_t o = 3 * (size_t)row;
@@ -684,9 +657,9 @@ __global__ __launch_bounds__(TPB) void spmv3_a01_resid_kernel(int nv, const int 
       a0 += cc[0] * xp; a1 += cc[1] * xp; a2 += cc[2] * xp;
     }
   }
-  a0 += dpp3<0xB1>(a0); a0 += dpp3<0x4E>(a0);
-  a1 += dpp3<0xB1>(a1); a1 += dpp3<0x4E>(a1);
-  a2 += dpp3<0xB1>(a2); a2 += dpp3<0x4E>(a2);
+  a0 += dpp_shuffle<0xB1>(a0); a0 += dpp_shuffle<0x4E>(a0);
+  a1 += dpp_shuffle<0xB1>(a1); a1 += dpp_shuffle<0x4E>(a1);
+  a2 += dpp_shuffle<0xB1>(a2); a2 += dpp_shuffle<0x4E>(a2);
   if (row < nv && l == 0) {
     const size_t o = 3 * (size_t)row;
     y[o] = bvec[o] - a0; y[o + 1] = bvec[o + 1] - a1; y[o + 2] = bvec[o + 2] - a2;
@@ -726,34 +699,12 @@ __global__ __launch_bounds__(TPB) void nulltest3_kernel(int nv, const int *__res
     a += s0 * s0 + s1 * s1 + s2 * s2 + s3 * s3;
     b += t0 * t0 + t1 * t1 + t2 * t2 + t3 * t3;
   }
-  a = bsum3(a, sh);
-  b = bsum3(b, sh);
+  a = block_sum(a, sh);
+  b = block_sum(b, sh);
   if (threadIdx.x == 0) { partial[blockIdx.x] = a; partial[gridDim.x + blockIdx.x] = b; }
 }
-__global__ __launch_bounds__(TPB) void final3_kernel(int nb, int stride, const double *__restrict__ partial, double *__restrict__ out) {
-  __shared__ double sh[4];
-  double a = 0;
-  for (int i = threadIdx.x; i < nb; i += TPB) a += partial[(size_t)blockIdx.x * stride + i];
-  a = bsum3(a, sh);
-  if (threadIdx.x == 0) out[blockIdx.x] = a;
-}
-static int read2(cfdh_ctx *c, double *v, int n) {
-  if (c->nranks > 1) CHK(comm_allreduce_dev(c, c->red_out.p, n, 0));  // sums over the parts of a partitioned mesh
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->red_out.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < n; i++) v[i] = c->h_pinned[i];
-  return 0;
-}
-int k3_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm) {
-  const int nb = 256;
-  c->mirror_src = nullptr;
+int k3_nullspace_partials(cfdh_ctx *c, int nb) {
   hipLaunchKernelGGL(nulltest3_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->A01.p, c->A11.p, c->red_partial.p);
-  hipLaunchKernelGGL(final3_kernel, dim3(2), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p);
-  HIPCHK(c, hipGetLastError());
-  double s[2];
-  CHK(read2(c, s, 2));
-  *nrm = sqrt(s[0]);
-  *absnrm = sqrt(s[1]);
   return 0;
 }
 
@@ -781,8 +732,8 @@ __global__ __launch_bounds__(TPB) void l2_3_kernel(int nc, int nv, const int *__
     au += vol * su * (1.0 / 20.0);
     ap += vol * sp * (1.0 / 20.0);
   }
-  au = bsum3(au, sh);
-  ap = bsum3(ap, sh);
+  au = block_sum(au, sh);
+  ap = block_sum(ap, sh);
   if (threadIdx.x == 0) { partial[blockIdx.x] = au; partial[gridDim.x + blockIdx.x] = ap; }
 }
 __global__ __launch_bounds__(TPB) void flux3_kernel(int nfac, int marker, int nv, const int *__restrict__ fcell, const int *__restrict__ flocal,
@@ -804,47 +755,20 @@ __global__ __launch_bounds__(TPB) void flux3_kernel(int nfac, int marker, int nv
     for (int a = 0; a < 4; a++) if (a != fl) for (int i = 0; i < 3; i++) um[i] += x[uo3(vs[a], nv) + i] * (1.0 / 3.0);
     q += -3.0 * vol * (g[fl][0] * um[0] + g[fl][1] * um[1] + g[fl][2] * um[2]);
   }
-  q = bsum3(q, sh);
+  q = block_sum(q, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = q;
 }
-int k3_functional(cfdh_ctx *c, int kind, int marker, double *out) {
-  const int nb = 256;
-  c->mirror_src = nullptr;
-  if (c->gen && (kind == 2 || kind == 3 || kind == 7)) {  // hexahedra / P2 tetrahedra: the element's own quadrature (cfdh_gen3.hip)
-    CHK(kg3_functional_partials(c, kind, marker, nb));
-    hipLaunchKernelGGL(final3_kernel, dim3(2), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p);
-    HIPCHK(c, hipGetLastError());
-    double v[2];
-    CHK(read2(c, v, 2));
-    *out = kind == 7 ? v[0] : sqrt(kind == 2 ? v[0] : v[1]);
-    return 0;
-  }
-  if (kind == 2 || kind == 3) {
-    hipLaunchKernelGGL(l2_3_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nc, c->nvo, c->cells.p, c->cell_owned.p, c->coords.p, c->x.p, c->red_partial.p);
-    hipLaunchKernelGGL(final3_kernel, dim3(2), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p);
-    HIPCHK(c, hipGetLastError());
-    double v[2];
-    CHK(read2(c, v, 2));
-    *out = sqrt(kind == 2 ? v[0] : v[1]);
-    return 0;
-  }
-  if (kind == 7) {
+// kind 2, 3: the rows [u.u, p^2] of nb partial sums; kind 7: one row
+int k3_functional_partials(cfdh_ctx *c, int kind, int marker, int nb) {
+  if (kind == 7)
     hipLaunchKernelGGL(flux3_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nfac, marker, c->nvo, c->d_fac_cell.p, c->d_fac_local.p,
                        c->d_fac_marker.p, c->cells.p, c->cell_owned.p, c->coords.p, c->x.p, c->red_partial.p);
-    hipLaunchKernelGGL(final3_kernel, dim3(1), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p);
-    HIPCHK(c, hipGetLastError());
-    return read2(c, out, 1);
-  }
-  if (kind >= 4 && kind <= 6) {
-    const int nu = 3 * c->nvo;
-    const double *a = kind == 5 ? c->xprev.p : c->x.p;
-    const double *b = kind == 6 ? c->xprev.p : nullptr;
-    return v_norminf_diff(c, nu, a, b, out);
-  }
-  return cfdh_fail(c, CFDH_E_ARG, "functional kind %d is not available for tetrahedra (2, 3: L2 norms; 4-6: inf-norms; 7: flux)", kind);
+  else
+    hipLaunchKernelGGL(l2_3_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nc, c->nvo, c->cells.p, c->cell_owned.p, c->coords.p, c->x.p, c->red_partial.p);
+  return 0;
 }
 
-// wall shear stress (solverBase.py:163-195) on triangles: (1/|f|) oint l_a Tt ds = Tt / 3 for the three facet vertices
+// wall shear stress (solverBase.py:163-195) on tetrahedra: (1/|f|) oint l_a Tt ds = Tt / 3 for the three facet vertices
 __global__ __launch_bounds__(TPB) void wss3_kernel(int nfac, int nv, const int *__restrict__ fcell, const int *__restrict__ flocal,
                                                    const int *__restrict__ cells, const double *__restrict__ coords,
                                                    const double *__restrict__ x, double mu, double *__restrict__ out) {

@@ -906,7 +906,7 @@ struct Builder {
     dbuf<double> v, w;
     HIPCHK(c, v.alloc(n)); HIPCHK(c, w.alloc(n));
     hipLaunchKernelGGL(lcg_vector_kernel, gr, bl, 0, s, n, v.p);
-    double *nrm = c->red_out.p + 30;
+    double *nrm = c->red_out.p + RO_AMG_NORM;
     for (int it = 0; it < 15; it++) {
       hipLaunchKernelGGL(spmv_dinv_kernel, gr8, bl, 0, s, n, A.rowptr.p, A.col.p, A.val.p, L.dinv.p, v.p, w.p);
       CHK(v_norm_to_dev_local(c, n, w.p, nrm));  // rank-local operator: no reduction over the ranks
@@ -1395,10 +1395,7 @@ int cfdh_proxy_ras_dev(cfdh_ctx *c, CsrDev &out) {
     int ml = 0;
     for (int i = 0; i < nvo; i++) ml = std::max(ml, c->h_vptr[i + 1] - c->h_vptr[i]);
     double mld = (double)ml;
-    HIPCHK(c, hipMemcpyAsync(c->red_out.p + 20, &mld, sizeof(double), hipMemcpyHostToDevice, s));
-    CHK(comm_allreduce_dev(c, c->red_out.p + 20, 1, 1));
-    HIPCHK(c, hipMemcpyAsync(&mld, c->red_out.p + 20, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    CHK(comm_allreduce_host(c, &mld, 1));
     R.maxlen = (int)mld;
     HIPCHK(c, R.gval.alloc((size_t)ng * R.maxlen + 1));
     dbuf<int> gid;

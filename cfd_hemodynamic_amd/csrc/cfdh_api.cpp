@@ -208,7 +208,7 @@ int cfdh_set_params(cfdh_ctx *c, double dt, double rho, double mu, double mu_fac
 
 int cfdh_set_options(cfdh_ctx *c, const cfdh_options *o) {
   if (!c || !o) return CFDH_E_ARG;
-  if (o->ksp_restart < 1 || o->ksp_restart > 1000 || o->cheb_degree < 1 || o->cc_smooth_degree < 1 || !(o->cheb_ratio > 1) || o->amg_smooth_degree < 1 ||
+  if (o->ksp_restart < 1 || o->ksp_restart > CFDH_KSP_RESTART_MAX || o->cheb_degree < 1 || o->cc_smooth_degree < 1 || !(o->cheb_ratio > 1) || o->amg_smooth_degree < 1 ||
       !(o->amg_smooth_ratio > 1) || o->amg_max_coarse < 8 || o->amg_max_coarse > 4000 || o->ksp_guess < 0 || o->ksp_guess > 8)
     return cfdh_fail(c, CFDH_E_ARG, "option out of range");
   const bool pc_changed = o->amg_theta != c->opt.amg_theta || o->amg_max_coarse != c->opt.amg_max_coarse ||
@@ -732,7 +732,7 @@ int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const doubl
   const bool mirrored = op == CFDH_KVOP_MULTIDOT || op == CFDH_KVOP_MULTIDOT32 || op == CFDH_KVOP_GS_UPDATE32;
   CHK(ensure_krylov(c));
   if ((size_t)(nvec + 2) * 1024 > c->red_partial.n) HIPCHK(c, c->red_partial.alloc((size_t)(nvec + 2) * 1024 + 1024));
-  if (mirrored && (size_t)nvec + 2 > (to_ring ? c->h_ring_stride : (size_t)(1024 - CFDH_MIRROR_OFF)))
+  if (mirrored && (size_t)nvec + 2 > (to_ring ? c->h_ring_stride : (size_t)HP_MIRROR_N))
     return cfdh_fail(c, CFDH_E_ARG, "cfdh_krylov_vec_op: nvec = %d does not fit the host-mapped words", nvec);
 
   const size_t N = (size_t)n, LD = (size_t)ld, blk = LD * (size_t)nvec;
@@ -756,8 +756,8 @@ int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const doubl
   CHK(ds.put(c, nullptr, (size_t)std::max(nvec + 2, 8 * 9), 0));  // device scalars: h, the Gram slots, a norm
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // the host-mapped words the op may write start from a pattern no result has
-  double *mir_host = to_ring && mirrored ? c->h_ring + (size_t)((nvec - 1) % cfdh_ctx::KRING) * c->h_ring_stride : c->h_pinned + CFDH_MIRROR_OFF;
-  double *mir_dev = to_ring && mirrored ? c->h_ring_dev + (size_t)((nvec - 1) % cfdh_ctx::KRING) * c->h_ring_stride : c->h_pinned_dev + CFDH_MIRROR_OFF;
+  double *mir_host = to_ring && mirrored ? c->h_ring + (size_t)((nvec - 1) % cfdh_ctx::KRING) * c->h_ring_stride : c->h_pinned + HP_MIRROR;
+  double *mir_dev = to_ring && mirrored ? c->h_ring_dev + (size_t)((nvec - 1) % cfdh_ctx::KRING) * c->h_ring_stride : scalars_mirror(c);
   const int nmir_max = mirrored ? nvec + 2 : 16;
   for (int i = 0; i < nmir_max; i++) mir_host[i] = -7.25;
   int ns = 0, nd = 0, nm = 0;  // scalars returned by the wrapper / left on the device / in the host-mapped words
@@ -770,7 +770,7 @@ int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const doubl
     case CFDH_KVOP_NORMINF_DIFF: CHK(v_norminf_diff(c, n, dx.p, ny ? dy.p : nullptr, scal_host)); ns = nd = nm = 1; dev_src = c->red_out.p; break;
     case CFDH_KVOP_SUB_MEAN:
       HIPCHK(c, hipMemcpyAsync(d1.p, dx.p, sizeof(double) * N, hipMemcpyDeviceToDevice, c->stream));
-      CHK(v_sub_mean(c, n, d1.p)); nd = 1; dev_src = c->red_out.p + 8; break;
+      CHK(v_sub_mean(c, n, d1.p)); nd = 1; dev_src = c->red_out.p + RO_MEAN; break;
     case CFDH_KVOP_NORM_SCALE_INV:
       CHK(v_norm_to_dev(c, n, dx.p, ds.p));
       CHK(v_scale_inv_dev(c, n, dx.p, ds.p, d1.p)); nd = 1; break;
@@ -802,7 +802,7 @@ int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const doubl
       if (flags & 1) CHK(v_scale_inv_lean(c, n, d2.p));
       ns = nm = 3 + nvec;
       // device side: the squared norm, then y as guess_combine_kernel read it
-      HIPCHK(c, hipMemcpyAsync(ds.p, c->red_out.p + CFDH_LEAN_S2, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(ds.p, c->red_out.p + RO_LEAN_S2, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
       HIPCHK(c, hipMemcpyAsync(ds.p + 1, c->ky.p, sizeof(double) * nvec, hipMemcpyDeviceToDevice, c->stream));
       nd = 1 + nvec; break;
     }
@@ -817,7 +817,6 @@ int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const doubl
     case CFDH_KVOP_PMULT: CHK(v_pointwise_mult(c, n, dx.p, dy.p, d1.p)); break;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->mirror_src = nullptr;  // no later read-back may take the words of this call for its own
   if (nd) HIPCHK(c, hipMemcpy(scal_dev, dev_src, sizeof(double) * nd, hipMemcpyDeviceToHost));
   for (int i = 0; i < nm; i++) scal_mirror[i] = mir_host[i];
   nscal[0] = ns; nscal[1] = nd; nscal[2] = nm;
@@ -1273,10 +1272,7 @@ int cfdh_set_global_pressure_space(cfdh_ctx *c, int64_t nvg, int64_t ncg, const 
       bool ok = true;
       for (int g = 0; g < n && ok; g++) ok = back[g] == (double)g;
       double bad = ok ? 0.0 : 1.0;  // every rank takes the same decision
-      HIPCHK(c, hipMemcpyAsync(c->red_out.p + 16, &bad, sizeof(double), hipMemcpyHostToDevice, c->stream));
-      CHK(comm_allreduce_dev(c, c->red_out.p + 16, 1, 1));
-      HIPCHK(c, hipMemcpyAsync(&bad, c->red_out.p + 16, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      CHK(comm_allreduce_host(c, &bad, 1));
       c->gp_allgather = bad == 0.0;
       if (!c->gp_allgather && c->rank == 0)
         fprintf(stderr, "[cfdh] WARNING: all-gather self-check failed; the pressure right-hand side is all-reduced instead\n");

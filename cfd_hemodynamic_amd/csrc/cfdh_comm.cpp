@@ -77,11 +77,8 @@ extern "C" int cfdh_comm_unique_id(void *id128) {
 
 static int global_counts(cfdh_ctx *c) {
   double cnt = (double)c->nvo;
-  HIPCHK(c, hipMemcpyAsync(c->red_out.p + 16, &cnt, sizeof(double), hipMemcpyHostToDevice, c->stream));
-  CHK(comm_allreduce_dev(c, c->red_out.p + 16, 1, 0));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->red_out.p + 16, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->nvo_global = c->h_pinned[0];
+  CHK(comm_allreduce_host(c, &cnt, 0));
+  c->nvo_global = cnt;
   return 0;
 }
 
@@ -126,8 +123,8 @@ int comm_allreduce_dev(cfdh_ctx *c, double *dev, int n, int op) {
     return 0;
   }
   if (!c->cb_ar) return cfdh_fail(c, CFDH_E_COMM, "multi-rank context without communicator");
-  double *h = c->h_pinned + 512;
-  if (n > 512) {
+  double *h = c->h_pinned + HP_CB_STAGE;
+  if (n > HP_CB_STAGE_N) {
     if (c->h_big_n < (size_t)n) {
       if (c->h_big) (void)hipHostFree(c->h_big);
       HIPCHK(c, hipHostMalloc((void **)&c->h_big, sizeof(double) * (size_t)n));
@@ -140,6 +137,16 @@ int comm_allreduce_dev(cfdh_ctx *c, double *dev, int n, int op) {
   if (c->cb_ar(c->cb_user, h, n, op) != 0) return cfdh_fail(c, CFDH_E_COMM, "allreduce callback failed");
   HIPCHK(c, hipMemcpyAsync(dev, h, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // h is reused by the next call
+  return 0;
+}
+
+// one host scalar through the reduction of the device words (set-up decisions every rank must take alike); blocking
+int comm_allreduce_host(cfdh_ctx *c, double *v, int op) {
+  double *slot = c->red_out.p + RO_HOST_SCALAR;
+  HIPCHK(c, hipMemcpyAsync(slot, v, sizeof(double), hipMemcpyHostToDevice, c->stream));
+  CHK(comm_allreduce_dev(c, slot, 1, op));
+  HIPCHK(c, hipMemcpyAsync(v, slot, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "cfdh.h"
+#include "cfdh_scratch.hpp"
 
 // geometry of a 2-D assembly workgroup (overridable for tuning experiments, tools/build_variant.sh)
 #ifndef CFDH_MAX_INC
@@ -272,11 +273,9 @@ struct cfdh_ctx {
 
   // reductions
   dbuf<double> red_partial, red_out;
-  double *h_pinned = nullptr;  // pinned host scratch for scalar read-back
+  double *h_pinned = nullptr;  // pinned, host-mapped scratch of the scalar read-backs: HP_WORDS words, regions in cfdh_scratch.hpp
   double *h_stage = nullptr;   // pinned staging of whole fields (set_state / get_* of the host-copy loop), NL doubles
   double *h_pinned_dev = nullptr;  // the same buffer as the device sees it (kernels write read-back scalars into it)
-  const double *mirror_src = nullptr;  // device scalars whose host-mapped copy is current (see read_scalars)
-  int mirror_cnt = 0;
   hipEvent_t ev_h = nullptr;   // marks 'Gram-Schmidt coefficients are in h_pinned'
   // FGMRES read-back ring: the host processes the Gram-Schmidt coefficients of an iteration up to KRING - 2 iterations after it
   // was launched (cfdh_fgmres), so every iteration in flight owns a slot of host-mapped memory and an event
@@ -499,8 +498,8 @@ int k3_spmv_full(cfdh_ctx *c, const double *x, double *y);
 int k3_spmv_full_multi(cfdh_ctx *c, const double *X, double *Y, int ld, int nvec);
 int k3_spmv_block(cfdh_ctx *c, int blk, const double *x, double *y, const double *b);
 int k3_spmv_block_ghost(cfdh_ctx *c, int blk, const double *xv, double *y, const double *b);  // xv: full vector with refreshed ghost tail  // 2: b - A01 x_p ; 3: b - A10 x_u (b may be null)
-int k3_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm);
-int k3_functional(cfdh_ctx *c, int kind, int marker, double *out);
+int k3_nullspace_partials(cfdh_ctx *c, int nb);                       // per-block partial sums of the two null-space norms
+int k3_functional_partials(cfdh_ctx *c, int kind, int marker, int nb);  // kind 2, 3: two values; 7: one
 int k3_wss(cfdh_ctx *c, double *out);
 
 // ---- nodal elements beyond P1 (cfdh_gen.hip) ------------------------------------------
@@ -541,8 +540,6 @@ void prof_flush(cfdh_ctx *c);
 
 int k_upload_quadrature(cfdh_ctx *c);
 int k_halo_pack(cfdh_ctx *c, const double *vec);
-#define CFDH_MIRROR_OFF 300  // h_pinned word where the host-mapped copies of reduced scalars start
-#define CFDH_LEAN_S2 12      // red_out word that holds the squared residual norm of the lean prologue / epilogue
 int v_pointwise_mult(cfdh_ctx *c, int n, const double *a, const double *b, double *out);
 int k_moments(cfdh_ctx *c);
 int k_assemble(cfdh_ctx *c, const double *xstate, int mode);  // mode 0: F only, 1: F+J, 2: F with lifting (no J write)
@@ -608,8 +605,26 @@ int v_pack_state(cfdh_ctx *c, const double *u_user, const double *p_user, double
 int k_functional(cfdh_ctx *c, int kind, int marker, double *out);
 int k_wss(cfdh_ctx *c, double *out);
 
+// ---- scalar reductions and read-backs (cfdh_reduce.hip; words: cfdh_scratch.hpp) ----------------------------------
+// A read-back goes through a handle: which device words, how many, and whether their host-mapped copy is current.
+struct ScalarRead { const double *dev; int n; bool mirrored; };
+int vgrid(int n);                         // blocks of a grid-stride vector kernel
+int red_grid(const cfdh_ctx *c, int n);   // the same, at most red_blocks: grid of a partial-sum kernel over n entries
+int red_partials_launch(cfdh_ctx *c, int op, int nb, int n, const double *x, const double *y, double *partial);  // op 0: x.y, 1: max |x - y|, 2: sum x
+// out[v] = reduce(partial[v stride .. + nblk)) for v < nval, also into mirror[v] if given; op 0: sum, 1: max, 2: sqrt of the sum
+int red_final(cfdh_ctx *c, int op, int nval, int nblk, int stride, const double *partial, double *out, double *mirror);
+int red_publish(cfdh_ctx *c, int n, const double *src, double *mirror);  // mirror[0..n) = src[0..n) by a one-block kernel
+inline double *scalars_mirror(const cfdh_ctx *c) { return c->h_pinned_dev + HP_MIRROR; }  // device view of the mirror words
+inline ScalarRead scalars_mirrored(int n) { return ScalarRead{nullptr, n, true}; }  // n words kernels wrote to scalars_mirror(c)
+// final kernel over the nblk-strided rows of red_partial into dev[0..n), reduction over the ranks, host-mapped copy;
+// h may be null when the values stay on the device
+int scalars_finish(cfdh_ctx *c, double *dev, int n, int op, int nblk, ScalarRead *h);
+// the ONE place that waits for the stream and counts it (cfdh_info 15; counted = false: set-up reads that never were)
+int scalars_read(cfdh_ctx *c, const ScalarRead &h, double *host, bool counted = true);
+
 // ---- comm (cfdh_comm.cpp) ----------------------------------------------------------
 int comm_allreduce_dev(cfdh_ctx *c, double *dev, int n, int op);
+int comm_allreduce_host(cfdh_ctx *c, double *v, int op);  // one host scalar through the same reduction (blocking)
 int comm_allgather_dev(cfdh_ctx *c, const double *send, double *recv, int count);  // RCCL communicators only  // in-stream
 int comm_halo(cfdh_ctx *c, double *vec);                          // fill the ghost tail of vec
 int comm_finalize(cfdh_ctx *c);

@@ -580,7 +580,7 @@ int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn64, int64_t nvert64, int64
   hipStream_t s = c->stream;
   // reduction scratch of the shared helpers (AMG set-up uses red_out)
   CHK(cfdh_alloc_reduction(c, false));  // no ev_h in this context
-  memset(c->h_pinned, 0, 1024 * sizeof(double));
+  memset(c->h_pinned, 0, HP_WORDS * sizeof(double));
 
   IpRef R;
   ip_reference(D, R);
@@ -873,12 +873,12 @@ static void ip_spmv(cfdh_ctx *c, const IpMat &A, const double *x, double *y, con
 template <int STAGE>
 static void ip_scal(cfdh_ctx *c, int nb, double rtol, double atol, int first) {
   IpcsData *I = IP(c);
-  IPL(c, ip_scal_kernel<STAGE>, 1, 0, nb, (const double *)I->P.p, I->S.p, rtol, atol, first, c->h_pinned_dev + 512);
+  IPL(c, ip_scal_kernel<STAGE>, 1, 0, nb, (const double *)I->P.p, I->S.p, rtol, atol, first, c->h_pinned_dev + HP_IPCS);
 }
 // mirror: |r|^2, done, its, bad
 static int ip_read(cfdh_ctx *c, double m[4]) {
   CHK(ip_sync(c));
-  for (int i = 0; i < 4; i++) m[i] = c->h_pinned[512 + i];
+  for (int i = 0; i < HP_IPCS_N; i++) m[i] = c->h_pinned[HP_IPCS + i];
   return 0;
 }
 static int ip_finish(cfdh_ctx *c, int which, const double m[4], bool capped, cfdh_ipcs_stats *st) {

@@ -1884,7 +1884,6 @@ __global__ __launch_bounds__(TPB) void waxpy_kernel(int n, double a, const doubl
 __global__ __launch_bounds__(TPB) void scale_kernel(int n, double a, double *__restrict__ x) {
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) x[i] *= a;
 }
-static inline int vgrid(int n) { int g = (n + TPB * 4 - 1) / (TPB * 4); return g < 1 ? 1 : (g > 2048 ? 2048 : g); }
 
 __global__ __launch_bounds__(TPB) void pmult_kernel(int n, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ o) {
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) o[i] = a[i] * b[i];
@@ -1918,90 +1917,17 @@ int v_scale(cfdh_ctx *c, int n, double a, double *x) {
   return 0;
 }
 
-// ---- reductions: per-block partials (fixed order) -> one final block; deterministic
-// OP 0: sum x*y, 1: max |x - y| (y may be null; NaN when an entry is NaN)
-template <int OP>
-__global__ __launch_bounds__(TPB) void reduce_partial_kernel(int n, const double *__restrict__ x, const double *__restrict__ y,
-                                                             double *__restrict__ partial) {
-  __shared__ double sh[4];
-  double a = 0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-    if (OP == 0) a += x[i] * y[i];
-    else a = max_nan(a, fabs(y ? x[i] - y[i] : x[i]));
-  }
-  a = (OP == 0) ? block_sum(a, sh) : block_max(a, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = a;
-}
-// out[v] = reduce(partial[v*stride .. +nblk)), one block per v; OP 2: sqrt of the sum
-template <int OP>
-__global__ __launch_bounds__(TPB) void reduce_final_kernel(int nblk, int stride, const double *__restrict__ partial,
-                                                           double *__restrict__ out, double *__restrict__ mirror = nullptr) {
-  __shared__ double sh[4];
-  const double *pp = partial + (size_t)blockIdx.x * stride;
-  double a = 0;
-  for (int i = threadIdx.x; i < nblk; i += TPB) a = (OP == 1) ? max_nan(a, pp[i]) : a + pp[i];
-  a = (OP == 1) ? block_max(a, sh) : block_sum(a, sh);
-  if (threadIdx.x == 0) {
-    const double v = (OP == 2) ? sqrt(a) : a;
-    out[blockIdx.x] = v;
-    if (mirror) mirror[blockIdx.x] = v;  // host-mapped copy: the host reads it after an event, no copy kernel
-  }
-}
-
-// Single rank: the final reduction kernel also stores its results into host-mapped memory (h_pinned + 300),
-// so reading them back costs a stream synchronisation instead of a copy kernel (~11 us each).
-static double *scalar_mirror(cfdh_ctx *c, const double *out_dev, int cnt) {
-  if (c->nranks > 1 || cnt > 64) { c->mirror_src = nullptr; return nullptr; }
-  c->mirror_src = out_dev; c->mirror_cnt = cnt;
-  return c->h_pinned_dev + CFDH_MIRROR_OFF;
-}
-__global__ __launch_bounds__(TPB) void mirror_copy_kernel(int n, const double *__restrict__ src, double *__restrict__ dst) {
-  for (int i = threadIdx.x; i < n; i += TPB) dst[i] = src[i];
-}
-// all-reduce of n freshly reduced scalars; in a partitioned run the REDUCED values are then published to the
-// host-mapped scratch by a one-block kernel behind the collective (one rank: the reduction kernel did it already)
-static int finish_scalars(cfdh_ctx *c, double *out_dev, int n, int op) {
-  CHK(comm_allreduce_dev(c, out_dev, n, op));
-  if (c->nranks > 1 && n <= 64) {
-    hipLaunchKernelGGL(mirror_copy_kernel, dim3(1), dim3(TPB), 0, c->stream, n, (const double *)out_dev, c->h_pinned_dev + CFDH_MIRROR_OFF);
-    HIPCHK(c, hipGetLastError());
-    c->mirror_src = out_dev; c->mirror_cnt = n;
-  }
-  return 0;
-}
-static int read_scalars(cfdh_ctx *c, const double *dev, int n, double *host) {
-  if (c->mirror_src == dev && n <= c->mirror_cnt) {
-    c->mirror_src = nullptr;  // one shot
-    c->n_host_sync++;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; i++) host[i] = c->h_pinned[CFDH_MIRROR_OFF + i];
-    return 0;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  c->n_host_sync++;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < n; i++) host[i] = c->h_pinned[i];
-  return 0;
-}
-
-static int reduce_dev(cfdh_ctx *c, int op, int n, const double *x, const double *y, double *out_dev) {
-  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
-  if (op == 0) {
-    hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nb), dim3(TPB), 0, c->stream, n, x, y, c->red_partial.p);
-    hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, out_dev,
-                       scalar_mirror(c, out_dev, 1));
-  } else {
-    hipLaunchKernelGGL(reduce_partial_kernel<1>, dim3(nb), dim3(TPB), 0, c->stream, n, x, y, c->red_partial.p);
-    hipLaunchKernelGGL(reduce_final_kernel<1>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, out_dev,
-                       scalar_mirror(c, out_dev, 1));
-  }
-  HIPCHK(c, hipGetLastError());
-  return finish_scalars(c, out_dev, 1, op);
+// ---- reductions (protocol and kernels: cfdh_reduce.hip)
+static int reduce_dev(cfdh_ctx *c, int op, int n, const double *x, const double *y, double *out_dev, ScalarRead *h) {
+  const int nb = red_grid(c, n);
+  CHK(red_partials_launch(c, op, nb, n, x, y, c->red_partial.p));
+  return scalars_finish(c, out_dev, 1, op, nb, h);
 }
 
 int v_dot(cfdh_ctx *c, int n, const double *x, const double *y, double *out_host) {
-  CHK(reduce_dev(c, 0, n, x, y, c->red_out.p));
-  return read_scalars(c, c->red_out.p, 1, out_host);
+  ScalarRead h;
+  CHK(reduce_dev(c, 0, n, x, y, c->red_out.p, &h));
+  return scalars_read(c, h, out_host);
 }
 int v_norm2(cfdh_ctx *c, int n, const double *x, double *out_host) {
   CHK(v_dot(c, n, x, x, out_host));
@@ -2010,43 +1936,33 @@ int v_norm2(cfdh_ctx *c, int n, const double *x, double *out_host) {
 }
 // |x| and |y| with one read-back (one host synchronisation instead of two)
 int v_norm2_pair(cfdh_ctx *c, int n, const double *x, const double *y, double *nx, double *ny) {
-  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
+  const int nb = red_grid(c, n);
   if ((size_t)2 * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "reduction workspace too small");
-  hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nb), dim3(TPB), 0, c->stream, n, x, x, c->red_partial.p);
-  hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nb), dim3(TPB), 0, c->stream, n, y, y, c->red_partial.p + nb);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(2), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p,
-                     scalar_mirror(c, c->red_out.p, 2));
-  HIPCHK(c, hipGetLastError());
-  CHK(finish_scalars(c, c->red_out.p, 2, 0));
+  CHK(red_partials_launch(c, 0, nb, n, x, x, c->red_partial.p));
+  CHK(red_partials_launch(c, 0, nb, n, y, y, c->red_partial.p + nb));
+  ScalarRead h;
+  CHK(scalars_finish(c, c->red_out.p, 2, 0, nb, &h));
   double v[2];
-  CHK(read_scalars(c, c->red_out.p, 2, v));
+  CHK(scalars_read(c, h, v));
   *nx = sqrt(v[0]); *ny = sqrt(v[1]);
   return 0;
 }
 int v_norminf_diff(cfdh_ctx *c, int n, const double *x, const double *y, double *out_host) {
-  CHK(reduce_dev(c, 1, n, x, y, c->red_out.p));
-  return read_scalars(c, c->red_out.p, 1, out_host);
+  ScalarRead h;
+  CHK(reduce_dev(c, 1, n, x, y, c->red_out.p, &h));
+  return scalars_read(c, h, out_host);
 }
 
 __global__ __launch_bounds__(TPB) void sub_scalar_kernel(int n, double *__restrict__ p, const double *__restrict__ s, double scale) {
   const double m = s[0] * scale;
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) p[i] -= m;
 }
-__global__ __launch_bounds__(TPB) void sum_partial_kernel(int n, const double *__restrict__ x, double *__restrict__ partial) {
-  __shared__ double sh[4];
-  double a = 0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) a += x[i];
-  a = block_sum(a, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = a;
-}
 // p -= mean(p) over all ranks (constant-pressure null vector, stabilized_schur.py:282-293,319)
 int v_sub_mean(cfdh_ctx *c, int n, double *p) {
-  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
-  double *acc = c->red_out.p + 8;  // [sum, count]
-  hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, p, c->red_partial.p);
-  c->mirror_src = nullptr;
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, acc);
-  HIPCHK(c, hipGetLastError());
+  const int nb = red_grid(c, n);
+  double *acc = c->red_out.p + RO_MEAN;  // [sum, count]
+  CHK(red_partials_launch(c, 2, nb, n, p, nullptr, c->red_partial.p));
+  CHK(red_final(c, 0, 1, nb, nb, c->red_partial.p, acc, nullptr));
   double scale = 1.0 / n;
   if (c->nranks > 1) {
     CHK(comm_allreduce_dev(c, acc, 1, 0));
@@ -2162,9 +2078,8 @@ int v_gram(cfdh_ctx *c, int n, const double *W, int ld, int k, const double *b, 
   if (k == 2) hipLaunchKernelGGL((gram_kernel<2>), dim3(nb), dim3(TPB), 0, c->stream, n, W, (size_t)ld, b, c->red_partial.p, nb);
   else if (k == 3) hipLaunchKernelGGL((gram_kernel<3>), dim3(nb), dim3(TPB), 0, c->stream, n, W, (size_t)ld, b, c->red_partial.p, nb);
   else hipLaunchKernelGGL((gram_kernel<4>), dim3(nb), dim3(TPB), 0, c->stream, n, W, (size_t)ld, b, c->red_partial.p, nb);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(nout), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, out_dev, (double *)nullptr);
   HIPCHK(c, hipGetLastError());
-  return 0;
+  return red_final(c, 0, nout, nb, nb, c->red_partial.p, out_dev, nullptr);
 }
 // (A "last block does the final reduction" variant was measured and dropped: the device-scope release fence every
 // block needs before taking its ticket writes the XCD's L2 back -- 133 us per launch against 17 + 4 us for two kernels.)
@@ -2176,15 +2091,12 @@ int v_multidot(cfdh_ctx *c, int n, const double *V, int ld, int nvec, const doub
                      with_ww ? 1 : 0);
   // single rank: the h values also land in host-mapped memory (`mirror`: device view of a slot of the FGMRES read-back ring)
   // straight from the kernel
-  double *mir = (mirror && c->nranks <= 1) ? mirror : nullptr;
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(nout), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, h_dev, mir);
   HIPCHK(c, hipGetLastError());
+  CHK(red_final(c, 0, nout, nb, nb, c->red_partial.p, h_dev, (mirror && c->nranks <= 1) ? mirror : nullptr));
   if (!reduce_ranks) return 0;  // the caller reduces several results over the ranks at once
   CHK(comm_allreduce_dev(c, h_dev, nout, 0));
-  if (mirror && c->nranks > 1) {  // partitioned: publish the REDUCED coefficients the same way (behind the all-reduce)
-    hipLaunchKernelGGL(mirror_copy_kernel, dim3(1), dim3(TPB), 0, c->stream, nout, (const double *)h_dev, mirror);
-    HIPCHK(c, hipGetLastError());
-  }
+  // partitioned: publish the REDUCED coefficients the same way (behind the all-reduce)
+  if (mirror && c->nranks > 1) CHK(red_publish(c, nout, h_dev, mirror));
   return 0;
 }
 __global__ __launch_bounds__(TPB) void scale_to_kernel(int n, double a, const double *__restrict__ x, double *__restrict__ y) {
@@ -2303,14 +2215,10 @@ int v_multidot32(cfdh_ctx *c, int n, const float *V, int ld, int nvec, const dou
   const int nb = MD_NB, nout = nvec + 1;
   if ((size_t)nout * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "multidot workspace too small");
   hipLaunchKernelGGL(multidot32_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, V, (size_t)ld, nvec, w, c->red_partial.p, nb);
-  double *mir = c->nranks <= 1 ? mirror : nullptr;
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(nout), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, h_dev, mir);
   HIPCHK(c, hipGetLastError());
+  CHK(red_final(c, 0, nout, nb, nb, c->red_partial.p, h_dev, c->nranks <= 1 ? mirror : nullptr));
   CHK(comm_allreduce_dev(c, h_dev, nout, 0));
-  if (c->nranks > 1) {
-    hipLaunchKernelGGL(mirror_copy_kernel, dim3(1), dim3(TPB), 0, c->stream, nout, (const double *)h_dev, mirror);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (c->nranks > 1) CHK(red_publish(c, nout, h_dev, mirror));
   return 0;
 }
 // vn = w - V32 h (not normalised) and the block partials of |vn|^2
@@ -2359,17 +2267,16 @@ int v_store32(cfdh_ctx *c, int n, const double *v, float *v32) {
 // the host-mapped word `mirror` for the host
 int v_gs_update32(cfdh_ctx *c, int n, const float *V, int ld, int nvec, const double *h_dev, const double *w, double *vn, float *v32n,
                   double *s_dev, double *mirror) {
-  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
+  const int nb = red_grid(c, n);
   double *part = c->red_partial.p + (size_t)(MD_NB) * 8;  // behind the first multi-dot groups (the stream serialises the users)
   hipLaunchKernelGGL(gs_update32_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, V, (size_t)ld, nvec, h_dev, w, vn, part);
   if (c->nranks <= 1) {  // square root and host-mapped copy in the reduction kernel itself
-    hipLaunchKernelGGL(reduce_final_kernel<2>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, part, s_dev, mirror);
+    CHK(red_final(c, 2, 1, nb, nb, part, s_dev, mirror));
   } else {
-    hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, part, s_dev, (double *)nullptr);
-    HIPCHK(c, hipGetLastError());
+    CHK(red_final(c, 0, 1, nb, nb, part, s_dev, nullptr));
     CHK(comm_allreduce_dev(c, s_dev, 1, 0));
     hipLaunchKernelGGL(sqrt_kernel, dim3(1), dim3(1), 0, c->stream, s_dev);
-    hipLaunchKernelGGL(mirror_copy_kernel, dim3(1), dim3(TPB), 0, c->stream, 1, (const double *)s_dev, mirror);
+    CHK(red_publish(c, 1, s_dev, mirror));
   }
   hipLaunchKernelGGL(scale_store32_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, vn, (const double *)s_dev, v32n);
   HIPCHK(c, hipGetLastError());
@@ -2382,8 +2289,7 @@ int v_lincomb(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const doubl
 }
 
 // ---- lean solve path: prologue and epilogue of a linear solve with one read-back each (cfdh_solver.cpp) ----------------------
-// Host-mapped words behind CFDH_MIRROR_OFF: [0] squared norm of the residual, [1] 1 when the projected guess is used, [2] rank
-// of the Gram system, [3 .. 3 + k) the coefficients y.
+// (the mirror words of the prologue: DESIGN.md, "Scalar reductions and read-backs")
 // The k x k Gram system of the projected guess (k <= 8), solved by one lane: cfdh_krylov::gram_solve, the same function the
 // general path calls on the host.
 __global__ void gram_solve_kernel(int k, const double *__restrict__ hd, double *__restrict__ y, double *__restrict__ info) {
@@ -2457,28 +2363,21 @@ __global__ __launch_bounds__(TPB) void norm3_partial_kernel(int n, const double 
   s2 = block_sum(s2, sh);
   if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; partial[2 * gridDim.x + blockIdx.x] = s2; }
 }
-static double *lean_mirror(cfdh_ctx *c) { c->mirror_src = nullptr; return c->h_pinned_dev + CFDH_MIRROR_OFF; }
-static int lean_sync(cfdh_ctx *c) {
-  c->n_host_sync++;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
-}
 // Prologue of a solve with k kept vectors, hd = Gram system from v_gram: y on the device (ky), x = U y, r = b - W y, |r|^2 and the
 // "used" flag in the host-mapped words.  Nothing is read back here.
 int v_guess_combine(cfdh_ctx *c, int n, const double *U, const double *W, int ld, int k, const double *hd, const double *b, double *x, double *r) {
   if (k < 1 || k > 8) return cfdh_fail(c, CFDH_E_STATE, "projected guess: %d kept vectors", k);
-  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
-  double *mir = lean_mirror(c);
+  const int nb = red_grid(c, n);
+  double *mir = scalars_mirror(c);
   hipLaunchKernelGGL(gram_solve_kernel, dim3(1), dim3(64), 0, c->stream, k, hd, c->ky.p, mir);
   hipLaunchKernelGGL(guess_combine_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, U, W, (size_t)ld, k, (const double *)c->ky.p, b, x, r, c->red_partial.p);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p + CFDH_LEAN_S2, mir);
   HIPCHK(c, hipGetLastError());
-  return 0;
+  return red_final(c, 0, 1, nb, nb, c->red_partial.p, c->red_out.p + RO_LEAN_S2, mir);
 }
 // the one read-back of the prologue: |r0|, whether the guess is used, the rank and the coefficients
 int v_guess_read(cfdh_ctx *c, int k, double *beta, bool *used, int *rank, double *y) {
-  CHK(lean_sync(c));
-  const double *m = c->h_pinned + CFDH_MIRROR_OFF;
+  double m[3 + 8];
+  CHK(scalars_read(c, scalars_mirrored(3 + k), m));
   *beta = sqrt(m[0]);
   *used = m[1] != 0.0;
   *rank = (int)m[2];
@@ -2487,7 +2386,7 @@ int v_guess_read(cfdh_ctx *c, int k, double *beta, bool *used, int *rank, double
 }
 // x /= the norm the last lean prologue / epilogue left on the device
 int v_scale_inv_lean(cfdh_ctx *c, int n, double *x) {
-  hipLaunchKernelGGL(scale_inv_sqrt_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, x, (const double *)(c->red_out.p + CFDH_LEAN_S2));
+  hipLaunchKernelGGL(scale_inv_sqrt_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, x, (const double *)(c->red_out.p + RO_LEAN_S2));
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -2498,13 +2397,13 @@ int k_resid_norm(cfdh_ctx *c, const double *x, const double *b, double *r, doubl
   const long long nb = (nthreads + TPB - 1) / TPB;
   *done = false;
   if (c->dim != 2 || (size_t)nb > c->red_partial.n) return 0;
-  double *mir = lean_mirror(c);
   hipLaunchKernelGGL((spmv_full_lean_kernel<false, true>), dim3((unsigned)nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->vcol.p, c->A00.p,
                      c->A01.p, c->A10.p, c->A11.p, x, r, (const double *)nullptr, b, c->red_partial.p);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, (int)nb, (int)nb, c->red_partial.p, c->red_out.p + CFDH_LEAN_S2, mir);
   HIPCHK(c, hipGetLastError());
-  CHK(lean_sync(c));
-  *nrm = sqrt(c->h_pinned[CFDH_MIRROR_OFF]);
+  CHK(red_final(c, 0, 1, (int)nb, (int)nb, c->red_partial.p, c->red_out.p + RO_LEAN_S2, scalars_mirror(c)));
+  double s2;
+  CHK(scalars_read(c, scalars_mirrored(1), &s2));
+  *nrm = sqrt(s2);
   *done = true;
   return 0;
 }
@@ -2515,28 +2414,27 @@ int v_lincomb_keep(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const 
 }
 // |a|, |b|, |cc| with one pass and one read-back (one rank)
 int v_norm2_triple(cfdh_ctx *c, int n, const double *a, const double *b, const double *cc, double *out) {
-  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
+  const int nb = red_grid(c, n);
   if ((size_t)3 * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "reduction workspace too small");
-  double *mir = lean_mirror(c);
   hipLaunchKernelGGL(norm3_partial_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, a, b, cc, c->red_partial.p);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(3), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p, mir);
   HIPCHK(c, hipGetLastError());
-  CHK(lean_sync(c));
-  for (int i = 0; i < 3; i++) out[i] = sqrt(c->h_pinned[CFDH_MIRROR_OFF + i]);
+  CHK(red_final(c, 0, 3, nb, nb, c->red_partial.p, c->red_out.p, scalars_mirror(c)));
+  CHK(scalars_read(c, scalars_mirrored(3), out));
+  for (int i = 0; i < 3; i++) out[i] = sqrt(out[i]);
   return 0;
 }
 __global__ void sqrt_kernel(double *s) { s[0] = sqrt(s[0]); }
 int v_norm_to_dev(cfdh_ctx *c, int n, const double *w, double *out_dev) {
-  CHK(reduce_dev(c, 0, n, w, w, out_dev));
+  CHK(reduce_dev(c, 0, n, w, w, out_dev, nullptr));  // stays on the device
   hipLaunchKernelGGL(sqrt_kernel, dim3(1), dim3(1), 0, c->stream, out_dev);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
 // the same without the reduction over the ranks: norms of rank-local operators (hierarchy set-up of a partitioned run)
 int v_norm_to_dev_local(cfdh_ctx *c, int n, const double *w, double *out_dev) {
-  const int nb = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
-  hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nb), dim3(TPB), 0, c->stream, n, w, w, c->red_partial.p);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, out_dev, (double *)nullptr);
+  const int nb = red_grid(c, n);
+  CHK(red_partials_launch(c, 0, nb, n, w, w, c->red_partial.p));
+  CHK(red_final(c, 0, 1, nb, nb, c->red_partial.p, out_dev, nullptr));
   hipLaunchKernelGGL(sqrt_kernel, dim3(1), dim3(1), 0, c->stream, out_dev);
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -2573,15 +2471,14 @@ __global__ __launch_bounds__(TPB) void nulltest_kernel(int nvo, const int *__res
   if (threadIdx.x == 0) { partial[blockIdx.x] = a; partial[gridDim.x + blockIdx.x] = b; }
 }
 int k_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm) {
-  if (c->dim == 3) return k3_nullspace_test(c, nrm, absnrm);
-  const int nb = vgrid(c->nvo) > c->red_blocks ? c->red_blocks : vgrid(c->nvo);
-  hipLaunchKernelGGL(nulltest_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->A01.p, c->A11.p, c->red_partial.p);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(2), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p,
-                     scalar_mirror(c, c->red_out.p, 2));
+  const int nb = c->dim == 3 ? 256 : red_grid(c, c->nvo);
+  if (c->dim == 3) CHK(k3_nullspace_partials(c, nb));
+  else hipLaunchKernelGGL(nulltest_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->A01.p, c->A11.p, c->red_partial.p);
   HIPCHK(c, hipGetLastError());
-  CHK(finish_scalars(c, c->red_out.p, 2, 0));
+  ScalarRead h;
+  CHK(scalars_finish(c, c->red_out.p, 2, 0, nb, &h));
   double s[2];
-  CHK(read_scalars(c, c->red_out.p, 2, s));
+  CHK(scalars_read(c, h, s));
   *nrm = sqrt(s[0]);
   *absnrm = sqrt(s[1]);
   return 0;
@@ -2589,17 +2486,16 @@ int k_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm) {
 // |F| and the two numbers of the null-space test with ONE read-back (one rank, triangles): each value is reduced exactly as
 // v_norm2 / k_nullspace_test reduce it
 int k_fnorm_nulltest(cfdh_ctx *c, int n, const double *F, double *fn, double *nrm, double *absnrm) {
-  const int nbf = vgrid(n) > c->red_blocks ? c->red_blocks : vgrid(n);
-  const int nb = vgrid(c->nvo) > c->red_blocks ? c->red_blocks : vgrid(c->nvo);
+  const int nbf = red_grid(c, n), nb = red_grid(c, c->nvo);
   if ((size_t)nbf + 2 * (size_t)nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "reduction workspace too small");
-  double *mir = lean_mirror(c), *pn = c->red_partial.p + nbf;
-  hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nbf), dim3(TPB), 0, c->stream, n, F, F, c->red_partial.p);
+  double *mir = scalars_mirror(c), *pn = c->red_partial.p + nbf;
+  CHK(red_partials_launch(c, 0, nbf, n, F, F, c->red_partial.p));
   hipLaunchKernelGGL(nulltest_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->A01.p, c->A11.p, pn);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(1), dim3(TPB), 0, c->stream, nbf, nbf, c->red_partial.p, c->red_out.p, mir);
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(2), dim3(TPB), 0, c->stream, nb, nb, pn, c->red_out.p + 1, mir + 1);
   HIPCHK(c, hipGetLastError());
-  CHK(lean_sync(c));
-  const double *m = c->h_pinned + CFDH_MIRROR_OFF;
+  CHK(red_final(c, 0, 1, nbf, nbf, c->red_partial.p, c->red_out.p, mir));
+  CHK(red_final(c, 0, 2, nb, nb, pn, c->red_out.p + RO_RESULT + 1, mir + 1));
+  double m[3];
+  CHK(scalars_read(c, scalars_mirrored(3), m));
   *fn = sqrt(m[0]); *nrm = sqrt(m[1]); *absnrm = sqrt(m[2]);
   return 0;
 }
@@ -2773,11 +2669,21 @@ int k_wss(cfdh_ctx *c, double *out) {
   return 0;
 }
 
+// kinds 0 .. 3 and 7: 256 blocks of partial sums by the kernel of the element family, then one tail for all of them
 int k_functional(cfdh_ctx *c, int kind, int marker, double *out) {
-  if (c->dim == 3) return k3_functional(c, kind, marker, out);
   const int nb = 256;
-  if (c->gen && (kind <= 3 || kind == 7)) {
-    CHK(kg_functional_partials(c, kind, marker, nb));
+  int nval = 2;  // rows of partial sums the kernel writes
+  if (kind >= 4 && kind <= 6) {
+    const double *a = kind == 5 ? c->xprev.p : c->x.p;
+    const double *b = kind == 6 ? c->xprev.p : nullptr;
+    return v_norminf_diff(c, c->dim * c->nvo, a, b, out);
+  } else if (c->dim == 3 && kind != 2 && kind != 3 && kind != 7) {
+    return cfdh_fail(c, CFDH_E_ARG, "functional kind %d is not available for tetrahedra (2, 3: L2 norms; 4-6: inf-norms; 7: flux)", kind);
+  } else if (c->gen && (kind <= 3 || kind == 7)) {  // the element's own quadrature (cfdh_gen.hip, cfdh_gen3.hip)
+    CHK(c->dim == 3 ? kg3_functional_partials(c, kind, marker, nb) : kg_functional_partials(c, kind, marker, nb));
+  } else if (c->dim == 3) {
+    CHK(k3_functional_partials(c, kind, marker, nb));
+    if (kind == 7) nval = 1;
   } else if (kind == 0 || kind == 1) {
     // a part without exterior facets (nfac == 0) still launches: the kernel then only writes zero partials, and the
     // rank takes part in the reduction below like every other one (skipping it would desynchronise the collectives)
@@ -2790,24 +2696,14 @@ int k_functional(cfdh_ctx *c, int kind, int marker, double *out) {
   } else if (kind == 2 || kind == 3) {
     hipLaunchKernelGGL(l2_kernel, dim3(nb), dim3(TPB), 0, c->stream, c->nc, c->nvo, c->cells.p, c->cell_owned.p, c->coords.p,
                        c->x.p, c->red_partial.p);
-  } else if (kind >= 4 && kind <= 6) {
-    const int nu = 2 * c->nvo;
-    const double *a = kind == 5 ? c->xprev.p : c->x.p;
-    const double *b = kind == 6 ? c->xprev.p : nullptr;
-    double v;
-    CHK(reduce_dev(c, 1, nu, a, b, c->red_out.p));
-    CHK(read_scalars(c, c->red_out.p, 1, &v));
-    *out = v;
-    return 0;
   } else {
     return cfdh_fail(c, CFDH_E_ARG, "unknown functional kind %d", kind);
   }
-  hipLaunchKernelGGL(reduce_final_kernel<0>, dim3(2), dim3(TPB), 0, c->stream, nb, nb, c->red_partial.p, c->red_out.p,
-                     scalar_mirror(c, c->red_out.p, 2));
   HIPCHK(c, hipGetLastError());
-  CHK(finish_scalars(c, c->red_out.p, 2, 0));
+  ScalarRead h;
+  CHK(scalars_finish(c, c->red_out.p, nval, 0, nb, &h));
   double v[2];
-  CHK(read_scalars(c, c->red_out.p, 2, v));
+  CHK(scalars_read(c, h, v));
   if (kind == 0 || kind == 7) *out = v[0];
   else if (kind == 1) *out = v[1];
   else if (kind == 2) *out = sqrt(v[0]);

@@ -46,8 +46,8 @@ bool cfdh_renumber_enabled() {
 int cfdh_alloc_reduction(cfdh_ctx *c, bool with_event) {
   c->red_blocks = 1024;
   HIPCHK(c, c->red_partial.alloc((size_t)c->red_blocks * 260));
-  HIPCHK(c, c->red_out.alloc(1024));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, 1024 * sizeof(double)));
+  HIPCHK(c, c->red_out.alloc(RO_WORDS));
+  HIPCHK(c, hipHostMalloc((void **)&c->h_pinned, HP_WORDS * sizeof(double)));
   HIPCHK(c, hipHostGetDevicePointer((void **)&c->h_pinned_dev, c->h_pinned, 0));
   if (with_event) HIPCHK(c, hipEventCreateWithFlags(&c->ev_h, hipEventDisableTiming));
   return 0;

@@ -219,10 +219,7 @@ static int build_global_pressure(cfdh_ctx *c) {
         { const char *e = getenv("CFDH_DL0_GHOST_RHS"); d.ghost_rhs = e && e[0] == '1'; }
       }
       double bad = d.on ? 0.0 : 1.0;  // all ranks or none
-      HIPCHK(c, hipMemcpyAsync(c->red_out.p + 21, &bad, sizeof(double), hipMemcpyHostToDevice, c->stream));
-      CHK(comm_allreduce_dev(c, c->red_out.p + 21, 1, 1));
-      HIPCHK(c, hipMemcpyAsync(&bad, c->red_out.p + 21, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      CHK(comm_allreduce_host(c, &bad, 1));
       d.on = bad == 0.0;
       c->hLg.h_A0 = CsrHost(); c->hLg.h_P0 = CsrHost(); c->hLg.h_wdinv0.clear();
     }
@@ -264,10 +261,7 @@ static int build_cc_host(cfdh_ctx *c) {
     }
     if (ras) {
       double ml = (double)maxlen;  // rounds = longest owned row over all ranks
-      HIPCHK(c, hipMemcpyAsync(c->red_out.p + 20, &ml, sizeof(double), hipMemcpyHostToDevice, c->stream));
-      CHK(comm_allreduce_dev(c, c->red_out.p + 20, 1, 1));
-      HIPCHK(c, hipMemcpyAsync(&ml, c->red_out.p + 20, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+      CHK(comm_allreduce_host(c, &ml, 1));
       const int rounds = (int)ml;
       if (!c->pcw.p) { HIPCHK(c, c->pcw.alloc(c->NL)); }
       std::vector<std::vector<std::pair<int, double>>> grow(c->ng);
@@ -539,12 +533,10 @@ int cfdh_pc_update(cfdh_ctx *c, bool refresh_amg) {
   for (int it = 0; it < 8; it++) {
     CHK(k_spmv_block(c, 1, v, w, nullptr, 0));
     CHK(v_pointwise_mult(c, nu, w, c->dinvA.p, w));
-    CHK(v_norm_to_dev(c, nu, w, c->red_out.p + 4));
-    CHK(v_scale_inv_dev(c, nu, w, c->red_out.p + 4, v));
+    CHK(v_norm_to_dev(c, nu, w, c->red_out.p + RO_POWER));
+    CHK(v_scale_inv_dev(c, nu, w, c->red_out.p + RO_POWER, v));
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->red_out.p + 4, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  lam = c->h_pinned[0];
+  CHK(scalars_read(c, ScalarRead{c->red_out.p + RO_POWER, 1, false}, &lam, false));  // a set-up read: not in cfdh_info 15
   if (!(lam > 0) || !std::isfinite(lam)) return cfdh_fail(c, CFDH_E_DIVERGED, "non-finite spectral estimate of D^-1 A00 (NaN in the Jacobian?)");
   c->lmaxA = 1.15 * lam;
   CHK(k_cheb_a00_coeffs(c));
@@ -934,12 +926,9 @@ static int guess_project(cfdh_ctx *c, const double *b, double *x, bool *used) {
   HIPCHK(c, hipMemsetAsync(hd, 0, sizeof(double) * 8 * (size_t)(k + 1), c->stream));
   CHK(v_gram(c, n, Z, (int)ld, k, b, hd));  // one pass over W and b, ONE read-back
   CHK(comm_allreduce_dev(c, hd, 8 * (k + 1), 0));  // ONE reduction over the ranks for the whole Gram system
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, hd, sizeof(double) * 8 * (size_t)(k + 1), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->n_host_sync++;
+  double gram[8 * 9];
+  CHK(scalars_read(c, ScalarRead{hd, 8 * (k + 1), false}, gram));
   c->n_guess_projections++;
-  double gram[8 * 9];  // a copy: the pinned words are reused by the next read-back
-  std::copy(c->h_pinned, c->h_pinned + 8 * (size_t)(k + 1), gram);
   if (c->opt.verbose > 1) {
     double bb = 0.0;
     CHK(v_norm2(c, n, b, &bb));
@@ -1058,7 +1047,10 @@ struct Fgmres {
   float *V32 = nullptr;
   int e_its = 0;  // expected length of this solve: the last solve with the same Newton index took that many iterations (0: unknown)
   cfdh_krylov::ArnoldiLsq lsq;
-  std::vector<double> hh;  // Gram-Schmidt coefficients of the iteration being processed
+  // [0, m]: Gram-Schmidt coefficients of the iteration being processed; from HH2_AT(m): the m + 4 words a second pass reads back
+  static constexpr size_t HH2_AT(int m) { return (size_t)m + 1; }
+  static constexpr size_t HH_WORDS(int m) { return HH2_AT(m) + (size_t)m + 4; }
+  std::vector<double> hh;
   int its = 0, reason = 0;
   int j_prev = 0;             // length of the last cycle
   bool converged = false;     // the last cycle ended with the recurrence below the tolerance
@@ -1068,7 +1060,7 @@ struct Fgmres {
   bool kept_copy = false;     // the copy guess_store makes is current (written by the last update of x)
   Fgmres(cfdh_ctx *c_, const double *b_, double *x_)
       : c(c_), b(b_), x(x_), n(c_->NO), m(c_->kry_m), ld(krylov_ld(c_)), ld32((ld + 3) & ~(size_t)3),  // columns of the copy start on 16-B boundaries (float4 loads)
-        lsq(c_->kry_m), hh(2 * (size_t)(c_->kry_m + 1) + 8) {}
+        lsq(c_->kry_m), hh(HH_WORDS(c_->kry_m)) {}
 };
 
 // Start of a solve on both paths: x0 (zero or the projected guess), |b|, the tolerance, and V_0 = r0 with its norm *beta when a
@@ -1250,18 +1242,18 @@ static int fgmres_second_pass(Fgmres &s, int j, const double *hs, double ww, dou
   CHK(v_multidot(c, n, V, (int)s.ld, j + 1, vn, hd + (m + 2), true));
   CHK(v_multiaxpy(c, n, V, (int)s.ld, j + 1, hd + (m + 2), vn));
   if (s.use32) CHK(v_norm_to_dev(c, n, vn, hd + 2 * (m + 2)));
-  HIPCHK(c, hipMemcpyAsync(c->h_pinned, hd + (m + 2), sizeof(double) * (m + 4), hipMemcpyDeviceToHost, c->stream));
-  c->n_host_sync++; c->n_iter_sync++;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  double *h2 = s.hh.data() + Fgmres::HH2_AT(m);
+  CHK(scalars_read(c, ScalarRead{hd + (m + 2), m + 4, false}, h2));
+  c->n_iter_sync++;
   // scale of the first pass, formed by the function gs_update_normalize_kernel forms it with (the device word s_dev may belong to
   // an iteration that ran ahead by now); the fp32 path measured it: slot word j + 2
   const double sc = s.use32 ? hs[j + 2] : cfdh_krylov::gs_scale(ww, hh2);
   double h22 = 0.0;
-  for (int i = 0; i <= j; i++) { s.hh[i] += sc * c->h_pinned[i]; h22 += c->h_pinned[i] * c->h_pinned[i]; }
+  for (int i = 0; i <= j; i++) { s.hh[i] += sc * h2[i]; h22 += h2[i] * h2[i]; }
   double vnorm;
-  if (s.use32) vnorm = c->h_pinned[m + 2];
+  if (s.use32) vnorm = h2[m + 2];
   else {
-    const double d2 = c->h_pinned[j + 1] - h22;
+    const double d2 = h2[j + 1] - h22;
     vnorm = d2 > 0.0 ? std::sqrt(d2) : 0.0;
   }
   *hnorm = sc * vnorm;

@@ -7,7 +7,9 @@ host code: numbering, graph and staging order decide the summation order of the 
 
 One small context of every family: closed-form P1 in 2-D / 3-D (also with CFDH_NO_RENUMBER=1), generic P1 / P2 / Q1 in 2-D / 3-D,
 IPCS in 2-D / 3-D, and one part of a 2-part split (two cell layers) of a closed-form mesh and of a P2 tetrahedral mesh.  Per context:
-Jacobian structure and values, residual, and -- whole meshes -- solution and iteration counts of two time steps."""
+Jacobian structure and values, residual, and -- whole meshes -- solution and iteration counts of two time steps; then the
+functionals of kinds 2 to 7 (bit patterns) and cfdh_info 76.  The info counters 13 to 17 of every context go to stdout, not
+into the file: they count collectives and read-backs, which two builds may do differently while computing the same numbers."""
 import argparse
 import hashlib
 import os
@@ -47,6 +49,15 @@ def main():
     def put(case, item, *arrays):
         lines.append("%s %s %s" % (case, item, sha(*arrays)))
 
+    def scalars(case, ctx):
+        for kind in range(2, 8):
+            try:
+                lines.append("%s functional%d %s" % (case, kind, np.float64(ctx.functional(kind)).tobytes().hex()))
+            except (RuntimeError, ValueError) as e:  # a kind the context family does not have
+                lines.append("%s functional%d %s" % (case, kind, str(e).split("(")[0].strip()))
+        lines.append("%s info76 %d" % (case, ctx.info(76)))
+        print("%s counters 13-17: %s" % (case, " ".join(str(ctx.info(k)) for k in range(13, 18))))
+
     def part(m, rank):
         g = types.SimpleNamespace(x=m.x, cells=m.cells, num_vertices=len(m.x), num_cells=len(m.cells), facet_cells=m.facet_cells,
                                   facet_local=m.facet_local, facet_marker=np.zeros(len(m.facet_cells), np.int32))
@@ -79,6 +90,7 @@ def main():
                     lines.append("%s step%d %s" % (case, k, str(e).split("(")[0].strip()))
                 put(case, "step%d-solution" % k, *ctx.get_solution())
                 ctx.advance()
+        scalars(case, ctx)
         ctx.close()
 
     def ipcs_context(case, m, nm):
@@ -104,6 +116,7 @@ def main():
         for which in range(3 + 2 * d):
             A = ctx.get_operator(which)
             put(case, "operator%d" % which, A.indptr, A.indices, A.data)
+        scalars(case, ctx)
         ctx.close()
 
     tri, tet = dfg_case(6).mesh, create_unit_cube(4)
