@@ -1120,8 +1120,8 @@ int cfdh_amg_setup_dev(cfdh_ctx *c, AmgHier &H, CsrDev &A0, bool singular, int n
     CHK(B.level_quantities(*L, A, o.amg_smooth_ratio, &lm));
     CHK(B.work_vectors(*L, ncol));
     TICK(0);
-    L->fine = A.nnz <= (c->dim == 3 ? 20ll : 12ll) * A.n && A.n >= 16384;
-    L->sell = L->fine && (A.nnz <= 12ll * A.n || ncol == 1);
+    L->fine = cfdh_level_fine(c->dim, A.nnz, A.n);
+    L->sell = cfdh_level_sell(c->dim, A.nnz, A.n, ncol);
     const bool last = A.n <= o.amg_max_coarse || (int)H.lev.size() >= maxlev;
     int na = 0;
     dbuf<int> agg;

@@ -119,6 +119,7 @@ static int create_ctx(cfdh_ctx **out, int device, int gdim, int etype, int64_t n
     if ((e = getenv("CFDH_GS_ETA2"))) v.gs_eta2 = atof(e);
     if ((e = getenv("CFDH_L_CYCLES"))) v.l_cycles = atoi(e);
     if ((e = getenv("CFDH_A_CYCLES"))) v.a_cycles = atoi(e);
+    e = getenv("CFDH_DL0_COARSE_SWEEPS"); v.dl0_coarse_sweeps = e && e[0] == '1';
   }
   // No hipGraph replay under a rocprofiler-sdk tool on a HIP runtime >= 7.2.  That runtime submits the kernel packets of a graph
   // launch with ONE doorbell; ROCr's intercepted queue hands such a batch to the profiler's queue interceptor as (pointer into
@@ -692,7 +693,7 @@ int cfdh_apply_operator(cfdh_ctx *c, const double *r, double *z, double *w) {
   return 0;
 }
 
-// ---- test hook: ONE Krylov vector wrapper (v_* of cfdh_kernels.hip) on caller data, launched as the solver launches it ------
+// ---- test hook: ONE Krylov vector wrapper (v_* of cfdh_krylov_vec.hip) on caller data, launched as the solver launches it ------
 int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const double *A, const double *B, const double *x, const double *y,
                        const double *coef, double scalar, int flags, double *out1, double *out2, float *out32, int32_t *nscal,
                        double *scal_host, double *scal_dev, double *scal_mirror) {

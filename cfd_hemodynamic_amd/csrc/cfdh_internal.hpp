@@ -96,8 +96,29 @@ struct CsrDev {
   dbuf<float> valf;         // CSR-order fp32 copy of val (composite operators of the fine levels), optional
   // Measured on the level-0 up-sweep of the fused cycle (14.8 us) and dropped: column and fp32 value packed into one
   // 8-byte word (17.5 us); four lanes per row on 16-row slices (18.5 us).
+  // What a kernel of the preconditioner application asks before it takes the SELL arrays (CSR every operator has)
+  bool has_sell() const { return sptr.p && scol.p && sval.p; }
+  bool has_sell_weighted() const { return sptr.p && scol.p && svalw.p; }
 };
 enum { CFDH_UP_CSR = 1, CFDH_UP_SELL = 2, CFDH_UP_CSRF = 4};  // parts of a CsrDev to upload
+
+// ---- SELL-64 or CSR: the size rules, here and nowhere else.  The hierarchy builds (cfdh_setup.cpp, cfdh_amg_dev.hip) store the
+// first two in AmgLevel::fine / sell and make the copies those select; the sweep kernels (cfdh_amg_apply.hip) combine the other
+// two with CsrDev::has_sell*, so that a rule can never hand a kernel an array nobody built.
+// Short, regular rows on a level large enough to fill the device with one lane per row (the finest levels of FE operators):
+// SELL-64, one lane per row; long coarse-level rows: 8 lanes (or more) per row over CSR.
+inline bool cfdh_short_rows(long long nnz, int n, int per_row) { return nnz <= (long long)per_row * n && n >= 16384; }
+// fp32 values in G (down-sweep of the fused cycle): the finest level of a P1 operator, ~7 entries per row on triangles, ~15 on
+// tetrahedra
+inline bool cfdh_level_fine(int dim, long long nnz, int n) { return cfdh_short_rows(nnz, n, dim == 3 ? 20 : 12); }
+// ... and SELL-64 / fp32 for Sb, Sc (up-sweep); the longer rows of tetrahedra only for one right-hand side (three: measured slower)
+inline bool cfdh_level_sell(int dim, long long nnz, int n, int ncol) {
+  return cfdh_level_fine(dim, nnz, n) && (cfdh_short_rows(nnz, n, 12) || ncol == 1);
+}
+// A and P of a level in the sweep-by-sweep Jacobi cycle, and of the distributed finest level
+inline bool cfdh_sweep_sell(long long nnz, int n) { return cfdh_short_rows(nnz, n, 12); }
+// the two-step Chebyshev kernel of the Cahouet-Chabard operator: rows of up to ~15 entries (tetrahedra), 10 preloaded + tail
+inline bool cfdh_cheb2_sell(long long nnz, int n) { return cfdh_short_rows(nnz, n, 20); }
 
 struct AmgLevel {
   int n = 0;
@@ -439,6 +460,7 @@ struct cfdh_ctx {
     int ksp_lag = KRING - 3;          // CFDH_KSP_LAG: iterations launched ahead of the host at most
     double gs_eta2 = 1e-6;            // CFDH_GS_ETA2: refine when |w'|^2 <= eta2 |w|^2
     int l_cycles = 1, a_cycles = 1;   // CFDH_L_CYCLES, CFDH_A_CYCLES: V-cycles per pressure / velocity solve of the preconditioner
+    bool dl0_coarse_sweeps = false;   // CFDH_DL0_COARSE_SWEEPS=1: sweep-by-sweep cycle on the replicated levels below a distributed level 0
   } env;
   dbuf<double> qu;                           // [2 nvo] A01 z_p of the last preconditioner application; its address is baked into the captured graphs
   long long n_guess_projections = 0;         // linear solves whose prologue projected a guess, used or not (cfdh_info 86), reset likewise
@@ -533,14 +555,12 @@ int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out
 int k_ws_accumulate(cfdh_ctx *c, int n, double w, const double *tau);     // S += w tau, A += w |tau|, M = max(M, |tau|) on n vertices
 int k_ws_derive(cfdh_ctx *c, int n, int which, double *out);              // the field `which` (0 .. 4) of cfdh_wall_stats_get
 
-// ---- kernels (cfdh_kernels.hip) ----------------------------------------------------
+// ---- closed-form P1-triangle kernels, block SpMV, functionals, profiling (cfdh_kernels.hip) ---------------------------
 void prof_begin(cfdh_ctx *c, int kind);
 void prof_end(cfdh_ctx *c, int kind);
 void prof_flush(cfdh_ctx *c);
-
 int k_upload_quadrature(cfdh_ctx *c);
 int k_halo_pack(cfdh_ctx *c, const double *vec);
-int v_pointwise_mult(cfdh_ctx *c, int n, const double *a, const double *b, double *out);
 int k_moments(cfdh_ctx *c);
 int k_assemble(cfdh_ctx *c, const double *xstate, int mode);  // mode 0: F only, 1: F+J, 2: F with lifting (no J write)
 int k_spmv_full(cfdh_ctx *c, const double *x, double *y);
@@ -550,6 +570,19 @@ int k_spmv_block_ghost(cfdh_ctx *c, int blk, const double *xv, double *y, const 
 int k_extract_diag(cfdh_ctx *c);
 int k_cheb_a00(cfdh_ctx *c, const double *b, double *x);
 int k_cheb_a00_coeffs(cfdh_ctx *c);  // x = Cheb_k(A00) b, zero initial guess
+int k_cheb_init(cfdh_ctx *c, int n, const double *dinv, const double *b, double *d0, double *x, double itheta, int accumulate,
+                const double *coef);  // d0 = D^-1 b / theta (1 / theta from coef[0] when given); x = d0 or x += d0
+int k_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm);
+int k_spmv_a01_keep(cfdh_ctx *c, const double *x, double *y, const double *b, double *q);  // y = b - A01 x and q = A01 x
+int k_spmv_full_kept(cfdh_ctx *c, const double *x, double *y, const double *q);            // y = J x with q = A01 x_p given
+int k_resid_norm(cfdh_ctx *c, const double *x, const double *b, double *r, double *nrm, bool *done);  // r = b - J x, |r|: one read-back
+int k_fnorm_nulltest(cfdh_ctx *c, int n, const double *F, double *fn, double *nrm, double *absnrm);  // one read-back
+int k_bc_scatter(cfdh_ctx *c, int n, int ncomp, const int *idx, const unsigned char *flag, const double *val, const double *mult);
+int v_pack_state(cfdh_ctx *c, const double *u_user, const double *p_user, double *dst);  // host staging helpers
+int k_functional(cfdh_ctx *c, int kind, int marker, double *out);
+int k_wss(cfdh_ctx *c, double *out);
+
+// ---- preconditioner application: AMG cycles, scalar CSR / SELL operators, Cahouet-Chabard steps (cfdh_amg_apply.hip) -----
 int k_csr_spmv(cfdh_ctx *c, const CsrDev &A, const double *x, double *y, int mode, const double *b);  // mode 0: y=Ax, 1: y=b-Ax, 2: y+=Ax
 int k_csr_spmv_ncol(cfdh_ctx *c, const CsrDev &A, const double *x, double *y, int mode, const double *b, int ncol);
 int k_amg_vcycle(cfdh_ctx *c, AmgHier &H, const double *b, double *x);
@@ -562,20 +595,14 @@ int k_ext_pack(cfdh_ctx *c, const double *vec, double *out);  // [u | p | ghost 
 int k_scatter_global(cfdh_ctx *c, int n, const int *l2g, const double *loc, double *glob);
 int k_gather_global(cfdh_ctx *c, int n, const int *l2g, const double *glob, double *loc);
 int k_cc_combine(cfdh_ctx *c, int n, double alpha, double beta, const double *t, const double *z, const double *r, const unsigned char *pbc, double *out, double *out2 = nullptr);
-int k_nullspace_test(cfdh_ctx *c, double *nrm, double *absnrm);
-// lean solve path (one rank, P1 triangles)
-int k_spmv_a01_keep(cfdh_ctx *c, const double *x, double *y, const double *b, double *q);  // y = b - A01 x and q = A01 x
-int k_spmv_full_kept(cfdh_ctx *c, const double *x, double *y, const double *q);            // y = J x with q = A01 x_p given
-int k_resid_norm(cfdh_ctx *c, const double *x, const double *b, double *r, double *nrm, bool *done);  // r = b - J x, |r|: one read-back
-int k_fnorm_nulltest(cfdh_ctx *c, int n, const double *F, double *fn, double *nrm, double *absnrm);  // one read-back
+
+// ---- vector kernels of FGMRES and of the lean solve prologue / epilogue, on [0,n) (cfdh_krylov_vec.hip) ---------------
+int v_pointwise_mult(cfdh_ctx *c, int n, const double *a, const double *b, double *out);
 int v_guess_combine(cfdh_ctx *c, int n, const double *U, const double *W, int ld, int k, const double *hd, const double *b, double *x, double *r);
 int v_guess_read(cfdh_ctx *c, int k, double *beta, bool *used, int *rank, double *y);
 int v_scale_inv_lean(cfdh_ctx *c, int n, double *x);
 int v_lincomb_keep(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const double *y_dev, double *x, double *x2);  // x += sum y_k Z_k, x2 = x
 int v_norm2_triple(cfdh_ctx *c, int n, const double *a, const double *b, const double *cc, double *out);  // three norms, one read-back
-int k_bc_scatter(cfdh_ctx *c, int n, int ncomp, const int *idx, const unsigned char *flag, const double *val, const double *mult);
-
-// vector ops on [0,n)
 int v_copy(cfdh_ctx *c, int n, const double *x, double *y);
 int v_zero(cfdh_ctx *c, int n, double *y);
 int v_axpy(cfdh_ctx *c, int n, double a, const double *x, double *y);
@@ -601,9 +628,6 @@ int v_norm_to_dev(cfdh_ctx *c, int n, const double *w, double *out_dev);  // ||w
 int v_norm_to_dev_local(cfdh_ctx *c, int n, const double *w, double *out_dev);  // no reduction over the ranks
 int v_scale_inv_dev(cfdh_ctx *c, int n, const double *w, const double *nrm_dev, double *v);  // v = w / *nrm
 int v_lincomb(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const double *y_dev, double *x);  // x += sum y_k Z_k
-int v_pack_state(cfdh_ctx *c, const double *u_user, const double *p_user, double *dst);  // host staging helpers
-int k_functional(cfdh_ctx *c, int kind, int marker, double *out);
-int k_wss(cfdh_ctx *c, double *out);
 
 // ---- scalar reductions and read-backs (cfdh_reduce.hip; words: cfdh_scratch.hpp) ----------------------------------
 // A read-back goes through a handle: which device words, how many, and whether their host-mapped copy is current.

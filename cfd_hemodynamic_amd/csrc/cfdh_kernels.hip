@@ -1,4 +1,5 @@
-// Hand-written gfx950 (CDNA4, wave64) kernels of the stabilized_schur hot path.
+// Hand-written gfx950 (CDNA4, wave64) kernels of the stabilized_schur hot path on P1 triangles: the closed-form element
+// kernels and the products with the block matrix they assemble (cfdh3_kernels.hip is the same for tetrahedra).
 //
 //  * k_moments    : tau / tau_LSIC moments per cell (stabilized_schur.py:100-118)
 //  * asm_kernel   : fused element residual + Jacobian, one lane per (row vertex, cell)
@@ -8,12 +9,13 @@
 //                   wavefront reduction -- no LDS accumulation, no atomics, fixed order
 //                   (bitwise reproducible); plain stores of complete 3x3 blocks
 //                   (stabilized_schur.py:67-123,144-175,185-189)
-//  * spmv kernels : 8 lanes per vertex row over the block CSR, DPP reductions
-//  * AMG          : fused V(1,1) Jacobi cycle on composite operators (one kernel per level
-//                   and direction), SELL-64 / fp32 on the fine levels, dense coarse solve
-//                   folded into the level above; sweep-by-sweep cycle for the other smoothers
-//                   and the distributed finest level of a partitioned run
-//  * vector kernels of FGMRES (fused multi-dot, Gram-Schmidt update + normalisation)
+//  * spmv kernels : 8 lanes per vertex row over the block CSR, DPP reductions; the lean-solve variants with their wrappers
+//  * diagonal of A00, Chebyshev on D^-1 A00, null-space test, sparse Dirichlet update
+//  * functionals, wall shear stress, halo pack
+//  * quadrature upload and the profiling brackets (prof_begin / prof_end) every kernel file uses
+//
+// The AMG cycles and the other steps of a preconditioner application live in cfdh_amg_apply.hip, the vector kernels of FGMRES
+// in cfdh_krylov_vec.hip, the scalar reductions in cfdh_reduce.hip.
 //
 // Everything is HBM-bound fp64 stream/gather work; MFMA is not used (nothing
 // here is a dense contraction).  Algebra: SURVEY.md Appendix A / DESIGN.md.
@@ -22,13 +24,8 @@
 #include <cmath>
 
 #include "cfdh_internal.hpp"
-#include "cfdh_krylov_host.hpp"
 #include "cfdh_quad_tri.h"
-
-#define TPB 256
-// streamed-once operands (matrix values / columns of the AMG sweeps): non-temporal loads keep them from evicting the
-// gathered vector entries out of the 32 KB L1
-#define NTLOAD(p) __builtin_nontemporal_load(p)
+#include "cfdh_wave.hpp"
 
 __constant__ double d_qw[CFDH_NQ];
 __constant__ double d_ql[CFDH_NQ][3];
@@ -66,8 +63,6 @@ void prof_flush(cfdh_ctx *c) {
   c->ev_pending.clear();
   c->ev_next = 0;
 }
-
-#include "cfdh_wave.hpp"
 
 // vector layout: [u owned 2*nvo | p owned nvo | ghosts (ux,uy,p) x ng]
 __device__ __forceinline__ int uoff(int w, int nvo) { return w < nvo ? 2 * w : 3 * w; }
@@ -938,6 +933,23 @@ int k_spmv_full_kept(cfdh_ctx *c, const double *x, double *y, const double *q) {
   HIPCHK(c, hipGetLastError());
   return 0;
 }
+// true residual r = b - J x and its norm with one kernel over the matrix and ONE read-back; false in *done when the partial
+// sums of this mesh do not fit the reduction workspace (the caller then takes the three-kernel path)
+int k_resid_norm(cfdh_ctx *c, const double *x, const double *b, double *r, double *nrm, bool *done) {
+  const long long nthreads = 8ll * c->nvo;
+  const long long nb = (nthreads + TPB - 1) / TPB;
+  *done = false;
+  if (c->dim != 2 || (size_t)nb > c->red_partial.n) return 0;
+  hipLaunchKernelGGL((spmv_full_lean_kernel<false, true>), dim3((unsigned)nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->vcol.p, c->A00.p,
+                     c->A01.p, c->A10.p, c->A11.p, x, r, (const double *)nullptr, b, c->red_partial.p);
+  HIPCHK(c, hipGetLastError());
+  CHK(red_final(c, 0, 1, (int)nb, (int)nb, c->red_partial.p, c->red_out.p + RO_LEAN_S2, scalars_mirror(c)));
+  double s2;
+  CHK(scalars_read(c, scalars_mirrored(1), &s2));
+  *nrm = sqrt(s2);
+  *done = true;
+  return 0;
+}
 
 __global__ __launch_bounds__(TPB) void extract_diag_kernel(int nvo, const int *__restrict__ vdiag,
                                                            const double *__restrict__ A00, double *__restrict__ dinv) {
@@ -1021,6 +1033,13 @@ __global__ __launch_bounds__(TPB) void cheb_init_kernel(int n, const double *__r
   d0[i] = v;
   x[i] = accumulate ? x[i] + v : v;
 }
+// its launch: the start of the A00 solve below and of the level smoother in cfdh_amg_apply.hip
+int k_cheb_init(cfdh_ctx *c, int n, const double *dinv, const double *b, double *d0, double *x, double itheta, int accumulate,
+                const double *coef) {
+  hipLaunchKernelGGL(cheb_init_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, dinv, b, d0, x, itheta, accumulate, coef);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
 
 // Chebyshev coefficients of the A00 solve -> device (called whenever lmaxA changes)
 int k_cheb_a00_coeffs(cfdh_ctx *c) {
@@ -1046,10 +1065,7 @@ int k_cheb_a00(cfdh_ctx *c, const double *b, double *x) {
   const int nu = 2 * c->nvo, deg = c->opt.cheb_degree;
   double *dold = c->pu1.p, *dnew = c->pu2.p, *r = c->pr.p;
   if (deg == 1) {
-    hipLaunchKernelGGL(cheb_init_kernel, dim3((nu + TPB - 1) / TPB), dim3(TPB), 0, c->stream, nu, c->dinvA.p, b, dold, x,
-                       0.0, 0, c->cheb_coef.p);
-    HIPCHK(c, hipGetLastError());
-    return 0;
+    return k_cheb_init(c, nu, c->dinvA.p, b, dold, x, 0.0, 0, c->cheb_coef.p);
   }
   const long long nthreads = 8ll * c->nvo;
   dim3 grid((unsigned)((nthreads + TPB - 1) / TPB)), block(TPB);
@@ -1063,1389 +1079,6 @@ int k_cheb_a00(cfdh_ctx *c, const double *b, double *x) {
     prof_end(c, 3);
     std::swap(dold, dnew);
   }
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------- scalar CSR operators (AMG levels)
-// All level kernels are templated on the vector element T: double (one right-hand side) or
-// double2 (two right-hand sides sharing one scalar operator: the two velocity components).
-// three right-hand sides sharing one scalar operator: the velocity components of a tetrahedral mesh
-struct d3 { double x, y, z; };
-__device__ __forceinline__ d3 vzero(const d3 *) { return d3{0.0, 0.0, 0.0}; }
-__device__ __forceinline__ d3 vfma(double a, d3 x, d3 acc) { return d3{acc.x + a * x.x, acc.y + a * x.y, acc.z + a * x.z}; }
-__device__ __forceinline__ d3 vsub(d3 a, d3 b) { return d3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ d3 vadd(d3 a, d3 b) { return d3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ d3 vscale(double a, d3 x) { return d3{a * x.x, a * x.y, a * x.z}; }
-__device__ __forceinline__ d3 g8(d3 v) { return d3{group8_sum(v.x), group8_sum(v.y), group8_sum(v.z)}; }
-__device__ __forceinline__ d3 wsum(d3 v) { return d3{wave_sum(v.x), wave_sum(v.y), wave_sum(v.z)}; }
-__device__ __forceinline__ double vzero(const double *) { return 0.0; }
-__device__ __forceinline__ double2 vzero(const double2 *) { return make_double2(0.0, 0.0); }
-__device__ __forceinline__ double vfma(double a, double x, double acc) { return acc + a * x; }
-__device__ __forceinline__ double2 vfma(double a, double2 x, double2 acc) { return make_double2(acc.x + a * x.x, acc.y + a * x.y); }
-__device__ __forceinline__ double vsub(double a, double b) { return a - b; }
-__device__ __forceinline__ double2 vsub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double vadd(double a, double b) { return a + b; }
-__device__ __forceinline__ double2 vadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double vscale(double a, double x) { return a * x; }
-__device__ __forceinline__ double2 vscale(double a, double2 x) { return make_double2(a * x.x, a * x.y); }
-__device__ __forceinline__ double g8(double v) { return group8_sum(v); }
-__device__ __forceinline__ double2 g8(double2 v) { return make_double2(group8_sum(v.x), group8_sum(v.y)); }
-__device__ __forceinline__ double wsum(double v) { return wave_sum(v); }
-__device__ __forceinline__ double2 wsum(double2 v) { return make_double2(wave_sum(v.x), wave_sum(v.y)); }
-
-// One row of a SELL-64 matrix times x, latency-oriented: at ~1 M DOF a sweep is one wave of work per SIMD lane group and
-// 85 % of a wave's life is spent waiting on memory (SQ_WAIT_ANY / SQ_WAVE_CYCLES, profiles/r02_pmc_sq_tcc.json), in a
-// chain  columns -> gathers -> next columns ...  With all column/value loads of the row issued first, then all gathers,
-// the chain is three round trips whatever the row length.  The slice width is wave-uniform: the guards are scalar branches.
-template <int MAXW, typename T>
-__device__ __forceinline__ T sell_row_dot(const int *__restrict__ sp, const int *__restrict__ sc, const float *__restrict__ sv,
-                                          const T *__restrict__ x, int sl, int lane, T a) {
-  sl = __builtin_amdgcn_readfirstlane(sl);  // wave-uniform: slice pointers and width live in scalar registers
-  const int p0 = sp[sl], w = (sp[sl + 1] - p0) >> 6;
-  int cidx[MAXW];
-  float cval[MAXW];
-#pragma unroll
-  for (int k = 0; k < MAXW; k++)
-    if (k < w) { const int p = p0 + k * 64 + lane; cidx[k] = NTLOAD(sc + p); cval[k] = NTLOAD(sv + p); }
-  T g[MAXW];
-#pragma unroll
-  for (int k = 0; k < MAXW; k++)
-    if (k < w) g[k] = x[cidx[k]];
-#pragma unroll
-  for (int k = 0; k < MAXW; k++)
-    if (k < w) a = vfma((double)cval[k], g[k], a);
-  for (int k = MAXW; k < w; k++) { const int p = p0 + k * 64 + lane; a = vfma((double)sv[p], x[sc[p]], a); }
-  return a;
-}
-
-// MODE 0: y = A x; 1: y = b - A x; 2: y += A x; 3: y = b + A x
-template <int MODE, typename T>
-__global__ __launch_bounds__(TPB) void csr_spmv_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                       const double *__restrict__ val, const T *__restrict__ x,
-                                                       T *__restrict__ y, const T *__restrict__ b) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid >> 3, l = gid & 7;
-  T a = vzero((const T *)nullptr);
-  if (row < n) {
-    const int ks = rowptr[row], ke = rowptr[row + 1];
-    for (int k = ks + l; k < ke; k += 8) a = vfma(val[k], x[col[k]], a);
-  }
-  a = g8(a);
-  if (row < n && l == 0) {
-    if (MODE == 0) y[row] = a;
-    else if (MODE == 1) y[row] = vsub(b[row], a);
-    else if (MODE == 2) y[row] = vadd(y[row], a);
-    else y[row] = vadd(b[row], a);
-  }
-}
-
-template <typename T>
-static int csr_spmv_t(cfdh_ctx *c, const CsrDev &A, const T *x, T *y, int mode, const T *b) {
-  const long long nthreads = 8ll * A.n;
-  dim3 grid((unsigned)((nthreads + TPB - 1) / TPB)), block(TPB);
-  if (mode == 0) hipLaunchKernelGGL((csr_spmv_kernel<0, T>), grid, block, 0, c->stream, A.n, A.rowptr.p, A.col.p, A.val.p, x, y, b);
-  else if (mode == 1) hipLaunchKernelGGL((csr_spmv_kernel<1, T>), grid, block, 0, c->stream, A.n, A.rowptr.p, A.col.p, A.val.p, x, y, b);
-  else if (mode == 2) hipLaunchKernelGGL((csr_spmv_kernel<2, T>), grid, block, 0, c->stream, A.n, A.rowptr.p, A.col.p, A.val.p, x, y, b);
-  else hipLaunchKernelGGL((csr_spmv_kernel<3, T>), grid, block, 0, c->stream, A.n, A.rowptr.p, A.col.p, A.val.p, x, y, b);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int k_csr_spmv(cfdh_ctx *c, const CsrDev &A, const double *x, double *y, int mode, const double *b) {
-  return csr_spmv_t<double>(c, A, x, y, mode, b);
-}
-// the same scalar matrix applied to ncol interleaved right-hand sides (velocity components through the scalar proxy)
-int k_csr_spmv_ncol(cfdh_ctx *c, const CsrDev &A, const double *x, double *y, int mode, const double *b, int ncol) {
-  if (ncol == 2) return csr_spmv_t<double2>(c, A, (const double2 *)x, (double2 *)y, mode, (const double2 *)b);
-  if (ncol == 3) return csr_spmv_t<d3>(c, A, (const d3 *)x, (d3 *)y, mode, (const d3 *)b);
-  return csr_spmv_t<double>(c, A, x, y, mode, b);
-}
-
-// One Chebyshev step on a scalar CSR level (single right-hand side):
-//   r_out = r_in - A d_old ; d_new = c1 d_old + c2 D^-1 r_out ; x (+)= ...
-// MODE 0: x += d_new.
-// MODE 1: first step of a zero-guess smoothing fused with its initialisation: d_old = D^-1 r_in / theta
-//         is formed on the fly while gathering (never stored), x = d_old + d_new.
-// MODE 2: first step after csr_resid_init_kernel (which left d_old = D^-1 r / theta unapplied): x += d_old + d_new.
-// LAST: r_out / d_new are not needed any more and are not written.
-template <int MODE, bool LAST>
-__global__ __launch_bounds__(TPB) void cheb_csr_step_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                            const double *__restrict__ val, const double *__restrict__ dinv,
-                                                            const double *__restrict__ rin, double *__restrict__ rout,
-                                                            const double *__restrict__ dold, double *__restrict__ dnew,
-                                                            double *__restrict__ x, double c1, double c2, double itheta) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid >> 3, l = gid & 7;
-  double a = 0;
-  if (row < n) {
-    const int ks = rowptr[row], ke = rowptr[row + 1];
-    for (int k = ks + l; k < ke; k += 8) {
-      const int j = col[k];
-      a += val[k] * (MODE == 1 ? dinv[j] * rin[j] * itheta : dold[j]);
-    }
-  }
-  a = group8_sum(a);
-  if (row < n && l == 0) {
-    const double di = dinv[row], ri = rin[row];
-    const double dd = (MODE == 1) ? di * ri * itheta : dold[row];
-    const double r = ri - a;
-    const double dn = c1 * dd + c2 * di * r;
-    if (!LAST) { rout[row] = r; dnew[row] = dn; }
-    if (MODE == 0) x[row] += dn;
-    else if (MODE == 1) x[row] = dd + dn;
-    else x[row] += dd + dn;
-  }
-}
-
-// r = b - A x ; d0 = D^-1 r / theta   (residual of a non-zero guess fused with the Chebyshev initialisation)
-__global__ __launch_bounds__(TPB) void csr_resid_init_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                             const double *__restrict__ val, const double *__restrict__ dinv,
-                                                             const double *__restrict__ b, const double *__restrict__ x,
-                                                             double *__restrict__ r, double *__restrict__ d0, double itheta) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid >> 3, l = gid & 7;
-  double a = 0;
-  if (row < n) {
-    const int ks = rowptr[row], ke = rowptr[row + 1];
-    for (int k = ks + l; k < ke; k += 8) a += val[k] * x[col[k]];
-  }
-  a = group8_sum(a);
-  if (row < n && l == 0) {
-    const double rr = b[row] - a;
-    r[row] = rr;
-    d0[row] = dinv[row] * rr * itheta;
-  }
-}
-
-// Chebyshev smoothing with the level operator (ncol = 1): zero_guess ? x = S b : x <- x + S (b - A x)
-static int level_cheb(cfdh_ctx *c, AmgLevel *L, const double *b, double *x, bool zero_guess, int deg, bool prof) {
-  const int n = L->n;
-  const double theta = 0.5 * (L->lmax + L->lmin), delta = 0.5 * (L->lmax - L->lmin), sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  double *dold = L->d0.p, *dnew = L->d1.p, *r = L->r.p;
-  const double *rin = b;
-  const double itheta = 1.0 / theta;
-  const long long nthreads = 8ll * n;
-  dim3 grid((unsigned)((nthreads + TPB - 1) / TPB)), block(TPB);
-  const int *rp = L->A.rowptr.p, *cl = L->A.col.p;
-  const double *vl = L->A.val.p, *di = L->dinv.p;
-  if (deg == 1) {  // plain damped Jacobi
-    if (!zero_guess) { CHK(k_csr_spmv(c, L->A, x, r, 1, b)); rin = r; }
-    hipLaunchKernelGGL(cheb_init_kernel, dim3((n + TPB - 1) / TPB), block, 0, c->stream, n, di, rin, dold, x, itheta,
-                       zero_guess ? 0 : 1, (const double *)nullptr);
-    HIPCHK(c, hipGetLastError());
-    return 0;
-  }
-  if (!zero_guess) {
-    hipLaunchKernelGGL(csr_resid_init_kernel, grid, block, 0, c->stream, n, rp, cl, vl, di, b, x, r, dold, itheta);
-    rin = r;
-  }
-  for (int k = 1; k < deg; k++) {
-    const double rho_new = 1.0 / (2.0 * sigma - rho);
-    const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-    const bool last = (k == deg - 1);
-    const int mode = (k == 1) ? (zero_guess ? 1 : 2) : 0;
-    if (prof) prof_begin(c, 4);
-#define LAUNCH_STEP(M, LST) hipLaunchKernelGGL((cheb_csr_step_kernel<M, LST>), grid, block, 0, c->stream, n, rp, cl, vl, di, rin, r, dold, dnew, x, c1, c2, itheta)
-    if (mode == 1) { if (last) LAUNCH_STEP(1, true); else LAUNCH_STEP(1, false); }
-    else if (mode == 2) { if (last) LAUNCH_STEP(2, true); else LAUNCH_STEP(2, false); }
-    else { if (last) LAUNCH_STEP(0, true); else LAUNCH_STEP(0, false); }
-#undef LAUNCH_STEP
-    if (prof) prof_end(c, 4);
-    rin = r;
-    std::swap(dold, dnew);
-    rho = rho_new;
-  }
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int k_level_smooth(cfdh_ctx *c, AmgLevel *L, const double *b, double *x, int degree) { return level_cheb(c, L, b, x, true, degree, false); }
-
-// Two Chebyshev steps from a zero guess on a SELL-64 level in ONE pass over the matrix, with the
-// Cahouet-Chabard scaling fused:  d = w D^-1 b ; r = b - A d ; x = d + (c1 d + c2 D^-1 r) ; y = ml .* x.
-// (svalw carries the column weights w D^-1, as in the Jacobi pre-sweep.)
-__global__ __launch_bounds__(TPB) void sell_cheb2_scale_kernel(int n, const int *__restrict__ sptr, const int *__restrict__ scol,
-                                                               const float *__restrict__ svalw, const double *__restrict__ wdinv,
-                                                               const double *__restrict__ dinv, const double *__restrict__ b,
-                                                               double *__restrict__ x, const double *__restrict__ ml,
-                                                               double *__restrict__ y, double c1, double c2) {
-  const int row = blockIdx.x * TPB + threadIdx.x;
-  if (row >= n) return;
-  const int sl = row >> 6, lane = row & 63;
-  const int p0 = sptr[sl], w = (sptr[sl + 1] - p0) >> 6;
-  (void)p0; (void)w;
-  const double a = sell_row_dot<10, double>(sptr, scol, svalw, b, sl, lane, 0.0);
-  const double bi = b[row];
-  const double dd = wdinv[row] * bi;
-  const double xv = dd + (c1 * dd + c2 * dinv[row] * (bi - a));
-  x[row] = xv;
-  y[row] = ml[row] * xv;
-}
-// x = Cheb2(H) b and y = ml .* x; false when the level does not qualify (the caller takes the generic path)
-bool k_cc_cheb2_scale(cfdh_ctx *c, AmgLevel *L, const double *b, double *x, const double *ml, double *y) {
-  const int n = L->n;
-  if (!(L->A.nnz <= 20ll * n && n >= 16384)) return false;  // rows of up to ~15 entries (tetrahedra): 10 preloaded + tail
-  const double theta = 0.5 * (L->lmax + L->lmin), delta = 0.5 * (L->lmax - L->lmin), sigma = theta / delta;
-  const double rho = 1.0 / sigma, rho_new = 1.0 / (2.0 * sigma - rho);
-  const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-  hipLaunchKernelGGL(sell_cheb2_scale_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, L->A.sptr.p, L->A.scol.p,
-                     L->A.svalw.p, L->wdinv.p, L->dinv.p, b, x, ml, y, c1, c2);
-  return hipGetLastError() == hipSuccess;
-}
-
-// y = Minv b for the dense coarsest inverse: one wave per row
-template <typename T>
-__global__ __launch_bounds__(64) void dense_mv_kernel(int n, const double *__restrict__ Minv, const T *__restrict__ b,
-                                                      T *__restrict__ y) {
-  const int row = blockIdx.x, l = threadIdx.x;
-  T a = vzero((const T *)nullptr);
-  for (int k = l; k < n; k += 64) a = vfma(Minv[(size_t)row * n + k], b[k], a);
-  a = wsum(a);
-  if (l == 0) y[row] = a;
-}
-
-// damped-Jacobi V-cycle building blocks: each touches the level matrix once.  A row whose only entry is
-// its diagonal (Dirichlet row, isolated unknown) is solved exactly (weight 1 instead of 1/theta).
-//   pre : xa = w D^-1 b (formed while gathering) ; r = b - A xa
-//   post: x_out = x_in + w D^-1 (b - A x_in)
-template <typename T>
-__global__ __launch_bounds__(TPB) void jacobi_pre_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                         const double *__restrict__ val, const double *__restrict__ wdinv,
-                                                         const T *__restrict__ b, T *__restrict__ xa, T *__restrict__ r) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid >> 3, l = gid & 7;
-  T a = vzero((const T *)nullptr);
-  if (row < n) {
-    const int ks = rowptr[row], ke = rowptr[row + 1];
-    for (int k = ks + l; k < ke; k += 8) {
-      const int j = col[k];
-      a = vfma(val[k] * wdinv[j], b[j], a);
-    }
-  }
-  a = g8(a);
-  if (row < n && l == 0) {
-    const T bi = b[row];
-    xa[row] = vscale(wdinv[row], bi);
-    r[row] = vsub(bi, a);
-  }
-}
-template <typename T>
-__global__ __launch_bounds__(TPB) void jacobi_post_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                          const double *__restrict__ val, const double *__restrict__ wdinv,
-                                                          const T *__restrict__ b, const T *__restrict__ xin,
-                                                          T *__restrict__ xout) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid >> 3, l = gid & 7;
-  T a = vzero((const T *)nullptr);
-  if (row < n) {
-    const int ks = rowptr[row], ke = rowptr[row + 1];
-    for (int k = ks + l; k < ke; k += 8) a = vfma(val[k], xin[col[k]], a);
-  }
-  a = g8(a);
-  if (row < n && l == 0) {
-    xout[row] = vadd(xin[row], vscale(wdinv[row], vsub(b[row], a)));
-  }
-}
-
-// ---- SELL-64 variants: one lane per row, fully coalesced matrix stream, no cross-lane reduction
-template <int MODE, typename T>
-__global__ __launch_bounds__(TPB) void sell_spmv_kernel(int n, const int *__restrict__ sptr, const int *__restrict__ scol,
-                                                        const float *__restrict__ sval, const T *__restrict__ x,
-                                                        T *__restrict__ y, const T *__restrict__ b) {
-  const int row = blockIdx.x * TPB + threadIdx.x;
-  if (row >= n) return;
-  const int sl = row >> 6, lane = row & 63;
-  const int p0 = sptr[sl], w = (sptr[sl + 1] - p0) >> 6;
-  T a = vzero((const T *)nullptr);
-#pragma unroll 4
-  for (int k = 0; k < w; k++) {
-    const int p = p0 + k * 64 + lane;
-    a = vfma((double)sval[p], x[scol[p]], a);
-  }
-  if (MODE == 0) y[row] = a;
-  else if (MODE == 1) y[row] = vsub(b[row], a);
-  else if (MODE == 2) y[row] = vadd(y[row], a);
-  else y[row] = vadd(b[row], a);
-}
-template <typename T>
-__global__ __launch_bounds__(TPB) void sell_jacobi_pre_kernel(int n, const int *__restrict__ sptr, const int *__restrict__ scol,
-                                                              const float *__restrict__ svalw, const double *__restrict__ wdinv,
-                                                              const T *__restrict__ b, T *__restrict__ xa, T *__restrict__ r) {
-  const int row = blockIdx.x * TPB + threadIdx.x;
-  if (row >= n) return;
-  const int sl = row >> 6, lane = row & 63;
-  const int p0 = sptr[sl], w = (sptr[sl + 1] - p0) >> 6;
-  T a = vzero((const T *)nullptr);
-#pragma unroll 4
-  for (int k = 0; k < w; k++) {
-    const int p = p0 + k * 64 + lane;
-    a = vfma((double)svalw[p], b[scol[p]], a);   // A (w D^-1 b): the column weight is folded into svalw
-  }
-  const T bi = b[row];
-  xa[row] = vscale(wdinv[row], bi);
-  r[row] = vsub(bi, a);
-}
-template <typename T>
-__global__ __launch_bounds__(TPB) void sell_jacobi_post_kernel(int n, const int *__restrict__ sptr, const int *__restrict__ scol,
-                                                               const float *__restrict__ sval, const double *__restrict__ wdinv,
-                                                               const T *__restrict__ b, const T *__restrict__ xin,
-                                                               T *__restrict__ xout) {
-  const int row = blockIdx.x * TPB + threadIdx.x;
-  if (row >= n) return;
-  const int sl = row >> 6, lane = row & 63;
-  const int p0 = sptr[sl], w = (sptr[sl + 1] - p0) >> 6;
-  T a = vzero((const T *)nullptr);
-#pragma unroll 4
-  for (int k = 0; k < w; k++) {
-    const int p = p0 + k * 64 + lane;
-    a = vfma((double)sval[p], xin[scol[p]], a);
-  }
-  xout[row] = vadd(xin[row], vscale(wdinv[row], vsub(b[row], a)));
-}
-
-template <typename T>
-static int amg_cycle_jacobi(cfdh_ctx *c, AmgHier &H, size_t lev, const T *b, T *x, int prof) {
-  AmgLevel *L = H.lev[lev];
-  if (lev + 1 == H.lev.size()) {
-    if (H.coarse_n > 0) {
-      hipLaunchKernelGGL((dense_mv_kernel<T>), dim3(H.coarse_n), dim3(64), 0, c->stream, H.coarse_n, H.coarse_inv.p, b, x);
-    } else {
-      // near-diagonal coarsest level (coarsening stalled, cfdh_amg_setup): two damped-Jacobi sweeps
-      const int n = L->n;
-      dim3 block(TPB), gridC((unsigned)((8ll * n + TPB - 1) / TPB));
-      T *xa = (T *)L->d0.p, *r = (T *)L->r.p;
-      hipLaunchKernelGGL((jacobi_pre_kernel<T>), gridC, block, 0, c->stream, n, L->A.rowptr.p, L->A.col.p, L->A.val.p,
-                         L->wdinv.p, b, xa, r);
-      hipLaunchKernelGGL((jacobi_post_kernel<T>), gridC, block, 0, c->stream, n, L->A.rowptr.p, L->A.col.p, L->A.val.p,
-                         L->wdinv.p, b, (const T *)xa, x);
-    }
-    HIPCHK(c, hipGetLastError());
-    return 0;
-  }
-  AmgLevel *N = H.lev[lev + 1];
-  const int n = L->n;
-  // short, regular rows (the finest levels of FE operators): SELL-64, one lane per row;
-  // long coarse-level rows: 8 lanes per row over CSR
-  const bool sell = L->A.nnz <= 12ll * n && n >= 16384;
-  dim3 block(TPB), gridS((unsigned)((n + TPB - 1) / TPB)), gridC((unsigned)((8ll * n + TPB - 1) / TPB));
-  T *xa = (T *)L->d0.p, *x1 = (T *)L->d1.p, *r = (T *)L->r.p;
-  if (prof && lev == 0) prof_begin(c, prof);
-  if (sell)
-    hipLaunchKernelGGL((sell_jacobi_pre_kernel<T>), gridS, block, 0, c->stream, n, L->A.sptr.p, L->A.scol.p, L->A.svalw.p,
-                       L->wdinv.p, b, xa, r);
-  else
-    hipLaunchKernelGGL((jacobi_pre_kernel<T>), gridC, block, 0, c->stream, n, L->A.rowptr.p, L->A.col.p, L->A.val.p,
-                       L->wdinv.p, b, xa, r);
-  if (prof && lev == 0) prof_end(c, prof);
-  CHK(csr_spmv_t<T>(c, L->R, r, (T *)N->b.p, 0, (const T *)nullptr));   // b_c = R r
-  CHK(amg_cycle_jacobi<T>(c, H, lev + 1, (const T *)N->b.p, (T *)N->x.p, prof));
-  if (sell)
-    hipLaunchKernelGGL((sell_spmv_kernel<3, T>), gridS, block, 0, c->stream, n, L->P.sptr.p, L->P.scol.p, L->P.sval.p,
-                       (const T *)N->x.p, x1, (const T *)xa);           // x1 = xa + P x_c
-  else
-    CHK(csr_spmv_t<T>(c, L->P, (const T *)N->x.p, x1, 3, xa));
-  if (prof && lev == 0) prof_begin(c, prof);
-  if (sell)
-    hipLaunchKernelGGL((sell_jacobi_post_kernel<T>), gridS, block, 0, c->stream, n, L->A.sptr.p, L->A.scol.p, L->A.sval.p,
-                       L->wdinv.p, b, x1, x);
-  else
-    hipLaunchKernelGGL((jacobi_post_kernel<T>), gridC, block, 0, c->stream, n, L->A.rowptr.p, L->A.col.p, L->A.val.p,
-                       L->wdinv.p, b, x1, x);
-  if (prof && lev == 0) prof_end(c, prof);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// ---- fused V(1,1) Jacobi cycle: one kernel per level and direction on precomputed composite operators
-// (AmgLevel::G / Sb / Sc / D, built in cfdh_amg_setup).  Same linear map as amg_cycle_jacobi.
-template <int LPR>
-__device__ __forceinline__ double lpr_sum(double v) {
-  v = group8_sum(v);
-  if (LPR >= 16) v += dpp_shuffle<0x140>(v);  // row_mirror: sums of 16
-  if (LPR >= 32) v += __shfl_xor(v, 16);
-  if (LPR >= 64) v += __shfl_xor(v, 32);
-  return v;
-}
-template <int LPR> __device__ __forceinline__ double lsum(double v) { return lpr_sum<LPR>(v); }
-template <int LPR> __device__ __forceinline__ double2 lsum(double2 v) { return make_double2(lpr_sum<LPR>(v.x), lpr_sum<LPR>(v.y)); }
-template <int LPR> __device__ __forceinline__ d3 lsum(d3 v) { return d3{lpr_sum<LPR>(v.x), lpr_sum<LPR>(v.y), lpr_sum<LPR>(v.z)}; }
-
-__device__ __forceinline__ double epi_apply(double acc, int row, double alpha, double beta, const double *zH, const double *r, const unsigned char *pbc) {
-  return (pbc[row] & 1) ? r[row] : alpha * acc + beta * zH[row];
-}
-__device__ __forceinline__ double2 epi_apply(double2 acc, int, double, double, const double *, const double *, const unsigned char *) { return acc; }
-__device__ __forceinline__ double epi_value(double acc, unsigned flag, double alpha, double beta, double zh, double r) { return (flag & 1u) ? r : alpha * acc + beta * zh; }
-__device__ __forceinline__ double2 epi_value(double2 acc, unsigned, double, double, double, double) { return acc; }
-__device__ __forceinline__ d3 epi_apply(d3 acc, int, double, double, const double *, const double *, const unsigned char *) { return acc; }
-__device__ __forceinline__ d3 epi_value(d3 acc, unsigned, double, double, double, double) { return acc; }
-
-// y = G x, LPR lanes per row (rows of the coarse level: tens to hundreds of entries)
-template <int LPR, typename VT, typename T>
-__global__ __launch_bounds__(TPB) void fused_down_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                         const VT *__restrict__ val, const T *__restrict__ x, T *__restrict__ y) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid / LPR, l = gid % LPR;
-  T a = vzero((const T *)nullptr);
-  if (row < n) {
-    const int ks = rowptr[row], ke = rowptr[row + 1];
-    // up to four entries per lane with all loads in flight together, then the gathers (see sell_row_dot)
-    int cidx[4];
-    VT cval[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) { const int k = ks + l + q * LPR; if (k < ke) { cidx[q] = col[k]; cval[q] = val[k]; } }
-    T g[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) { const int k = ks + l + q * LPR; if (k < ke) g[q] = x[cidx[q]]; }
-#pragma unroll
-    for (int q = 0; q < 4; q++) { const int k = ks + l + q * LPR; if (k < ke) a = vfma((double)cval[q], g[q], a); }
-    for (int k = ks + l + 4 * LPR; k < ke; k += LPR) a = vfma((double)val[k], x[col[k]], a);
-  }
-  a = lsum<LPR>(a);
-  if (row < n && l == 0) y[row] = a;
-}
-// x = Sb b + Sc xc  (Sc may be absent: smoothing-only coarsest level), 8 lanes per row over CSR
-template <typename T>
-__global__ __launch_bounds__(TPB) void fused_up_csr_kernel(int n, const int *__restrict__ rpB, const int *__restrict__ clB,
-                                                           const double *__restrict__ vlB, const T *__restrict__ b,
-                                                           const int *__restrict__ rpC, const int *__restrict__ clC,
-                                                           const double *__restrict__ vlC, const T *__restrict__ xc,
-                                                           T *__restrict__ x, double ea, double eb, const double *__restrict__ ezH,
-                                                           const double *__restrict__ er, const unsigned char *__restrict__ epbc) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid >> 3, l = gid & 7;
-  T a = vzero((const T *)nullptr);
-  if (row < n) {
-    // two entries of each matrix per lane requested together, then their gathers (rows of 10-30 entries on the coarse levels:
-    // the plain loops make two to four dependent round trips per matrix)
-    const int kb = rpB[row] + l, keB = rpB[row + 1];
-    int kc = 0, keC = 0;
-    if (rpC) { kc = rpC[row] + l; keC = rpC[row + 1]; }
-    int cb[2], cc[2];
-    double vb[2], vc[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      if (kb + 8 * q < keB) { cb[q] = clB[kb + 8 * q]; vb[q] = vlB[kb + 8 * q]; }
-      if (kc + 8 * q < keC) { cc[q] = clC[kc + 8 * q]; vc[q] = vlC[kc + 8 * q]; }
-    }
-    T gb[2], gc[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      if (kb + 8 * q < keB) gb[q] = b[cb[q]];
-      if (kc + 8 * q < keC) gc[q] = xc[cc[q]];
-    }
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      if (kb + 8 * q < keB) a = vfma(vb[q], gb[q], a);
-      if (kc + 8 * q < keC) a = vfma(vc[q], gc[q], a);
-    }
-    for (int k = kb + 16; k < keB; k += 8) a = vfma(vlB[k], b[clB[k]], a);
-    for (int k = kc + 16; k < keC; k += 8) a = vfma(vlC[k], xc[clC[k]], a);
-  }
-  a = g8(a);
-  if (row < n && l == 0) x[row] = epbc ? epi_apply(a, row, ea, eb, ezH, er, epbc) : a;
-}
-// the same on SELL-64 (fp32 values), one lane per row.  WIDE: rows longer than one chunk of preloaded entries (tetrahedra)
-template <typename T, bool WIDE>
-__global__ __launch_bounds__(TPB) void fused_up_sell_kernel(int n, const int *__restrict__ spB, const int *__restrict__ scB,
-                                                            const float *__restrict__ svB, const T *__restrict__ b,
-                                                            const int *__restrict__ spC, const int *__restrict__ scC,
-                                                            const float *__restrict__ svC, const T *__restrict__ xc,
-                                                            T *__restrict__ x, double ea, double eb, const double *__restrict__ ezH,
-                                                            const double *__restrict__ er, const unsigned char *__restrict__ epbc) {
-  const int row = blockIdx.x * TPB + threadIdx.x;
-  if (row >= n) return;
-  const int sl = __builtin_amdgcn_readfirstlane(row >> 6), lane = row & 63;
-  T a = vzero((const T *)nullptr);
-  // operands of the epilogue: requested now, so that they arrive together with the matrix data
-  double e_zh = 0.0, e_r = 0.0;
-  unsigned e_f = 0;
-  if (epbc) { e_f = epbc[row]; e_zh = ezH[row]; e_r = er[row]; }
-  // both matrices together: slice pointers, then ALL column/value loads of a chunk of the row, then ALL its gathers (three
-  // dependent round trips; the straightforward loops make about ten).  Triangle meshes need one chunk (rows of <= 10
-  // entries), the 15- to 25-entry rows of tetrahedral meshes two or three.
-  constexpr int MW = sizeof(T) > 8 ? 8 : 10;
-  const int pB = spB[sl], wB = (spB[sl + 1] - pB) >> 6;
-  int pC = 0, wC = 0;
-  if (spC) { pC = spC[sl]; wC = (spC[sl + 1] - pC) >> 6; }
-  const int wmax = wB > wC ? wB : wC;
-  for (int k0 = 0; k0 < (WIDE ? wmax : 1); k0 += MW) {
-    int cB[MW], cC[MW];
-    float vB[MW], vC[MW];
-#pragma unroll
-    for (int k = 0; k < MW; k++) if (k0 + k < wB) { const int p = pB + (k0 + k) * 64 + lane; cB[k] = NTLOAD(scB + p); vB[k] = NTLOAD(svB + p); }
-#pragma unroll
-    for (int k = 0; k < MW; k++) if (k0 + k < wC) { const int p = pC + (k0 + k) * 64 + lane; cC[k] = NTLOAD(scC + p); vC[k] = NTLOAD(svC + p); }
-    T gB[MW], gC[MW];
-#pragma unroll
-    for (int k = 0; k < MW; k++) if (k0 + k < wB) gB[k] = b[cB[k]];
-#pragma unroll
-    for (int k = 0; k < MW; k++) if (k0 + k < wC) gC[k] = xc[cC[k]];
-#pragma unroll
-    for (int k = 0; k < MW; k++) if (k0 + k < wB) a = vfma((double)vB[k], gB[k], a);
-#pragma unroll
-    for (int k = 0; k < MW; k++) if (k0 + k < wC) a = vfma((double)vC[k], gC[k], a);
-  }
-  if (!WIDE) {  // rows beyond the chunk (none on triangle meshes)
-    for (int k = MW; k < wB; k++) { const int p = pB + k * 64 + lane; a = vfma((double)svB[p], b[scB[p]], a); }
-    for (int k = MW; k < wC; k++) { const int p = pC + k * 64 + lane; a = vfma((double)svC[p], xc[scC[p]], a); }
-  }
-  x[row] = epbc ? epi_value(a, e_f, ea, eb, e_zh, e_r) : a;
-}
-// x = Sb b + D bc with the dense folded coarse correction D [n][nc] (fp32), one wave per row
-template <typename T>
-__global__ __launch_bounds__(TPB) void fused_up_dense_kernel(int n, const int *__restrict__ rpB, const int *__restrict__ clB,
-                                                             const double *__restrict__ vlB, const T *__restrict__ b,
-                                                             const float *__restrict__ D, int nc, const T *__restrict__ bc,
-                                                             T *__restrict__ x) {
-  const int gid = blockIdx.x * TPB + threadIdx.x;
-  const int row = gid >> 6, l = gid & 63;
-  T a = vzero((const T *)nullptr);
-  if (row < n) {
-    for (int k = rpB[row] + l, ke = rpB[row + 1]; k < ke; k += 64) a = vfma(vlB[k], b[clB[k]], a);
-    const float *Dr = D + (size_t)row * nc;
-    // the whole row in flight at once when it fits 12 steps (coarsest levels of <= 768 unknowns), remainder in a loop
-    float dv[12];
-    T bv[12];
-#pragma unroll
-    for (int q = 0; q < 12; q++) { const int j = l + 64 * q; if (j < nc) { dv[q] = Dr[j]; bv[q] = bc[j]; } }
-#pragma unroll
-    for (int q = 0; q < 12; q++) { const int j = l + 64 * q; if (j < nc) a = vfma((double)dv[q], bv[q], a); }
-    for (int j = l + 768; j < nc; j += 64) a = vfma((double)Dr[j], bc[j], a);
-  }
-  a = wsum(a);
-  if (row < n && l == 0) x[row] = a;
-}
-
-template <typename VT, typename T>
-static void launch_down(cfdh_ctx *c, const CsrDev &G, const VT *val, const T *x, T *y) {
-  const long long avg = G.n > 0 ? (G.nnz + G.n - 1) / G.n : 1;
-  const int lpr = avg > 96 ? 64 : (avg > 48 ? 32 : (avg > 20 ? 16 : 8));  // 2-4 entries per lane, loaded together
-  dim3 block(TPB), grid((unsigned)(((long long)G.n * lpr + TPB - 1) / TPB));
-  if (lpr == 64) hipLaunchKernelGGL((fused_down_kernel<64, VT, T>), grid, block, 0, c->stream, G.n, G.rowptr.p, G.col.p, val, x, y);
-  else if (lpr == 32) hipLaunchKernelGGL((fused_down_kernel<32, VT, T>), grid, block, 0, c->stream, G.n, G.rowptr.p, G.col.p, val, x, y);
-  else if (lpr == 16) hipLaunchKernelGGL((fused_down_kernel<16, VT, T>), grid, block, 0, c->stream, G.n, G.rowptr.p, G.col.p, val, x, y);
-  else hipLaunchKernelGGL((fused_down_kernel<8, VT, T>), grid, block, 0, c->stream, G.n, G.rowptr.p, G.col.p, val, x, y);
-}
-
-template <typename T>
-// l0 > 0: the cycle of the levels l0 .. (the replicated levels of a partitioned run below its distributed finest pressure level);
-// b / x are then level l0's vectors
-static int amg_cycle_fused(cfdh_ctx *c, AmgHier &H, const T *b, T *x, int prof, int l0 = 0) {
-  const int nl = (int)H.lev.size();
-  // down: right-hand sides of all coarse levels.  (Merging the coarse levels' down-sweeps into one launch through the
-  // products G_2 G_1, ... was measured and dropped: the products fill in -- 1.1 M entries for a 713-row level -- and the one
-  // launch costs more than the two it replaces.)
-  for (int l = l0; l + 1 < nl; l++) {
-    AmgLevel *L = H.lev[l], *N = H.lev[l + 1];
-    const T *src = l == l0 ? b : (const T *)L->b.p;
-    if (prof && l == 0) prof_begin(c, prof + 4);
-    if (L->fine) launch_down<float, T>(c, L->G, L->G.valf.p, src, (T *)N->b.p);
-    else launch_down<double, T>(c, L->G, L->G.val.p, src, (T *)N->b.p);
-    if (prof && l == 0) prof_end(c, prof + 4);
-  }
-  // coarsest level (or the level above it when the dense solve is folded into its up-sweep)
-  int l = nl - 1;
-  {
-    AmgLevel *L = H.lev[l];
-    const T *bl = l == l0 ? b : (const T *)L->b.p;
-    T *xl = l == l0 ? x : (T *)L->x.p;
-    if (nl - 2 >= l0 && H.lev[nl - 2]->Dn > 0) {
-      AmgLevel *U = H.lev[nl - 2];
-      const T *bu = nl - 2 == l0 ? b : (const T *)U->b.p;
-      T *xu = nl - 2 == l0 ? x : (T *)U->x.p;
-      // (a two-level hierarchy: this IS the finest up-sweep -- owned rows only where the caller keeps just those)
-      const int un = (nl - 2 == 0 && c->up0_rows > 0 && c->up0_rows < U->n) ? c->up0_rows : U->n;
-      hipLaunchKernelGGL((fused_up_dense_kernel<T>), dim3((unsigned)((64ll * un + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, un,
-                         U->Sb.rowptr.p, U->Sb.col.p, U->Sb.val.p, bu, U->D.p, U->Dn, bl, xu);
-      l = nl - 3;
-    } else {
-      if (H.coarse_n > 0)
-        hipLaunchKernelGGL((dense_mv_kernel<T>), dim3(H.coarse_n), dim3(64), 0, c->stream, H.coarse_n, H.coarse_inv.p, bl, xl);
-      else if (L->sell)
-        hipLaunchKernelGGL((fused_up_sell_kernel<T, true>), dim3((unsigned)((L->n + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, L->n,
-                           L->Sb.sptr.p, L->Sb.scol.p, L->Sb.sval.p, bl, (const int *)nullptr, (const int *)nullptr,
-                           (const float *)nullptr, (const T *)nullptr, xl, 0.0, 0.0, (const double *)nullptr, (const double *)nullptr,
-                           (const unsigned char *)nullptr);
-      else
-        hipLaunchKernelGGL((fused_up_csr_kernel<T>), dim3((unsigned)((8ll * L->n + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, L->n,
-                           L->Sb.rowptr.p, L->Sb.col.p, L->Sb.val.p, bl, (const int *)nullptr, (const int *)nullptr,
-                           (const double *)nullptr, (const T *)nullptr, xl, 0.0, 0.0, (const double *)nullptr, (const double *)nullptr,
-                           (const unsigned char *)nullptr);
-      l = nl - 2;
-    }
-  }
-  // up
-  for (; l >= l0; l--) {
-    AmgLevel *L = H.lev[l], *N = H.lev[l + 1];
-    const T *bl = l == l0 ? b : (const T *)L->b.p;
-    T *xl = l == l0 ? x : (T *)L->x.p;
-    // Cahouet-Chabard combination in the epilogue of the last kernel of the (single right-hand side) pressure cycle
-    const bool epi = l == 0 && c->epi.on && sizeof(T) == sizeof(double);
-    const double ea = epi ? c->epi.alpha : 0.0, eb = epi ? c->epi.beta : 0.0;
-    const double *ezH = epi ? c->epi.zH : nullptr, *er = epi ? c->epi.r : nullptr;
-    const unsigned char *epbc = epi ? c->epi.pbc : nullptr;
-    if (epi) { xl = (T *)c->epi.out; c->epi.done = true; }
-    // overlapping velocity cycle of a partitioned run: only the owned rows (the first ones) of the finest level's result are kept
-    const int nrow = (l == 0 && c->up0_rows > 0 && c->up0_rows < L->n) ? c->up0_rows : L->n;
-    if (prof && l == 0) prof_begin(c, prof);
-    // a few longer rows (irregular vertices of a triangle mesh) go through the tail loop of the one-chunk kernel; the chunked
-    // kernel is for meshes whose typical row exceeds a chunk (tetrahedra)
-    if (L->sell && L->Sb.sell_maxw <= 14 && L->Sc.sell_maxw <= 14)
-      hipLaunchKernelGGL((fused_up_sell_kernel<T, false>), dim3((unsigned)((nrow + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, nrow,
-                         L->Sb.sptr.p, L->Sb.scol.p, L->Sb.sval.p, bl, L->Sc.sptr.p, L->Sc.scol.p, L->Sc.sval.p, (const T *)N->x.p, xl,
-                         ea, eb, ezH, er, epbc);
-    else if (L->sell)
-      hipLaunchKernelGGL((fused_up_sell_kernel<T, true>), dim3((unsigned)((nrow + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, nrow,
-                         L->Sb.sptr.p, L->Sb.scol.p, L->Sb.sval.p, bl, L->Sc.sptr.p, L->Sc.scol.p, L->Sc.sval.p, (const T *)N->x.p, xl,
-                         ea, eb, ezH, er, epbc);
-    else
-      hipLaunchKernelGGL((fused_up_csr_kernel<T>), dim3((unsigned)((8ll * nrow + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, nrow,
-                         L->Sb.rowptr.p, L->Sb.col.p, L->Sb.val.p, bl, L->Sc.rowptr.p, L->Sc.col.p, L->Sc.val.p, (const T *)N->x.p, xl,
-                         ea, eb, ezH, er, epbc);
-    if (prof && l == 0) prof_end(c, prof);
-  }
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// V-cycle with Chebyshev smoothing of degree >= 2 (single right-hand side)
-static int amg_cycle_cheb(cfdh_ctx *c, AmgHier &H, size_t lev, const double *b, double *x, bool prof) {
-  AmgLevel *L = H.lev[lev];
-  if (lev + 1 == H.lev.size()) {
-    if (H.coarse_n > 0) {
-      hipLaunchKernelGGL((dense_mv_kernel<double>), dim3(H.coarse_n), dim3(64), 0, c->stream, H.coarse_n, H.coarse_inv.p, b, x);
-      HIPCHK(c, hipGetLastError());
-      return 0;
-    }
-    return level_cheb(c, L, b, x, true, c->opt.amg_smooth_degree > 2 ? c->opt.amg_smooth_degree : 2, false);  // near-diagonal coarsest level: smoothing only
-  }
-  AmgLevel *N = H.lev[lev + 1];
-  const int deg = c->opt.amg_smooth_degree;
-  CHK(level_cheb(c, L, b, x, true, deg, prof && lev == 0));
-  CHK(k_csr_spmv(c, L->A, x, L->r.p, 1, b));     // r = b - A x
-  CHK(k_csr_spmv(c, L->R, L->r.p, N->b.p, 0, nullptr));  // b_c = R r
-  CHK(amg_cycle_cheb(c, H, lev + 1, N->b.p, N->x.p, prof));
-  CHK(k_csr_spmv(c, L->P, N->x.p, x, 2, nullptr));  // x += P x_c
-  CHK(level_cheb(c, L, b, x, false, deg, prof && lev == 0));
-  return 0;
-}
-
-// ---- distributed finest level of the replicated pressure hierarchy (cfdh_ctx::DistL0)
-// b_loc = pressure slot of a halo-layout vector on owned + ghost vertices; xa = w D^-1 b on all of them
-__global__ __launch_bounds__(TPB) void dl0_pack_kernel(int nvo, int nv, int dim, const double *__restrict__ vec, const double *__restrict__ wdinv,
-                                                       double *__restrict__ b, double *__restrict__ xa, int ghosts) {
-  const int i = blockIdx.x * TPB + threadIdx.x;
-  if (i >= nv) return;
-  // pressure slot: owned at dim nvo + i, ghost record (u..., p) of dim + 1 doubles behind the owned part
-  // ghosts == 0: the ghost layer of the right-hand side was not exchanged -- the pre-smoothed iterate is taken as zero there
-  const double v = i < nvo ? vec[(size_t)dim * nvo + i] : (ghosts ? vec[((size_t)dim + 1) * nvo + ((size_t)dim + 1) * (size_t)(i - nvo) + dim] : 0.0);
-  b[i] = v;
-  xa[i] = wdinv[i] * v;
-}
-// pre-smoothing on the owned rows and the owned part of the coarse right-hand side: lev[1].b = P_owned^T (b - A xa)
-int k_dl0_down(cfdh_ctx *c, const double *halo_vec) {
-  cfdh_ctx::DistL0 &d = c->dl0;
-  AmgLevel *N = c->hLg.lev[1];
-  const int nvo = c->nvo, nv = c->nv;
-  // without the exchange of the right-hand side's ghost layer the producer (the H solve) has written the owned part of d.b itself;
-  // the ghost parts of d.b and d.xa stay zero
-  if (d.ghost_rhs) hipLaunchKernelGGL(dl0_pack_kernel, dim3((nv + TPB - 1) / TPB), dim3(TPB), 0, c->stream, nvo, nv, c->dim, halo_vec, d.wdinv.p, d.b.p, d.xa.p, 1);
-  dim3 block(TPB), grid((unsigned)((8ll * nvo + TPB - 1) / TPB)), gridS((unsigned)((nvo + TPB - 1) / TPB));
-  if (d.A.nnz <= 12ll * nvo && nvo >= 16384)  // short regular rows: SELL-64 (as the replicated level 0 would use)
-    hipLaunchKernelGGL((sell_jacobi_pre_kernel<double>), gridS, block, 0, c->stream, nvo, d.A.sptr.p, d.A.scol.p, d.A.svalw.p,
-                       d.wdinv.p, (const double *)d.b.p, d.xa.p, d.r.p);
-  else
-    hipLaunchKernelGGL((jacobi_pre_kernel<double>), grid, block, 0, c->stream, nvo, d.A.rowptr.p, d.A.col.p, d.A.val.p, d.wdinv.p,
-                       (const double *)d.b.p, d.xa.p, d.r.p);
-  HIPCHK(c, hipGetLastError());
-  return csr_spmv_t<double>(c, d.PT, d.r.p, N->b.p, 0, (const double *)nullptr);
-}
-// replicated coarse cycle from level 1, prolongation to owned + ghost rows, post-smoothing of the owned rows -> out
-int k_dl0_up(cfdh_ctx *c, double *out) {
-  cfdh_ctx::DistL0 &d = c->dl0;
-  AmgLevel *N = c->hLg.lev[1];
-  const int nvo = c->nvo;
-  // the replicated levels: composite-operator cycle from level 1 (6 launches for four coarse levels instead of 13 sweeps)
-  static const bool sweeps = getenv("CFDH_DL0_COARSE_SWEEPS") && getenv("CFDH_DL0_COARSE_SWEEPS")[0] == '1';
-  if (c->hLg.fused && c->opt.amg_smooth_degree == 1 && !sweeps) CHK(amg_cycle_fused<double>(c, c->hLg, (const double *)N->b.p, N->x.p, 0, 1));
-  else CHK(amg_cycle_jacobi<double>(c, c->hLg, 1, (const double *)N->b.p, N->x.p, 0));
-  if (d.P.nnz <= 12ll * c->nv && c->nv >= 16384)
-    hipLaunchKernelGGL((sell_spmv_kernel<3, double>), dim3((unsigned)((c->nv + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, c->nv,
-                       d.P.sptr.p, d.P.scol.p, d.P.sval.p, (const double *)N->x.p, d.x1.p, (const double *)d.xa.p);
-  else
-    CHK(csr_spmv_t<double>(c, d.P, (const double *)N->x.p, d.x1.p, 3, (const double *)d.xa.p));  // x1 = xa + P x_c
-  dim3 block(TPB), grid((unsigned)((8ll * nvo + TPB - 1) / TPB)), gridS((unsigned)((nvo + TPB - 1) / TPB));
-  if (d.A.nnz <= 12ll * nvo && nvo >= 16384)
-    hipLaunchKernelGGL((sell_jacobi_post_kernel<double>), gridS, block, 0, c->stream, nvo, d.A.sptr.p, d.A.scol.p, d.A.sval.p,
-                       d.wdinv.p, (const double *)d.b.p, (const double *)d.x1.p, out);
-  else
-    hipLaunchKernelGGL((jacobi_post_kernel<double>), grid, block, 0, c->stream, nvo, d.A.rowptr.p, d.A.col.p, d.A.val.p, d.wdinv.p,
-                       (const double *)d.b.p, (const double *)d.x1.p, out);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// x = V(H) b; for ncol == 2 b and x hold interleaved pairs
-int k_amg_vcycle(cfdh_ctx *c, AmgHier &H, const double *b, double *x) {
-  if (!H.valid || H.lev.empty()) return cfdh_fail(c, CFDH_E_STATE, "AMG hierarchy not built");
-  const bool prof = (&H == &c->hS) || (&H == &c->hL) || (&H == &c->hLg);
-  if (H.ncol == 3) {
-    if (H.fused && c->opt.amg_smooth_degree == 1 && H.lev.size() >= 2) return amg_cycle_fused<d3>(c, H, (const d3 *)b, (d3 *)x, 5);
-    return amg_cycle_jacobi<d3>(c, H, 0, (const d3 *)b, (d3 *)x, 5);
-  }
-  if (H.fused && c->opt.amg_smooth_degree == 1 && H.lev.size() >= 2) {
-    if (H.ncol == 2) return amg_cycle_fused<double2>(c, H, (const double2 *)b, (double2 *)x, 5);
-    return amg_cycle_fused<double>(c, H, b, x, prof ? 4 : 0);
-  }
-  if (H.ncol == 2) return amg_cycle_jacobi<double2>(c, H, 0, (const double2 *)b, (double2 *)x, 5);
-  if (c->opt.amg_smooth_degree == 1) return amg_cycle_jacobi<double>(c, H, 0, b, x, prof ? 4 : 0);
-  return amg_cycle_cheb(c, H, 0, b, x, prof);
-}
-
-// Cahouet-Chabard combination: y = M_l z (0 on Dirichlet rows) ; out = alpha t + beta z, out = r on Dirichlet rows
-__global__ __launch_bounds__(TPB) void cc_scale_kernel(int n, const double *__restrict__ ml, const double *__restrict__ z, double *__restrict__ y) {
-  const int i = blockIdx.x * TPB + threadIdx.x;
-  if (i < n) y[i] = ml[i] * z[i];
-}
-__global__ __launch_bounds__(TPB) void cc_combine_kernel(int n, double alpha, double beta, const double *__restrict__ t,
-                                                         const double *__restrict__ z, const double *__restrict__ r,
-                                                         const unsigned char *__restrict__ pbc, double *__restrict__ out, double *__restrict__ out2) {
-  const int i = blockIdx.x * TPB + threadIdx.x;
-  if (i < n) {
-    const double v = (pbc[i] & 1) ? r[i] : alpha * t[i] + beta * z[i];
-    out[i] = v;
-    if (out2) out2[i] = v;  // partitioned run: z_p also into the pressure slot of the halo scratch vector
-  }
-}
-__global__ __launch_bounds__(TPB) void scatter_global_kernel(int n, const int *__restrict__ l2g, const double *__restrict__ loc, double *__restrict__ glob) {
-  const int i = blockIdx.x * TPB + threadIdx.x;
-  if (i < n) glob[l2g[i]] = loc[i];
-}
-__global__ __launch_bounds__(TPB) void gather_global_kernel(int n, const int *__restrict__ l2g, const double *__restrict__ glob, double *__restrict__ loc) {
-  const int i = blockIdx.x * TPB + threadIdx.x;
-  if (i < n) loc[i] = glob[l2g[i]];
-}
-// velocity part of a halo-layout vector ([u owned | p owned | (ux,uy,p) per ghost]) as nv contiguous pairs
-__global__ __launch_bounds__(TPB) void ext_pack_kernel(int nvo, int nv, const double *__restrict__ vec, double2 *__restrict__ out) {
-  const int i = blockIdx.x * TPB + threadIdx.x;
-  if (i >= nv) return;
-  if (i < nvo) out[i] = make_double2(vec[2 * (size_t)i], vec[2 * (size_t)i + 1]);
-  else {
-    const double *t = vec + 3 * (size_t)nvo + 3 * (size_t)(i - nvo);
-    out[i] = make_double2(t[0], t[1]);
-  }
-}
-__global__ __launch_bounds__(TPB) void ext_pack3_kernel(int nvo, int nv, const double *__restrict__ vec, double *__restrict__ out) {
-  const int i = blockIdx.x * TPB + threadIdx.x;
-  if (i >= nv) return;
-  const double *t = i < nvo ? vec + 3 * (size_t)i : vec + 4 * (size_t)i;  // ghost record (ux, uy, uz, p) at 4 nvo + 4 (i - nvo)
-  out[3 * (size_t)i] = t[0]; out[3 * (size_t)i + 1] = t[1]; out[3 * (size_t)i + 2] = t[2];
-}
-int k_ext_pack(cfdh_ctx *c, const double *vec, double *out) {
-  if (c->dim == 3) {
-    hipLaunchKernelGGL(ext_pack3_kernel, dim3((c->nv + TPB - 1) / TPB), dim3(TPB), 0, c->stream, c->nvo, c->nv, vec, out);
-    HIPCHK(c, hipGetLastError());
-    return 0;
-  }
-  hipLaunchKernelGGL(ext_pack_kernel, dim3((c->nv + TPB - 1) / TPB), dim3(TPB), 0, c->stream, c->nvo, c->nv, vec, (double2 *)out);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int k_scatter_global(cfdh_ctx *c, int n, const int *l2g, const double *loc, double *glob) {
-  hipLaunchKernelGGL(scatter_global_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, l2g, loc, glob);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int k_gather_global(cfdh_ctx *c, int n, const int *l2g, const double *glob, double *loc) {
-  hipLaunchKernelGGL(gather_global_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, l2g, glob, loc);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int k_cc_scale(cfdh_ctx *c, int n, const double *ml, const double *z, double *y) {
-  hipLaunchKernelGGL(cc_scale_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, ml, z, y);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int k_cc_combine(cfdh_ctx *c, int n, double alpha, double beta, const double *t, const double *z, const double *r,
-                 const unsigned char *pbc, double *out, double *out2) {
-  hipLaunchKernelGGL(cc_combine_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, alpha, beta, t, z, r, pbc, out, out2);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------- vector kernels
-__global__ __launch_bounds__(TPB) void axpy_kernel(int n, double a, const double *__restrict__ x, double *__restrict__ y) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) y[i] += a * x[i];
-}
-__global__ __launch_bounds__(TPB) void waxpy_kernel(int n, double a, const double *__restrict__ x, const double *__restrict__ y,
-                                                    double *__restrict__ w) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) w[i] = y[i] + a * x[i];
-}
-__global__ __launch_bounds__(TPB) void scale_kernel(int n, double a, double *__restrict__ x) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) x[i] *= a;
-}
-
-__global__ __launch_bounds__(TPB) void pmult_kernel(int n, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ o) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) o[i] = a[i] * b[i];
-}
-int v_pointwise_mult(cfdh_ctx *c, int n, const double *a, const double *b, double *out) {
-  hipLaunchKernelGGL(pmult_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, a, b, out);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int v_copy(cfdh_ctx *c, int n, const double *x, double *y) {
-  HIPCHK(c, hipMemcpyAsync(y, x, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
-  return 0;
-}
-int v_zero(cfdh_ctx *c, int n, double *y) {
-  HIPCHK(c, hipMemsetAsync(y, 0, sizeof(double) * (size_t)n, c->stream));
-  return 0;
-}
-int v_axpy(cfdh_ctx *c, int n, double a, const double *x, double *y) {
-  hipLaunchKernelGGL(axpy_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, a, x, y);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int v_waxpy(cfdh_ctx *c, int n, double a, const double *x, const double *y, double *w) {
-  hipLaunchKernelGGL(waxpy_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, a, x, y, w);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int v_scale(cfdh_ctx *c, int n, double a, double *x) {
-  hipLaunchKernelGGL(scale_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, a, x);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// ---- reductions (protocol and kernels: cfdh_reduce.hip)
-static int reduce_dev(cfdh_ctx *c, int op, int n, const double *x, const double *y, double *out_dev, ScalarRead *h) {
-  const int nb = red_grid(c, n);
-  CHK(red_partials_launch(c, op, nb, n, x, y, c->red_partial.p));
-  return scalars_finish(c, out_dev, 1, op, nb, h);
-}
-
-int v_dot(cfdh_ctx *c, int n, const double *x, const double *y, double *out_host) {
-  ScalarRead h;
-  CHK(reduce_dev(c, 0, n, x, y, c->red_out.p, &h));
-  return scalars_read(c, h, out_host);
-}
-int v_norm2(cfdh_ctx *c, int n, const double *x, double *out_host) {
-  CHK(v_dot(c, n, x, x, out_host));
-  *out_host = sqrt(*out_host);
-  return 0;
-}
-// |x| and |y| with one read-back (one host synchronisation instead of two)
-int v_norm2_pair(cfdh_ctx *c, int n, const double *x, const double *y, double *nx, double *ny) {
-  const int nb = red_grid(c, n);
-  if ((size_t)2 * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "reduction workspace too small");
-  CHK(red_partials_launch(c, 0, nb, n, x, x, c->red_partial.p));
-  CHK(red_partials_launch(c, 0, nb, n, y, y, c->red_partial.p + nb));
-  ScalarRead h;
-  CHK(scalars_finish(c, c->red_out.p, 2, 0, nb, &h));
-  double v[2];
-  CHK(scalars_read(c, h, v));
-  *nx = sqrt(v[0]); *ny = sqrt(v[1]);
-  return 0;
-}
-int v_norminf_diff(cfdh_ctx *c, int n, const double *x, const double *y, double *out_host) {
-  ScalarRead h;
-  CHK(reduce_dev(c, 1, n, x, y, c->red_out.p, &h));
-  return scalars_read(c, h, out_host);
-}
-
-__global__ __launch_bounds__(TPB) void sub_scalar_kernel(int n, double *__restrict__ p, const double *__restrict__ s, double scale) {
-  const double m = s[0] * scale;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) p[i] -= m;
-}
-// p -= mean(p) over all ranks (constant-pressure null vector, stabilized_schur.py:282-293,319)
-int v_sub_mean(cfdh_ctx *c, int n, double *p) {
-  const int nb = red_grid(c, n);
-  double *acc = c->red_out.p + RO_MEAN;  // [sum, count]
-  CHK(red_partials_launch(c, 2, nb, n, p, nullptr, c->red_partial.p));
-  CHK(red_final(c, 0, 1, nb, nb, c->red_partial.p, acc, nullptr));
-  double scale = 1.0 / n;
-  if (c->nranks > 1) {
-    CHK(comm_allreduce_dev(c, acc, 1, 0));
-    // global number of pressure dofs: constant, reduced once when the communicator is attached (global_counts)
-    if (n != c->nvo || !(c->nvo_global > 0)) return cfdh_fail(c, CFDH_E_STATE, "v_sub_mean: global count unknown");
-    scale = 1.0 / c->nvo_global;
-  }
-  hipLaunchKernelGGL(sub_scalar_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, p, acc, scale);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// ---- Gram-Schmidt building blocks: h_i = V_i . w for i < nvec (V column-major, leading dim ld)
-#define MD_G 8     // vectors reduced together: one pass over the w chunk feeds 8 dot products
-#define MD_NB 1024 // blocks: 4 per CU, each owning a contiguous chunk (w stays L1/L2 resident across groups)
-__global__ __launch_bounds__(TPB) void multidot_kernel(int n, const double *__restrict__ V, size_t ld, int nvec,
-                                                       const double *__restrict__ w, double *__restrict__ partial, int nblk,
-                                                       int with_ww) {
-  __shared__ double sh[4][MD_G];
-  const int nout = nvec + with_ww;
-  const int per = (((n + nblk - 1) / nblk) + 1) & ~1;
-  const int lo = blockIdx.x * per, hi = min(n, lo + per);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (int g0 = 0; g0 < nout; g0 += MD_G) {
-    const double *ptr[MD_G];
-    double acc[MD_G];
-#pragma unroll
-    for (int q = 0; q < MD_G; q++) {
-      const int v = g0 + q;
-      ptr[q] = (v < nvec) ? V + (size_t)v * ld : w;  // v == nvec: w.w ; v > nvec: dummy (discarded)
-      acc[q] = 0.0;
-    }
-    // two consecutive entries per lane (16-B loads; lo and the leading dimension are even), odd tail by the last lane
-    const int hi2 = hi > lo ? lo + ((hi - lo) & ~1) : hi;  // blocks past the end of a short vector own nothing
-    for (int i = lo + 2 * threadIdx.x; i < hi2; i += 2 * TPB) {
-      const double2 wi = *(const double2 *)(w + i);
-#pragma unroll
-      for (int q = 0; q < MD_G; q++) {
-        const double2 vi = *(const double2 *)(ptr[q] + i);
-        acc[q] += vi.x * wi.x + vi.y * wi.y;
-      }
-    }
-    if (hi2 < hi && threadIdx.x == 0) {
-      const double wi = w[hi2];
-#pragma unroll
-      for (int q = 0; q < MD_G; q++) acc[q] += ptr[q][hi2] * wi;
-    }
-#pragma unroll
-    for (int q = 0; q < MD_G; q++) {
-      const double r = wave_sum(acc[q]);
-      if (lane == 0) sh[wv][q] = r;
-    }
-    __syncthreads();
-    if (threadIdx.x < MD_G && g0 + (int)threadIdx.x < nout)
-      partial[(size_t)(g0 + threadIdx.x) * nblk + blockIdx.x] =
-          (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-    __syncthreads();
-  }
-}
-// Gram system of the projected initial guess in ONE pass over the K + 1 vectors: out slot (i, q) = W_q . W_i for i < K and
-// W_q . b for i = K, laid out as out[8 i + q] (the unused slots of the 8-wide rows are written as zeros).
-template <int K>
-__global__ __launch_bounds__(TPB) void gram_kernel(int n, const double *__restrict__ W, size_t ld, const double *__restrict__ b,
-                                                   double *__restrict__ partial, int nblk) {
-  constexpr int NP = K * (K + 1) / 2 + K;
-  __shared__ double sh[4][NP];
-  const int per = (((n + nblk - 1) / nblk) + 1) & ~1;
-  const int lo = blockIdx.x * per, hi = min(n, lo + per);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  double acc[NP];
-#pragma unroll
-  for (int t = 0; t < NP; t++) acc[t] = 0.0;
-  for (int i = lo + threadIdx.x; i < hi; i += TPB) {
-    double x[K];
-#pragma unroll
-    for (int q = 0; q < K; q++) x[q] = W[(size_t)q * ld + i];
-    const double bi = b[i];
-    int t = 0;
-#pragma unroll
-    for (int q = 0; q < K; q++) {
-#pragma unroll
-      for (int r = q; r < K; r++) acc[t++] += x[q] * x[r];
-    }
-#pragma unroll
-    for (int q = 0; q < K; q++) acc[t++] += x[q] * bi;
-  }
-#pragma unroll
-  for (int t = 0; t < NP; t++) {
-    const double r = wave_sum(acc[t]);
-    if (lane == 0) sh[wv][t] = r;
-  }
-  __syncthreads();
-  // scatter into the 8-wide slot layout (symmetric entries twice)
-  if (threadIdx.x < 8 * (K + 1)) {
-    const int i = threadIdx.x >> 3, q = threadIdx.x & 7;
-    double v = 0.0;
-    if (q < K) {
-      int t;
-      if (i < K) { const int lo_ = min(i, q), hi_ = max(i, q); t = lo_ * K - lo_ * (lo_ - 1) / 2 + (hi_ - lo_); }
-      else t = K * (K + 1) / 2 + q;
-      v = (sh[0][t] + sh[1][t]) + (sh[2][t] + sh[3][t]);
-    }
-    partial[(size_t)threadIdx.x * nblk + blockIdx.x] = v;
-  }
-}
-// out_dev[8 i + q] as above, NOT reduced over the ranks (the caller does that once)
-int v_gram(cfdh_ctx *c, int n, const double *W, int ld, int k, const double *b, double *out_dev) {
-  const int nb = MD_NB, nout = 8 * (k + 1);
-  if (k < 2 || k > 4 || (size_t)nout * nb > c->red_partial.n) {
-    for (int i = 0; i <= k; i++) CHK(v_multidot(c, n, W, ld, k, i < k ? W + (size_t)i * ld : b, out_dev + (size_t)i * 8, false, nullptr, false));
-    return 0;
-  }
-  if (k == 2) hipLaunchKernelGGL((gram_kernel<2>), dim3(nb), dim3(TPB), 0, c->stream, n, W, (size_t)ld, b, c->red_partial.p, nb);
-  else if (k == 3) hipLaunchKernelGGL((gram_kernel<3>), dim3(nb), dim3(TPB), 0, c->stream, n, W, (size_t)ld, b, c->red_partial.p, nb);
-  else hipLaunchKernelGGL((gram_kernel<4>), dim3(nb), dim3(TPB), 0, c->stream, n, W, (size_t)ld, b, c->red_partial.p, nb);
-  HIPCHK(c, hipGetLastError());
-  return red_final(c, 0, nout, nb, nb, c->red_partial.p, out_dev, nullptr);
-}
-// (A "last block does the final reduction" variant was measured and dropped: the device-scope release fence every
-// block needs before taking its ticket writes the XCD's L2 back -- 133 us per launch against 17 + 4 us for two kernels.)
-// h_dev[0..nvec) = V^T w (and h_dev[nvec] = w.w when with_ww), reduced over all ranks
-int v_multidot(cfdh_ctx *c, int n, const double *V, int ld, int nvec, const double *w, double *h_dev, bool with_ww, double *mirror, bool reduce_ranks) {
-  const int nb = MD_NB, nout = nvec + (with_ww ? 1 : 0);
-  if ((size_t)nout * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "multidot workspace too small");
-  hipLaunchKernelGGL(multidot_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, V, (size_t)ld, nvec, w, c->red_partial.p, nb,
-                     with_ww ? 1 : 0);
-  // single rank: the h values also land in host-mapped memory (`mirror`: device view of a slot of the FGMRES read-back ring)
-  // straight from the kernel
-  HIPCHK(c, hipGetLastError());
-  CHK(red_final(c, 0, nout, nb, nb, c->red_partial.p, h_dev, (mirror && c->nranks <= 1) ? mirror : nullptr));
-  if (!reduce_ranks) return 0;  // the caller reduces several results over the ranks at once
-  CHK(comm_allreduce_dev(c, h_dev, nout, 0));
-  // partitioned: publish the REDUCED coefficients the same way (behind the all-reduce)
-  if (mirror && c->nranks > 1) CHK(red_publish(c, nout, h_dev, mirror));
-  return 0;
-}
-__global__ __launch_bounds__(TPB) void scale_to_kernel(int n, double a, const double *__restrict__ x, double *__restrict__ y) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) y[i] = a * x[i];
-}
-int v_scale_to(cfdh_ctx *c, int n, double a, const double *x, double *y) {
-  hipLaunchKernelGGL(scale_to_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, a, x, y);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-// w -= sum_i h_i V_i
-__global__ __launch_bounds__(TPB) void multiaxpy_kernel(int n, const double *__restrict__ V, size_t ld, int nvec,
-                                                        const double *__restrict__ h, double *__restrict__ w, double sign) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-    double a0 = w[i], a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    int v = 0;
-    for (; v + 4 <= nvec; v += 4) {  // four independent streams in flight
-      const double x0 = V[(size_t)v * ld + i], x1 = V[(size_t)(v + 1) * ld + i], x2 = V[(size_t)(v + 2) * ld + i],
-                   x3 = V[(size_t)(v + 3) * ld + i];
-      a0 += sign * h[v] * x0; a1 += sign * h[v + 1] * x1; a2 += sign * h[v + 2] * x2; a3 += sign * h[v + 3] * x3;
-    }
-    for (; v < nvec; v++) a0 += sign * h[v] * V[(size_t)v * ld + i];
-    w[i] = (a0 + a1) + (a2 + a3);
-  }
-}
-int v_multiaxpy(cfdh_ctx *c, int n, const double *V, int ld, int nvec, const double *h_dev, double *w) {
-  hipLaunchKernelGGL(multiaxpy_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, V, (size_t)ld, nvec, h_dev, w, -1.0);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-__global__ __launch_bounds__(TPB) void gs_update_normalize_kernel(int n, const double *__restrict__ V, size_t ld, int nvec,
-                                                                 const double *__restrict__ h, const double *__restrict__ w,
-                                                                 double *__restrict__ vn, double *__restrict__ s_out) {
-  const double ww = h[nvec];
-  double hh2 = 0.0;
-  for (int v = 0; v < nvec; v++) hh2 += h[v] * h[v];
-  const double s = cfdh_krylov::gs_scale(ww, hh2);  // cancellation: any positive scale, the caller re-orthogonalises
-  const double inv = s > 0.0 ? 1.0 / s : 0.0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *s_out = s;
-  // two consecutive entries per lane (16-B loads: ld is even and all vectors are 16-B aligned); same summation order per entry
-  const int n2 = n & ~1;
-  for (int i = 2 * (blockIdx.x * TPB + threadIdx.x); i < n2; i += 2 * gridDim.x * TPB) {
-    const double2 wi = *(const double2 *)(w + i);
-    double a0 = wi.x, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = wi.y, b1 = 0.0, b2 = 0.0, b3 = 0.0;
-    int v = 0;
-    for (; v + 4 <= nvec; v += 4) {
-      const double2 x0 = *(const double2 *)(V + (size_t)v * ld + i), x1 = *(const double2 *)(V + (size_t)(v + 1) * ld + i),
-                    x2 = *(const double2 *)(V + (size_t)(v + 2) * ld + i), x3 = *(const double2 *)(V + (size_t)(v + 3) * ld + i);
-      a0 -= h[v] * x0.x; a1 -= h[v + 1] * x1.x; a2 -= h[v + 2] * x2.x; a3 -= h[v + 3] * x3.x;
-      b0 -= h[v] * x0.y; b1 -= h[v + 1] * x1.y; b2 -= h[v + 2] * x2.y; b3 -= h[v + 3] * x3.y;
-    }
-    for (; v < nvec; v++) { const double2 xv = *(const double2 *)(V + (size_t)v * ld + i); a0 -= h[v] * xv.x; b0 -= h[v] * xv.y; }
-    *(double2 *)(vn + i) = make_double2(((a0 + a1) + (a2 + a3)) * inv, ((b0 + b1) + (b2 + b3)) * inv);
-  }
-  if (n2 < n && blockIdx.x == 0 && threadIdx.x == 0) {
-    double a0 = w[n2];
-    for (int v = 0; v < nvec; v++) a0 -= h[v] * V[(size_t)v * ld + n2];
-    vn[n2] = a0 * inv;
-  }
-}
-int v_gs_update_normalize(cfdh_ctx *c, int n, const double *V, int ld, int nvec, const double *h_dev, const double *w, double *vn, double *s_dev) {
-  hipLaunchKernelGGL(gs_update_normalize_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, V, (size_t)ld, nvec, h_dev, w, vn, s_dev);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-__global__ void sqrt_kernel(double *s);
-// ---- Gram-Schmidt against an fp32 COPY of the basis (long Krylov cycles: the two passes over V are 40 % of an iteration at
-// depth 25; the fp64 vectors stay where the preconditioner reads them).  The norm of the new vector is measured, not inferred
-// from w.w - |h|^2 (that identity needs an orthonormal basis to round-off, which rounded columns are not).
-__global__ __launch_bounds__(TPB) void multidot32_kernel(int n, const float *__restrict__ V, size_t ld, int nvec,
-                                                         const double *__restrict__ w, double *__restrict__ partial, int nblk) {
-  __shared__ double sh[4][MD_G + 1];
-  const int per = (((n + nblk - 1) / nblk) + 3) & ~3;  // chunks of whole float4 / 2 x double2 groups
-  const int lo = blockIdx.x * per, hi = min(n, lo + per);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int hi4 = hi > lo ? lo + ((hi - lo) & ~3) : hi;
-  for (int g0 = 0; g0 < nvec; g0 += MD_G) {
-    const float *ptr[MD_G];
-    double acc[MD_G], aww = 0.0;
-#pragma unroll
-    for (int q = 0; q < MD_G; q++) { ptr[q] = V + (size_t)min(g0 + q, nvec - 1) * ld; acc[q] = 0.0; }  // past the end: a dummy, discarded
-    // four consecutive entries per lane: one 16-B load per fp32 column, two for w
-    for (int i = lo + 4 * threadIdx.x; i < hi4; i += 4 * TPB) {
-      const double2 w0 = *(const double2 *)(w + i), w1 = *(const double2 *)(w + i + 2);
-      if (g0 == 0) aww += (w0.x * w0.x + w0.y * w0.y) + (w1.x * w1.x + w1.y * w1.y);
-#pragma unroll
-      for (int q = 0; q < MD_G; q++) {
-        const float4 vi = *(const float4 *)(ptr[q] + i);
-        acc[q] += ((double)vi.x * w0.x + (double)vi.y * w0.y) + ((double)vi.z * w1.x + (double)vi.w * w1.y);
-      }
-    }
-    if (threadIdx.x == 0)
-      for (int i = hi4; i < hi; i++) {
-        const double wi = w[i];
-        if (g0 == 0) aww += wi * wi;
-#pragma unroll
-        for (int q = 0; q < MD_G; q++) acc[q] += (double)ptr[q][i] * wi;
-      }
-#pragma unroll
-    for (int q = 0; q < MD_G; q++) {
-      const double r = wave_sum(acc[q]);
-      if (lane == 0) sh[wv][q] = r;
-    }
-    if (g0 == 0) { const double r = wave_sum(aww); if (lane == 0) sh[wv][MD_G] = r; }
-    __syncthreads();
-    if (threadIdx.x < MD_G && g0 + (int)threadIdx.x < nvec)
-      partial[(size_t)(g0 + threadIdx.x) * nblk + blockIdx.x] =
-          (sh[0][threadIdx.x] + sh[1][threadIdx.x]) + (sh[2][threadIdx.x] + sh[3][threadIdx.x]);
-    if (g0 == 0 && threadIdx.x == MD_G)
-      partial[(size_t)nvec * nblk + blockIdx.x] = (sh[0][MD_G] + sh[1][MD_G]) + (sh[2][MD_G] + sh[3][MD_G]);
-    __syncthreads();
-  }
-}
-// h_dev[0..nvec) = V32^T w, h_dev[nvec] = w.w (reduced over the ranks, mirrored like v_multidot)
-int v_multidot32(cfdh_ctx *c, int n, const float *V, int ld, int nvec, const double *w, double *h_dev, double *mirror) {
-  const int nb = MD_NB, nout = nvec + 1;
-  if ((size_t)nout * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "multidot workspace too small");
-  hipLaunchKernelGGL(multidot32_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, V, (size_t)ld, nvec, w, c->red_partial.p, nb);
-  HIPCHK(c, hipGetLastError());
-  CHK(red_final(c, 0, nout, nb, nb, c->red_partial.p, h_dev, c->nranks <= 1 ? mirror : nullptr));
-  CHK(comm_allreduce_dev(c, h_dev, nout, 0));
-  if (c->nranks > 1) CHK(red_publish(c, nout, h_dev, mirror));
-  return 0;
-}
-// vn = w - V32 h (not normalised) and the block partials of |vn|^2
-__global__ __launch_bounds__(TPB) void gs_update32_kernel(int n, const float *__restrict__ V, size_t ld, int nvec, const double *__restrict__ h,
-                                                          const double *__restrict__ w, double *__restrict__ vn, double *__restrict__ partial) {
-  __shared__ double sh[4];
-  double ss = 0.0;
-  const int n2 = n & ~1;
-  for (int i = 2 * (blockIdx.x * TPB + threadIdx.x); i < n2; i += 2 * gridDim.x * TPB) {
-    const double2 wi = *(const double2 *)(w + i);
-    double a0 = wi.x, a1 = 0.0, b0 = wi.y, b1 = 0.0;
-    int v = 0;
-    for (; v + 2 <= nvec; v += 2) {
-      const float2 x0 = *(const float2 *)(V + (size_t)v * ld + i), x1 = *(const float2 *)(V + (size_t)(v + 1) * ld + i);
-      a0 -= h[v] * (double)x0.x; a1 -= h[v + 1] * (double)x1.x;
-      b0 -= h[v] * (double)x0.y; b1 -= h[v + 1] * (double)x1.y;
-    }
-    for (; v < nvec; v++) { const float2 xv = *(const float2 *)(V + (size_t)v * ld + i); a0 -= h[v] * (double)xv.x; b0 -= h[v] * (double)xv.y; }
-    const double r0 = a0 + a1, r1 = b0 + b1;
-    *(double2 *)(vn + i) = make_double2(r0, r1);
-    ss += r0 * r0 + r1 * r1;
-  }
-  if (n2 < n && blockIdx.x == 0 && threadIdx.x == 0) {
-    double a0 = w[n2];
-    for (int v = 0; v < nvec; v++) a0 -= h[v] * (double)V[(size_t)v * ld + n2];
-    vn[n2] = a0;
-    ss += a0 * a0;
-  }
-  ss = block_sum(ss, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = ss;
-}
-// vn /= s (s on the device) and its fp32 copy
-__global__ __launch_bounds__(TPB) void scale_store32_kernel(int n, double *__restrict__ vn, const double *__restrict__ s, float *__restrict__ v32) {
-  const double inv = s[0] > 0.0 ? 1.0 / s[0] : 0.0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) { const double x = vn[i] * inv; vn[i] = x; v32[i] = (float)x; }
-}
-__global__ __launch_bounds__(TPB) void store32_kernel(int n, const double *__restrict__ v, float *__restrict__ v32) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) v32[i] = (float)v[i];
-}
-int v_store32(cfdh_ctx *c, int n, const double *v, float *v32) {
-  hipLaunchKernelGGL(store32_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, v, v32);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-// vn = (w - V32 h) / |w - V32 h| with its fp32 copy in v32n; s_dev[0] = that norm (reduced over the ranks), mirrored to
-// the host-mapped word `mirror` for the host
-int v_gs_update32(cfdh_ctx *c, int n, const float *V, int ld, int nvec, const double *h_dev, const double *w, double *vn, float *v32n,
-                  double *s_dev, double *mirror) {
-  const int nb = red_grid(c, n);
-  double *part = c->red_partial.p + (size_t)(MD_NB) * 8;  // behind the first multi-dot groups (the stream serialises the users)
-  hipLaunchKernelGGL(gs_update32_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, V, (size_t)ld, nvec, h_dev, w, vn, part);
-  if (c->nranks <= 1) {  // square root and host-mapped copy in the reduction kernel itself
-    CHK(red_final(c, 2, 1, nb, nb, part, s_dev, mirror));
-  } else {
-    CHK(red_final(c, 0, 1, nb, nb, part, s_dev, nullptr));
-    CHK(comm_allreduce_dev(c, s_dev, 1, 0));
-    hipLaunchKernelGGL(sqrt_kernel, dim3(1), dim3(1), 0, c->stream, s_dev);
-    CHK(red_publish(c, 1, s_dev, mirror));
-  }
-  hipLaunchKernelGGL(scale_store32_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, vn, (const double *)s_dev, v32n);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-int v_lincomb(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const double *y_dev, double *x) {
-  hipLaunchKernelGGL(multiaxpy_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, Z, (size_t)ld, nvec, y_dev, x, 1.0);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-
-// ---- lean solve path: prologue and epilogue of a linear solve with one read-back each (cfdh_solver.cpp) ----------------------
-// (the mirror words of the prologue: DESIGN.md, "Scalar reductions and read-backs")
-// The k x k Gram system of the projected guess (k <= 8), solved by one lane: cfdh_krylov::gram_solve, the same function the
-// general path calls on the host.
-__global__ void gram_solve_kernel(int k, const double *__restrict__ hd, double *__restrict__ y, double *__restrict__ info) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int r = 0;
-  const bool used = cfdh_krylov::gram_solve(k, hd, y, &r);
-  for (int i = 0; i < k; i++) info[3 + i] = y[i];
-  info[1] = used ? 1.0 : 0.0;
-  info[2] = (double)r;
-}
-// x = U y, r = b - W y and the block partials of |r|^2 in one pass over U, W and b.  Entry by entry the arithmetic of
-// multiaxpy_kernel (on a zeroed x, and on a copy of b), block by block the partial sums of reduce_partial_kernel<0>.
-__global__ __launch_bounds__(TPB) void guess_combine_kernel(int n, const double *__restrict__ U, const double *__restrict__ W, size_t ld,
-                                                            int nvec, const double *__restrict__ y, const double *__restrict__ b,
-                                                            double *__restrict__ x, double *__restrict__ r, double *__restrict__ partial) {
-  __shared__ double sh[4];
-  double ss = 0.0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, c0 = b[i], c1 = 0.0, c2 = 0.0, c3 = 0.0;
-    int v = 0;
-    for (; v + 4 <= nvec; v += 4) {
-      const double y0 = y[v], y1 = y[v + 1], y2 = y[v + 2], y3 = y[v + 3];
-      const double u0 = U[(size_t)v * ld + i], u1 = U[(size_t)(v + 1) * ld + i], u2 = U[(size_t)(v + 2) * ld + i], u3 = U[(size_t)(v + 3) * ld + i];
-      const double w0 = W[(size_t)v * ld + i], w1 = W[(size_t)(v + 1) * ld + i], w2 = W[(size_t)(v + 2) * ld + i], w3 = W[(size_t)(v + 3) * ld + i];
-      a0 += y0 * u0; a1 += y1 * u1; a2 += y2 * u2; a3 += y3 * u3;
-      c0 -= y0 * w0; c1 -= y1 * w1; c2 -= y2 * w2; c3 -= y3 * w3;
-    }
-    for (; v < nvec; v++) { a0 += y[v] * U[(size_t)v * ld + i]; c0 -= y[v] * W[(size_t)v * ld + i]; }
-    const double ri = (c0 + c1) + (c2 + c3);
-    x[i] = (a0 + a1) + (a2 + a3);
-    r[i] = ri;
-    ss += ri * ri;
-  }
-  ss = block_sum(ss, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = ss;
-}
-// x *= 1 / sqrt(s2[0]) with the squared norm read on the device (0 when it is not positive)
-__global__ __launch_bounds__(TPB) void scale_inv_sqrt_kernel(int n, double *__restrict__ x, const double *__restrict__ s2) {
-  const double beta = sqrt(s2[0]);
-  const double a = beta > 0.0 ? 1.0 / beta : 0.0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) x[i] *= a;
-}
-// x += sum_i y_i Z_i as v_lincomb, and the result stored a second time in x2 (the kept copy of a converged solve)
-__global__ __launch_bounds__(TPB) void lincomb_keep_kernel(int n, const double *__restrict__ V, size_t ld, int nvec,
-                                                           const double *__restrict__ h, double *__restrict__ w, double *__restrict__ w2) {
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-    double a0 = w[i], a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    int v = 0;
-    for (; v + 4 <= nvec; v += 4) {
-      const double x0 = V[(size_t)v * ld + i], x1 = V[(size_t)(v + 1) * ld + i], x2 = V[(size_t)(v + 2) * ld + i],
-                   x3 = V[(size_t)(v + 3) * ld + i];
-      a0 += h[v] * x0; a1 += h[v + 1] * x1; a2 += h[v + 2] * x2; a3 += h[v + 3] * x3;
-    }
-    for (; v < nvec; v++) a0 += h[v] * V[(size_t)v * ld + i];
-    const double o = (a0 + a1) + (a2 + a3);
-    w[i] = o;
-    w2[i] = o;
-  }
-}
-// block partials of a.a, b.b and c.c in one pass (each sum in the order of reduce_partial_kernel<0>)
-__global__ __launch_bounds__(TPB) void norm3_partial_kernel(int n, const double *__restrict__ a, const double *__restrict__ b,
-                                                            const double *__restrict__ cc, double *__restrict__ partial) {
-  __shared__ double sh[4];
-  double s0 = 0, s1 = 0, s2 = 0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
-    const double ai = a[i], bi = b[i], ci = cc[i];
-    s0 += ai * ai; s1 += bi * bi; s2 += ci * ci;
-  }
-  s0 = block_sum(s0, sh);
-  s1 = block_sum(s1, sh);
-  s2 = block_sum(s2, sh);
-  if (threadIdx.x == 0) { partial[blockIdx.x] = s0; partial[gridDim.x + blockIdx.x] = s1; partial[2 * gridDim.x + blockIdx.x] = s2; }
-}
-// Prologue of a solve with k kept vectors, hd = Gram system from v_gram: y on the device (ky), x = U y, r = b - W y, |r|^2 and the
-// "used" flag in the host-mapped words.  Nothing is read back here.
-int v_guess_combine(cfdh_ctx *c, int n, const double *U, const double *W, int ld, int k, const double *hd, const double *b, double *x, double *r) {
-  if (k < 1 || k > 8) return cfdh_fail(c, CFDH_E_STATE, "projected guess: %d kept vectors", k);
-  const int nb = red_grid(c, n);
-  double *mir = scalars_mirror(c);
-  hipLaunchKernelGGL(gram_solve_kernel, dim3(1), dim3(64), 0, c->stream, k, hd, c->ky.p, mir);
-  hipLaunchKernelGGL(guess_combine_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, U, W, (size_t)ld, k, (const double *)c->ky.p, b, x, r, c->red_partial.p);
-  HIPCHK(c, hipGetLastError());
-  return red_final(c, 0, 1, nb, nb, c->red_partial.p, c->red_out.p + RO_LEAN_S2, mir);
-}
-// the one read-back of the prologue: |r0|, whether the guess is used, the rank and the coefficients
-int v_guess_read(cfdh_ctx *c, int k, double *beta, bool *used, int *rank, double *y) {
-  double m[3 + 8];
-  CHK(scalars_read(c, scalars_mirrored(3 + k), m));
-  *beta = sqrt(m[0]);
-  *used = m[1] != 0.0;
-  *rank = (int)m[2];
-  for (int i = 0; i < k; i++) y[i] = m[3 + i];
-  return 0;
-}
-// x /= the norm the last lean prologue / epilogue left on the device
-int v_scale_inv_lean(cfdh_ctx *c, int n, double *x) {
-  hipLaunchKernelGGL(scale_inv_sqrt_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, x, (const double *)(c->red_out.p + RO_LEAN_S2));
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-// true residual r = b - J x and its norm with one kernel over the matrix and ONE read-back; false in *done when the partial
-// sums of this mesh do not fit the reduction workspace (the caller then takes the three-kernel path)
-int k_resid_norm(cfdh_ctx *c, const double *x, const double *b, double *r, double *nrm, bool *done) {
-  const long long nthreads = 8ll * c->nvo;
-  const long long nb = (nthreads + TPB - 1) / TPB;
-  *done = false;
-  if (c->dim != 2 || (size_t)nb > c->red_partial.n) return 0;
-  hipLaunchKernelGGL((spmv_full_lean_kernel<false, true>), dim3((unsigned)nb), dim3(TPB), 0, c->stream, c->nvo, c->vptr.p, c->vcol.p, c->A00.p,
-                     c->A01.p, c->A10.p, c->A11.p, x, r, (const double *)nullptr, b, c->red_partial.p);
-  HIPCHK(c, hipGetLastError());
-  CHK(red_final(c, 0, 1, (int)nb, (int)nb, c->red_partial.p, c->red_out.p + RO_LEAN_S2, scalars_mirror(c)));
-  double s2;
-  CHK(scalars_read(c, scalars_mirrored(1), &s2));
-  *nrm = sqrt(s2);
-  *done = true;
-  return 0;
-}
-int v_lincomb_keep(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const double *y_dev, double *x, double *x2) {
-  hipLaunchKernelGGL(lincomb_keep_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, Z, (size_t)ld, nvec, y_dev, x, x2);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-// |a|, |b|, |cc| with one pass and one read-back (one rank)
-int v_norm2_triple(cfdh_ctx *c, int n, const double *a, const double *b, const double *cc, double *out) {
-  const int nb = red_grid(c, n);
-  if ((size_t)3 * nb > c->red_partial.n) return cfdh_fail(c, CFDH_E_STATE, "reduction workspace too small");
-  hipLaunchKernelGGL(norm3_partial_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, a, b, cc, c->red_partial.p);
-  HIPCHK(c, hipGetLastError());
-  CHK(red_final(c, 0, 3, nb, nb, c->red_partial.p, c->red_out.p, scalars_mirror(c)));
-  CHK(scalars_read(c, scalars_mirrored(3), out));
-  for (int i = 0; i < 3; i++) out[i] = sqrt(out[i]);
-  return 0;
-}
-__global__ void sqrt_kernel(double *s) { s[0] = sqrt(s[0]); }
-int v_norm_to_dev(cfdh_ctx *c, int n, const double *w, double *out_dev) {
-  CHK(reduce_dev(c, 0, n, w, w, out_dev, nullptr));  // stays on the device
-  hipLaunchKernelGGL(sqrt_kernel, dim3(1), dim3(1), 0, c->stream, out_dev);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-// the same without the reduction over the ranks: norms of rank-local operators (hierarchy set-up of a partitioned run)
-int v_norm_to_dev_local(cfdh_ctx *c, int n, const double *w, double *out_dev) {
-  const int nb = red_grid(c, n);
-  CHK(red_partials_launch(c, 0, nb, n, w, w, c->red_partial.p));
-  CHK(red_final(c, 0, 1, nb, nb, c->red_partial.p, out_dev, nullptr));
-  hipLaunchKernelGGL(sqrt_kernel, dim3(1), dim3(1), 0, c->stream, out_dev);
-  HIPCHK(c, hipGetLastError());
-  return 0;
-}
-__global__ __launch_bounds__(TPB) void scale_inv_dev_kernel(int n, const double *__restrict__ w, const double *__restrict__ nrm,
-                                                            double *__restrict__ v) {
-  const double s = nrm[0] != 0.0 ? 1.0 / nrm[0] : 0.0;
-  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) v[i] = w[i] * s;
-}
-int v_scale_inv_dev(cfdh_ctx *c, int n, const double *w, const double *nrm_dev, double *v) {
-  hipLaunchKernelGGL(scale_inv_dev_kernel, dim3(vgrid(n)), dim3(TPB), 0, c->stream, n, w, nrm_dev, v);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

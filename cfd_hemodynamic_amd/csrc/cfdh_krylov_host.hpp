@@ -1,7 +1,7 @@
 // The arithmetic of the linear solve that needs no device: the Gram system of the projected guess, the least-squares problem of
 // the Arnoldi recurrence, the scale of a Gram-Schmidt pass and the launch-ahead policy.  Plain C++17 without HIP and without the
 // context, so that the CPU tests compile it with the host compiler (tests/krylov_host_shim.cpp); gram_solve and gs_scale are also
-// called from kernels (cfdh_kernels.hip), which is what keeps the host and the device to ONE copy of each.
+// called from kernels (cfdh_krylov_vec.hip), which is what keeps the host and the device to ONE copy of each.
 #pragma once
 #include <algorithm>
 #include <cmath>

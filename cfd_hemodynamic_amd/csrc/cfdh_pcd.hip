@@ -5,7 +5,7 @@
 //   K = rho N(w) - rho R_in(w) + c_t M   (N_ij = int phi_i w . grad phi_j, R_in,ij = int_{inlet} (w . n) phi_i phi_j, M consistent mass),
 //   A_p = the P1 pressure Laplacian with Dirichlet rows on the outlet vertices (bcs_pcd, :215-218) and the pressure-Dirichlet ones.
 // Two kernels: the row-owner assembly of K (once per Newton iteration, cfdh_pc_update) and the apply pass that feeds the V-cycle of
-// A_p; the combination mu t + y runs in the epilogue of that cycle's last kernel (the Cahouet-Chabard epilogue of cfdh_kernels.hip).
+// A_p; the combination mu t + y runs in the epilogue of that cycle's last kernel (the Cahouet-Chabard epilogue of cfdh_amg_apply.hip).
 #include <algorithm>
 #include <cmath>
 

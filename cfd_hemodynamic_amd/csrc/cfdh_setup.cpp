@@ -624,9 +624,9 @@ int cfdh_amg_setup(cfdh_ctx *c, AmgHier &H, const CsrHost &A0, bool singular, in
     CHK(cfdh_level_setup(c, *L, A, o.amg_smooth_ratio, ncol, &w));
     TICK(0);
     if (keep0) { H.h_wdinv0 = w; H.h_A0 = A; }
-    // short regular rows (finest level of a P1 operator: ~7 entries on triangles, ~15 on tetrahedra): SELL-64 / fp32 kernels
-    L->fine = A.nnz() <= (c->dim == 3 ? 20ll : 12ll) * A.n && A.n >= 16384;
-    L->sell = L->fine && (A.nnz() <= 12ll * A.n || ncol == 1);
+    // SELL-64 / fp32 kernels of the fused cycle on short regular rows: the rules of cfdh_internal.hpp
+    L->fine = cfdh_level_fine(c->dim, A.nnz(), A.n);
+    L->sell = cfdh_level_sell(c->dim, A.nnz(), A.n, ncol);
     prevW.swap(curW); curW = w;
     const double lm = L->lmax / 1.1;
     if (A.n <= o.amg_max_coarse || (int)H.lev.size() >= maxlev) break;

@@ -3,6 +3,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+// threads per block of the kernel files that include this header (one that states it again must state the same value: the
+// compiler warns about any other)
+#define TPB 256
+// streamed-once operands (matrix values / columns of the AMG sweeps): non-temporal loads keep them from evicting the
+// gathered vector entries out of the 32 KB L1
+#define NTLOAD(p) __builtin_nontemporal_load(p)
+
 // ---------------------------------------------------------------- wave-level helpers
 template <int CTRL>
 __device__ __forceinline__ double dpp_shuffle(double v) {

@@ -1,6 +1,6 @@
-"""Plain numpy references of the Krylov vector wrappers (v_* of csrc/cfdh_kernels.hip) and the inputs of their tests.
+"""Plain numpy references of the Krylov vector wrappers (v_* of csrc/cfdh_krylov_vec.hip) and the inputs of their tests.
 
-Every function states the CONTRACT of one wrapper (the comments of cfdh_internal.hpp and cfdh_kernels.hip), not its loops, and
+Every function states the CONTRACT of one wrapper (the comments of cfdh_internal.hpp and cfdh_krylov_vec.hip), not its loops, and
 works in the arithmetic of its arguments:
 
 * exact data -- int64 arrays.  Blocks hold integers in [-4, 4], coefficients integers in [-3, 3], and every scale is a power of

@@ -1,4 +1,4 @@
-"""The Krylov vector kernels of csrc/cfdh_kernels.hip one by one, through cfdh_krylov_vec_op (Context.krylov_vec_op), against the
+"""The Krylov vector kernels of csrc/cfdh_krylov_vec.hip one by one, through cfdh_krylov_vec_op (Context.krylov_vec_op), against the
 plain references of krylov_vec_ref.py.
 
 Exact data (integers in [-4, 4], coefficients in [-3, 3], power-of-two scales): every partial sum in any order is an integer

@@ -9,7 +9,15 @@ One small context of every family: closed-form P1 in 2-D / 3-D (also with CFDH_N
 IPCS in 2-D / 3-D, and one part of a 2-part split (two cell layers) of a closed-form mesh and of a P2 tetrahedral mesh.  Per context:
 Jacobian structure and values, residual, and -- whole meshes -- solution and iteration counts of two time steps; then the
 functionals of kinds 2 to 7 (bit patterns) and cfdh_info 76.  The info counters 13 to 17 of every context go to stdout, not
-into the file: they count collectives and read-backs, which two builds may do differently while computing the same numbers."""
+into the file: they count collectives and read-backs, which two builds may do differently while computing the same numbers.
+
+All of those meshes are far below the 16384 rows from which the AMG levels use SELL-64 / fp32 (cfdh_level_fine, cfdh_sweep_sell
+in csrc/cfdh_internal.hpp).  The pc-* contexts are above it: z = apply_preconditioner(r) for one seeded r on dfg_case(64) with
+pc_type 0, 1, 2 (fused cycle, SELL on level 0), the same with CFDH_NO_FUSED_AMG=1 (host-built hierarchy, sweep-by-sweep cycle
+on SELL A and P) and with amg_smooth_degree 2 on top (Chebyshev cycle, the two-step SELL kernel of the Cahouet-Chabard
+operator), and pc_type 1 on create_unit_cube(26) (19683 vertices, rows between 12 and 20 entries: the chunked SELL up-sweep in
+the pressure hierarchy, CSR in the velocity hierarchy).  CFDH_NO_FUSED_AMG is read with getenv at every hierarchy build and
+nowhere else, so it is set in this process around the context it is meant for."""
 import argparse
 import hashlib
 import os
@@ -119,6 +127,32 @@ def main():
         scalars(case, ctx)
         ctx.close()
 
+    def pc_context(case, m, bcs, dt, rho, mu, r, env=None, pcd=None, **opts):
+        d, nv = m.x.shape[1], len(m.x)
+        os.environ.update(env or {})
+        ctx = _lib.Context(m.x, m.cells, m.facet_cells, m.facet_local, m.facet_marker)
+        ctx.set_params(dt, rho, mu, f=np.zeros(d))
+        for field, nodes, vals in bcs:
+            ctx.add_dirichlet(field, nodes, vals)
+        o = ctx.default_options()
+        for key, val in opts.items():
+            setattr(o, key, val)
+        ctx.set_options(o)
+        if pcd:
+            ctx.set_schur_pcd(*pcd)
+        rng = np.random.default_rng(17)
+        u, un = 0.3 * rng.standard_normal(d * nv), 0.3 * rng.standard_normal(d * nv)
+        ctx.set_state(u_prev=un, p_prev=np.zeros(nv), u=u, p=rng.standard_normal(nv))
+        ctx.assemble(True)
+        put(case, "csr-values", ctx.get_csr().data)
+        put(case, "pc-apply", ctx.apply_preconditioner(r))  # builds the preconditioner first
+        put(case, "pc-apply-again", ctx.apply_preconditioner(r))
+        lines.append("%s info76 %d" % (case, ctx.info(76)))
+        print("%s counters 13-17: %s" % (case, " ".join(str(ctx.info(k)) for k in range(13, 18))))
+        ctx.close()
+        for key in env or {}:
+            os.environ.pop(key)
+
     tri, tet = dfg_case(6).mesh, create_unit_cube(4)
     for env in ("", "1"):
         os.environ["CFDH_NO_RENUMBER"] = env
@@ -134,6 +168,22 @@ def main():
         lp = part(m, 1)
         pm = types.SimpleNamespace(x=lp.x, cells=lp.cells, facet_cells=lp.facet_cells, facet_local=lp.facet_local)
         fgmres_context(case, pm, etype, nvo=lp.nvo)
+    # ---- above the SELL threshold: one preconditioner application per cycle kind
+    k = dfg_case(64)
+    assert k.mesh.num_vertices >= 16384
+    r2 = np.random.default_rng(23).standard_normal(3 * k.mesh.num_vertices)
+    sweeps = {"CFDH_NO_FUSED_AMG": "1"}
+    pc_context("pc-2d-type0", k.mesh, k.bcs, k.dt, k.rho, k.mu, r2, pc_type=0)
+    pc_context("pc-2d-type1", k.mesh, k.bcs, k.dt, k.rho, k.mu, r2, pc_type=1)
+    pc_context("pc-2d-type2", k.mesh, k.bcs, k.dt, k.rho, k.mu, r2, pcd=(2, 3, 1), pc_type=2)
+    pc_context("pc-2d-type1-sweeps", k.mesh, k.bcs, k.dt, k.rho, k.mu, r2, env=sweeps, pc_type=1)
+    pc_context("pc-2d-type1-sweeps-cheb2", k.mesh, k.bcs, k.dt, k.rho, k.mu, r2, env=sweeps, pc_type=1, amg_smooth_degree=2)
+    cube = create_unit_cube(26)
+    bnd = np.nonzero(np.abs(cube.x - 0.5).max(axis=1) > 0.5 - 1e-12)[0].astype(np.int32)
+    out = bnd[np.isclose(cube.x[bnd, 0], 1.0)]
+    wall = np.setdiff1d(bnd, out).astype(np.int32)
+    r3 = np.random.default_rng(29).standard_normal(4 * cube.num_vertices)
+    pc_context("pc-3d-type1", cube, [(0, wall, np.zeros((len(wall), 3))), (1, out, np.zeros(len(out)))], 0.01, 1.0, 1e-2, r3, pc_type=1)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
     print("%d lines -> %s" % (len(lines), a.out))
