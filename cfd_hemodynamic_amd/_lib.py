@@ -57,7 +57,7 @@ SYMBOLS = [
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
     "cfdh_get_amg_operator", "cfdh_get_amg_vectors", "cfdh_krylov_vec_op",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
-    "cfdh_ipcs_apply_pressure_pc",
+    "cfdh_ipcs_apply_pressure_pc", "cfdh_ipcs_krylov_solve",
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
 ]
 
@@ -147,6 +147,7 @@ def lib():
     L.cfdh_ipcs_get_operator.argtypes = [vp, C.c_int, lp, ip, ip, dp]
     L.cfdh_ipcs_get_intermediate.argtypes = [vp, C.c_int, dp]
     L.cfdh_ipcs_apply_pressure_pc.argtypes = [vp, dp, dp]
+    L.cfdh_ipcs_krylov_solve.argtypes = [vp, C.c_int, dp, dp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(IpcsStats), dp]
     L.cfdh_wall_stats_reset.argtypes = [vp]
     L.cfdh_wall_stats_accumulate.argtypes = [vp, C.c_double]
     L.cfdh_wall_stats_get.argtypes = [vp, C.c_int, lp, dp]
@@ -184,6 +185,10 @@ AMG_HIER_A, AMG_HIER_P, AMG_HIER_H = 0, 1, 2  # cfdh_get_amg_operator / cfdh_get
 AMG_OP_A, AMG_OP_P, AMG_OP_G, AMG_OP_SB, AMG_OP_SC = 0, 1, 2, 3, 4
 (AMG_VEC_DINV, AMG_VEC_WDINV, AMG_VEC_AGG, AMG_VEC_COARSE_INV, AMG_VEC_D, AMG_VEC_LAMBDA, AMG_VEC_CC_SCALARS, AMG_VEC_CC_ML,
  AMG_VEC_CC_PBC, AMG_VEC_SPGEMM_ROWS, AMG_VEC_SHAPE, AMG_VEC_ORDER, AMG_VEC_A00_LMAX, AMG_VEC_A00_DINV) = range(14)
+# cfdh_ipcs_krylov_solve: words of the scalar block
+IP_RHO, IP_RHO_OLD, IP_ALPHA, IP_OMEGA, IP_BETA, IP_RZ, IP_TOL2, IP_BN2, IP_RN2, IP_DONE, IP_ITS, IP_BAD = range(12)
+IP_NSCAL = 16
+
 # cfdh_krylov_vec_op
 (KVOP_DOT, KVOP_NORM2, KVOP_NORM2_PAIR, KVOP_NORM2_TRIPLE, KVOP_NORMINF_DIFF, KVOP_SUB_MEAN, KVOP_NORM_SCALE_INV, KVOP_MULTIDOT,
  KVOP_MULTIDOT32, KVOP_GRAM, KVOP_MULTIAXPY, KVOP_LINCOMB, KVOP_LINCOMB_KEEP, KVOP_GS_UPDATE_NORMALIZE, KVOP_GS_UPDATE32, KVOP_STORE32,
@@ -637,8 +642,9 @@ class IpcsContext(Context):
         return sp.csr_matrix((val, col, rowptr), shape=shape)
 
     def get_intermediate(self, which):
-        """0 u*, 1 phi, 2 b1, 3 b2, 4 b3 of the last step / assembly."""
-        out = np.empty(self.nvert if which in (1, 3) else self.dim * self.nv)
+        """0 u*, 1 phi, 2 b1, 3 b2, 4 b3 of the last step / assembly; 5, 6: the search direction of the last velocity-sized /
+        pressure Krylov solve."""
+        out = np.empty(self.nvert if which in (1, 3, 6) else self.dim * self.nv)
         self._chk(self.L.cfdh_ipcs_get_intermediate(self.h, int(which), _dp(out)))
         return out
 
@@ -649,6 +655,21 @@ class IpcsContext(Context):
         z = np.zeros_like(r)
         self._chk(self.L.cfdh_ipcs_apply_pressure_pc(self.h, _dp(r), _dp(z)))
         return z
+
+    def krylov_solve(self, which, b, x0, rtol, atol, max_it):
+        """One Krylov driver of the step on the caller's right-hand side and initial guess (cfdh_ipcs_krylov_solve): which 0
+        BiCGStab on A1, 1 flexible PCG on L, 2 CG on rho M.  Returns (x, its, reason, rel_res, scalars); `scalars` holds the 16
+        words of the device scalar block, indexed by IP_RHO .. IP_BAD.  A capped solve returns, it does not raise."""
+        n = self.nvert if which == 1 else self.dim * self.nv
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
+        if which in (0, 1, 2) and (b.size != n or x0.size != n):
+            raise ValueError("b and x0 need %d entries" % n)
+        x, scal, st = np.empty(n), np.zeros(IP_NSCAL), IpcsStats()
+        self._chk(self.L.cfdh_ipcs_krylov_solve(self.h, int(which), _dp(b), _dp(x0), float(rtol), float(atol), int(max_it), _dp(x),
+                                                C.byref(st), _dp(scal)))
+        k = int(which)
+        return x, st.its[k], st.reason[k], st.rel_res[k], scal
 
 
 def rccl_unique_id():

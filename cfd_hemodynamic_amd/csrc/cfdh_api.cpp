@@ -1592,8 +1592,8 @@ int cfdh_ipcs_get_operator(cfdh_ctx *c, int which, int64_t *nnz, int32_t *rowptr
 int cfdh_ipcs_get_intermediate(cfdh_ctx *c, int which, double *out) {
   NEED_IPCS(c, "cfdh_ipcs_get_intermediate");
   IpcsData *I = c->ipcs;
-  if (!out || which < 0 || which > 4) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_intermediate: which in [0, 4]");
-  const dbuf<double> *src[5] = {&I->us, &I->phi, &I->b1, &I->b2, &I->b3};
+  if (!out || which < 0 || which > 6) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_intermediate: which in [0, 6]");
+  const dbuf<double> *src[7] = {&I->us, &I->phi, &I->b1, &I->b2, &I->b3, &I->kp, &I->pp};
   I->n_field_copies++;
   HIPCHK(c, hipMemcpyAsync(out, src[which]->p, sizeof(double) * src[which]->n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1604,6 +1604,17 @@ int cfdh_ipcs_apply_pressure_pc(cfdh_ctx *c, const double *r, double *z) {
   NEED_IPCS(c, "cfdh_ipcs_apply_pressure_pc");
   if (!r || !z) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_apply_pressure_pc: null array");
   return cfdh_ipcs_apply_pc(c, r, z);
+}
+
+int cfdh_ipcs_krylov_solve(cfdh_ctx *c, int which, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,
+                           cfdh_ipcs_stats *stats, double *scalars) {
+  NEED_IPCS(c, "cfdh_ipcs_krylov_solve");
+  if (!b || !x0 || !x || !stats) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_krylov_solve: null array");
+  if (which < 0 || which > 2) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_krylov_solve: which = %d outside 0 .. 2", which);
+  if (!(rtol >= 0) || !(rtol < 1) || !(atol >= 0) || max_it < 1)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_krylov_solve: 0 <= rtol < 1, atol >= 0, max_it >= 1");
+  c->err.clear();
+  return cfdh_ipcs_krylov_solve_impl(c, which, b, x0, rtol, atol, max_it, x, stats, scalars);
 }
 
 }  // extern "C"

@@ -28,9 +28,6 @@
 #define TPB 256
 #define IP_NB 2048  // most blocks (= partial sums per dot product) of the reducing kernels
 
-// scalars of the Krylov loops (device array of IP_NS doubles; [IP_RN2, IP_BAD] are mirrored into host-mapped memory)
-enum { IP_RHO = 0, IP_RHO_OLD, IP_ALPHA, IP_OMEGA, IP_BETA, IP_RZ, IP_TOL2, IP_BN2, IP_RN2, IP_DONE, IP_ITS, IP_BAD, IP_NS = 16 };
-
 // ---------------------------------------------------------------- assembly
 // cw[cell][k][e] = |det| sum_d w_k,d Jinv[e][d],  w = 1.5 u_prev - 0.5 u_n1 at local node k;  geo[cell] = (Jinv [D][D], |det|)
 template <int D>
@@ -892,6 +889,16 @@ static int ip_finish(cfdh_ctx *c, int which, const double m[4], bool capped, cfd
   return 0;
 }
 
+// cfdh_ipcs_krylov_solve only: the closing true-residual stage resets the recurrence scalars, so the hook keeps the block as the
+// last iteration left it.  A step never takes this copy.
+static int ip_snapshot(cfdh_ctx *c) {
+  IpcsData *I = IP(c);
+  if (!I->snap_on) return 0;
+  HIPCHK(c, hipMemcpyAsync(I->snap, I->S.p, sizeof I->snap, hipMemcpyDeviceToHost, c->stream));
+  I->snap_set = true;
+  return 0;
+}
+
 // BiCGStab + Jacobi, A1 x = b on D interleaved columns; x holds the initial guess
 template <int D>
 static int ip_bicgstab(cfdh_ctx *c, const IpMat &A, const double *dinv, const double *b, double *x, cfdh_ipcs_stats *st) {
@@ -930,6 +937,7 @@ static int ip_bicgstab(cfdh_ctx *c, const IpMat &A, const double *dinv, const do
       if (m[1] != 0.0) break;
     }
     if (m[3] != 0.0) break;
+    CHK(ip_snapshot(c));
     ip_spmv<D, 2>(c, A, x, I->kr.p, b);  // the recurrence says converged (or the cap is reached): the true residual decides
     ip_scal<0>(c, nbs, rtol, atol, 0);
     CHK(ip_read(c, m));
@@ -982,6 +990,7 @@ static int ip_cg(cfdh_ctx *c, int which, const IpMat &A, const double *dinv, con
       }
     }
     if (m[3] != 0.0) break;
+    CHK(ip_snapshot(c));
     ip_spmv<D, 2>(c, A, x, r, b);
     ip_scal<0>(c, nbs, rtol, atol, 0);
     CHK(ip_read(c, m));
@@ -1064,6 +1073,58 @@ int cfdh_ipcs_apply_pc(cfdh_ctx *c, const double *r, double *z) {
   CHK(k_amg_vcycle(c, I->hLam, I->pr.p, I->pz.p));
   HIPCHK(c, hipMemcpyAsync(z, I->pz.p, sizeof(double) * I->nvert, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// One driver on the caller's b and x0 (cfdh_ipcs_krylov_solve): the step's instantiation, matrix, Jacobi weights and work vectors;
+// b and x live in buffers of the hook's own, the tolerances of the context are put back, b1 is kept over the assembly.
+template <int D>
+static int ip_krylov_solve_t(cfdh_ctx *c, int which, cfdh_ipcs_stats *st) {
+  IpcsData *I = IP(c);
+  if (which == 0) {
+    const IpMat A1{I->nn, I->rp2.p, I->col2.p, I->A1v.p};
+    return ip_bicgstab<D>(c, A1, I->dinv1.p, I->hk_b.p, I->hk_x.p, st);
+  }
+  if (which == 1) {
+    const IpMat L{I->nvert, I->rp1.p, I->col1.p, I->Lv.p};
+    return ip_cg<1, false>(c, 1, L, nullptr, I->hk_b.p, I->hk_x.p, I->pr.p, I->pz.p, I->pp.p, I->pq.p, st);
+  }
+  const IpMat RM{I->nn, I->rp2.p, I->col2.p, I->RMv.p};
+  return ip_cg<D, true>(c, 2, RM, I->dinv3.p, I->hk_b.p, I->hk_x.p, I->kr.p, I->kz.p, I->kp.p, I->kv.p, st);
+}
+
+int cfdh_ipcs_krylov_solve_impl(cfdh_ctx *c, int which, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,
+                                cfdh_ipcs_stats *st, double *scalars) {
+  IpcsData *I = IP(c);
+  hipStream_t s = c->stream;
+  const size_t n1 = (size_t)I->nn * I->D, n = which == 1 ? (size_t)I->nvert : n1;
+  memset(st, 0, sizeof *st);
+  CHK(ip_prepare(c));
+  HIPCHK(c, I->hk_b.alloc(n1)); HIPCHK(c, I->hk_x.alloc(n1));
+  const long long launch0 = I->n_launch, sync0 = I->n_sync;
+  if (which == 0) {  // A1 of the current state; the assembly also writes b1, which is kept
+    const bool was = I->assembled;
+    HIPCHK(c, hipMemcpyAsync(I->hk_x.p, I->b1.p, sizeof(double) * n1, hipMemcpyDeviceToDevice, s));
+    CHK(I->D == 2 ? ip_assemble_t<2>(c) : ip_assemble_t<3>(c));
+    HIPCHK(c, hipMemcpyAsync(I->b1.p, I->hk_x.p, sizeof(double) * n1, hipMemcpyDeviceToDevice, s));
+    I->assembled = was;
+  }
+  HIPCHK(c, hipMemcpyAsync(I->hk_b.p, b, sizeof(double) * n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(I->hk_x.p, x0, sizeof(double) * n, hipMemcpyHostToDevice, s));
+  const double rtol0 = I->rtol[which], atol0 = I->atol;
+  const int max0 = I->max_it[which];
+  I->rtol[which] = rtol; I->atol = atol; I->max_it[which] = max_it;
+  I->snap_on = true; I->snap_set = false;
+  const int rc = I->D == 2 ? ip_krylov_solve_t<2>(c, which, st) : ip_krylov_solve_t<3>(c, which, st);
+  I->snap_on = false;
+  I->rtol[which] = rtol0; I->atol = atol0; I->max_it[which] = max0;
+  I->n_launch = launch0; I->n_sync = sync0;
+  CHK(rc);
+  HIPCHK(c, hipMemcpyAsync(x, I->hk_x.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  if (scalars) HIPCHK(c, hipMemcpyAsync(scalars, I->S.p, sizeof(double) * IP_NS, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (scalars && I->snap_set)
+    for (int k = IP_RHO; k <= IP_BETA; k++) scalars[k] = I->snap[k];
   return 0;
 }
 

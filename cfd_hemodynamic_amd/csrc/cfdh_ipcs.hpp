@@ -2,6 +2,11 @@
 #pragma once
 #include "cfdh_internal.hpp"
 
+// scalars of the Krylov loops (device array of IP_NS doubles; [IP_RN2, IP_BAD] are mirrored into host-mapped memory); the indices
+// are part of cfdh_ipcs_krylov_solve's contract (include/cfdh.h)
+enum { IP_RHO = 0, IP_RHO_OLD, IP_ALPHA, IP_OMEGA, IP_BETA, IP_RZ, IP_TOL2, IP_BN2, IP_RN2, IP_DONE, IP_ITS, IP_BAD, IP_NS = 16 };
+static_assert(IP_NS == CFDH_IPCS_NSCAL, "include/cfdh.h documents the scalar block");
+
 struct IpcsData {
   int D = 2, NL = 6, nn = 0, nvert = 0, nc = 0;
   // host mesh and constant operators (P2 pattern: hM.rowptr / hM.col, shared by K and A1; P1 pattern: hL.rowptr / hL.col)
@@ -36,6 +41,10 @@ struct IpcsData {
   int max_it[3] = {10000, 10000, 10000};
   long long n_launch = 0, n_sync = 0, n_field_copies = 0;  // of the step in progress; whole-field host copies since creation
   cfdh_ipcs_stats last = {};
+  // cfdh_ipcs_krylov_solve: right-hand side and iterate of its own, and the scalar block as the last iteration left it
+  dbuf<double> hk_b, hk_x;
+  bool snap_on = false, snap_set = false;
+  double snap[IP_NS] = {};
 };
 
 int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells, const double *coords, int64_t nfac,
@@ -46,4 +55,6 @@ int cfdh_ipcs_add_dirichlet(cfdh_ctx *c, int field, int64_t n, const int32_t *no
 int cfdh_ipcs_assemble(cfdh_ctx *c);   // A1, b1 at the current state
 int cfdh_ipcs_step_impl(cfdh_ctx *c, cfdh_ipcs_stats *st);
 int cfdh_ipcs_apply_pc(cfdh_ctx *c, const double *r, double *z);
+int cfdh_ipcs_krylov_solve_impl(cfdh_ctx *c, int which, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,
+                                cfdh_ipcs_stats *st, double *scalars);
 int cfdh_ipcs_functional(cfdh_ctx *c, int kind, int marker, double *out);

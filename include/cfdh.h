@@ -431,11 +431,36 @@ int cfdh_ipcs_step(cfdh_ctx *ctx, cfdh_ipcs_stats *stats);
  * cfdh_get_pcd_operator. */
 int cfdh_ipcs_get_operator(cfdh_ctx *ctx, int which, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals);
 /* Vectors of the last step (or, for b1, of the assembly cfdh_ipcs_get_operator(0) triggered): which 0: u* [nn][gdim], 1: phi
- * [nvert], 2: b1 [nn][gdim], 3: b2 [nvert], 4: b3 [nn][gdim]. */
+ * [nvert], 2: b1 [nn][gdim], 3: b2 [nvert], 4: b3 [nn][gdim]; the search direction p as the last velocity-sized (5, [nn][gdim])
+ * or pressure (6, [nvert]) Krylov solve left it -- work vectors, exposed so that a test can see that the iterations launched
+ * behind a converged one moved nothing. */
 int cfdh_ipcs_get_intermediate(cfdh_ctx *ctx, int which, double *out);
 /* z = V r, one V-cycle of the pressure hierarchy for the current pressure Dirichlet set ([nvert] host arrays).  Exposed so that
  * a test can measure how symmetric the cycle is (it decides between PCG and flexible PCG). */
 int cfdh_ipcs_apply_pressure_pc(cfdh_ctx *ctx, const double *r, double *z);
+/* One of the step's three Krylov drivers on data of the caller's: which 0: BiCGStab + Jacobi on A1 (assembled from the current
+ * state by this call), 1: flexible PCG + one V-cycle on L, 2: CG + Jacobi on rho M.  b, x0, x: host arrays with that solve's
+ * unknowns ([nn][gdim] for 0 and 2, [nvert] for 1); the same kernels, matrix, Jacobi weights and work vectors as in
+ * cfdh_ipcs_step, with rtol, atol and max_it of this call.  No mean is subtracted: on a singular pressure problem pass a
+ * mean-free b.  The time state (u_sol, u_prev, u_n1, p_sol, u*, phi, b1 .. b3) and the tolerances of cfdh_ipcs_set_tolerances
+ * stay as they were.  A capped or broken-down solve is no failed call: 0 is returned, x is the last iterate and
+ * stats->reason[which] says what happened (of stats only its / reason / rel_res [which] are meaningful).  CFDH_E_ARG, before
+ * anything is launched, for a null b / x0 / x / stats, which outside 0 .. 2, max_it < 1, rtol outside [0, 1) or atol < 0.
+ * scalars (or NULL) receives the CFDH_IPCS_NSCAL words of the device's scalar block after the solve:
+ *    0 IP_RHO      rh . r (BiCGStab) after the last iteration       6 IP_TOL2  max(rtol |b|, atol)^2
+ *    1 IP_RHO_OLD  the one before                                  7 IP_BN2   |b|^2
+ *    2 IP_ALPHA    of the last iteration                           8 IP_RN2   |b - A x|^2 of the returned x
+ *    3 IP_OMEGA    of the last iteration (BiCGStab)                9 IP_DONE  1 when the solve stopped by itself
+ *    4 IP_BETA     computed last: by iteration k for k + 1        10 IP_ITS   iterations
+ *                  (flexible PCG: by k - 1 for k, none after k)   11 IP_BAD   1 after a NaN / inf or a breakdown
+ *    5 IP_RZ       r . z: after the last iteration (CG), at the    12 .. 15 unused
+ *                  start of the last one (flexible PCG)
+ * On the device the closing true-residual stage resets words 0 .. 4 (to |r|^2, 1, 1, 1, 0, for a restart); the call returns them
+ * as they were just before it, as the last iteration left them.  A solve that ends at its = 0 returns the reset values.
+ * Exposed for tests, like cfdh_krylov_vec_op. */
+#define CFDH_IPCS_NSCAL 16
+int cfdh_ipcs_krylov_solve(cfdh_ctx *ctx, int which, const double *b, const double *x0, double rtol, double atol, int max_it,
+                           double *x, cfdh_ipcs_stats *stats, double *scalars);
 
 /* u_prev2 (stabilized_schur_bdf2.py:72): upload / download; nv local vertices x gdim */
 int cfdh_set_previous2(cfdh_ctx *ctx, const double *u_prev2);
