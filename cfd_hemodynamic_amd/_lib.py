@@ -182,9 +182,10 @@ def _raise(code, msg):
 FORM_CONVECTIVE, FORM_ROTATIONAL = 0, 1  # cfdh_set_formulation
 PC_SELFP, PC_CAHOUET_CHABARD, PC_PCD = 0, 1, 2  # cfdh_options.pc_type
 AMG_HIER_A, AMG_HIER_P, AMG_HIER_H = 0, 1, 2  # cfdh_get_amg_operator / cfdh_get_amg_vectors
-AMG_OP_A, AMG_OP_P, AMG_OP_G, AMG_OP_SB, AMG_OP_SC = 0, 1, 2, 3, 4
+AMG_HIER_PG, AMG_HIER_DL0 = 3, 4  # partitioned run: the replicated pressure hierarchy, this rank's share of its finest level
+AMG_OP_A, AMG_OP_P, AMG_OP_G, AMG_OP_SB, AMG_OP_SC, AMG_OP_PT = 0, 1, 2, 3, 4, 5
 (AMG_VEC_DINV, AMG_VEC_WDINV, AMG_VEC_AGG, AMG_VEC_COARSE_INV, AMG_VEC_D, AMG_VEC_LAMBDA, AMG_VEC_CC_SCALARS, AMG_VEC_CC_ML,
- AMG_VEC_CC_PBC, AMG_VEC_SPGEMM_ROWS, AMG_VEC_SHAPE, AMG_VEC_ORDER, AMG_VEC_A00_LMAX, AMG_VEC_A00_DINV) = range(14)
+ AMG_VEC_CC_PBC, AMG_VEC_SPGEMM_ROWS, AMG_VEC_SHAPE, AMG_VEC_ORDER, AMG_VEC_A00_LMAX, AMG_VEC_A00_DINV, AMG_VEC_DL0_SHAPE) = range(15)
 # cfdh_ipcs_krylov_solve: words of the scalar block
 IP_RHO, IP_RHO_OLD, IP_ALPHA, IP_OMEGA, IP_BETA, IP_RZ, IP_TOL2, IP_BN2, IP_RN2, IP_DONE, IP_ITS, IP_BAD = range(12)
 IP_NSCAL = 16

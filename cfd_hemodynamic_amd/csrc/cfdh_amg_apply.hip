@@ -358,7 +358,7 @@ __global__ __launch_bounds__(TPB) void sell_jacobi_post_kernel(int n, const int 
 template <typename T>
 static void launch_jacobi_pre(cfdh_ctx *c, const CsrDev &A, bool sell, int n, const double *wdinv, const T *b, T *xa, T *r) {
   dim3 block(TPB), gridS((unsigned)((n + TPB - 1) / TPB)), gridC((unsigned)((8ll * n + TPB - 1) / TPB));
-  if (sell && A.has_sell_weighted())
+  if (cfdh_pre_takes_sell(A, sell))
     hipLaunchKernelGGL((sell_jacobi_pre_kernel<T>), gridS, block, 0, c->stream, n, A.sptr.p, A.scol.p, A.svalw.p, wdinv, b, xa, r);
   else
     hipLaunchKernelGGL((jacobi_pre_kernel<T>), gridC, block, 0, c->stream, n, A.rowptr.p, A.col.p, A.val.p, wdinv, b, xa, r);
@@ -367,7 +367,7 @@ static void launch_jacobi_pre(cfdh_ctx *c, const CsrDev &A, bool sell, int n, co
 template <typename T>
 static void launch_jacobi_post(cfdh_ctx *c, const CsrDev &A, bool sell, int n, const double *wdinv, const T *b, const T *x1, T *x) {
   dim3 block(TPB), gridS((unsigned)((n + TPB - 1) / TPB)), gridC((unsigned)((8ll * n + TPB - 1) / TPB));
-  if (sell && A.has_sell())
+  if (cfdh_post_takes_sell(A, sell))
     hipLaunchKernelGGL((sell_jacobi_post_kernel<T>), gridS, block, 0, c->stream, n, A.sptr.p, A.scol.p, A.sval.p, wdinv, b, x1, x);
   else
     hipLaunchKernelGGL((jacobi_post_kernel<T>), gridC, block, 0, c->stream, n, A.rowptr.p, A.col.p, A.val.p, wdinv, b, x1, x);
@@ -376,7 +376,7 @@ static void launch_jacobi_post(cfdh_ctx *c, const CsrDev &A, bool sell, int n, c
 template <typename T>
 static void launch_prolong_add(cfdh_ctx *c, const CsrDev &P, bool sell, int n, const T *x, T *y, const T *b) {
   dim3 block(TPB), gridS((unsigned)((n + TPB - 1) / TPB)), gridC((unsigned)((8ll * n + TPB - 1) / TPB));
-  if (sell && P.has_sell())
+  if (cfdh_prolong_takes_sell(P, sell))
     hipLaunchKernelGGL((sell_spmv_kernel<3, T>), gridS, block, 0, c->stream, n, P.sptr.p, P.scol.p, P.sval.p, x, y, b);
   else
     hipLaunchKernelGGL((csr_spmv_kernel<3, T>), gridC, block, 0, c->stream, n, P.rowptr.p, P.col.p, P.val.p, x, y, b);
@@ -711,7 +711,7 @@ int k_dl0_down(cfdh_ctx *c, const double *halo_vec) {
   // the ghost parts of d.b and d.xa stay zero
   if (d.ghost_rhs) hipLaunchKernelGGL(dl0_pack_kernel, dim3((nv + TPB - 1) / TPB), dim3(TPB), 0, c->stream, nvo, nv, c->dim, halo_vec, d.wdinv.p, d.b.p, d.xa.p, 1);
   // short regular rows: SELL-64 (as the replicated level 0 would use)
-  launch_jacobi_pre<double>(c, d.A, cfdh_sweep_sell(d.A.nnz, nvo), nvo, d.wdinv.p, (const double *)d.b.p, d.xa.p, d.r.p);
+  launch_jacobi_pre<double>(c, d.A, cfdh_dl0_rule_A(c), nvo, d.wdinv.p, (const double *)d.b.p, d.xa.p, d.r.p);
   HIPCHK(c, hipGetLastError());
   return csr_spmv_t<double>(c, d.PT, d.r.p, N->b.p, 0, (const double *)nullptr);
 }
@@ -721,11 +721,11 @@ int k_dl0_up(cfdh_ctx *c, double *out) {
   AmgLevel *N = c->hLg.lev[1];
   const int nvo = c->nvo, nv = c->nv;
   // the replicated levels: composite-operator cycle from level 1 (6 launches for four coarse levels instead of 13 sweeps)
-  if (c->hLg.fused && c->opt.amg_smooth_degree == 1 && !c->env.dl0_coarse_sweeps) CHK(amg_cycle_fused<double>(c, c->hLg, (const double *)N->b.p, N->x.p, 0, 1));
+  if (cfdh_dl0_coarse_fused(c)) CHK(amg_cycle_fused<double>(c, c->hLg, (const double *)N->b.p, N->x.p, 0, 1));
   else CHK(amg_cycle_jacobi<double>(c, c->hLg, 1, (const double *)N->b.p, N->x.p, 0));
-  launch_prolong_add<double>(c, d.P, cfdh_sweep_sell(d.P.nnz, nv), nv, (const double *)N->x.p, d.x1.p, (const double *)d.xa.p);  // x1 = xa + P x_c
+  launch_prolong_add<double>(c, d.P, cfdh_dl0_rule_P(c), nv, (const double *)N->x.p, d.x1.p, (const double *)d.xa.p);  // x1 = xa + P x_c
   HIPCHK(c, hipGetLastError());
-  launch_jacobi_post<double>(c, d.A, cfdh_sweep_sell(d.A.nnz, nvo), nvo, d.wdinv.p, (const double *)d.b.p, (const double *)d.x1.p, out);
+  launch_jacobi_post<double>(c, d.A, cfdh_dl0_rule_A(c), nvo, d.wdinv.p, (const double *)d.b.p, (const double *)d.x1.p, out);
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -1211,7 +1211,7 @@ int cfdh_amg_setup_dev(cfdh_ctx *c, AmgHier &H, CsrDev &A0, bool singular, int n
     if (H.lev.size() == 1) { H.nnz_G0 = L->G.nnz; H.nnz_S0 = (long long)L->Sb.nnz + L->Sc.nnz; }
     // a partitioned run also uses the sweep-by-sweep cycle (distributed finest pressure level, overlapping velocity block): it
     // needs the plain transfer operators
-    if (c->nranks > 1) { move_csr(L->P, P); move_csr(L->R, R); }
+    if (c->nranks > 1) { move_csr(L->P, P); move_csr(L->R, R); if (keep) L->agg.adopt(agg); }
     else if (keep) { move_csr(L->P, P); L->agg.adopt(agg); }
     move_csr(L->A, A);
     lastL = L;

@@ -829,23 +829,32 @@ int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const doubl
 
 // ---- read-only view of the built hierarchies (cfdh_get_amg_operator / cfdh_get_amg_vectors)
 static int amg_pick(cfdh_ctx *c, const char *name, int hier, int level, AmgHier **H, AmgLevel **L) {
-  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_STATE, "%s: one GPU only", name);
   if (!c->pc_valid) return cfdh_fail(c, CFDH_E_STATE, "%s: no preconditioner built yet (cfdh_apply_preconditioner or cfdh_solve_step first)", name);
   *H = nullptr;
+  *L = nullptr;
   if (hier == CFDH_AMG_HIER_H) {
     if (c->opt.pc_type != 1 || c->Hlev.n <= 0) return cfdh_fail(c, CFDH_E_STATE, "%s: H exists for pc_type 1 only", name);
     *L = &c->Hlev;
     return 0;
   }
-  if (hier != CFDH_AMG_HIER_A && hier != CFDH_AMG_HIER_P) return cfdh_fail(c, CFDH_E_ARG, "%s: unknown hierarchy %d", name, hier);
+  if (hier == CFDH_AMG_HIER_DL0) {  // the distributed level has its own operators and no AmgLevel: the callers take c->dl0
+    if (c->gp_n <= 0 || !c->hLg.valid || !c->dl0.on) return cfdh_fail(c, CFDH_E_STATE, "%s: no distributed finest pressure level on this context", name);
+    *H = &c->hLg;
+    return 0;
+  }
+  if (hier != CFDH_AMG_HIER_A && hier != CFDH_AMG_HIER_P && hier != CFDH_AMG_HIER_PG) return cfdh_fail(c, CFDH_E_ARG, "%s: unknown hierarchy %d", name, hier);
   if (hier == CFDH_AMG_HIER_A && c->opt.pc_type == 0) return cfdh_fail(c, CFDH_E_STATE, "%s: pc_type 0 has no velocity hierarchy", name);
-  AmgHier *h = hier == CFDH_AMG_HIER_A ? &c->hA : (c->opt.pc_type == 0 ? &c->hS : &c->hL);
+  if (hier == CFDH_AMG_HIER_PG && c->gp_n <= 0) return cfdh_fail(c, CFDH_E_STATE, "%s: no replicated pressure space (cfdh_set_global_pressure_space)", name);
+  AmgHier *h = hier == CFDH_AMG_HIER_A ? &c->hA : hier == CFDH_AMG_HIER_PG ? &c->hLg : (c->opt.pc_type == 0 ? &c->hS : &c->hL);
   if (!h->valid) return cfdh_fail(c, CFDH_E_STATE, "%s: hierarchy %d is not built", name, hier);
   if (level < 0 || level >= (int)h->lev.size()) return cfdh_fail(c, CFDH_E_ARG, "%s: level %d of %d", name, level, (int)h->lev.size());
   *H = h;
   *L = h->lev[level];
   return 0;
 }
+// Level 0 of a rank's own hierarchies numbers the local nodes (all of them, or the owned ones, which come first and are permuted
+// among themselves); level 0 of the replicated hierarchy numbers the global pressure space, which the library never renumbers.
+static bool amg_local_dim(const cfdh_ctx *c, int n) { return n == (int)c->perm.size() || n == c->nvo; }
 
 int cfdh_get_amg_operator(cfdh_ctx *c, int hier, int level, int which, int64_t *nrow, int64_t *ncol, int64_t *nnz, int32_t *rowptr,
                           int32_t *col, double *vals) {
@@ -855,9 +864,12 @@ int cfdh_get_amg_operator(cfdh_ctx *c, int hier, int level, int which, int64_t *
   AmgHier *H = nullptr;
   AmgLevel *L = nullptr;
   CHK(amg_pick(c, "cfdh_get_amg_operator", hier, level, &H, &L));
-  if (which < CFDH_AMG_OP_A || which > CFDH_AMG_OP_SC) return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_operator: unknown operator %d", which);
-  if (!H) level = 0;
-  const CsrDev &M = which == CFDH_AMG_OP_A ? L->A : which == CFDH_AMG_OP_P ? L->P : which == CFDH_AMG_OP_G ? L->G : which == CFDH_AMG_OP_SB ? L->Sb : L->Sc;
+  const bool dl0 = hier == CFDH_AMG_HIER_DL0;
+  if (dl0 ? (which != CFDH_AMG_OP_A && which != CFDH_AMG_OP_P && which != CFDH_AMG_OP_PT) : (which < CFDH_AMG_OP_A || which > CFDH_AMG_OP_SC))
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_operator: unknown operator %d", which);
+  if (!H || dl0) level = 0;
+  const CsrDev &M = dl0 ? (which == CFDH_AMG_OP_A ? c->dl0.A : which == CFDH_AMG_OP_P ? c->dl0.P : c->dl0.PT)
+                        : which == CFDH_AMG_OP_A ? L->A : which == CFDH_AMG_OP_P ? L->P : which == CFDH_AMG_OP_G ? L->G : which == CFDH_AMG_OP_SB ? L->Sb : L->Sc;
   if (M.n <= 0 || !M.rowptr.p || !M.col.p || !M.val.p)
     return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_operator: operator %d of level %d is not kept in fp64 CSR (P: CFDH_AMG_KEEP=1 before the build)", which, level);
   *nrow = M.n; *ncol = M.m; *nnz = M.nnz;
@@ -873,8 +885,11 @@ int cfdh_get_amg_operator(cfdh_ctx *c, int hier, int level, int which, int64_t *
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (rp[M.n] != M.nnz) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_operator: rowptr ends at %d, the operator holds %d entries", rp[M.n], M.nnz);
   // level 0 lives in the internal numbering: rows / columns that number it go back to the caller's
-  const bool rows0 = level == 0 && which != CFDH_AMG_OP_G && (int)c->perm.size() == M.n;
-  const bool cols0 = level == 0 && (which == CFDH_AMG_OP_A || which == CFDH_AMG_OP_SB || which == CFDH_AMG_OP_G) && (int)c->iperm.size() == M.m;
+  const bool local0 = level == 0 && hier != CFDH_AMG_HIER_PG;
+  const bool rows0 = local0 && which != CFDH_AMG_OP_G && which != CFDH_AMG_OP_PT && amg_local_dim(c, M.n);
+  const bool cols0 = local0 && (which == CFDH_AMG_OP_A || which == CFDH_AMG_OP_SB || which == CFDH_AMG_OP_G || which == CFDH_AMG_OP_PT) && amg_local_dim(c, M.m);
+  // the restriction of the distributed level sums every coarse row in the stored order: its entries stay in that order
+  const bool resort = cols0 && which != CFDH_AMG_OP_PT;
   int64_t pos = 0;
   std::vector<std::pair<int, double>> row;
   for (int ru = 0; ru < M.n; ru++) {
@@ -883,7 +898,7 @@ int cfdh_get_amg_operator(cfdh_ctx *c, int hier, int level, int which, int64_t *
     row.clear();
     for (int k = rp[r]; k < rp[r + 1]; k++) row.push_back({cols0 ? c->iperm[cl[k]] : cl[k], vl[k]});
     // a stable sort by column only: the order in which the build stored equal or descending columns stays visible to the caller
-    if (cols0) std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
+    if (resort) std::stable_sort(row.begin(), row.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
     for (auto &e : row) { col[pos] = e.first; vals[pos] = e.second; pos++; }
   }
   rowptr[M.n] = (int32_t)pos;
@@ -897,8 +912,13 @@ int cfdh_get_amg_vectors(cfdh_ctx *c, int hier, int level, int which, int64_t *n
   AmgHier *H = nullptr;
   AmgLevel *L = nullptr;
   CHK(amg_pick(c, "cfdh_get_amg_vectors", hier, level, &H, &L));
-  if (!H) level = 0;
-  const bool perm0 = level == 0 && (int)c->perm.size() == L->n;
+  const bool dl0 = hier == CFDH_AMG_HIER_DL0;
+  if (!H || dl0) level = 0;
+  if (dl0 && which != CFDH_AMG_VEC_WDINV && which != CFDH_AMG_VEC_ORDER && which != CFDH_AMG_VEC_DL0_SHAPE)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_vectors: the distributed level has no item %d", which);
+  AmgLevel dl0_view;  // n and nothing else: the vectors of the distributed level live in c->dl0
+  if (dl0) { dl0_view.n = c->nv; L = &dl0_view; }
+  const bool perm0 = level == 0 && hier != CFDH_AMG_HIER_PG && amg_local_dim(c, L->n);
   auto fetch = [&](const void *src, size_t bytes, void *dst) -> int {
     HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -908,7 +928,7 @@ int cfdh_get_amg_vectors(cfdh_ctx *c, int hier, int level, int which, int64_t *n
   switch (which) {
     case CFDH_AMG_VEC_DINV:
     case CFDH_AMG_VEC_WDINV: {
-      const dbuf<double> &v = which == CFDH_AMG_VEC_DINV ? L->dinv : L->wdinv;
+      const dbuf<double> &v = dl0 ? c->dl0.wdinv : which == CFDH_AMG_VEC_DINV ? L->dinv : L->wdinv;
       if (!v.p || (int)v.n < L->n) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: vector %d is not there", which);
       *n = L->n;
       if (!out) return 0;
@@ -930,6 +950,15 @@ int cfdh_get_amg_vectors(cfdh_ctx *c, int hier, int level, int which, int64_t *n
       if (!H || H->coarse_n <= 0 || !H->coarse_inv.p) return cfdh_fail(c, CFDH_E_STATE, "cfdh_get_amg_vectors: no dense coarsest inverse");
       *n = (int64_t)H->coarse_n * H->coarse_n;
       if (!out) return 0;
+      // a hierarchy of one level: its coarsest operator is level 0, which lives in the internal numbering
+      if (H->lev.size() == 1 && hier != CFDH_AMG_HIER_PG && amg_local_dim(c, H->coarse_n)) {
+        const size_t m = (size_t)H->coarse_n;
+        std::vector<double> h(m * m);
+        CHK(fetch(H->coarse_inv.p, sizeof(double) * h.size(), h.data()));
+        for (size_t i = 0; i < m; i++)
+          for (size_t j = 0; j < m; j++) out[i * m + j] = h[(size_t)c->perm[i] * m + (size_t)c->perm[j]];
+        return 0;
+      }
       return fetch(H->coarse_inv.p, sizeof(double) * (size_t)*n, out);
     }
     case CFDH_AMG_VEC_D: {
@@ -1001,6 +1030,20 @@ int cfdh_get_amg_vectors(cfdh_ctx *c, int hier, int level, int which, int64_t *n
       CHK(fetch(c->dinvA.p, sizeof(double) * nu, h.data()));
       for (int i = 0; i < nvo; i++)
         for (int q = 0; q < c->dim; q++) out[(size_t)c->dim * i + q] = h[(size_t)c->dim * c->perm[i] + q];
+      return 0;
+    }
+    case CFDH_AMG_VEC_DL0_SHAPE: {
+      if (!dl0) return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_vectors: item %d belongs to CFDH_AMG_HIER_DL0", which);
+      *n = 8;
+      if (!out) return 0;
+      // the decisions of k_dl0_down / k_dl0_up, through the functions they call (cfdh_internal.hpp)
+      const cfdh_ctx::DistL0 &d = c->dl0;
+      out[0] = d.n1; out[1] = d.ghost_rhs ? 1 : 0;
+      out[2] = cfdh_pre_takes_sell(d.A, cfdh_dl0_rule_A(c)) ? 1 : 0;
+      out[3] = cfdh_post_takes_sell(d.A, cfdh_dl0_rule_A(c)) ? 1 : 0;
+      out[4] = cfdh_prolong_takes_sell(d.P, cfdh_dl0_rule_P(c)) ? 1 : 0;
+      out[5] = cfdh_dl0_coarse_fused(c) ? 1 : 0;
+      out[6] = c->nvo; out[7] = c->nv;
       return 0;
     }
     case CFDH_AMG_VEC_ORDER:

@@ -471,6 +471,17 @@ struct cfdh_ctx {
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
 
+// ---- which copy a sweep streams: the size rule said SELL and the operator has the copy (launch_jacobi_pre / _post / launch_prolong_add
+// in cfdh_amg_apply.hip), and the rules of the distributed finest pressure level (k_dl0_down / k_dl0_up).  cfdh_get_amg_vectors reports
+// the decisions through these same functions.
+inline bool cfdh_pre_takes_sell(const CsrDev &A, bool rule) { return rule && A.has_sell_weighted(); }
+inline bool cfdh_post_takes_sell(const CsrDev &A, bool rule) { return rule && A.has_sell(); }
+inline bool cfdh_prolong_takes_sell(const CsrDev &P, bool rule) { return rule && P.has_sell(); }
+inline bool cfdh_dl0_rule_A(const cfdh_ctx *c) { return cfdh_sweep_sell(c->dl0.A.nnz, c->nvo); }
+inline bool cfdh_dl0_rule_P(const cfdh_ctx *c) { return cfdh_sweep_sell(c->dl0.P.nnz, c->nv); }
+// the replicated levels below it: composite-operator cycle from level 1, or sweep by sweep
+inline bool cfdh_dl0_coarse_fused(const cfdh_ctx *c) { return c->hLg.fused && c->opt.amg_smooth_degree == 1 && !c->env.dl0_coarse_sweeps; }
+
 // ---- error helpers -----------------------------------------------------------
 int cfdh_fail(cfdh_ctx *c, int code, const char *fmt, ...);
 #define HIPCHK(c, call)                                                                           \

@@ -299,23 +299,30 @@ int cfdh_apply_operator(cfdh_ctx *ctx, const double *r, double *z, double *w);
 #define CFDH_AMG_HIER_A 0 /* scalar proxy of the velocity block (pc_type 1, 2) */
 #define CFDH_AMG_HIER_P 1 /* pressure hierarchy: the Laplacian (pc_type 1, 2) or the SELFP Schur matrix (pc_type 0) */
 #define CFDH_AMG_HIER_H 2 /* the single level H of the Cahouet-Chabard approximation */
+#define CFDH_AMG_HIER_PG 3  /* partitioned run: the replicated hierarchy of the global pressure space (every rank holds all of it; level 0 in
+                              the global vertex ids of cfdh_set_global_pressure_space) */
+#define CFDH_AMG_HIER_DL0 4 /* partitioned run: this rank's share of level 0 of CFDH_AMG_HIER_PG, the distributed finest level (level ignored):
+                              CFDH_AMG_OP_A [owned x local], CFDH_AMG_OP_P [local x level 1], CFDH_AMG_OP_PT [level 1 x owned] */
 #define CFDH_AMG_OP_A 0   /* level operator */
 #define CFDH_AMG_OP_P 1   /* prolongator to the next level */
 #define CFDH_AMG_OP_G 2   /* G = P^T (I - A W) */
 #define CFDH_AMG_OP_SB 3  /* Sb = 2W - W A W */
 #define CFDH_AMG_OP_SC 4  /* Sc = (I - W A) P */
+#define CFDH_AMG_OP_PT 5  /* CFDH_AMG_HIER_DL0: the restriction, P^T of the owned rows; the entries of a row in the order they are summed in */
 /* One operator of one level as CSR with ascending columns.  Query convention of cfdh_get_csr: with rowptr = col = vals = NULL
  * only *nrow, *ncol, *nnz are set.  Indices that number level 0 are returned in the caller's node numbering (as
  * cfdh_get_pcd_operator does; the entries of such a row are re-sorted after the renumbering, so the stored order of its columns
- * is not visible to the caller, duplicates are), coarse indices as stored.  One GPU only; CFDH_E_STATE on a partitioned or pressure-correction
- * context, before the preconditioner exists, and for an operator the build did not keep: the device build releases P and the
- * aggregate ids unless CFDH_AMG_KEEP=1 is in the environment when the hierarchy is built. */
+ * is not visible to the caller, duplicates are), coarse indices as stored.  On one part of a partitioned run the hierarchies are this
+ * rank's: local numbering (owned nodes, then ghosts), the velocity hierarchy on owned + ghost nodes where the overlapping cycle runs,
+ * H and the rank's own pressure hierarchy on the owned nodes.  Rank-local: no exchange runs inside a getter.  CFDH_E_STATE on a
+ * pressure-correction context, before the preconditioner exists, and for an operator the build did not keep: the device build
+ * releases P (one GPU) and the aggregate ids unless CFDH_AMG_KEEP=1 is in the environment when the hierarchy is built. */
 int cfdh_get_amg_operator(cfdh_ctx *ctx, int hier, int level, int which, int64_t *nrow, int64_t *ncol, int64_t *nnz, int32_t *rowptr,
                           int32_t *col, double *vals);
 #define CFDH_AMG_VEC_DINV 0        /* 1 / a_ii of the level [n] */
 #define CFDH_AMG_VEC_WDINV 1       /* Jacobi weight times dinv [n] */
 #define CFDH_AMG_VEC_AGG 2         /* aggregate ids [n], -1: row without coarse correction (needs CFDH_AMG_KEEP=1) */
-#define CFDH_AMG_VEC_COARSE_INV 3  /* dense inverse of the coarsest operator, row-major [coarse_n^2] (level ignored) */
+#define CFDH_AMG_VEC_COARSE_INV 3  /* dense inverse of the coarsest operator, row-major [coarse_n^2] (level ignored; level 0 in a hierarchy of one level) */
 #define CFDH_AMG_VEC_D 4           /* folded dense correction D = Sc A_c^-1 of the level, row-major [n x Dn], fp32 widened */
 #define CFDH_AMG_VEC_LAMBDA 5      /* lmax, lmin of the level [2] */
 #define CFDH_AMG_VEC_CC_SCALARS 6  /* cc_alpha, cc_beta [2] */
@@ -327,6 +334,8 @@ int cfdh_get_amg_operator(cfdh_ctx *ctx, int hier, int level, int which, int64_t
                                       the fixed start vector of the spectral estimate is indexed by it) */
 #define CFDH_AMG_VEC_A00_LMAX 12   /* pc_type 0: the spectral bound lmaxA of D^-1 A00 used by the Chebyshev solve [1] */
 #define CFDH_AMG_VEC_A00_DINV 13   /* pc_type 0: 1 / diag(A00), [gdim nv] as the velocity part of a monolithic vector */
+#define CFDH_AMG_VEC_DL0_SHAPE 14  /* CFDH_AMG_HIER_DL0 (which also answers WDINV [local] and ORDER): n1, ghost layer of the right-hand side exchanged,
+                                      SELL taken by the pre-sweep / post-sweep / prolongation, fused cycle on the replicated levels, owned, local [8] */
 /* Vectors and scalars of the same, as doubles; *n receives the count, out may be NULL (query).  Level-0 vectors in the caller's
  * numbering.  Error codes as above. */
 int cfdh_get_amg_vectors(cfdh_ctx *ctx, int hier, int level, int which, int64_t *n, double *out);
