@@ -12,64 +12,140 @@
 #else
 #define CFDH_HD
 #endif
+#ifdef __clang__
+#define CFDH_UNROLL _Pragma("unroll")
+#else
+#define CFDH_UNROLL _Pragma("GCC unroll 8")
+#endif
 
 namespace cfdh_krylov {
+
+// c - a b as the compiler in use forms it in a plain loop: one fused operation in device code (hipcc contracts there, and a
+// select between the product and the sum must not undo it), a product and a difference on the host
+CFDH_HD inline double gram_nmsub(double c, double a, double b) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __builtin_fma(-a, b, c);
+#else
+  return c - a * b;
+#endif
+}
 
 // The k x k Gram system of the projected guess (k <= 8): y = argmin |b - W y| from the normal equations, by a pivoted Cholesky
 // that drops directions which have become numerically dependent -- a pivot whose remaining diagonal is not above 1e-10 of its
 // own G_pp, or not above 1e-14 of the largest diagonal entry.  Device layout: hd[8 i + q] = W_q . W_i (i < k), hd[8 k + q] = W_q . b.
 // Dropped directions get y = 0.  Rank 0, a non-finite diagonal or a non-finite y: y = 0 and the guess is not used.
-CFDH_HD inline bool gram_solve(int k, const double *hd, double *y, int *rank) {
-  double G[64], Lc[64], dg[8], g[8], yy[8], t[8];
-  int piv[8];
-  bool taken[8];
-  for (int i = 0; i < k; i++) {
-    for (int q = 0; q < k; q++) { G[q * k + i] = hd[i * 8 + q]; Lc[q * k + i] = 0.0; }
-    g[i] = hd[k * 8 + i]; yy[i] = 0.0; taken[i] = false;
+//
+// K is a template parameter and no array is indexed by a run-time value: every loop has constant bounds, the pivot row and
+// column are picked with selects, and a stopped factorisation is a flag instead of a break.  On the device the system then
+// lives in registers (one lane, no scratch memory); the operations and their order are those of the plain loops
+//   for it < k: p = argmax of the remaining diagonal (first of equals); stop at a dropped pivot; l_pp = sqrt(d_p);
+//               t_it = (g_p - sum_{q < it} l_pq t_q) / l_pp                       (forward substitution, row by row)
+//               for i not taken: l_i = (G_ip - sum_{q < it} l_iq l_pq) / l_pp, d_i -= l_i^2
+//   backward substitution over the taken pivots, last taken first
+template <int K>
+CFDH_HD inline bool gram_solve_k(const double *hd, double *y, int *rank) {
+  double G[K][K], Lc[K][K], dg[K], g[K];
+  int piv[K];
+  bool taken[K];
+  CFDH_UNROLL
+  for (int i = 0; i < K; i++) {
+    CFDH_UNROLL
+    for (int q = 0; q < K; q++) { G[q][i] = hd[i * 8 + q]; Lc[q][i] = 0.0; }
+    g[i] = hd[K * 8 + i]; taken[i] = false; piv[i] = -1;
   }
   double dmax0 = 0.0;
   bool ok = true;
-  for (int i = 0; i < k; i++) {
-    dg[i] = G[i * k + i];
+  CFDH_UNROLL
+  for (int i = 0; i < K; i++) {
+    dg[i] = G[i][i];
     if (!std::isfinite(dg[i])) ok = false;
     if (i == 0 || dg[i] > dmax0) dmax0 = dg[i];
   }
   ok = ok && dmax0 > 0.0 && std::isfinite(dmax0);
+  // LP: the rows of the factor in pivot order (row `it` is complete when pivot `it` is taken); t: the forward substitution,
+  // which needs exactly that row and is done on the spot
+  double LP[K][K], t[K], yp[K];
   int r = 0;
-  if (ok) {
-    for (int it = 0; it < k; it++) {
-      int p = -1;
-      for (int i = 0; i < k; i++) if (!taken[i] && (p < 0 || dg[i] > dg[p])) p = i;
-      if (p < 0 || !(dg[p] > 1e-10 * G[p * k + p]) || !(dg[p] > 1e-14 * dmax0)) break;
-      taken[p] = true;
-      const int rr = r;
-      piv[r++] = p;
-      const double lpp = std::sqrt(dg[p]);
-      Lc[p * k + rr] = lpp;
-      for (int i = 0; i < k; i++) {
+  bool go = ok;
+  CFDH_UNROLL
+  for (int it = 0; it < K; it++) {  // while it runs, r == it
+    // the pivot, and with it its diagonal, its right-hand side, column p of G and row p of the factor so far
+    int p = -1;
+    double dgp = 0.0, gpp = 0.0, gp = 0.0, Gp[K], Lp[K];
+    CFDH_UNROLL
+    for (int i = 0; i < K; i++) { Gp[i] = 0.0; Lp[i] = 0.0; }
+    CFDH_UNROLL
+    for (int i = 0; i < K; i++)
+      if (!taken[i] && (p < 0 || dg[i] > dgp)) {
+        p = i; dgp = dg[i]; gpp = G[i][i]; gp = g[i];
+        CFDH_UNROLL
+        for (int j = 0; j < K; j++) Gp[j] = G[j][i];
+        CFDH_UNROLL
+        for (int q = 0; q < it; q++) Lp[q] = Lc[i][q];
+      }
+    if (p < 0 || !(dgp > 1e-10 * gpp) || !(dgp > 1e-14 * dmax0)) go = false;
+    t[it] = 0.0; yp[it] = 0.0;
+    CFDH_UNROLL
+    for (int q = 0; q < K; q++) LP[it][q] = 0.0;
+    if (go) {
+      r = it + 1;
+      piv[it] = p;
+      const double lpp = std::sqrt(dgp);
+      CFDH_UNROLL
+      for (int q = 0; q < it; q++) LP[it][q] = Lp[q];
+      LP[it][it] = lpp;
+      double sacc = gp;
+      CFDH_UNROLL
+      for (int q = 0; q < it; q++) sacc = gram_nmsub(sacc, Lp[q], t[q]);
+      t[it] = sacc / lpp;
+      CFDH_UNROLL
+      for (int i = 0; i < K; i++) {
+        if (i == p) taken[i] = true;
         if (taken[i]) continue;
-        double sacc = G[i * k + p];
-        for (int q = 0; q < rr; q++) sacc -= Lc[i * k + q] * Lc[p * k + q];
-        Lc[i * k + rr] = sacc / lpp;
-        dg[i] -= Lc[i * k + rr] * Lc[i * k + rr];
+        sacc = Gp[i];
+        CFDH_UNROLL
+        for (int q = 0; q < it; q++) sacc = gram_nmsub(sacc, Lc[i][q], Lp[q]);
+        Lc[i][it] = sacc / lpp;
+        dg[i] = gram_nmsub(dg[i], Lc[i][it], Lc[i][it]);
       }
     }
-    for (int a = 0; a < r; a++) {
-      double sacc = g[piv[a]];
-      for (int q = 0; q < a; q++) sacc -= Lc[piv[a] * k + q] * t[q];
-      t[a] = sacc / Lc[piv[a] * k + a];
-    }
-    for (int a = r - 1; a >= 0; a--) {
+  }
+  CFDH_UNROLL
+  for (int a = K - 1; a >= 0; a--) {
+    if (a < r) {
       double sacc = t[a];
-      for (int q = a + 1; q < r; q++) sacc -= Lc[piv[q] * k + a] * yy[piv[q]];
-      yy[piv[a]] = sacc / Lc[piv[a] * k + a];
+      CFDH_UNROLL
+      for (int q = a + 1; q < K; q++) if (q < r) sacc = gram_nmsub(sacc, LP[q][a], yp[q]);
+      yp[a] = sacc / LP[a][a];
     }
   }
+  double yy[K];
   bool used = ok && r > 0;
-  for (int i = 0; i < k; i++) if (!std::isfinite(yy[i])) used = false;
-  for (int i = 0; i < k; i++) y[i] = used ? yy[i] : 0.0;
+  CFDH_UNROLL
+  for (int i = 0; i < K; i++) {
+    yy[i] = 0.0;
+    CFDH_UNROLL
+    for (int a = 0; a < K; a++) if (a < r && piv[a] == i) yy[i] = yp[a];
+    if (!std::isfinite(yy[i])) used = false;
+  }
+  CFDH_UNROLL
+  for (int i = 0; i < K; i++) y[i] = used ? yy[i] : 0.0;
   *rank = r;
   return used;
+}
+// the same with k known at run time (host callers); k outside 1 .. 8 has no system to solve: rank 0, not used
+CFDH_HD inline bool gram_solve(int k, const double *hd, double *y, int *rank) {
+  switch (k) {
+    case 1: return gram_solve_k<1>(hd, y, rank);
+    case 2: return gram_solve_k<2>(hd, y, rank);
+    case 3: return gram_solve_k<3>(hd, y, rank);
+    case 4: return gram_solve_k<4>(hd, y, rank);
+    case 5: return gram_solve_k<5>(hd, y, rank);
+    case 6: return gram_solve_k<6>(hd, y, rank);
+    case 7: return gram_solve_k<7>(hd, y, rank);
+    case 8: return gram_solve_k<8>(hd, y, rank);
+    default: *rank = 0; return false;
+  }
 }
 
 // Scale of the first Gram-Schmidt pass from the reduced coefficients: s = sqrt(w.w - |h|^2), or, when that difference has

@@ -434,15 +434,28 @@ int v_lincomb(cfdh_ctx *c, int n, const double *Z, int ld, int nvec, const doubl
 
 // ---- lean solve path: prologue and epilogue of a linear solve with one read-back each (cfdh_solver.cpp) ----------------------
 // (the mirror words of the prologue: DESIGN.md, "Scalar reductions and read-backs")
-// The k x k Gram system of the projected guess (k <= 8), solved by one lane: cfdh_krylov::gram_solve, the same function the
-// general path calls on the host.
-__global__ void gram_solve_kernel(int k, const double *__restrict__ hd, double *__restrict__ y, double *__restrict__ info) {
+// The K x K Gram system of the projected guess (K <= 8), solved by one lane: cfdh_krylov::gram_solve_k<K>, the function behind the
+// gram_solve the general path calls on the host.  With K a template parameter the system stays in registers (the one kernel for
+// all k worked out of scratch memory and took 22 us).
+template <int K>
+__global__ __launch_bounds__(64) void gram_solve_kernel(const double *__restrict__ hd, double *__restrict__ y, double *__restrict__ info) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  // the whole system requested at once, through vector loads (K (K + 1) doubles; as scalars they would crowd the scalar registers)
+  double h[8 * K + K], yy[K];
+#pragma unroll
+  for (int i = 0; i <= K; i++)
+#pragma unroll
+    for (int q = 0; q < K; q++) h[8 * i + q] = NTLOAD(hd + 8 * i + q);
   int r = 0;
-  const bool used = cfdh_krylov::gram_solve(k, hd, y, &r);
-  for (int i = 0; i < k; i++) info[3 + i] = y[i];
+  const bool used = cfdh_krylov::gram_solve_k<K>(h, yy, &r);
+#pragma unroll
+  for (int i = 0; i < K; i++) { y[i] = yy[i]; info[3 + i] = yy[i]; }
   info[1] = used ? 1.0 : 0.0;
   info[2] = (double)r;
+}
+template <int K>
+static void launch_gram_solve(cfdh_ctx *c, const double *hd, double *y, double *info) {
+  hipLaunchKernelGGL(gram_solve_kernel<K>, dim3(1), dim3(64), 0, c->stream, hd, y, info);
 }
 // x = U y, r = b - W y and the block partials of |r|^2 in one pass over U, W and b.  Entry by entry the arithmetic of
 // multiaxpy_kernel (on a zeroed x, and on a copy of b), block by block the partial sums of reduce_partial_kernel<0>.
@@ -513,7 +526,16 @@ int v_guess_combine(cfdh_ctx *c, int n, const double *U, const double *W, int ld
   if (k < 1 || k > 8) return cfdh_fail(c, CFDH_E_STATE, "projected guess: %d kept vectors", k);
   const int nb = red_grid(c, n);
   double *mir = scalars_mirror(c);
-  hipLaunchKernelGGL(gram_solve_kernel, dim3(1), dim3(64), 0, c->stream, k, hd, c->ky.p, mir);
+  switch (k) {
+    case 1: launch_gram_solve<1>(c, hd, c->ky.p, mir); break;
+    case 2: launch_gram_solve<2>(c, hd, c->ky.p, mir); break;
+    case 3: launch_gram_solve<3>(c, hd, c->ky.p, mir); break;
+    case 4: launch_gram_solve<4>(c, hd, c->ky.p, mir); break;
+    case 5: launch_gram_solve<5>(c, hd, c->ky.p, mir); break;
+    case 6: launch_gram_solve<6>(c, hd, c->ky.p, mir); break;
+    case 7: launch_gram_solve<7>(c, hd, c->ky.p, mir); break;
+    default: launch_gram_solve<8>(c, hd, c->ky.p, mir); break;
+  }
   hipLaunchKernelGGL(guess_combine_kernel, dim3(nb), dim3(TPB), 0, c->stream, n, U, W, (size_t)ld, k, (const double *)c->ky.p, b, x, r, c->red_partial.p);
   HIPCHK(c, hipGetLastError());
   return red_final(c, 0, 1, nb, nb, c->red_partial.p, c->red_out.p + RO_LEAN_S2, mir);
