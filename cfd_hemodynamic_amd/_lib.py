@@ -51,7 +51,7 @@ SYMBOLS = [
     "cfdh_create", "cfdh_create_elem", "cfdh_create_elem_part", "cfdh_set_facet_markers", "cfdh_destroy", "cfdh_last_error", "cfdh_abi_version", "cfdh_set_params", "cfdh_default_options",
     "cfdh_set_options", "cfdh_clear_dirichlet", "cfdh_add_dirichlet", "cfdh_update_dirichlet", "cfdh_set_state", "cfdh_get_solution",
     "cfdh_get_previous", "cfdh_get_residual", "cfdh_advance", "cfdh_advance_field", "cfdh_set_time_scheme", "cfdh_set_previous2", "cfdh_get_previous2",
-    "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_set_formulation", "cfdh_set_pressure_boundaries", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
+    "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_set_formulation", "cfdh_set_pressure_boundaries", "cfdh_set_pressure_boundaries_ex", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
@@ -111,6 +111,7 @@ def lib():
     L.cfdh_set_boundary_terms.argtypes = [vp, C.c_int, C.c_int, C.c_double]
     L.cfdh_set_formulation.argtypes = [vp, C.c_int]
     L.cfdh_set_pressure_boundaries.argtypes = [vp, C.c_int, ip, dp, C.c_double]
+    L.cfdh_set_pressure_boundaries_ex.argtypes = [vp, C.c_int, ip, dp, C.c_double, C.POINTER(C.c_uint8), dp]
     L.cfdh_get_residual.argtypes = [vp, dp, dp]
     L.cfdh_get_previous.argtypes = [vp, dp, dp]
     L.cfdh_advance.argtypes = [vp]
@@ -333,14 +334,25 @@ class Context:
         """FORM_CONVECTIVE (default) or FORM_ROTATIONAL (the curl-curl form of the pressure-driven solvers)."""
         self._chk(self.L.cfdh_set_formulation(self.h, int(form)))
 
-    def set_pressure_boundaries(self, markers, values, beta_nitsche=0.0):
+    def set_pressure_boundaries(self, markers, values, beta_nitsche=0.0, nitsche=None, beta_backflow=None):
         """Natural pressure + Nitsche tangential terms on the exterior facets of each marker (rotational form).  A call that
-        changes only `values` keeps the Jacobian and the preconditioner."""
+        changes only `values` keeps the Jacobian and the preconditioner.  Per boundary (cfdh_set_pressure_boundaries_ex):
+        `nitsche[k]` false drops the tangential terms there (None: all on), `beta_backflow[k]` > 0 adds the backflow
+        stabilisation -beta rho (u_prev . n)_- (u_mid . v) (None: none)."""
         m = np.ascontiguousarray(markers, dtype=np.int32).reshape(-1)
         v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
         if len(m) != len(v):
             raise ValueError("one value per pressure-boundary marker")
-        self._chk(self.L.cfdh_set_pressure_boundaries(self.h, len(m), _ip(m), _dp(v), float(beta_nitsche)))
+        if nitsche is None and beta_backflow is None:
+            self._chk(self.L.cfdh_set_pressure_boundaries(self.h, len(m), _ip(m), _dp(v), float(beta_nitsche)))
+            return
+        nit = None if nitsche is None else np.ascontiguousarray(np.asarray(nitsche, dtype=bool), dtype=np.uint8).reshape(-1)
+        bf = None if beta_backflow is None else np.ascontiguousarray(beta_backflow, dtype=np.float64).reshape(-1)
+        if (nit is not None and len(nit) != len(m)) or (bf is not None and len(bf) != len(m)):
+            raise ValueError("one Nitsche switch and one backflow coefficient per pressure-boundary marker")
+        self._chk(self.L.cfdh_set_pressure_boundaries_ex(
+            self.h, len(m), _ip(m), _dp(v), float(beta_nitsche),
+            None if nit is None else nit.ctypes.data_as(C.POINTER(C.c_uint8)), None if bf is None else _dp(bf)))
 
     def wall_shear_stress(self, download=True):
         if not download:

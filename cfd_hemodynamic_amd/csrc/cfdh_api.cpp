@@ -491,7 +491,7 @@ int cfdh_set_boundary_terms(cfdh_ctx *c, int ds_terms, int backflow_marker, doub
   ENTER(c);
   if (beta < 0) return cfdh_fail(c, CFDH_E_ARG, "backflow beta must be >= 0");
   if (beta > 0 && c->form == CFDH_FORM_ROTATIONAL)
-    return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_boundary_terms: the backflow term is not available with the rotational formulation");
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_boundary_terms: the rotational formulation takes its backflow term per pressure boundary (cfdh_set_pressure_boundaries_ex)");
   if (!(beta > 0)) backflow_marker = -1;
   const bool changed = (ds_terms != 0) != c->ds_terms || beta != c->bf_beta || backflow_marker != c->bf_marker;
   c->ds_terms = ds_terms != 0; c->bf_beta = beta; c->bf_marker = backflow_marker;
@@ -554,9 +554,9 @@ int cfdh_set_formulation(cfdh_ctx *c, int form) {
   return 0;
 }
 
-int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, const double *values, double beta_nitsche) {
-  NOT_IPCS(c, "cfdh_set_pressure_boundaries");
-  ENTER(c);
+// both entry points (the validation messages of the plain call are kept); nitsche NULL: all on, beta_backflow NULL: all 0
+static int set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, const double *values, double beta_nitsche,
+                                   const uint8_t *nitsche, const double *beta_backflow) {
   if (n < 0 || n > CFDH_MAX_PBND) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: 0 <= n <= %d", CFDH_MAX_PBND);
   if (n > 0 && (!markers || !values)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: null marker / value array");
   if (!(beta_nitsche >= 0) || !std::isfinite(beta_nitsche)) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: beta_nitsche must be finite and >= 0");
@@ -570,13 +570,38 @@ int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, con
     if (c->form != CFDH_FORM_ROTATIONAL)
       return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries: pressure boundaries need the rotational formulation (cfdh_set_formulation)");
   }
-  bool same = (size_t)n == c->pb_markers.size() && beta_nitsche == c->pb_beta;
-  for (int k = 0; same && k < n; k++) same = markers[k] == c->pb_markers[k];
+  unsigned nit = 0;
+  std::vector<double> bf((size_t)n, 0.0);
+  for (int k = 0; k < n; k++) {
+    if (!nitsche || nitsche[k]) nit |= 1u << k;
+    if (beta_backflow) {
+      if (!(beta_backflow[k] >= 0) || !std::isfinite(beta_backflow[k]))
+        return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_pressure_boundaries_ex: beta_backflow %d must be finite and >= 0", k);
+      bf[k] = beta_backflow[k];
+    }
+  }
+  bool same = (size_t)n == c->pb_markers.size() && beta_nitsche == c->pb_beta && nit == c->pb_nitsche;
+  for (int k = 0; same && k < n; k++) same = markers[k] == c->pb_markers[k] && bf[k] == c->pb_backflow[k];
   c->pb_values.assign(values, values + n);
   if (same) return 0;  // values only: they enter the residual, Jacobian and preconditioner stay valid
   c->pb_markers.assign(markers, markers + n);
   c->pb_beta = beta_nitsche;
+  c->pb_nitsche = nit;
+  c->pb_backflow = bf;
   return upload_cell_facet_flags(c);
+}
+
+int cfdh_set_pressure_boundaries(cfdh_ctx *c, int n, const int32_t *markers, const double *values, double beta_nitsche) {
+  NOT_IPCS(c, "cfdh_set_pressure_boundaries");
+  ENTER(c);
+  return set_pressure_boundaries(c, n, markers, values, beta_nitsche, nullptr, nullptr);
+}
+
+int cfdh_set_pressure_boundaries_ex(cfdh_ctx *c, int n, const int32_t *markers, const double *values, double beta_nitsche,
+                                    const uint8_t *nitsche, const double *beta_backflow) {
+  NOT_IPCS(c, "cfdh_set_pressure_boundaries_ex");
+  ENTER(c);
+  return set_pressure_boundaries(c, n, markers, values, beta_nitsche, nitsche, beta_backflow);
 }
 
 int cfdh_set_schur_pcd(cfdh_ctx *c, int inlet_marker, int outlet_marker, int time_term) {

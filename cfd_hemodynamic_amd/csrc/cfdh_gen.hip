@@ -140,6 +140,10 @@ struct GenArgs {
   // P_k in pval, Nitsche penalty pbeta
   const unsigned char *pbidx;
   double pval[CFDH_MAX_PBND], pbeta;
+  // per slot (cfdh_set_pressure_boundaries_ex): bit k of pnit -- the three tangential (Nitsche) terms are on; pbf[k] -- coefficient
+  // beta_bf of the backflow term -beta_bf rho (u_prev . n)_- (ubar . v)
+  unsigned pnit;
+  double pbf[CFDH_MAX_PBND];
 };
 
 __device__ __forceinline__ void tau_pair(double s, double h, double dt, double nu, double &tau, double &tauL) {
@@ -164,6 +168,12 @@ struct CellData {
   int node[NL];
 };
 
+// backflow coefficients of the pressure-boundary slots in LDS (ROT pass only: instantiated nowhere else)
+__device__ __forceinline__ double *gen_pbf_lds() {
+  __shared__ double pbf[CFDH_MAX_PBND];
+  return pbf;
+}
+
 // JAC = false: residual-only pass (trial point of the line search).  The element Jacobian is then formed only in cells whose
 // Dirichlet nodes still need lifting (F += J (g - x)) -- none once the first Newton update has put the boundary values in place.
 //
@@ -172,7 +182,9 @@ struct CellData {
 //   rho w_t . v + mu omega(ubar) omega(v) - p div v + rho (omega x ubar) . v - rho/2 |ubar|^2 div v - rho f . v + q div ubar
 //   + SUPG / PSPG / LSIC with R = rho (w_t + omega x ubar) + grad p - rho f (no viscous part: no Hessians in this pass),
 // and on the facets of pressure boundary k (flag bit 4 + f, value P_k, outward n, tangent t = (-n_y, n_x)):
-//   P_k v . n - mu omega(ubar) (t . v) - mu omega(v) (t . ubar) + (beta mu / h) (t . ubar)(t . v).
+//   P_k v . n - mu omega(ubar) (t . v) - mu omega(v) (t . ubar) + (beta mu / h) (t . ubar)(t . v)      [the last three: bit k of pnit]
+//   - pbf_k rho (u_prev . n)_- (ubar . v),  (s)_- = (s - |s|) / 2                                       [pbf_k > 0]
+// (the outlet of the reference's src/solvers/stabilized_schur_vascularbc_backflow.py:214-244 is P_k v . n plus the last line alone).
 template <int ET, bool JAC, bool ROT>
 __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
   constexpr int NL = ET == 0 ? 3 : (ET == 1 ? 6 : 4);
@@ -184,6 +196,13 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
   const int cell = blockIdx.x * CPB + lc;
   const bool live = lc < CPB && cell < P.nc;
   const int nvo = P.nvo;
+  if constexpr (ROT) {
+    // the slots' backflow coefficients go through LDS: selected from the argument block in the facet loop, as pval is, they
+    // stayed in 16 more SGPRs through the whole kernel and the P2 instantiation spilled 12 of them
+#pragma unroll
+    for (int k = 0; k < CFDH_MAX_PBND; k++)
+      if (threadIdx.x == k) gen_pbf_lds()[k] = P.pbf[k];  // static indices into the argument block
+  }
   if (live) {
     // lane a stages node a of its cell
     CellData<NL> &D = sh[lc];
@@ -353,10 +372,20 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
     for (int q = 0; q < NV; q++) { cen[0] += D.X[q][0] * (1.0 / NV); cen[1] += D.X[q][1] * (1.0 / NV); }
     constexpr int NQF = ET == 1 ? 4 : 2;
     for (int f = 0; f < NF; f++) {
-      // (the rotational form has no ds pair, :177-205; its backflow combination is refused by the API)
+      // (the rotational form has no ds pair, :177-205; its backflow term comes per pressure boundary, pbf below, not by flag bit 8 + f)
       const bool ext = !ROT && P.ds_terms && ((fl >> f) & 1u), bfl = P.beta != 0.0 && ((fl >> (8 + f)) & 1u);
       const bool pfl = ROT && ((fl >> (4 + f)) & 1u);
       if (!ext && !bfl && !pfl) continue;
+      // pressure boundary: value, Nitsche switch and backflow coefficient of the facet's slot
+      double pk = 0.0, pbf = 0.0;
+      bool pnit = false;
+      if (pfl) {
+        const int slot = P.pbidx[4 * (size_t)cell + f];
+#pragma unroll
+        for (int k = 0; k < CFDH_MAX_PBND; k++) pk = k == slot ? P.pval[k] : pk;  // static indices: the argument block stays in SGPRs
+        if constexpr (ROT) pbf = gen_pbf_lds()[slot & (CFDH_MAX_PBND - 1)];
+        pnit = (P.pnit >> slot) & 1u;
+      }
       const int va = facet_node<ET>(f, 0), vb = facet_node<ET>(f, 1);
       const double tx = D.X[vb][0] - D.X[va][0], ty = D.X[vb][1] - D.X[va][1], elen = hypot(tx, ty);
       double n[2] = {ty / elen, -tx / elen};
@@ -367,7 +396,7 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
         const double t = ET == 1 ? d_gl4[0][q] : d_gl2[0][q], m = elen * (ET == 1 ? d_gl4[1][q] : d_gl2[1][q]);
         double ph[GEN_MAXL], dr[GEN_MAXL][2], g[NL][2];
         tabulate<ET>((1 - t) * ra[0] + t * rb[0], (1 - t) * ra[1] + t * rb[1], ph, dr);
-        if (ph[a] == 0.0 && !pfl) continue;  // test function vanishes on this facet (omega(v) does not: Nitsche symmetry term)
+        if (ph[a] == 0.0 && !pnit) continue;  // test function vanishes on this facet (omega(v) does not: Nitsche symmetry term)
 #pragma unroll
         for (int b = 0; b < NL; b++) { g[b][0] = dr[b][0] * Ji[0][0] + dr[b][1] * Ji[1][0]; g[b][1] = dr[b][0] * Ji[0][1] + dr[b][1] * Ji[1][1]; }
         double uq[2] = {0, 0}, G[2][2] = {{0, 0}, {0, 0}}, pq = 0.0, sn = 0.0;
@@ -402,12 +431,8 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
             for (int b = 0; b < NL; b++) Juu[b][i][i] -= th * cq * ph[a] * ph[b];
           }
         }
-        if (pfl) {
+        if (pfl && pnit) {
           // pressure boundary: natural pressure (residual only) + Nitsche tangential condition, omega from this cell's gradients
-          const int slot = P.pbidx[4 * (size_t)cell + f];
-          double pk = 0.0;
-#pragma unroll
-          for (int k = 0; k < CFDH_MAX_PBND; k++) pk = k == slot ? P.pval[k] : pk;  // static indices: the argument block stays in SGPRs
           const double t[2] = {-n[1], n[0]}, om = G[0][1] - G[1][0], ut = t[0] * uq[0] + t[1] * uq[1];
           const double oma[2] = {-g[a][1], g[a][0]}, nit = P.pbeta * mu / h;
 #pragma unroll
@@ -419,6 +444,18 @@ __global__ __launch_bounds__(TPB) void gen_asm_kernel(GenArgs P) {
 #pragma unroll
               for (int j = 0; j < 2; j++) Juu[b][i][j] += th * m * (-mu * omb[j] * ph[a] * t[i] - mu * oma[i] * ph[b] * t[j] + nit * ph[a] * t[i] * ph[b] * t[j]);
             }
+          }
+        } else if (pfl) {  // pure traction boundary: the natural pressure alone
+          Fa[0] += m * ph[a] * pk * n[0];
+          Fa[1] += m * ph[a] * pk * n[1];
+        }
+        if (pfl && pbf != 0.0) {  // backflow stabilisation of this pressure boundary: coefficient from u_prev, velocity ubar
+          const double cq = pbf * rho * 0.5 * (sn - fabs(sn)) * m;
+#pragma unroll
+          for (int i = 0; i < 2; i++) {
+            Fa[i] -= cq * ph[a] * uq[i];
+#pragma unroll
+            for (int b = 0; b < NL; b++) Juu[b][i][i] -= th * cq * ph[a] * ph[b];
           }
         }
       }
@@ -801,6 +838,8 @@ int kg_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   const bool rot = c->form == CFDH_FORM_ROTATIONAL;
   P.pbidx = c->gpbidx.p; P.pbeta = c->pb_beta;
   for (int k = 0; k < CFDH_MAX_PBND; k++) P.pval[k] = k < (int)c->pb_values.size() ? c->pb_values[k] : 0.0;
+  P.pnit = c->pb_nitsche;
+  for (int k = 0; k < CFDH_MAX_PBND; k++) P.pbf[k] = k < (int)c->pb_backflow.size() ? c->pb_backflow[k] : 0.0;
   const dim3 grid((c->nc + cpb - 1) / cpb), block(TPB);
   prof_begin(c, 0);
 #define CFDH_GEN_LAUNCH(ET, ROT) do { if (mode == 1) hipLaunchKernelGGL((gen_asm_kernel<ET, true, ROT>), grid, block, 0, c->stream, P); \

@@ -232,6 +232,10 @@ struct Gen3Args {
   // values P_k in pval, Nitsche penalty pbeta
   const unsigned char *pbslot;
   double pval[CFDH_MAX_PBND], pbeta;
+  // per slot (cfdh_set_pressure_boundaries_ex): bit k of pnit -- the three tangential (Nitsche) terms are on; pbf[k] -- coefficient
+  // beta_bf of the backflow term -beta_bf rho (u_prev . n)_- (ubar . v)
+  unsigned pnit;
+  double pbf[CFDH_MAX_PBND];
 };
 
 template <int NL>
@@ -559,6 +563,10 @@ __global__ __launch_bounds__(g3_wgs(ET), 2) void gen3_asm_kernel(Gen3Args P) {
 //   P_k v . n - mu (omega x n) . v_T - mu (curl v x n) . ubar_T + (beta mu / h) ubar_T . v_T,   omega = curl ubar,
 // where (omega x n) . v_T = (omega x n) . v, and for v = phi_a e_i: (curl v x n) . ubar = ubar_i (ga . n) - (ga . ubar) n_i.
 // curl v does not vanish off the facet: every lane of a cell with a pressure facet contributes, whatever its test function there.
+// Per slot: the last three terms only where bit k of pnit is set, and with pbf_k > 0 the backflow term of the reference's
+// stabilized_schur_vascularbc_backflow.py:237-244, - pbf_k rho (u_prev . n)_- (ubar . v), (s)_- = (s - |s|) / 2 (coefficient from
+// u_prev: residual and theta times it on the diagonal of the (a, b) block).  With the bit off a lane whose test function vanishes
+// at a point has nothing to add there.
 template <int ET, bool ROT>
 __global__ __launch_bounds__(128) void gen3_facet_kernel(Gen3Args P, const int *__restrict__ fcells) {
   constexpr int NL = g3_nloc(ET), NF = ET == 2 ? 6 : 4;
@@ -605,12 +613,16 @@ __global__ __launch_bounds__(128) void gen3_facet_kernel(Gen3Args P, const int *
     for (int f = 0; f < NF; f++) {
       const int slot = P.pbslot[NF * (size_t)cell + f];
       if (slot == 0xff) continue;  // not a pressure-boundary facet (uniform in the workgroup)
-      double pk = 0.0;
+      double pk = 0.0, pbf = 0.0;
 #pragma unroll
-      for (int k = 0; k < CFDH_MAX_PBND; k++) pk = k == slot ? P.pval[k] : pk;  // static indices: the argument block stays in SGPRs
+      for (int k = 0; k < CFDH_MAX_PBND; k++) { pk = k == slot ? P.pval[k] : pk; pbf = k == slot ? P.pbf[k] : pbf; }  // static indices: the argument block stays in SGPRs
+      const bool pnit = (P.pnit >> slot) & 1u, bfon = pbf != 0.0;  // both uniform in the workgroup
       double n[3], area;
       facet_geom3<ET, decltype(D.X), true>(D.X, f, n, area);
-      for (int q = 0; q < facet_nq<ET>(); q++) {
+      // two passes over the facet points: the Nitsche boundary as before, then the terms that need no gradients (the natural pressure
+      // of a pure traction boundary, the backflow term).  The second pass is kept rolled: unrolled into the first it took the
+      // hexahedral instantiation from two workgroups per SIMD to one (276 registers instead of 252; now 250)
+      for (int q = 0; pnit && q < facet_nq<ET>(); q++) {
         double pt[3], w;
         facet_point<ET, true>(f, q, pt, w);
         const double m = area * w;
@@ -644,6 +656,31 @@ __global__ __launch_bounds__(128) void gen3_facet_kernel(Gen3Args P, const int *
         for (int i = 0; i < 3; i++) {
           for (int j = 0; j < 3; j++) Juu[i][j] += tm * (mu * (pha * gb[i] * n[j] + phb * ga[j] * n[i]) - nit * pha * phb * n[i] * n[j]);
           Juu[i][i] += cab;
+        }
+      }
+#pragma unroll 1
+      for (int q = 0; (!pnit || bfon) && q < facet_nq<ET>(); q++) {
+        double pt[3], w;
+        facet_point<ET, true>(f, q, pt, w);
+        const double m = area * w;
+        double pha, phb, dr[3];
+        basis3<ET, true>(a, pt, pha, dr);
+        if (pha == 0.0) continue;  // the test function vanishes at this point
+        basis3<ET, true>(b, pt, phb, dr);
+        double uq[3] = {0, 0, 0}, sn = 0.0;
+#pragma unroll 1
+        for (int c = 0; c < NL; c++) {
+          double ph;
+          basis3<ET, true>(c, pt, ph, dr);
+          for (int i = 0; i < 3; i++) {
+            uq[i] += ph * D.ub[c][i];
+            sn += ph * D.un[c][i] * n[i];
+          }
+        }
+        const double cq = pbf * rho * 0.5 * (sn - fabs(sn)) * m, pm = pnit ? 0.0 : m * pha * pk;
+        for (int i = 0; i < 3; i++) {
+          if (b == 0) Fa[i] += pm * n[i] - cq * pha * uq[i];
+          Juu[i][i] -= th * cq * pha * phb;
         }
       }
     }
@@ -1085,6 +1122,8 @@ int kg3_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   const bool rot = c->form == CFDH_FORM_ROTATIONAL;
   P.pbslot = c->g3_pbslot.p; P.pbeta = c->pb_beta;
   for (int k = 0; k < CFDH_MAX_PBND; k++) P.pval[k] = k < (int)c->pb_values.size() ? c->pb_values[k] : 0.0;
+  P.pnit = c->pb_nitsche;
+  for (int k = 0; k < CFDH_MAX_PBND; k++) P.pbf[k] = k < (int)c->pb_backflow.size() ? c->pb_backflow[k] : 0.0;
   const dim3 grid(c->nc);
   prof_begin(c, 0);
 #define G3_LAUNCH(ET, ROT) do { if (mode == 1) hipLaunchKernelGGL((gen3_asm_kernel<ET, true, ROT>), grid, dim3(g3_wgs(ET)), 0, c->stream, P); \

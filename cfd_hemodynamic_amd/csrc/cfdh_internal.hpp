@@ -290,6 +290,8 @@ struct cfdh_ctx {
   std::vector<int> pb_markers;       // facet markers of the pressure boundaries, at most CFDH_MAX_PBND
   std::vector<double> pb_values;     // their values P_k (residual only)
   double pb_beta = 0.0;              // Nitsche penalty beta of the tangential condition
+  unsigned pb_nitsche = 0;           // bit k: boundary k carries the three tangential (Nitsche) terms (cfdh_set_pressure_boundaries_ex)
+  std::vector<double> pb_backflow;   // per boundary: coefficient of the backflow term -beta_bf rho (u_prev . n)_- (u_mid . v), 0: none
   bool state_set = false;
 
   // reductions

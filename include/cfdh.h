@@ -221,7 +221,8 @@ int cfdh_set_time_scheme(cfdh_ctx *ctx, double theta, double a0, double a1, doub
  * -beta rho (u_prev.n)_- (u_mid . v) ds, (s)_- = (s-|s|)/2, on the exterior facets whose marker
  * (facet_marker of cfdh_create) equals backflow_marker (`ds_out`, tags["outlet"],
  * stabilized_schur_backflow.py:158-176), integrated with a rule of FFCx's estimated degree 3:
- * 2-point Gauss on edges, the 6-point Strang-Fix rule on the triangles of a tetrahedral mesh. */
+ * 2-point Gauss on edges, the 6-point Strang-Fix rule on the triangles of a tetrahedral mesh.  CFDH_E_ARG for beta > 0 on a
+ * rotational context: the rotational form takes its backflow term per pressure boundary, cfdh_set_pressure_boundaries_ex. */
 int cfdh_set_boundary_terms(cfdh_ctx *ctx, int ds_terms, int backflow_marker, double beta);
 
 /* ---- pressure-driven flow (the `stabilized_schur_pressurebc` / `_vascularbc` variants) -------- */
@@ -233,8 +234,9 @@ int cfdh_set_boundary_terms(cfdh_ctx *ctx, int ds_terms, int backflow_marker, do
  * In gdim 2 omega = d_x u_y - d_y u_x is a scalar and omega x a = (-omega a_y, omega a_x).  The time scheme of
  * cfdh_set_time_scheme applies as before.  Contexts: gdim 2 on the generic kernels, gdim 3 for CFDH_ELEM_P2 (tetrahedra) and
  * CFDH_ELEM_Q1 (hexahedra).  CFDH_E_ARG on the closed-form P1 path (gdim 2: create the context with CFDH_ELEM_P1_GENERIC), for
- * P1 tetrahedra in gdim 3 (closed-form or generic), on a part of a partitioned run, with an active backflow term (beta > 0), and
- * when switching back to the convective form while pressure boundaries are set.  A change invalidates Jacobian and
+ * P1 tetrahedra in gdim 3 (closed-form or generic), on a part of a partitioned run, with an active backflow term of
+ * cfdh_set_boundary_terms (beta > 0: the rotational form takes its backflow term per pressure boundary,
+ * cfdh_set_pressure_boundaries_ex), and when switching back to the convective form while pressure boundaries are set.  A change invalidates Jacobian and
  * preconditioner. */
 enum { CFDH_FORM_CONVECTIVE = 0, CFDH_FORM_ROTATIONAL = 1 };
 int cfdh_set_formulation(cfdh_ctx *ctx, int form);
@@ -250,6 +252,17 @@ int cfdh_set_formulation(cfdh_ctx *ctx, int form);
  * (and the contexts it allows).  Use with ds_terms = 0 (cfdh_set_boundary_terms): the preconditioner's pressure Laplacian then
  * takes Dirichlet rows on every exterior facet that is not fully velocity-constrained, the pressure boundaries among them. */
 int cfdh_set_pressure_boundaries(cfdh_ctx *ctx, int n, const int32_t *markers, const double *values, double beta_nitsche);
+/* The same with two per-boundary switches (the outlet of stabilized_schur_vascularbc_backflow.py:214-244 is a pure traction boundary
+ * with backflow stabilisation).  nitsche[k] == 0 drops the three tangential terms on boundary k, which keeps values[k] v . n alone;
+ * NULL: all on.  beta_backflow[k] > 0 adds on boundary k
+ *   - beta_backflow[k] rho (u_prev . n)_- (u_mid . v),   (s)_- = (s - |s|) / 2
+ * (Moghadam et al. 2011, eq. 10; the same term as cfdh_set_boundary_terms adds to the convective form), coefficient from u_prev,
+ * so the Jacobian gains theta (-beta_backflow[k] rho (u_prev . n)_-) phi_a phi_b delta_ij in A00; integrated with the facet rule of
+ * the pressure terms.  NULL: all 0.  CFDH_E_ARG for a negative or non-finite beta_backflow[k].  cfdh_set_pressure_boundaries is
+ * this call with both arrays NULL.  A call that changes only `values` keeps Jacobian and preconditioner valid; a change of
+ * nitsche[k] or beta_backflow[k] invalidates both, as a marker change does. */
+int cfdh_set_pressure_boundaries_ex(cfdh_ctx *ctx, int n, const int32_t *markers, const double *values, double beta_nitsche,
+                                    const uint8_t *nitsche, const double *beta_backflow);
 
 /* ---- pressure convection-diffusion preconditioner and forcing (the `stabilized_pcd` variant) ---------------- */
 
