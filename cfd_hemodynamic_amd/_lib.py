@@ -57,7 +57,7 @@ SYMBOLS = [
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
     "cfdh_get_amg_operator", "cfdh_get_amg_vectors", "cfdh_krylov_vec_op",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
-    "cfdh_ipcs_apply_pressure_pc", "cfdh_ipcs_krylov_solve",
+    "cfdh_ipcs_apply_pressure_pc", "cfdh_ipcs_krylov_solve", "cfdh_ipcs_set_scheme", "cfdh_ipcs_get_block_operator",
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
 ]
 
@@ -147,6 +147,8 @@ def lib():
     L.cfdh_ipcs_step.argtypes = [vp, C.POINTER(IpcsStats)]
     L.cfdh_ipcs_get_operator.argtypes = [vp, C.c_int, lp, ip, ip, dp]
     L.cfdh_ipcs_get_intermediate.argtypes = [vp, C.c_int, dp]
+    L.cfdh_ipcs_set_scheme.argtypes = [vp, C.c_int]
+    L.cfdh_ipcs_get_block_operator.argtypes = [vp, C.c_int, lp, ip, ip, dp]
     L.cfdh_ipcs_apply_pressure_pc.argtypes = [vp, dp, dp]
     L.cfdh_ipcs_krylov_solve.argtypes = [vp, C.c_int, dp, dp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(IpcsStats), dp]
     L.cfdh_wall_stats_reset.argtypes = [vp]
@@ -187,6 +189,8 @@ AMG_HIER_PG, AMG_HIER_DL0 = 3, 4  # partitioned run: the replicated pressure hie
 AMG_OP_A, AMG_OP_P, AMG_OP_G, AMG_OP_SB, AMG_OP_SC, AMG_OP_PT = 0, 1, 2, 3, 4, 5
 (AMG_VEC_DINV, AMG_VEC_WDINV, AMG_VEC_AGG, AMG_VEC_COARSE_INV, AMG_VEC_D, AMG_VEC_LAMBDA, AMG_VEC_CC_SCALARS, AMG_VEC_CC_ML,
  AMG_VEC_CC_PBC, AMG_VEC_SPGEMM_ROWS, AMG_VEC_SHAPE, AMG_VEC_ORDER, AMG_VEC_A00_LMAX, AMG_VEC_A00_DINV, AMG_VEC_DL0_SHAPE) = range(15)
+# cfdh_ipcs_set_scheme
+IPCS_BDF2, IPCS_MIDPOINT = 0, 1
 # cfdh_ipcs_krylov_solve: words of the scalar block
 IP_RHO, IP_RHO_OLD, IP_ALPHA, IP_OMEGA, IP_BETA, IP_RZ, IP_TOL2, IP_BN2, IP_RN2, IP_DONE, IP_ITS, IP_BAD = range(12)
 IP_NSCAL = 16
@@ -623,6 +627,24 @@ class IpcsContext(Context):
     def set_form(self, conv_coeff, force_coeff):
         """Coefficients c (convection) and s_f (force) of the scheme; the context's default is (rho, +rho)."""
         self._chk(self.L.cfdh_ipcs_set_form(self.h, float(conv_coeff), float(force_coeff)))
+
+    def set_scheme(self, scheme):
+        """IPCS_BDF2 (0, the default) or IPCS_MIDPOINT (1, or the name "midpoint"): cfdh_ipcs_set_scheme."""
+        k = {"bdf2": IPCS_BDF2, "ipcs_bdf2": IPCS_BDF2, "midpoint": IPCS_MIDPOINT, "ipcs_midpoint": IPCS_MIDPOINT}.get(scheme, scheme)
+        self._chk(self.L.cfdh_ipcs_set_scheme(self.h, int(k)))
+
+    def get_block_operator(self, which):
+        """scipy BSR of size gdim * nn with gdim x gdim blocks on the P2 node pattern (ipcs_midpoint): 0 A1 with the Dirichlet
+        treatment, 1 A1_free.  Rows and columns are (node, component), as the interleaved velocity arrays."""
+        import scipy.sparse as sp
+        nnz = C.c_int64()
+        self._chk(self.L.cfdh_ipcs_get_block_operator(self.h, int(which), C.byref(nnz), None, None, None))
+        d = self.dim
+        rowptr = np.empty(self.nv + 1, dtype=np.int32)
+        col = np.empty(nnz.value, dtype=np.int32)
+        val = np.empty((nnz.value, d, d))
+        self._chk(self.L.cfdh_ipcs_get_block_operator(self.h, int(which), C.byref(nnz), _ip(rowptr), _ip(col), _dp(val)))
+        return sp.bsr_matrix((val, col, rowptr), shape=(d * self.nv, d * self.nv))
 
     def set_tolerances(self, rtol=(1e-5, 1e-5, 1e-5), atol=1e-50, max_it=(10000, 10000, 10000)):
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(rtol, dtype=np.float64), (3,)))

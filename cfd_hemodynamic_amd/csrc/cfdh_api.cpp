@@ -1504,6 +1504,8 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
       case 82: return I->n_field_copies;
       case 83: return 1;
       case 84: case 90: return c->ws_count;  // accumulations of the wall shear indices since the last reset
+      case 91: return I->scheme;
+      case 92: return I->n_assemblies;
       default: return -1;
     }
   }
@@ -1631,6 +1633,8 @@ int cfdh_ipcs_get_operator(cfdh_ctx *c, int which, int64_t *nnz, int32_t *rowptr
   IpcsData *I = c->ipcs;
   const int D = I->D;
   if (!nnz || which < 0 || which >= 3 + 2 * D) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_operator: which in [0, %d)", 3 + 2 * D);
+  if (which == 0 && I->scheme == CFDH_IPCS_MIDPOINT)
+    return cfdh_fail(c, CFDH_E_STATE, "cfdh_ipcs_get_operator: A1 of the ipcs_midpoint scheme is a block matrix (cfdh_ipcs_get_block_operator)");
   const std::vector<int> &ptr = which == 1 ? I->hL.rowptr : which < 3 ? I->hM.rowptr : which < 3 + D ? I->bptr : I->gptr;
   const std::vector<int> &cl = which == 1 ? I->hL.col : which < 3 ? I->hM.col : which < 3 + D ? I->bcol : I->gcol;
   *nnz = (int64_t)cl.size();
@@ -1653,6 +1657,29 @@ int cfdh_ipcs_get_operator(cfdh_ctx *c, int which, int64_t *nnz, int32_t *rowptr
   }
   const double *src = which == 0 ? I->A1v.p : which == 1 ? I->Lv.p : I->RMv.p;
   HIPCHK(c, hipMemcpyAsync(vals, src, sizeof(double) * cl.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int cfdh_ipcs_set_scheme(cfdh_ctx *c, int scheme) {
+  NEED_IPCS(c, "cfdh_ipcs_set_scheme");
+  if (scheme != CFDH_IPCS_BDF2 && scheme != CFDH_IPCS_MIDPOINT) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_set_scheme: unknown scheme %d", scheme);
+  return cfdh_ipcs_set_scheme_impl(c, scheme);
+}
+
+int cfdh_ipcs_get_block_operator(cfdh_ctx *c, int which, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals) {
+  NEED_IPCS(c, "cfdh_ipcs_get_block_operator");
+  IpcsData *I = c->ipcs;
+  if (!nnz || which < 0 || which > 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_block_operator: which in [0, 2)");
+  if (I->scheme != CFDH_IPCS_MIDPOINT)
+    return cfdh_fail(c, CFDH_E_STATE, "cfdh_ipcs_get_block_operator: the context runs the ipcs_bdf2 scheme (cfdh_ipcs_set_scheme)");
+  *nnz = (int64_t)I->hM.col.size();
+  if (!rowptr && !col && !vals) return 0;
+  if (!rowptr || !col || !vals) return cfdh_fail(c, CFDH_E_ARG, "pass all of rowptr/col/vals or none");
+  std::copy(I->hM.rowptr.begin(), I->hM.rowptr.end(), rowptr);
+  std::copy(I->hM.col.begin(), I->hM.col.end(), col);
+  if (!I->assembled) CHK(cfdh_ipcs_assemble(c));
+  HIPCHK(c, hipMemcpyAsync(vals, which == 0 ? I->A1B.p : I->AfreeB.p, sizeof(double) * I->hM.col.size() * I->D * I->D, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -12,6 +12,10 @@
 // The Krylov loops keep their scalars on the device: every dot product ends in per-block partial sums that a one-block kernel
 // folds into the scalars; a `done` scalar freezes the kernels of the iterations launched ahead of the host's convergence test.
 // Node numbering is the caller's (no renumbering): vertices [0, nvert), then the edge nodes.
+// A second scheme on the same context, `ipcs_midpoint` (cfdh_ipcs_set_scheme): the vector-coupled epsilon form with its ds pair
+// and explicit convection.  A1 is then a matrix of [D][D] blocks on the same pattern, constant over a run (assembled when dt, rho,
+// mu or the constrained velocity nodes change), the convection is applied matrix-free from cw and T2 into b1, and the pressure
+// Dirichlet data of a step are formed on the device from g - p_prev; the Krylov drivers, the pressure and the mass solve are shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,8 +33,9 @@
 #define IP_NB 2048  // most blocks (= partial sums per dot product) of the reducing kernels
 
 // ---------------------------------------------------------------- assembly
-// cw[cell][k][e] = |det| sum_d w_k,d Jinv[e][d],  w = 1.5 u_prev - 0.5 u_n1 at local node k;  geo[cell] = (Jinv [D][D], |det|)
-template <int D>
+// cw[cell][k][e] = |det| sum_d w_k,d Jinv[e][d],  w = 1.5 u_prev - 0.5 u_n1 at local node k (MID: w = u_prev, the explicit
+// convection of ipcs_midpoint);  geo[cell] = (Jinv [D][D], |det|)
+template <int D, bool MID = false>
 __global__ __launch_bounds__(TPB) void ip_cw_kernel(int nc, const int *__restrict__ cells, const double *__restrict__ geo,
                                                    const double *__restrict__ up, const double *__restrict__ un1, double *__restrict__ cw) {
   constexpr int NL = D == 2 ? 6 : 10;
@@ -42,7 +47,7 @@ __global__ __launch_bounds__(TPB) void ip_cw_kernel(int nc, const int *__restric
   for (int k = 0; k < NL; k++) {
     const int v = cells[(size_t)NL * e + k];
     double w[D];
-    for (int d = 0; d < D; d++) w[d] = 1.5 * up[(size_t)D * v + d] - 0.5 * un1[(size_t)D * v + d];
+    for (int d = 0; d < D; d++) w[d] = MID ? up[(size_t)D * v + d] : 1.5 * up[(size_t)D * v + d] - 0.5 * un1[(size_t)D * v + d];
     for (int q = 0; q < D; q++) {
       double a = 0.0;
       for (int d = 0; d < D; d++) a += w[d] * J[D * q + d];
@@ -161,6 +166,131 @@ __global__ __launch_bounds__(TPB) void ip_b3_kernel(int nn, const int *__restric
     for (int d = 0; d < D; d++) b[(size_t)D * row + d] = a[d];
 }
 
+// ---------------------------------------------------------------- ipcs_midpoint: vector-coupled momentum matrix
+// Blocks [nnz][D][D] (row-major alpha, beta) on the P2 pattern: Afree = (cm M + ck K) I + ck ES, ES = E - S the coupling part of the
+// epsilon form and its ds term (built on the host, constant); A1 with the Dirichlet treatment (the count on the D diagonal entries of
+// a constrained node); dinv [nn][D] the Jacobi weights of the D nn diagonal.  Eight lanes per row.
+template <int D>
+__global__ __launch_bounds__(TPB) void ip_asm_blk_kernel(int nn, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ Mv,
+                                                        const double *__restrict__ Kv, const double *__restrict__ ES, double cm, double ck,
+                                                        const unsigned char *__restrict__ flag, const double *__restrict__ cnt,
+                                                        double *__restrict__ Afree, double *__restrict__ A1, double *__restrict__ dinv) {
+  const int gid = blockIdx.x * TPB + threadIdx.x;
+  const int row = gid >> 3, l = gid & 7;
+  if (row >= nn) return;
+  const bool rf = flag[row] != 0;
+  for (int k = rowptr[row] + l; k < rowptr[row + 1]; k += 8) {
+    const int j = col[k];
+    const double s = cm * Mv[k] + ck * Kv[k];
+    const bool fj = flag[j] != 0;
+    for (int a = 0; a < D; a++)
+      for (int b = 0; b < D; b++) {
+        const size_t q = ((size_t)k * D + a) * D + b;
+        const double v = (a == b ? s : 0.0) + ck * ES[q];
+        Afree[q] = v;
+        const double vc = rf ? (j == row && a == b ? cnt[row] : 0.0) : (fj ? 0.0 : v);
+        A1[q] = vc;
+        if (j == row && a == b) dinv[(size_t)D * row + a] = 1.0 / vc;
+      }
+  }
+}
+
+// explicit convection, matrix-free: out[i][alpha] = int phi_i (w . grad) w_alpha = sum over the cells of node i (nlist[nptr[i] ..):
+// cell * NL + local node, ascending) of sum_b (sum_{k,e} cw[cell][k][e] T2[a][b][k][e]) w_b,alpha.  No matrix N is written.  Eight
+// lanes per row node take its cells in turn; T2 is staged in LDS.
+template <int D>
+__global__ __launch_bounds__(TPB) void ip_conv_kernel(int nn, const int *__restrict__ nptr, const int *__restrict__ nlist, const int *__restrict__ cells,
+                                                     const double *__restrict__ T2, const double *__restrict__ cw, const double *__restrict__ w,
+                                                     double *__restrict__ out) {
+  constexpr int NL = D == 2 ? 6 : 10, NT = NL * D;
+  extern __shared__ double sT[];
+  for (int i = threadIdx.x; i < NL * NL * NT; i += TPB) sT[i] = T2[i];
+  __syncthreads();
+  const int gid = blockIdx.x * TPB + threadIdx.x;
+  const int row = gid >> 3, l = gid & 7;
+  double a[D];
+  for (int d = 0; d < D; d++) a[d] = 0.0;
+  if (row < nn)
+    for (int q = nptr[row] + l; q < nptr[row + 1]; q += 8) {
+      const int code = nlist[q], e = code / NL, la = code - e * NL;
+      const double *wc = cw + (size_t)e * NT;
+      const int *cv = cells + (size_t)NL * e;
+      for (int b = 0; b < NL; b++) {
+        const double *t = sT + (la * NL + b) * NT;
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < NT; j++) s += wc[j] * t[j];
+        for (int d = 0; d < D; d++) a[d] += s * w[(size_t)D * cv[b] + d];
+      }
+    }
+  for (int d = 0; d < D; d++) a[d] = group8_sum(a[d]);
+  if (row < nn && l == 0)
+    for (int d = 0; d < D; d++) out[(size_t)D * row + d] = a[d];
+}
+
+// b1 of the block form = (2 rho/dt M I - Afree) u_prev - Afree g + (B^T - Pn) p_prev + sf f m1 - cc conv ; constrained rows:
+// count * value.  BTP holds B^T - Pn on the gptr / gcol pattern.
+template <int D>
+__global__ __launch_bounds__(TPB) void ip_b1_blk_kernel(int nn, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ Mv,
+                                                       const double *__restrict__ Afree, double cm2, const double *__restrict__ up,
+                                                       const unsigned char *__restrict__ flag, const double *__restrict__ cnt,
+                                                       const double *__restrict__ gval, const int *__restrict__ gptr, const int *__restrict__ gcol,
+                                                       const double *__restrict__ BTP, const double *__restrict__ p, const double *__restrict__ m1,
+                                                       double f0, double f1, double f2, const double *__restrict__ conv, double cc,
+                                                       double *__restrict__ b) {
+  const int gid = blockIdx.x * TPB + threadIdx.x;
+  const int row = gid >> 3, l = gid & 7;
+  double a[D];
+  for (int d = 0; d < D; d++) a[d] = 0.0;
+  if (row < nn) {
+    for (int k = rowptr[row] + l; k < rowptr[row + 1]; k += 8) {
+      const int j = col[k];
+      const double m = cm2 * Mv[k];
+      const bool fj = flag[j] != 0;
+      double uj[D], gj[D];
+      for (int d = 0; d < D; d++) { uj[d] = up[(size_t)D * j + d]; gj[d] = fj ? gval[(size_t)D * j + d] : 0.0; }
+      const double *af = Afree + (size_t)k * D * D;
+      for (int d = 0; d < D; d++)
+        for (int e = 0; e < D; e++) {
+          const double v = af[D * d + e];
+          a[d] += ((d == e ? m : 0.0) - v) * uj[e] - (fj ? v * gj[e] : 0.0);
+        }
+    }
+    for (int k = gptr[row] + l; k < gptr[row + 1]; k += 8) {
+      const double pv = p[gcol[k]];
+      for (int d = 0; d < D; d++) a[d] += BTP[(size_t)D * k + d] * pv;
+    }
+  }
+  for (int d = 0; d < D; d++) a[d] = group8_sum(a[d]);
+  if (row < nn && l == 0) {
+    const double f[3] = {f0, f1, f2};
+    const bool rf = flag[row] != 0;
+    for (int d = 0; d < D; d++)
+      b[(size_t)D * row + d] = rf ? cnt[row] * gval[(size_t)D * row + d] : a[d] + f[d] * m1[row] - cc * conv[(size_t)D * row + d];
+  }
+}
+
+// pressure Dirichlet data of one ipcs_midpoint step: the VALUE g goes into p, so phi = p - p_prev takes g - p_prev on the
+// constrained vertices.  lift = L_free (g - p_prev) over the constrained columns, rhsfix = count (g - p_prev) (ip_b2_kernel)
+__global__ __launch_bounds__(TPB) void ip_plift_kernel(int nv, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ Lf,
+                                                      const unsigned char *__restrict__ pflag, const double *__restrict__ pcnt,
+                                                      const double *__restrict__ pval, const double *__restrict__ pprev, double *__restrict__ lift,
+                                                      double *__restrict__ rhsfix) {
+  const int gid = blockIdx.x * TPB + threadIdx.x;
+  const int row = gid >> 3, l = gid & 7;
+  double a = 0.0;
+  if (row < nv)
+    for (int k = rowptr[row] + l; k < rowptr[row + 1]; k += 8) {
+      const int j = col[k];
+      if (pflag[j]) a += Lf[k] * (pval[j] - pprev[j]);
+    }
+  a = group8_sum(a);
+  if (row < nv && l == 0) {
+    lift[row] = a;
+    rhsfix[row] = pflag[row] ? pcnt[row] * (pval[row] - pprev[row]) : 0.0;
+  }
+}
+
 // ---------------------------------------------------------------- Krylov kernels
 // y = A x for D interleaved columns (the matrix is read once), eight lanes per row, grid-stride over the rows, with the dot
 // products the iteration needs next.  MODE 0: P0 = y . q ; 1: P0 = y . q, P1 = y . y ; 2: y = q - A x, P0 = y . y, P1 = q . q
@@ -182,6 +312,43 @@ __global__ __launch_bounds__(TPB) void ip_spmv_kernel(int n, const int *__restri
         const int j = col[k];
         const double v = val[k];
         for (int d = 0; d < D; d++) a[d] += v * x[(size_t)D * j + d];
+      }
+    for (int d = 0; d < D; d++) a[d] = group8_sum(a[d]);
+    if (row < n && l == 0)
+      for (int d = 0; d < D; d++) {
+        const double qv = q[(size_t)D * row + d];
+        const double r = MODE == 2 ? qv - a[d] : a[d];
+        y[(size_t)D * row + d] = r;
+        if (MODE == 2) { d0 += r * r; d1 += qv * qv; }
+        else { d0 += r * qv; if (MODE == 1) d1 += r * r; }
+      }
+  }
+  d0 = block_sum(d0, sh);
+  if (MODE != 0) d1 = block_sum(d1, sh);
+  if (threadIdx.x == 0) { P[blockIdx.x] = d0; if (MODE != 0) P[IP_NB + blockIdx.x] = d1; }
+}
+
+// the same three MODEs for a matrix of [nnz][D][D] blocks (row-major) on the interleaved vector: the block A1 of ipcs_midpoint
+template <int D, int MODE>
+__global__ __launch_bounds__(TPB) void ip_spmv_blk_kernel(int n, const int *__restrict__ rowptr, const int *__restrict__ col, const double *__restrict__ val,
+                                                         const double *__restrict__ x, double *__restrict__ y, const double *__restrict__ q,
+                                                         const double *__restrict__ S, double *__restrict__ P) {
+  __shared__ double sh[4];
+  if (MODE != 2 && S[IP_DONE] != 0.0) return;
+  const int l = threadIdx.x & 7;
+  double d0 = 0.0, d1 = 0.0;
+  for (int base = blockIdx.x * (TPB / 8); base < n; base += gridDim.x * (TPB / 8)) {
+    const int row = base + (threadIdx.x >> 3);
+    double a[D];
+    for (int d = 0; d < D; d++) a[d] = 0.0;
+    if (row < n)
+      for (int k = rowptr[row] + l; k < rowptr[row + 1]; k += 8) {
+        const int j = col[k];
+        const double *v = val + (size_t)k * D * D;
+        double xj[D];
+        for (int e = 0; e < D; e++) xj[e] = x[(size_t)D * j + e];
+        for (int d = 0; d < D; d++)
+          for (int e = 0; e < D; e++) a[d] += v[D * d + e] * xj[e];
       }
     for (int d = 0; d < D; d++) a[d] = group8_sum(a[d]);
     if (row < n && l == 0)
@@ -269,8 +436,8 @@ __global__ __launch_bounds__(TPB) void ip_scal_kernel(int nb, const double *__re
 __global__ __launch_bounds__(TPB) void ip_bicg_start_kernel(int n, const double *__restrict__ r, double *__restrict__ rh, double *__restrict__ p, double *__restrict__ v) {
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) { rh[i] = r[i]; p[i] = 0.0; v[i] = 0.0; }
 }
-// p = r + beta (p - omega v) ; y = dinv p
-template <int D>
+// p = r + beta (p - omega v) ; y = dinv p (dinv per node, or per unknown for the block matrix: BLK)
+template <int D, bool BLK>
 __global__ __launch_bounds__(TPB) void ip_bicg1_kernel(int n, const double *__restrict__ S, const double *__restrict__ r, const double *__restrict__ v,
                                                       const double *__restrict__ dinv, double *__restrict__ p, double *__restrict__ y) {
   if (S[IP_DONE] != 0.0) return;
@@ -278,11 +445,11 @@ __global__ __launch_bounds__(TPB) void ip_bicg1_kernel(int n, const double *__re
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
     const double pn = r[i] + beta * (p[i] - om * v[i]);
     p[i] = pn;
-    y[i] = dinv[i / D] * pn;
+    y[i] = dinv[BLK ? i : i / D] * pn;
   }
 }
 // s = r - alpha v ; z = dinv s
-template <int D>
+template <int D, bool BLK>
 __global__ __launch_bounds__(TPB) void ip_bicg2_kernel(int n, const double *__restrict__ S, const double *__restrict__ r, const double *__restrict__ v,
                                                       const double *__restrict__ dinv, double *__restrict__ s, double *__restrict__ z) {
   if (S[IP_DONE] != 0.0) return;
@@ -290,7 +457,7 @@ __global__ __launch_bounds__(TPB) void ip_bicg2_kernel(int n, const double *__re
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
     const double sn = r[i] - al * v[i];
     s[i] = sn;
-    z[i] = dinv[i / D] * sn;
+    z[i] = dinv[BLK ? i : i / D] * sn;
   }
 }
 // x += alpha y + omega z ; r = s - omega t ; P0 = rh . r, P1 = r . r
@@ -582,7 +749,8 @@ int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn64, int64_t nvert64, int64
   IpRef R;
   ip_reference(D, R);
   // geometry: Jinv[q][d] = d xi_q / d x_d = grad lambda_{q+1}, |det|
-  std::vector<double> geo((size_t)(D * D + 1) * nc);
+  std::vector<double> &geo = I->geo;
+  geo.assign((size_t)(D * D + 1) * nc, 0.0);
   std::vector<int> c1((size_t)NV * nc);
   for (int e = 0; e < nc; e++) {
     const int *cv = cells + (size_t)NL * e;
@@ -721,7 +889,7 @@ int cfdh_ipcs_clear_dirichlet(cfdh_ctx *c) {
   IpcsData *I = IP(c);
   std::fill(I->h_uflag.begin(), I->h_uflag.end(), 0); std::fill(I->h_ucnt.begin(), I->h_ucnt.end(), 0.0); std::fill(I->h_uval.begin(), I->h_uval.end(), 0.0);
   std::fill(I->h_pflag.begin(), I->h_pflag.end(), 0); std::fill(I->h_pcnt.begin(), I->h_pcnt.end(), 0.0); std::fill(I->h_pval.begin(), I->h_pval.end(), 0.0);
-  I->ubc_dirty = I->pbc_dirty = I->pset_dirty = true;
+  I->ubc_dirty = I->pbc_dirty = I->pset_dirty = I->uset_dirty = true;
   I->assembled = false;
   return 0;
 }
@@ -736,7 +904,7 @@ int cfdh_ipcs_add_dirichlet(cfdh_ctx *c, int field, int64_t n, const int32_t *no
   for (int64_t k = 0; k < n; k++) {
     const int v = nodes[k];
     if (field == 0) {
-      if (!update) { I->h_uflag[v] = 1; I->h_ucnt[v] += 1.0; }
+      if (!update) { I->h_uflag[v] = 1; I->h_ucnt[v] += 1.0; I->uset_dirty = true; }
       for (int d = 0; d < D; d++) I->h_uval[(size_t)D * v + d] = values[(size_t)D * k + d];
     } else {
       if (!update) { I->h_pflag[v] = 1; I->h_pcnt[v] += 1.0; I->pset_dirty = true; }
@@ -797,6 +965,11 @@ static int ip_prepare_pressure(cfdh_ctx *c) {
     I->pset_dirty = false;
     I->pbc_dirty = true;
   }
+  if (I->pbc_dirty && I->scheme == CFDH_IPCS_MIDPOINT) {  // the lifting depends on p_prev: formed on the device each step (ip_plift_kernel)
+    HIPCHK(c, I->pval.upload(I->h_pval, s)); HIPCHK(c, I->pcnt.upload(I->h_pcnt, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    I->pbc_dirty = false;
+  }
   if (I->pbc_dirty) {
     std::vector<double> lift(nv, 0.0), fix(nv, 0.0);
     for (int i = 0; i < nv; i++) {
@@ -852,20 +1025,175 @@ static int ip_assemble_t(cfdh_ctx *c) {
       sf * c->f[1], sf * c->f[2], I->b1.p);
   HIPCHK(c, hipGetLastError());
   I->assembled = true;
+  I->n_assemblies++;
   return 0;
 }
+
+// ---- ipcs_midpoint ---------------------------------------------------------------------------------------------------
+// Constant parts of the vector-coupled form, built once on the host (cells, then exterior facets, in ascending order):
+//   E(i a, j b) = int d_b phi_i d_a phi_j dx              from 2 mu eps(u) : eps(v) = mu (grad phi_i . grad phi_j delta_ab + d_b phi_i d_a phi_j)
+//   S(i a, j b) = int_{dOmega} phi_i d_a phi_j n_b ds     the ds term -mu (nabla_grad(u) n) . v; on the P2 pattern (both nodes in the facet's cell)
+//   Pn(i a, k)  = int_{dOmega} phi_i psi_k n_a ds         the ds term p n . v; a sub-pattern of B^T, folded into BTPv = B^T - Pn
+// The facet integrands are polynomials of degree 3: three-point Gauss on an edge, the degree-13 triangle rule on a face.  With
+// gl_f = grad lambda_f of the vertex opposite the facet, n |facet| = -gl_f |det| / (D - 1)!.
+static int ip_mid_build(cfdh_ctx *c) {
+  IpcsData *I = IP(c);
+  if (I->mid_built) return 0;
+  const int D = I->D, NL = I->NL, NV = D + 1, nn = I->nn, nc = I->nc;
+  hipStream_t s = c->stream;
+  IpRef R;
+  ip_reference(D, R);
+  const size_t nnz2 = I->hM.col.size(), nnzG = I->gcol.size();
+  std::vector<double> E(nnz2 * D * D, 0.0), Sb(nnz2 * D * D, 0.0);
+  I->hPn.assign(nnzG * D, 0.0);
+  auto grads = [&](int e, double gl[4][3], double &det) {  // grad lambda_0 .. lambda_D and |det| from geo (cfdh_ipcs_create)
+    const double *g = I->geo.data() + (size_t)(D * D + 1) * e;
+    det = g[D * D];
+    for (int d = 0; d < D; d++) {
+      gl[0][d] = 0.0;
+      for (int q = 0; q < D; q++) { gl[q + 1][d] = g[D * q + d]; gl[0][d] -= g[D * q + d]; }
+    }
+  };
+  for (int e = 0; e < nc; e++) {
+    const int *cv = I->cells.data() + (size_t)NL * e;
+    double gl[4][3], det;
+    grads(e, gl, det);
+    for (int a = 0; a < NL; a++)
+      for (int b = 0; b < NL; b++) {
+        const size_t k = (size_t)ip_find(I->hM.rowptr, I->hM.col, cv[a], cv[b]);
+        const double *Kr = R.K.data() + ((size_t)a * NL + b) * NV * NV;
+        for (int al = 0; al < D; al++)
+          for (int be = 0; be < D; be++) {
+            double v = 0.0;
+            for (int i = 0; i < NV; i++)
+              for (int j = 0; j < NV; j++) v += Kr[i * NV + j] * gl[i][be] * gl[j][al];
+            E[(k * D + al) * D + be] += det * v;
+          }
+      }
+  }
+  // facet rule: barycentric points on the reference facet, weights summing to 1
+  std::vector<double> fl, fw;
+  if (D == 2) {
+    const double h = 0.5 * std::sqrt(0.6), t[3] = {0.5 - h, 0.5, 0.5 + h}, w[3] = {5.0 / 18.0, 8.0 / 18.0, 5.0 / 18.0};
+    for (int q = 0; q < 3; q++) { fl.push_back(1.0 - t[q]); fl.push_back(t[q]); fw.push_back(w[q]); }
+  } else {
+    for (int q = 0; q < CFDH_NQ; q++) { for (int i = 0; i < 3; i++) fl.push_back(CFDH_QL[q][i]); fw.push_back(CFDH_QW[q]); }
+  }
+  const double fact = D == 2 ? 1.0 : 0.5;  // 1 / (D - 1)!
+  std::vector<double> phi(NL), dl((size_t)NL * NV);
+  for (size_t kf = 0; kf < I->fcell.size(); kf++) {
+    const int e = I->fcell[kf], f = I->flocal[kf];
+    const int *cv = I->cells.data() + (size_t)NL * e;
+    double gl[4][3], det;
+    grads(e, gl, det);
+    for (size_t q = 0; q < fw.size(); q++) {
+      double lam[4];
+      int m = 0;
+      for (int i = 0; i < NV; i++) lam[i] = i == f ? 0.0 : fl[q * D + m++];
+      ip_p2(D, lam, phi.data(), dl.data());
+      const double w = fw[q] * det * fact;
+      for (int a = 0; a < NL; a++) {
+        if (phi[a] == 0.0) continue;  // nodes off the facet (their basis functions vanish on it identically)
+        for (int b = 0; b < NL; b++) {
+          const size_t k = (size_t)ip_find(I->hM.rowptr, I->hM.col, cv[a], cv[b]);
+          for (int al = 0; al < D; al++) {
+            double g = 0.0;
+            for (int i = 0; i < NV; i++) g += dl[b * NV + i] * gl[i][al];
+            for (int be = 0; be < D; be++) Sb[(k * D + al) * D + be] -= w * phi[a] * g * gl[f][be];
+          }
+        }
+        for (int v = 0; v < NV; v++) {
+          const size_t k = (size_t)ip_find(I->gptr, I->gcol, cv[a], cv[v]);
+          for (int al = 0; al < D; al++) I->hPn[k * D + al] -= w * phi[a] * lam[v] * gl[f][al];
+        }
+      }
+    }
+  }
+  I->hES.resize(E.size());
+  for (size_t k = 0; k < E.size(); k++) I->hES[k] = E[k] - Sb[k];
+  std::vector<double> btp(I->hBT.size());
+  for (size_t k = 0; k < btp.size(); k++) btp[k] = I->hBT[k] - I->hPn[k];
+  // the cells of every node, ascending
+  std::vector<int> nptr(nn + 1, 0), nlist((size_t)NL * nc);
+  for (size_t k = 0; k < nlist.size(); k++) nptr[I->cells[k] + 1]++;
+  for (int i = 0; i < nn; i++) nptr[i + 1] += nptr[i];
+  std::vector<int> fill(nptr.begin(), nptr.end() - 1);
+  for (size_t k = 0; k < nlist.size(); k++) nlist[fill[I->cells[k]]++] = (int)k;  // k = cell * NL + local node
+  HIPCHK(c, I->ESv.upload(I->hES, s)); HIPCHK(c, I->BTPv.upload(btp, s));
+  HIPCHK(c, I->nptr.upload(nptr, s)); HIPCHK(c, I->nlist.upload(nlist, s));
+  HIPCHK(c, I->Lfree.upload(I->hL.val, s));
+  HIPCHK(c, I->AfreeB.alloc(nnz2 * D * D)); HIPCHK(c, I->A1B.alloc(nnz2 * D * D));
+  HIPCHK(c, I->dinvB.alloc((size_t)nn * D)); HIPCHK(c, I->conv.alloc((size_t)nn * D));
+  HIPCHK(c, hipStreamSynchronize(s));
+  I->mid_built = true;
+  return 0;
+}
+
+int cfdh_ipcs_set_scheme_impl(cfdh_ctx *c, int scheme) {
+  IpcsData *I = IP(c);
+  if (scheme == I->scheme) return 0;
+  if (scheme == CFDH_IPCS_MIDPOINT) CHK(ip_mid_build(c));
+  I->scheme = scheme;
+  I->mid_valid = false; I->assembled = false;
+  I->pbc_dirty = true;              // lift2 / prhs hold the other scheme's data
+  HIPCHK(c, I->us.zero(c->stream));  // the initial guess of solve 1 belongs to the other scheme's u*
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// block A1 of ipcs_midpoint: assembled only when dt, rho, mu, the scheme or the constrained velocity nodes / their counts changed
+template <int D>
+static int ip_mid_matrix(cfdh_ctx *c) {
+  IpcsData *I = IP(c);
+  bool ok = I->mid_valid && I->mid_key[0] == c->dt && I->mid_key[1] == c->rho && I->mid_key[2] == c->mu;
+  if (ok && I->uset_dirty) ok = I->mid_flag == I->h_uflag && I->mid_cnt == I->h_ucnt;
+  I->uset_dirty = false;
+  if (ok) return 0;
+  IPL(c, ip_asm_blk_kernel<D>, ip_grid8(I->nn), 0, I->nn, (const int *)I->rp2.p, (const int *)I->col2.p, (const double *)I->Mv.p, (const double *)I->Kv.p,
+      (const double *)I->ESv.p, c->rho / c->dt, 0.5 * c->mu, (const unsigned char *)I->uflag.p, (const double *)I->ucnt.p, I->AfreeB.p, I->A1B.p,
+      I->dinvB.p);
+  HIPCHK(c, hipGetLastError());
+  I->mid_key[0] = c->dt; I->mid_key[1] = c->rho; I->mid_key[2] = c->mu;
+  I->mid_flag = I->h_uflag; I->mid_cnt = I->h_ucnt;
+  I->mid_valid = true;
+  I->n_assemblies++;
+  return 0;
+}
+
+// A1 (if it is out of date) and b1 of the current state
+template <int D>
+static int ip_assemble_mid_t(cfdh_ctx *c) {
+  IpcsData *I = IP(c);
+  constexpr int NL = D == 2 ? 6 : 10;
+  const double conv = I->conv_coeff < 0 ? c->rho : I->conv_coeff, sf = I->force_default ? c->rho : I->force_coeff;
+  CHK(ip_mid_matrix<D>(c));
+  IPL(c, (ip_cw_kernel<D, true>), (I->nc + TPB - 1) / TPB, 0, I->nc, (const int *)I->d_cells.p, (const double *)I->d_geo.p, (const double *)I->u_prev.p,
+      (const double *)I->u_prev.p, I->cw.p);
+  IPL(c, ip_conv_kernel<D>, ip_grid8(I->nn), sizeof(double) * NL * NL * NL * D, I->nn, (const int *)I->nptr.p, (const int *)I->nlist.p,
+      (const int *)I->d_cells.p, (const double *)I->d_T2.p, (const double *)I->cw.p, (const double *)I->u_prev.p, I->conv.p);
+  IPL(c, ip_b1_blk_kernel<D>, ip_grid8(I->nn), 0, I->nn, (const int *)I->rp2.p, (const int *)I->col2.p, (const double *)I->Mv.p, (const double *)I->AfreeB.p,
+      2.0 * c->rho / c->dt, (const double *)I->u_prev.p, (const unsigned char *)I->uflag.p, (const double *)I->ucnt.p, (const double *)I->uval.p,
+      (const int *)I->d_gptr.p, (const int *)I->d_gcol.p, (const double *)I->BTPv.p, (const double *)I->p_prev.p, (const double *)I->d_m1.p, sf * c->f[0],
+      sf * c->f[1], sf * c->f[2], (const double *)I->conv.p, conv, I->b1.p);
+  HIPCHK(c, hipGetLastError());
+  I->assembled = true;
+  return 0;
+}
+
 int cfdh_ipcs_assemble(cfdh_ctx *c) {
   CHK(ip_prepare(c));
+  if (IP(c)->scheme == CFDH_IPCS_MIDPOINT) return IP(c)->D == 2 ? ip_assemble_mid_t<2>(c) : ip_assemble_mid_t<3>(c);
   return IP(c)->D == 2 ? ip_assemble_t<2>(c) : ip_assemble_t<3>(c);
 }
 
 // ---- Krylov drivers ------------------------------------------------------------------------------------------------
 struct IpMat { int n; const int *rp, *col; const double *val; };
 
-template <int D, int MODE>
+template <int D, int MODE, bool BLK = false>
 static void ip_spmv(cfdh_ctx *c, const IpMat &A, const double *x, double *y, const double *q) {
   IpcsData *I = IP(c);
-  IPL(c, (ip_spmv_kernel<D, MODE>), ip_nb(A.n, TPB / 8), 0, A.n, A.rp, A.col, A.val, x, y, q, (const double *)I->S.p, I->P.p);
+  if (BLK) IPL(c, (ip_spmv_blk_kernel<D, MODE>), ip_nb(A.n, TPB / 8), 0, A.n, A.rp, A.col, A.val, x, y, q, (const double *)I->S.p, I->P.p);
+  else IPL(c, (ip_spmv_kernel<D, MODE>), ip_nb(A.n, TPB / 8), 0, A.n, A.rp, A.col, A.val, x, y, q, (const double *)I->S.p, I->P.p);
 }
 template <int STAGE>
 static void ip_scal(cfdh_ctx *c, int nb, double rtol, double atol, int first) {
@@ -899,8 +1227,9 @@ static int ip_snapshot(cfdh_ctx *c) {
   return 0;
 }
 
-// BiCGStab + Jacobi, A1 x = b on D interleaved columns; x holds the initial guess
-template <int D>
+// BiCGStab + Jacobi, A1 x = b on D interleaved columns; x holds the initial guess.  BLK: A.val holds [nnz][D][D] blocks and dinv
+// one weight per unknown (ipcs_midpoint); otherwise one scalar matrix for the D columns and one weight per node
+template <int D, bool BLK = false>
 static int ip_bicgstab(cfdh_ctx *c, const IpMat &A, const double *dinv, const double *b, double *x, cfdh_ipcs_stats *st) {
   IpcsData *I = IP(c);
   const int n = A.n * D, nbv = ip_nb(n, TPB * 4), nbs = ip_nb(A.n, TPB / 8);
@@ -908,7 +1237,7 @@ static int ip_bicgstab(cfdh_ctx *c, const IpMat &A, const double *dinv, const do
   const int max_it = I->max_it[0], batch = 4;
   const double *S = I->S.p;
   double m[4];
-  ip_spmv<D, 2>(c, A, x, I->kr.p, b);
+  ip_spmv<D, 2, BLK>(c, A, x, I->kr.p, b);
   ip_scal<0>(c, nbs, rtol, atol, 1);
   CHK(ip_read(c, m));
   // `launched` bounds the loop on the host, whatever the device counter says: at most max_it iterations are ever launched
@@ -922,11 +1251,11 @@ static int ip_bicgstab(cfdh_ctx *c, const IpMat &A, const double *dinv, const do
       const int nbatch = std::min(batch, max_it - launched);
       launched += nbatch;
       for (int k = 0; k < nbatch; k++) {
-        IPL(c, ip_bicg1_kernel<D>, nbv, 0, n, S, (const double *)I->kr.p, (const double *)I->kv.p, dinv, I->kp.p, I->ky.p);
-        ip_spmv<D, 0>(c, A, I->ky.p, I->kv.p, I->krh.p);
+        IPL(c, (ip_bicg1_kernel<D, BLK>), nbv, 0, n, S, (const double *)I->kr.p, (const double *)I->kv.p, dinv, I->kp.p, I->ky.p);
+        ip_spmv<D, 0, BLK>(c, A, I->ky.p, I->kv.p, I->krh.p);
         ip_scal<1>(c, nbs, 0, 0, 0);
-        IPL(c, ip_bicg2_kernel<D>, nbv, 0, n, S, (const double *)I->kr.p, (const double *)I->kv.p, dinv, I->ks.p, I->kz.p);
-        ip_spmv<D, 1>(c, A, I->kz.p, I->kt.p, I->ks.p);
+        IPL(c, (ip_bicg2_kernel<D, BLK>), nbv, 0, n, S, (const double *)I->kr.p, (const double *)I->kv.p, dinv, I->ks.p, I->kz.p);
+        ip_spmv<D, 1, BLK>(c, A, I->kz.p, I->kt.p, I->ks.p);
         ip_scal<2>(c, nbs, 0, 0, 0);
         IPL(c, ip_bicg3_kernel, nbv, 0, n, S, (const double *)I->ky.p, (const double *)I->kz.p, (const double *)I->ks.p, (const double *)I->kt.p,
             (const double *)I->krh.p, x, I->kr.p, I->P.p);
@@ -938,7 +1267,7 @@ static int ip_bicgstab(cfdh_ctx *c, const IpMat &A, const double *dinv, const do
     }
     if (m[3] != 0.0) break;
     CHK(ip_snapshot(c));
-    ip_spmv<D, 2>(c, A, x, I->kr.p, b);  // the recurrence says converged (or the cap is reached): the true residual decides
+    ip_spmv<D, 2, BLK>(c, A, x, I->kr.p, b);  // the recurrence says converged (or the cap is reached): the true residual decides
     ip_scal<0>(c, nbs, rtol, atol, 0);
     CHK(ip_read(c, m));
   }
@@ -1017,15 +1346,24 @@ static int ip_step_t(cfdh_ctx *c, cfdh_ipcs_stats *st) {
   CHK(ip_prepare(c));
   CHK(ip_sync(c));
   const double t1 = ip_now_ms();
-  CHK(ip_assemble_t<D>(c));
+  const bool mid = I->scheme == CFDH_IPCS_MIDPOINT;
+  CHK(mid ? ip_assemble_mid_t<D>(c) : ip_assemble_t<D>(c));
   CHK(ip_sync(c));
   const double t2 = ip_now_ms();
   // step 1 (initial guess: the previous u*)
-  const IpMat A1{nn, I->rp2.p, I->col2.p, I->A1v.p};
-  CHK(ip_bicgstab<D>(c, A1, I->dinv1.p, I->b1.p, I->us.p, st));
+  if (mid) {
+    const IpMat A1{nn, I->rp2.p, I->col2.p, I->A1B.p};
+    CHK((ip_bicgstab<D, true>(c, A1, I->dinvB.p, I->b1.p, I->us.p, st)));
+  } else {
+    const IpMat A1{nn, I->rp2.p, I->col2.p, I->A1v.p};
+    CHK(ip_bicgstab<D>(c, A1, I->dinv1.p, I->b1.p, I->us.p, st));
+  }
   const double t3 = ip_now_ms();
-  // step 2
+  // step 2 (ipcs_midpoint: the pressure Dirichlet value goes into p, so phi takes g - p_prev)
   if (st->reason[0] > 0) {
+    if (mid)  // without a pressure object both come out zero
+      IPL(c, ip_plift_kernel, ip_grid8(nv), 0, nv, (const int *)I->rp1.p, (const int *)I->col1.p, (const double *)I->Lfree.p,
+          (const unsigned char *)I->pflag.p, (const double *)I->pcnt.p, (const double *)I->pval.p, (const double *)I->p_prev.p, I->lift2.p, I->prhs.p);
     IPL(c, ip_b2_kernel<D>, ip_grid8(nv), 0, nv, (const int *)I->d_bptr.p, (const int *)I->d_bcol.p, (const double *)I->Bv.p, (const double *)I->us.p,
         -c->rho / c->dt, (const unsigned char *)I->pflag.p, (const double *)I->lift2.p, (const double *)I->prhs.p, I->b2.p);
     if (I->singular) CHK(ip_sub_mean(c, nv, I->b2.p));
@@ -1033,6 +1371,7 @@ static int ip_step_t(cfdh_ctx *c, cfdh_ipcs_stats *st) {
     const IpMat L{nv, I->rp1.p, I->col1.p, I->Lv.p};
     CHK((ip_cg<1, false>(c, 1, L, nullptr, I->b2.p, I->phi.p, I->pr.p, I->pz.p, I->pp.p, I->pq.p, st)));
     if (I->singular) CHK(ip_sub_mean(c, nv, I->phi.p));
+    if (mid) HIPCHK(c, hipMemcpyAsync(I->p_sol.p, I->p_prev.p, sizeof(double) * nv, hipMemcpyDeviceToDevice, s));  // p_sol = p_prev + phi
     IPL(c, ip_axpy_kernel, ip_nb(nv, TPB * 4), 0, nv, 1.0, (const double *)I->phi.p, I->p_sol.p);
   }
   const double t4 = ip_now_ms();
@@ -1042,8 +1381,8 @@ static int ip_step_t(cfdh_ctx *c, cfdh_ipcs_stats *st) {
         (const int *)I->d_gptr.p, (const int *)I->d_gcol.p, (const double *)I->Gv.p, c->dt, (const double *)I->phi.p, I->b3.p);
     const IpMat RM{nn, I->rp2.p, I->col2.p, I->RMv.p};
     CHK((ip_cg<D, true>(c, 2, RM, I->dinv3.p, I->b3.p, I->u_sol.p, I->kr.p, I->kz.p, I->kp.p, I->kv.p, st)));
-    // step 4
-    HIPCHK(c, hipMemcpyAsync(I->u_n1.p, I->u_prev.p, sizeof(double) * n1, hipMemcpyDeviceToDevice, s));
+    // step 4 (ipcs_midpoint has no second history level)
+    if (!mid) HIPCHK(c, hipMemcpyAsync(I->u_n1.p, I->u_prev.p, sizeof(double) * n1, hipMemcpyDeviceToDevice, s));
   }
   CHK(ip_sync(c));
   const double t5 = ip_now_ms();
@@ -1081,6 +1420,10 @@ int cfdh_ipcs_apply_pc(cfdh_ctx *c, const double *r, double *z) {
 template <int D>
 static int ip_krylov_solve_t(cfdh_ctx *c, int which, cfdh_ipcs_stats *st) {
   IpcsData *I = IP(c);
+  if (which == 0 && I->scheme == CFDH_IPCS_MIDPOINT) {
+    const IpMat A1{I->nn, I->rp2.p, I->col2.p, I->A1B.p};
+    return ip_bicgstab<D, true>(c, A1, I->dinvB.p, I->hk_b.p, I->hk_x.p, st);
+  }
   if (which == 0) {
     const IpMat A1{I->nn, I->rp2.p, I->col2.p, I->A1v.p};
     return ip_bicgstab<D>(c, A1, I->dinv1.p, I->hk_b.p, I->hk_x.p, st);
@@ -1102,7 +1445,9 @@ int cfdh_ipcs_krylov_solve_impl(cfdh_ctx *c, int which, const double *b, const d
   CHK(ip_prepare(c));
   HIPCHK(c, I->hk_b.alloc(n1)); HIPCHK(c, I->hk_x.alloc(n1));
   const long long launch0 = I->n_launch, sync0 = I->n_sync;
-  if (which == 0) {  // A1 of the current state; the assembly also writes b1, which is kept
+  if (which == 0 && I->scheme == CFDH_IPCS_MIDPOINT) {  // the constant block A1, assembled here only if it is out of date
+    CHK(I->D == 2 ? ip_mid_matrix<2>(c) : ip_mid_matrix<3>(c));
+  } else if (which == 0) {  // A1 of the current state; the assembly also writes b1, which is kept
     const bool was = I->assembled;
     HIPCHK(c, hipMemcpyAsync(I->hk_x.p, I->b1.p, sizeof(double) * n1, hipMemcpyDeviceToDevice, s));
     CHK(I->D == 2 ? ip_assemble_t<2>(c) : ip_assemble_t<3>(c));

@@ -11,7 +11,7 @@ struct IpcsData {
   int D = 2, NL = 6, nn = 0, nvert = 0, nc = 0;
   // host mesh and constant operators (P2 pattern: hM.rowptr / hM.col, shared by K and A1; P1 pattern: hL.rowptr / hL.col)
   std::vector<int> cells, fcell, flocal, fmarker;
-  std::vector<double> coords;
+  std::vector<double> coords, geo;   // geo[cell] = (Jinv [D][D], |det|)
   CsrHost hM, hL;                    // mass on the P2 nodes; unconstrained P1 stiffness
   std::vector<double> hK, hMp, m1;   // P2 stiffness, P1 mass, int phi_i
   std::vector<int> gptr, gcol, bptr, bcol;  // patterns [nn x nvert] (G_d, B_d^T) and [nvert x nn] (B_d)
@@ -45,6 +45,20 @@ struct IpcsData {
   dbuf<double> hk_b, hk_x;
   bool snap_on = false, snap_set = false;
   double snap[IP_NS] = {};
+  // ---- scheme `ipcs_midpoint` (cfdh_ipcs_set_scheme): vector-coupled momentum matrix, constant over the run.  Host: E - S as
+  // [nnz][D][D] blocks on the P2 pattern, Pn as [nnzG][D] on the gptr / gcol pattern (built once, cells and facets ascending);
+  // device: those, the block matrices A1_free / A1 and the Jacobi weights of the D nn diagonal, the cells of every node
+  // (nptr / nlist: cell * NL + local node, ascending) for the matrix-free convection, the unconstrained L and the pressure
+  // Dirichlet values / counts for the per-step lifting.
+  int scheme = 0;                    // CFDH_IPCS_BDF2 | CFDH_IPCS_MIDPOINT
+  bool mid_built = false, mid_valid = false, uset_dirty = true;
+  double mid_key[3] = {0, 0, 0};     // dt, rho, mu of the block A1
+  std::vector<unsigned char> mid_flag;  // constrained velocity nodes and their counts the block A1 was assembled for
+  std::vector<double> mid_cnt;
+  long long n_assemblies = 0;        // assemblies of A1 since creation (cfdh_info 92)
+  std::vector<double> hES, hPn;
+  dbuf<int> nptr, nlist;
+  dbuf<double> ESv, BTPv, AfreeB, A1B, dinvB, conv, Lfree, pval, pcnt;
 };
 
 int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells, const double *coords, int64_t nfac,
@@ -52,7 +66,8 @@ int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn, int64_t nvert, int64_t n
 void cfdh_ipcs_free(cfdh_ctx *c);
 int cfdh_ipcs_clear_dirichlet(cfdh_ctx *c);
 int cfdh_ipcs_add_dirichlet(cfdh_ctx *c, int field, int64_t n, const int32_t *nodes, const double *values, bool update);
-int cfdh_ipcs_assemble(cfdh_ctx *c);   // A1, b1 at the current state
+int cfdh_ipcs_assemble(cfdh_ctx *c);   // A1, b1 at the current state (of the current scheme)
+int cfdh_ipcs_set_scheme_impl(cfdh_ctx *c, int scheme);
 int cfdh_ipcs_step_impl(cfdh_ctx *c, cfdh_ipcs_stats *st);
 int cfdh_ipcs_apply_pc(cfdh_ctx *c, const double *r, double *z);
 int cfdh_ipcs_krylov_solve_impl(cfdh_ctx *c, int which, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,

@@ -34,19 +34,21 @@ from ..solverBase import SolverBase
 from .stabilized_schur import Solver as _SchurSolver
 
 
-def _refuse_unsupported(mesh, kwargs):
+def _refuse_unsupported(mesh, kwargs, name="ipcs_bdf2"):
     cell = mesh.topology.cell_name()
     if cell in ("quadrilateral", "hexahedron"):
-        raise NotImplementedError("ipcs_bdf2 runs on P2/P1 triangles and tetrahedra; on %s meshes use stabilized_schur" % cell)
+        raise NotImplementedError("%s runs on P2/P1 triangles and tetrahedra; on %s meshes use stabilized_schur" % (name, cell))
     comm = kwargs.get("comm", None)
     if comm is not None and comm.size > 1:
-        raise NotImplementedError("ipcs_bdf2 runs on one GPU: for a partitioned run use stabilized_schur")
+        raise NotImplementedError("%s runs on one GPU: for a partitioned run use stabilized_schur" % name)
 
 
 class Solver(SolverBase):
+    _name = "ipcs_bdf2"   # in messages; solvers/ipcs_midpoint.py runs the other scheme on the same context
+
     def __init__(self, mesh, dt: float, rho: float, mu: float, f: list,
                  initial_velocity: Callable[[np.ndarray], np.ndarray] = None, **kwargs):
-        _refuse_unsupported(mesh, kwargs)
+        _refuse_unsupported(mesh, kwargs, self._name)
         super().__init__(mesh, dt, rho, mu, f)
         gdim = mesh.geometry.dim
         super().initVelocitySpace("Lagrange", mesh.topology.cell_name(), 2, shape=(gdim,))
@@ -67,8 +69,7 @@ class Solver(SolverBase):
                                     device=int(kwargs.get("device", 0)))
         ff = np.atleast_1d(np.asarray(f, dtype=np.float64))
         self.ctx.set_params(float(dt), float(rho), float(mu), f=ff)
-        if not self.consistent:
-            self.ctx.set_form(1.0, -1.0)   # ipcs_bdf2.py:67-80: no rho on the convection term, + f . v in the residual
+        self._configure_scheme(float(rho))
         self.ctx.set_tolerances(kwargs.get("rtol", 1e-5), kwargs.get("atol", 1e-50), kwargs.get("max_it", 10000))
         if kwargs.get("options"):
             o = self.ctx.default_options()
@@ -95,6 +96,10 @@ class Solver(SolverBase):
             fn.x._post_access = self._mark_prev_dirty
         self._u_prev.x._assign_hook = lambda src: self._assign_previous(0, src)
         self._p_prev.x._assign_hook = lambda src: self._assign_previous(1, src)
+
+    def _configure_scheme(self, rho):
+        if not self.consistent:
+            self.ctx.set_form(1.0, -1.0)   # ipcs_bdf2.py:67-80: no rho on the convection term, + f . v in the residual
 
     _bc_nodes_values = _SchurSolver._bc_nodes_values
     _upload_bcs = _SchurSolver._upload_bcs
@@ -181,7 +186,7 @@ class Solver(SolverBase):
         self._sol_dev_newer = self._mid_dev_newer = True
         self._prev_dev_newer = True   # u_n1 <- u_prev happened on the device
         if self._verbose and not self._quiet:
-            print("ipcs_bdf2: iterations %s, |r|/|b| %s" % (list(st.its), ["%.2e" % r for r in st.rel_res]))
+            print("%s: iterations %s, |r|/|b| %s" % (self._name, list(st.its), ["%.2e" % r for r in st.rel_res]))
 
     def initStressForm(self):
         """The stress fields live on the vertex (degree-1) space whatever the velocity degree (solverBase.py:144-162: `vector` is

@@ -420,7 +420,8 @@ int cfdh_krylov_vec_op(cfdh_ctx *ctx, int op, int n, int ld, int nvec, const dou
  * cfdh_wall_shear_stress, cfdh_wall_stats_reset / accumulate / get,
  * cfdh_info (0, 1: nn; 2: nc; 3: entries of A1; 6: levels of the pressure hierarchy; 15: host synchronisations and 80: kernel
  * launches of the last step; 81: nvert; 82: whole-field host copies since creation; 83: 1 (the context kind); 84 and 90:
- * accumulations of the wall shear indices since the last reset), cfdh_last_error, cfdh_destroy.  Every other entry point returns CFDH_E_STATE on it, and the cfdh_ipcs_* entry points return CFDH_E_STATE on every
+ * accumulations of the wall shear indices since the last reset; 91: the scheme and 92: assemblies of A1 since creation, see
+ * cfdh_ipcs_set_scheme), cfdh_last_error, cfdh_destroy.  Every other entry point returns CFDH_E_STATE on it, and the cfdh_ipcs_* entry points return CFDH_E_STATE on every
  * other context. */
 int cfdh_create_ipcs(cfdh_ctx **out, int device, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells,
                      const double *node_coords, int64_t nfacets, const int32_t *facet_cells, const int32_t *facet_local,
@@ -483,6 +484,35 @@ int cfdh_ipcs_apply_pressure_pc(cfdh_ctx *ctx, const double *r, double *z);
 #define CFDH_IPCS_NSCAL 16
 int cfdh_ipcs_krylov_solve(cfdh_ctx *ctx, int which, const double *b, const double *x0, double rtol, double atol, int max_it,
                            double *x, cfdh_ipcs_stats *stats, double *scalars);
+
+/* The scheme of a cfdh_create_ipcs context.  CFDH_IPCS_BDF2 (default) is the one described above.  CFDH_IPCS_MIDPOINT is the
+ * reference's other pressure-correction solver (src/solvers/ipcs_midpoint.py:60-80 there): the vector-coupled epsilon
+ * form sigma = 2 mu eps(u) - p I at the midpoint, its ds pair p n . v - mu (nabla_grad(u) n) . v over ALL exterior facets, and
+ * EXPLICIT convection, so that the momentum matrix is constant over a run (the step is CFL-limited in exchange).  Rows and
+ * columns of the block operators are (node i, component a), (node j, component b) on the interleaved vectors:
+ *   V = mu (K x I + E) - mu S,   E(ia, jb) = int d_b phi_i d_a phi_j dx,   S(ia, jb) = int_{dOmega} phi_i d_a phi_j n_b ds,
+ *   Pn(ia, k) = int_{dOmega} phi_i psi_k n_a ds,   C(w)(ia) = int phi_i (w . grad) w_a dx
+ *   1. A1 u* = b1,  A1_free = rho/dt M x I + V / 2,
+ *      b1 = (rho/dt M x I - V / 2) u_prev - c C(u_prev) + (B^T - Pn) p_prev + s_f f m1;  velocity Dirichlet objects as above (all
+ *      d components of a node at once).  BiCGStab + point Jacobi on the d nn diagonal.  A1 is assembled only when dt, rho, mu, the
+ *      scheme, the set of constrained velocity nodes or their counts changed -- not by a step or a value-only
+ *      cfdh_update_dirichlet.
+ *   2. L phi = -rho/dt sum_d B_d u*_d with the pressure Dirichlet VALUE g imposed on p: phi takes g - p_prev on the constrained
+ *      vertices (lifting and fixed rows are formed on the device every step), so non-homogeneous pressure data are right.
+ *      p_sol = p_prev + phi.  Without a pressure object phi is mean-free.  Flexible PCG + one V-cycle, as above.
+ *   3. rho M u_sol = rho M u* - dt G phi, as above.  u_n1 is neither used nor shifted.
+ * c = conv_coeff and s_f = force_coeff of cfdh_ipcs_set_form (defaults rho and +rho; the reference's literal form is (rho, 1)).
+ * cfdh_ipcs_step, _get_intermediate, _krylov_solve (which 0 drives BiCGStab on the block A1), _set_form, _set_tolerances, the
+ * functionals and the wall shear act on the current scheme's operators.  A change of scheme invalidates A1 and resets the initial
+ * guess of solve 1 to zero.  CFDH_E_ARG on an unknown value.  cfdh_info 91: the scheme; 92: assemblies of A1 since creation. */
+enum { CFDH_IPCS_BDF2 = 0, CFDH_IPCS_MIDPOINT = 1 };
+int cfdh_ipcs_set_scheme(cfdh_ctx *ctx, int scheme);
+/* The block A1 of CFDH_IPCS_MIDPOINT as block CSR on the P2 node pattern, columns ascending, vals [nnz][gdim][gdim] row-major
+ * (a, b); query convention of cfdh_get_csr.  which 0: with the Dirichlet treatment, 1: A1_free.  Like cfdh_ipcs_get_operator(0) it
+ * assembles from the current state when no step has run, and forms b1 for cfdh_ipcs_get_intermediate(2).  CFDH_E_STATE under
+ * CFDH_IPCS_BDF2; conversely cfdh_ipcs_get_operator(0) returns CFDH_E_STATE under CFDH_IPCS_MIDPOINT (which >= 1 stay
+ * available).  Exposed for parity tests. */
+int cfdh_ipcs_get_block_operator(cfdh_ctx *ctx, int which, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals);
 
 /* u_prev2 (stabilized_schur_bdf2.py:72): upload / download; nv local vertices x gdim */
 int cfdh_set_previous2(cfdh_ctx *ctx, const double *u_prev2);

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Time steps of `ipcs_bdf2` (P2/P1 pressure correction) next to `stabilized_schur_backflow` with p_grade = 2 (the existing
 second-order path) on the same mesh, in one process, alternating blocks of steps.  Writes profiles/ipcs_measure.json.
+`--solvers ipcs_bdf2,ipcs_midpoint` puts the two pressure-correction schemes next to each other, same mesh and dt.
 
     python tools/ipcs_measure.py [--cases tg288,dfg110,bifurcation2.5e-4] [--steps 50] [--warmup 5] [--no-compare]
+                                 [--solvers ipcs_bdf2,ipcs_midpoint]
 
 Per case: unknowns, ms/step (host clock around a synchronised step; the step ends with a stream synchronisation), ms per phase
 (assembly, the three solves), iterations per solve, kernel launches and host synchronisations per step -- all from the step
@@ -33,7 +35,7 @@ def _scenario(case, solver, **kw):
         from cfd_hemodynamic_amd.scenarios.dfg_1 import DFG1Benchmark
         return DFG1Benchmark(solver, 0.001, 1.0, m=int(case[3:] or 110), quiet=True, **kw)
     if case.startswith("bifurcation"):
-        from cfd_hemodynamic_amd.scenarios.simple_bifurcation import SimpleBifurcationSimulation as S
+        from cfd_hemodynamic_amd.scenarios.simple_bifurcation import MicrovasculatureSimulation as S
         return S(solver, 1e-4, 1.0, res=float(case[11:] or 2.5e-4), quiet=True, **kw)
     raise SystemExit("unknown case " + case)
 
@@ -66,12 +68,14 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-compare", action="store_true")
+    ap.add_argument("--solvers", default="ipcs_bdf2", help="pressure-correction plugins to time, comma separated (ipcs_bdf2, ipcs_midpoint)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ipcs_measure.json"))
     a = ap.parse_args()
     res = {}
     block = 5
     for case in a.cases.split(","):
-        sim = _scenario(case, "ipcs_bdf2")
+        sims = {name: _scenario(case, name) for name in a.solvers.split(",")}
+        sim = next(iter(sims.values()))
         V, Q = sim.solver.V, sim.solver.Q
         r = {"velocity_dofs": V.num_dofs, "pressure_dofs": Q.num_dofs, "unknowns": V.num_dofs + Q.num_dofs}
         ref, why = None, None
@@ -80,22 +84,25 @@ def main():
                 ref = _scenario(case, "stabilized_schur_backflow", p_grade=2)
             except Exception as exc:
                 why = "%s: %s" % (type(exc).__name__, exc)
-        rec, rec_ref = [], []
-        _steps(sim, a.warmup, [])
-        for _ in range(0, a.steps, block):  # alternate blocks of steps of the two solvers
-            _steps(sim, block, rec)
+        recs, rec_ref = {name: [] for name in sims}, []
+        for x in sims.values():
+            _steps(x, a.warmup, [])
+        for _ in range(0, a.steps, block):  # alternate blocks of steps of the solvers
+            for name, x in sims.items():
+                _steps(x, block, recs[name])
             if ref is not None:
                 try:
                     _steps(ref, a.warmup if not rec_ref else 0, [])
                     _steps(ref, block, rec_ref)
                 except Exception as exc:  # the P2/P2 path does not converge everywhere: report it
                     ref, why = None, "%s: %s" % (type(exc).__name__, exc)
-        r["ipcs_bdf2"] = _summary(rec, True)
+        for name, x in sims.items():
+            r[name] = dict(_summary(recs[name], True), a1_assemblies=int(x.solver.ctx.info(92)), steps=len(recs[name]) + a.warmup)
         if rec_ref:
             r["stabilized_schur_backflow_p2"] = dict(_summary(rec_ref, False), steps=len(rec_ref))
         if why:
             r.setdefault("stabilized_schur_backflow_p2", {})["failed"] = why
-        del sim, ref
+        del sim, sims, ref
         res[case] = r
         print(case, json.dumps(r), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
