@@ -1493,7 +1493,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     switch (what) {
       case 0: case 1: return I->nn;
       case 2: return I->nc;
-      case 3: return (int64_t)I->hM.col.size();
+      case 3: return (int64_t)I->op.col2.size();
       case 6: return (int64_t)I->hLam.lev.size();
       case 15: return I->last.host_syncs;
       case 18: return 1;
@@ -1570,7 +1570,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
   }
 }
 
-// ---- incremental pressure correction (cfdh_ipcs.hip) ----------------------------------------------------------------------
+// ---- incremental pressure correction (cfdh_ipcs.hip, cfdh_ipcs_krylov.hip, cfdh_ipcs_setup.cpp) ----------------------------------------------------------------------
 
 int cfdh_create_ipcs(cfdh_ctx **out, int device, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells, const double *node_coords,
                      int64_t nfacets, const int32_t *facet_cells, const int32_t *facet_local, const int32_t *facet_marker) {
@@ -1635,15 +1635,15 @@ int cfdh_ipcs_get_operator(cfdh_ctx *c, int which, int64_t *nnz, int32_t *rowptr
   if (!nnz || which < 0 || which >= 3 + 2 * D) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_operator: which in [0, %d)", 3 + 2 * D);
   if (which == 0 && I->scheme == CFDH_IPCS_MIDPOINT)
     return cfdh_fail(c, CFDH_E_STATE, "cfdh_ipcs_get_operator: A1 of the ipcs_midpoint scheme is a block matrix (cfdh_ipcs_get_block_operator)");
-  const std::vector<int> &ptr = which == 1 ? I->hL.rowptr : which < 3 ? I->hM.rowptr : which < 3 + D ? I->bptr : I->gptr;
-  const std::vector<int> &cl = which == 1 ? I->hL.col : which < 3 ? I->hM.col : which < 3 + D ? I->bcol : I->gcol;
+  const std::vector<int> &ptr = which == 1 ? I->op.ptr1 : which < 3 ? I->op.ptr2 : which < 3 + D ? I->op.bptr : I->op.gptr;
+  const std::vector<int> &cl = which == 1 ? I->op.col1 : which < 3 ? I->op.col2 : which < 3 + D ? I->op.bcol : I->op.gcol;
   *nnz = (int64_t)cl.size();
   if (!rowptr && !col && !vals) return 0;
   if (!rowptr || !col || !vals) return cfdh_fail(c, CFDH_E_ARG, "pass all of rowptr/col/vals or none");
   std::copy(ptr.begin(), ptr.end(), rowptr);
   std::copy(cl.begin(), cl.end(), col);
   if (which >= 3) {
-    const std::vector<double> &v = which < 3 + D ? I->hB : I->hG;
+    const std::vector<double> &v = which < 3 + D ? I->op.B : I->op.G;
     const int d = which < 3 + D ? which - 3 : which - 3 - D;
     for (size_t k = 0; k < cl.size(); k++) vals[k] = v[(size_t)D * k + d];
     return 0;
@@ -1673,13 +1673,13 @@ int cfdh_ipcs_get_block_operator(cfdh_ctx *c, int which, int64_t *nnz, int32_t *
   if (!nnz || which < 0 || which > 1) return cfdh_fail(c, CFDH_E_ARG, "cfdh_ipcs_get_block_operator: which in [0, 2)");
   if (I->scheme != CFDH_IPCS_MIDPOINT)
     return cfdh_fail(c, CFDH_E_STATE, "cfdh_ipcs_get_block_operator: the context runs the ipcs_bdf2 scheme (cfdh_ipcs_set_scheme)");
-  *nnz = (int64_t)I->hM.col.size();
+  *nnz = (int64_t)I->op.col2.size();
   if (!rowptr && !col && !vals) return 0;
   if (!rowptr || !col || !vals) return cfdh_fail(c, CFDH_E_ARG, "pass all of rowptr/col/vals or none");
-  std::copy(I->hM.rowptr.begin(), I->hM.rowptr.end(), rowptr);
-  std::copy(I->hM.col.begin(), I->hM.col.end(), col);
+  std::copy(I->op.ptr2.begin(), I->op.ptr2.end(), rowptr);
+  std::copy(I->op.col2.begin(), I->op.col2.end(), col);
   if (!I->assembled) CHK(cfdh_ipcs_assemble(c));
-  HIPCHK(c, hipMemcpyAsync(vals, which == 0 ? I->A1B.p : I->AfreeB.p, sizeof(double) * I->hM.col.size() * I->D * I->D, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(vals, which == 0 ? I->A1B.p : I->AfreeB.p, sizeof(double) * I->op.col2.size() * I->D * I->D, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -1,6 +1,16 @@
-// State of an incremental pressure-correction context (cfdh_create_ipcs; cfdh_ipcs.hip).  Node numbering is the caller's.
+// State of an incremental pressure-correction context (cfdh_create_ipcs) and the internals its three files share:
+// cfdh_ipcs_setup.cpp (creation, Dirichlet data, uploads of what cfdh_ipcs_host.hpp computes), cfdh_ipcs_krylov.hip (Krylov
+// kernels, drivers, ip_solve) and cfdh_ipcs.hip (assembly, right-hand sides, the step, functionals).  Node numbering is the caller's.
 #pragma once
 #include "cfdh_internal.hpp"
+#include "cfdh_ipcs_host.hpp"
+#include "cfdh_wave.hpp"
+
+using cfdh_ipcs_host::IpMid;
+using cfdh_ipcs_host::IpOps;
+using cfdh_ipcs_host::IpRef;
+
+#define IP_NB 2048  // most blocks (= partial sums per dot product) of the reducing kernels
 
 // scalars of the Krylov loops (device array of IP_NS doubles; [IP_RN2, IP_BAD] are mirrored into host-mapped memory); the indices
 // are part of cfdh_ipcs_krylov_solve's contract (include/cfdh.h)
@@ -9,13 +19,11 @@ static_assert(IP_NS == CFDH_IPCS_NSCAL, "include/cfdh.h documents the scalar blo
 
 struct IpcsData {
   int D = 2, NL = 6, nn = 0, nvert = 0, nc = 0;
-  // host mesh and constant operators (P2 pattern: hM.rowptr / hM.col, shared by K and A1; P1 pattern: hL.rowptr / hL.col)
+  // host mesh, reference tensors and constant operators (cfdh_ipcs_host.hpp; op.eptr / op.elist are dropped once uploaded)
   std::vector<int> cells, fcell, flocal, fmarker;
   std::vector<double> coords, geo;   // geo[cell] = (Jinv [D][D], |det|)
-  CsrHost hM, hL;                    // mass on the P2 nodes; unconstrained P1 stiffness
-  std::vector<double> hK, hMp, m1;   // P2 stiffness, P1 mass, int phi_i
-  std::vector<int> gptr, gcol, bptr, bcol;  // patterns [nn x nvert] (G_d, B_d^T) and [nvert x nn] (B_d)
-  std::vector<double> hG, hBT, hB;   // [nnz][D] interleaved
+  IpRef ref;
+  IpOps op;
   // device copies
   dbuf<int> d_cells, rp2, col2, eptr, elist, d_gptr, d_gcol, d_bptr, d_bcol, rp1, col1, d_fcell, d_flocal, d_fmarker;
   dbuf<double> d_coords, d_geo, d_T2, Mv, Kv, Gv, BTv, Bv, d_m1, Mpv, Lv, Afree, A1v, RMv, dinv1, dinv3, cw, fout;
@@ -46,7 +54,7 @@ struct IpcsData {
   bool snap_on = false, snap_set = false;
   double snap[IP_NS] = {};
   // ---- scheme `ipcs_midpoint` (cfdh_ipcs_set_scheme): vector-coupled momentum matrix, constant over the run.  Host: E - S as
-  // [nnz][D][D] blocks on the P2 pattern, Pn as [nnzG][D] on the gptr / gcol pattern (built once, cells and facets ascending);
+  // [nnz][D][D] blocks on the P2 pattern, Pn as [nnzG][D] on the gptr / gcol pattern (mid, built once, cells and facets ascending);
   // device: those, the block matrices A1_free / A1 and the Jacobi weights of the D nn diagonal, the cells of every node
   // (nptr / nlist: cell * NL + local node, ascending) for the matrix-free convection, the unconstrained L and the pressure
   // Dirichlet values / counts for the per-step lifting.
@@ -56,10 +64,39 @@ struct IpcsData {
   std::vector<unsigned char> mid_flag;  // constrained velocity nodes and their counts the block A1 was assembled for
   std::vector<double> mid_cnt;
   long long n_assemblies = 0;        // assemblies of A1 since creation (cfdh_info 92)
-  std::vector<double> hES, hPn;
+  IpMid mid;
   dbuf<int> nptr, nlist;
   dbuf<double> ESv, BTPv, AfreeB, A1B, dinvB, conv, Lfree, pval, pcnt;
 };
+
+// ---- internals shared by the three files
+#define IP(c) ((c)->ipcs)
+#define IPL(c, kern, grid, shm, ...)                                                  \
+  do {                                                                                \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(TPB), shm, (c)->stream, __VA_ARGS__);   \
+    IP(c)->n_launch++;                                                                \
+  } while (0)
+static inline int ip_sync(cfdh_ctx *c) {
+  IP(c)->n_sync++;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+static inline int ip_grid8(int nrows) { return (int)((8ll * nrows + TPB - 1) / TPB); }
+static inline int ip_nb(long long n, int per) {  // blocks of a reducing grid-stride kernel
+  long long g = (n + per - 1) / per;
+  return (int)(g < 1 ? 1 : (g > IP_NB ? IP_NB : g));
+}
+struct IpMat { int n; const int *rp, *col; const double *val; };
+struct IpTol { double rtol, atol; int max_it; };
+
+int ip_prepare(cfdh_ctx *c);        // uploads whatever host data changed: Dirichlet data, the pressure hierarchy, rho M (setup)
+int ip_assemble_bdf2(cfdh_ctx *c);  // A1 and b1 of ipcs_bdf2 at the current state (cfdh_ipcs.hip)
+int ip_mid_matrix(cfdh_ctx *c);     // the block A1 of ipcs_midpoint, if it is out of date (cfdh_ipcs.hip)
+int ip_sub_mean(cfdh_ctx *c, int n, double *x);
+// The one place that knows which solve uses what: solve `which` (0 tentative velocity, 1 pressure, 2 velocity update) of the
+// current scheme on the caller's b and x (x holds the initial guess).  Instantiated for D = 2, 3 in cfdh_ipcs_krylov.hip.
+template <int D>
+int ip_solve(cfdh_ctx *c, int which, IpTol tol, const double *b, double *x, cfdh_ipcs_stats *st);
 
 int cfdh_ipcs_create(cfdh_ctx *c, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells, const double *coords, int64_t nfac,
                      const int32_t *fcell, const int32_t *flocal, const int32_t *fmarker);

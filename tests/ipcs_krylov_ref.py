@@ -1,4 +1,4 @@
-"""Trajectory versions of the three Krylov recurrences of csrc/cfdh_ipcs.hip, written in the order the drivers and the stage
+"""Trajectory versions of the three Krylov recurrences of csrc/cfdh_ipcs_krylov.hip, written in the order the drivers and the stage
 table of ip_scal_kernel take them, in np.longdouble (or any `dtype`): the references of tests/test_gpu_ipcs_krylov.py.
 
 Each function runs `nit` iterations of ONE cycle from the true residual r_0 = b - A x_0 -- no convergence test, no restart --
@@ -39,7 +39,7 @@ def _tools(A, b, x0, pre, dtype, perm):
     else:
         dot = lambda a, c: np.sum((a * c).ravel()[perm], dtype=dtype)
     if pre is None:
-        pre = 1.0 / M.diag                      # float64, as cfdh_ipcs.hip forms dinv
+        pre = 1.0 / M.diag                      # float64, as the device (dinv1, dinvB) and cfdh_ipcs_host.hpp (dinv3) form dinv
     if not callable(pre):
         w = np.asarray(pre, dtype=np.float64).astype(dtype)
         w = w[:, None] if b.ndim == 2 else w

@@ -1,4 +1,4 @@
-"""GPU tests of the incremental pressure-correction solver (csrc/cfdh_ipcs.hip, the `ipcs_bdf2` plugin) against its NumPy/SciPy
+"""GPU tests of the incremental pressure-correction solver (csrc/cfdh_ipcs*, the `ipcs_bdf2` plugin) against its NumPy/SciPy
 twin (tests/ipcs_twin.py): operator parity, bitwise reproducibility, steps against direct solves, the symmetry of the pressure
 preconditioner, Taylor-Green and DFG 2D-1 through the Scenario loop, iteration counts and wrong-context calls."""
 import ctypes

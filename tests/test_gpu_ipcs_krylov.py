@@ -1,4 +1,4 @@
-"""The three Krylov drivers of the pressure-correction step (csrc/cfdh_ipcs.hip: ip_bicgstab, ip_cg<1, false>, ip_cg<D, true>),
+"""The three Krylov drivers of the pressure-correction step (csrc/cfdh_ipcs_krylov.hip: ip_bicgstab, ip_cg<1, false>, ip_cg<D, true>),
 iterate by iterate, through cfdh_ipcs_krylov_solve: the device's x_k and recurrence scalars after k = 1 .. 10 iterations against
 the extended-precision recurrences of tests/ipcs_krylov_ref.py on the device's own matrices (get_operator), the reported
 residual against the residual of the returned vector, convergence in the middle of a batch of launches, the edges of

@@ -1,4 +1,4 @@
-"""GPU tests of the `ipcs_midpoint` scheme (cfdh_ipcs_set_scheme; csrc/cfdh_ipcs.hip; the `ipcs_midpoint` plugin) against its
+"""GPU tests of the `ipcs_midpoint` scheme (cfdh_ipcs_set_scheme; csrc/cfdh_ipcs*; the `ipcs_midpoint` plugin) against its
 NumPy/SciPy twin (tests/ipcs_mid_twin.py), piece by piece: the block operators and the right-hand sides, the Poiseuille residual,
 steps against direct solves, the BiCGStab driver on the block matrix, the assembly count and its invalidation, error codes, and
 the plugin through the Scenario loop and the command line.  Shapes and helpers are those of tests/test_gpu_ipcs.py."""

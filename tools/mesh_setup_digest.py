@@ -6,7 +6,8 @@ host code: numbering, graph and staging order decide the summation order of the 
     python tools/mesh_setup_digest.py --out old.txt --lib ../old-checkout/cfd_hemodynamic_amd/libcfdh.so && cmp old.txt new.txt
 
 One small context of every family: closed-form P1 in 2-D / 3-D (also with CFDH_NO_RENUMBER=1), generic P1 / P2 / Q1 in 2-D / 3-D,
-IPCS in 2-D / 3-D, and one part of a 2-part split (two cell layers) of a closed-form mesh and of a P2 tetrahedral mesh.  Per context:
+IPCS in 2-D / 3-D with either scheme (ipcs_bdf2; ipcs_midpoint with a pressure Dirichlet object and its block operators), and one
+part of a 2-part split (two cell layers) of a closed-form mesh and of a P2 tetrahedral mesh.  Per context (IPCS: the operators):
 Jacobian structure and values, residual, and -- whole meshes -- solution and iteration counts of two time steps; then the
 functionals of kinds 2 to 7 (bit patterns) and cfdh_info 76.  The info counters 13 to 17 of every context go to stdout, not
 into the file: they count collectives and read-backs, which two builds may do differently while computing the same numbers.
@@ -101,7 +102,7 @@ def main():
         scalars(case, ctx)
         ctx.close()
 
-    def ipcs_context(case, m, nm):
+    def ipcs_context(case, m, nm, midpoint=False):
         d = m.x.shape[1]
         nn, nvert = len(nm.x), m.num_vertices
         rng = np.random.default_rng(19)
@@ -111,6 +112,10 @@ def main():
         vals = np.zeros((len(bnd), d))
         vals[:, 0], vals[:, 1] = 0.1 * nm.x[bnd, 1], -0.1 * nm.x[bnd, 0]
         ctx.add_dirichlet(0, bnd, vals)
+        if midpoint:  # the block matrix, and a pressure value on the vertices of the side x = min: lifting formed on the device
+            ctx.set_scheme(_lib.IPCS_MIDPOINT)
+            side = np.nonzero(m.x[:, 0] == m.x[:, 0].min())[0].astype(np.int32)
+            ctx.add_dirichlet(1, side, np.full(len(side), 0.02))
         u = 0.05 * rng.standard_normal(d * nn)
         ctx.set_state(u_prev=u, p_prev=np.zeros(nvert), u=u, p=np.zeros(nvert))
         ctx.set_previous2(u)
@@ -121,7 +126,12 @@ def main():
             except RuntimeError as e:
                 lines.append("%s step%d %s" % (case, k, str(e).split("(")[0].strip()))
             put(case, "step%d-solution" % k, *ctx.get_solution())
-        for which in range(3 + 2 * d):
+            if midpoint:  # the second step starts from the first one's fields: its lifting sees p_prev != 0
+                ctx.advance()
+        for which in range(2) if midpoint else ():
+            A = ctx.get_block_operator(which)
+            put(case, "block-operator%d" % which, A.indptr, A.indices, A.data)
+        for which in range(1 if midpoint else 0, 3 + 2 * d):  # A1 of ipcs_midpoint is the block matrix above
             A = ctx.get_operator(which)
             put(case, "operator%d" % which, A.indptr, A.indices, A.data)
         scalars(case, ctx)
@@ -164,6 +174,8 @@ def main():
         fgmres_context("gen-3d-" + kind, node_mesh3(kind, 3 if kind == "P2" else 4, 0.05), LIB_ETYPE3[kind])
     ipcs_context("ipcs-2d", tri, NodeMesh(tri))
     ipcs_context("ipcs-3d", tet, NodeMesh3D(tet))
+    ipcs_context("ipcs-mid-2d", tri, NodeMesh(tri), midpoint=True)
+    ipcs_context("ipcs-mid-3d", tet, NodeMesh3D(tet), midpoint=True)
     for case, m, etype in (("part-closed-2d", tri, 0), ("part-closed-3d", tet, 0), ("part-gen-3d-P2", node_mesh3("P2", 3, 0.05), 1)):
         lp = part(m, 1)
         pm = types.SimpleNamespace(x=lp.x, cells=lp.cells, facet_cells=lp.facet_cells, facet_local=lp.facet_local)
