@@ -55,7 +55,7 @@ SYMBOLS = [
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
-    "cfdh_get_amg_operator", "cfdh_get_amg_vectors", "cfdh_krylov_vec_op",
+    "cfdh_get_amg_operator", "cfdh_get_amg_vectors", "cfdh_get_amg_head", "cfdh_krylov_vec_op",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
     "cfdh_ipcs_apply_pressure_pc", "cfdh_ipcs_krylov_solve", "cfdh_ipcs_set_scheme", "cfdh_ipcs_get_block_operator",
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
@@ -139,6 +139,7 @@ def lib():
     L.cfdh_apply_operator.argtypes = [vp, dp, dp, dp]
     L.cfdh_get_amg_operator.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, lp, lp, ip, ip, dp]
     L.cfdh_get_amg_vectors.argtypes = [vp, C.c_int, C.c_int, C.c_int, lp, dp]
+    L.cfdh_get_amg_head.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
     L.cfdh_krylov_vec_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int, dp, dp,
                                      C.POINTER(C.c_float), ip, dp, dp, dp]
     L.cfdh_create_ipcs.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, ip, dp, C.c_int64, ip, ip, ip]
@@ -558,6 +559,12 @@ class Context:
         if raw:
             return rowptr, col, val, (nr.value, nc.value), nnz.value
         return sp.csr_matrix((val, col, rowptr), shape=(nr.value, nc.value))
+
+    def get_amg_head(self, hier, level, which):
+        """Width of the head copy of one SELL-64 operator (AMG_HIER_*, AMG_OP_SB / _SC, AMG_OP_A of AMG_HIER_H); 0: it has none."""
+        w = C.c_int32()
+        self._chk(self.L.cfdh_get_amg_head(self.h, int(hier), int(level), int(which), C.byref(w)))
+        return w.value
 
     def get_amg_vectors(self, hier, level, which):
         """Vectors / scalars of a built hierarchy as float64 (AMG_VEC_*)."""

@@ -11,7 +11,8 @@
 //
 // SELL-64 or CSR: the size rules are cfdh_sweep_sell / cfdh_cheb2_sell (cfdh_internal.hpp); a kernel gets the SELL arrays only
 // when the rule says so AND the operator has them (CsrDev::has_sell*), CSR otherwise.  AmgLevel::fine / sell of the fused
-// cycle are set by the builds together with the copies they select.
+// cycle are set by the builds together with the copies they select.  Where the SELL-64 operators of an up-sweep (or H's Chebyshev
+// matrix) have head copies (CsrDev::head_w > 0), the sweep takes the head kernel, which needs no pointer for the head's entries.
 //
 // HBM-bound gather work, fixed summation order everywhere (bitwise reproducible).
 #include <hip/hip_runtime.h>
@@ -67,6 +68,49 @@ __device__ __forceinline__ T sell_row_dot(const int *__restrict__ sp, const int 
 #pragma unroll
   for (int k = 0; k < MAXW; k++)
     if (k < w) a = vfma((double)cval[k], g[k], a);
+  for (int k = MAXW; k < w; k++) { const int p = p0 + k * 64 + lane; a = vfma((double)sv[p], x[sc[p]], a); }
+  return a;
+}
+
+// ---- head copies of SELL-64 operators (CsrDev::hcol / hvalf / hlen): the pointer trip taken out of that chain.  The first head_w
+// entries of a slice sit at an address computed from the slice index, so columns and values are requested at once, together with the
+// width and the pointer; only the tail of a wider slice waits for the pointer.  Same entries, same lane -> entry mapping, same
+// guards k < width, same order of additions as the pointer kernels: bit-identical results (tests/test_gpu_amg_head.py).
+__device__ __forceinline__ int head_slice_len(const unsigned short *__restrict__ hlen, int sl) {
+  const unsigned wd = ((const unsigned *)hlen)[sl >> 1];  // sl is wave-uniform: one scalar load
+  return (int)((wd >> ((sl & 1) * 16)) & 0xffffu);
+}
+// sell_row_dot through the head (wh <= MAXW entries per row)
+template <int MAXW, typename T>
+__device__ __forceinline__ T sell_row_dot_head(const int *__restrict__ sp, const int *__restrict__ sc, const float *__restrict__ sv,
+                                               const int *__restrict__ hc, const float *__restrict__ hv,
+                                               const unsigned short *__restrict__ hlen, int wh, const T *__restrict__ x, int sl, int lane, T a) {
+  static_assert(MAXW <= 10, "ten named entries");
+  sl = __builtin_amdgcn_readfirstlane(sl);
+  // named scalars, not arrays: an entry is written in one of two places (head or tail), and the compiler keeps such an array as
+  // ONE register tuple that it copies -- and therefore waits for -- after the first load
+#define RDH_ALL(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
+#define RDH_DECL(k) int c##k = 0; float v##k = 0.0f;
+#define RDH_HEAD(k) if (k < MAXW && k < wh) { c##k = NTLOAD(hc + h0 + k * 64); v##k = NTLOAD(hv + h0 + k * 64); }
+#define RDH_TAIL(k) if (k < MAXW && k >= wh && k < w) { const int p = p0 + k * 64 + lane; c##k = NTLOAD(sc + p); v##k = NTLOAD(sv + p); }
+#define RDH_DECL_G(k) T g##k = vzero((const T *)nullptr);
+#define RDH_GATHER(k) if (k < MAXW && k < w) g##k = x[c##k];
+#define RDH_FMA(k) if (k < MAXW && k < w) a = vfma((double)v##k, g##k, a);
+  RDH_ALL(RDH_DECL)
+  const size_t h0 = (size_t)sl * wh * 64 + lane;
+  RDH_ALL(RDH_HEAD)
+  const int w = head_slice_len(hlen, sl), p0 = sp[sl];
+  RDH_ALL(RDH_TAIL)
+  RDH_ALL(RDH_DECL_G)
+  RDH_ALL(RDH_GATHER)
+  RDH_ALL(RDH_FMA)
+#undef RDH_ALL
+#undef RDH_DECL
+#undef RDH_HEAD
+#undef RDH_TAIL
+#undef RDH_DECL_G
+#undef RDH_GATHER
+#undef RDH_FMA
   for (int k = MAXW; k < w; k++) { const int p = p0 + k * 64 + lane; a = vfma((double)sv[p], x[sc[p]], a); }
   return a;
 }
@@ -213,17 +257,20 @@ int k_level_smooth(cfdh_ctx *c, AmgLevel *L, const double *b, double *x, int deg
 // Two Chebyshev steps from a zero guess on a SELL-64 level in ONE pass over the matrix, with the
 // Cahouet-Chabard scaling fused:  d = w D^-1 b ; r = b - A d ; x = d + (c1 d + c2 D^-1 r) ; y = ml .* x.
 // (svalw carries the column weights w D^-1, as in the Jacobi pre-sweep.)
+// HEAD: the matrix through its head copy (hcol, hval, hlen, wh: CsrDev::hcol ...)
+template <bool HEAD>
 __global__ __launch_bounds__(TPB) void sell_cheb2_scale_kernel(int n, const int *__restrict__ sptr, const int *__restrict__ scol,
-                                                               const float *__restrict__ svalw, const double *__restrict__ wdinv,
+                                                               const float *__restrict__ svalw, const int *__restrict__ hcol,
+                                                               const float *__restrict__ hval, const unsigned short *__restrict__ hlen, int wh,
+                                                               const double *__restrict__ wdinv,
                                                                const double *__restrict__ dinv, const double *__restrict__ b,
                                                                double *__restrict__ x, const double *__restrict__ ml,
                                                                double *__restrict__ y, double c1, double c2) {
   const int row = blockIdx.x * TPB + threadIdx.x;
   if (row >= n) return;
   const int sl = row >> 6, lane = row & 63;
-  const int p0 = sptr[sl], w = (sptr[sl + 1] - p0) >> 6;
-  (void)p0; (void)w;
-  const double a = sell_row_dot<10, double>(sptr, scol, svalw, b, sl, lane, 0.0);
+  const double a = HEAD ? sell_row_dot_head<10, double>(sptr, scol, svalw, hcol, hval, hlen, wh, b, sl, lane, 0.0)
+                        : sell_row_dot<10, double>(sptr, scol, svalw, b, sl, lane, 0.0);
   const double bi = b[row];
   const double dd = wdinv[row] * bi;
   const double xv = dd + (c1 * dd + c2 * dinv[row] * (bi - a));
@@ -237,8 +284,13 @@ bool k_cc_cheb2_scale(cfdh_ctx *c, AmgLevel *L, const double *b, double *x, cons
   const double theta = 0.5 * (L->lmax + L->lmin), delta = 0.5 * (L->lmax - L->lmin), sigma = theta / delta;
   const double rho = 1.0 / sigma, rho_new = 1.0 / (2.0 * sigma - rho);
   const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-  hipLaunchKernelGGL(sell_cheb2_scale_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, L->A.sptr.p, L->A.scol.p,
-                     L->A.svalw.p, L->wdinv.p, L->dinv.p, b, x, ml, y, c1, c2);
+  const CsrDev &A = L->A;
+  if (A.head_w > 0)
+    hipLaunchKernelGGL(sell_cheb2_scale_kernel<true>, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, A.sptr.p, A.scol.p, A.svalw.p,
+                       A.hcol.p, A.hvalf.p, A.hlen.p, A.head_w, L->wdinv.p, L->dinv.p, b, x, ml, y, c1, c2);
+  else
+    hipLaunchKernelGGL(sell_cheb2_scale_kernel<false>, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, c->stream, n, A.sptr.p, A.scol.p, A.svalw.p,
+                       (const int *)nullptr, (const float *)nullptr, (const unsigned short *)nullptr, 0, L->wdinv.p, L->dinv.p, b, x, ml, y, c1, c2);
   return hipGetLastError() == hipSuccess;
 }
 
@@ -448,16 +500,21 @@ __global__ __launch_bounds__(TPB) void fused_down_kernel(int n, const int *__res
   T a = vzero((const T *)nullptr);
   if (row < n) {
     const int ks = rowptr[row], ke = rowptr[row + 1];
-    // up to four entries per lane with all loads in flight together, then the gathers (see sell_row_dot)
-    int cidx[4];
-    VT cval[4];
+    // up to four entries per lane with all loads in flight together, then the gathers (see sell_row_dot).  The loads are
+    // unconditional, a lane past the end of its row re-reading the row's last entry (the same cache line as its neighbours'), and
+    // only the sums are guarded: with the loads under k < ke the compiler kept cidx / cval as register tuples, copied them after
+    // the first pair of loads and so waited for that pair before it requested the other three -- a fourth dependent round trip.
+    if (ks < ke) {
+      int cidx[4];
+      VT cval[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) { const int k = ks + l + q * LPR; if (k < ke) { cidx[q] = col[k]; cval[q] = val[k]; } }
-    T g[4];
+      for (int q = 0; q < 4; q++) { const int k = min(ks + l + q * LPR, ke - 1); cidx[q] = col[k]; cval[q] = val[k]; }
+      T g[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) { const int k = ks + l + q * LPR; if (k < ke) g[q] = x[cidx[q]]; }
+      for (int q = 0; q < 4; q++) g[q] = x[cidx[q]];
 #pragma unroll
-    for (int q = 0; q < 4; q++) { const int k = ks + l + q * LPR; if (k < ke) a = vfma((double)cval[q], g[q], a); }
+      for (int q = 0; q < 4; q++) { const T t = vfma((double)cval[q], g[q], a); if (ks + l + q * LPR < ke) a = t; }
+    }
     for (int k = ks + l + 4 * LPR; k < ke; k += LPR) a = vfma((double)val[k], x[col[k]], a);
   }
   a = lsum<LPR>(a);
@@ -551,6 +608,95 @@ __global__ __launch_bounds__(TPB) void fused_up_sell_kernel(int n, const int *__
   }
   x[row] = epbc ? epi_value(a, e_f, ea, eb, e_zh, e_r) : a;
 }
+// The same through the head copies of Sb and Sc (whB, whC <= MW entries per row; whC = 0 and spC = nullptr: no Sc).  The first chunk
+// is requested from the slice index alone; the operands of the epilogue are requested behind it, so that nothing stands between
+// the kernel's entry and the matrix stream.  Chunks beyond the first (WIDE) and rows beyond the chunk go through the pointers.
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(TPB) void fused_up_sell_head_kernel(int n, const int *__restrict__ spB, const int *__restrict__ scB,
+                                                                 const float *__restrict__ svB, const int *__restrict__ hcB,
+                                                                 const float *__restrict__ hvB, const unsigned short *__restrict__ hlB, int whB,
+                                                                 const T *__restrict__ b, const int *__restrict__ spC,
+                                                                 const int *__restrict__ scC, const float *__restrict__ svC,
+                                                                 const int *__restrict__ hcC, const float *__restrict__ hvC,
+                                                                 const unsigned short *__restrict__ hlC, int whC, const T *__restrict__ xc,
+                                                                 T *__restrict__ x, double ea, double eb, const double *__restrict__ ezH,
+                                                                 const double *__restrict__ er, const unsigned char *__restrict__ epbc) {
+  const int row = blockIdx.x * TPB + threadIdx.x;
+  if (row >= n) return;
+  const int sl = __builtin_amdgcn_readfirstlane(row >> 6), lane = row & 63;
+  T a = vzero((const T *)nullptr);
+  constexpr int MW = sizeof(T) > 8 ? 8 : 10;
+  // The first chunk lives in named scalars, not arrays: an entry is written in one of two places (head or tail), and the
+  // compiler keeps such an array as ONE register tuple that it copies -- and therefore waits for -- after the first load.
+#define UPH_ALL(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
+#define UPH_DECL(k) int cB##k = 0, cC##k = 0; float vB##k = 0.0f, vC##k = 0.0f;
+#define UPH_HEAD_B(k) if (k < MW && k < whB) { cB##k = NTLOAD(hcB + hB0 + k * 64); vB##k = NTLOAD(hvB + hB0 + k * 64); }
+#define UPH_HEAD_C(k) if (k < MW && k < whC) { cC##k = NTLOAD(hcC + hC0 + k * 64); vC##k = NTLOAD(hvC + hC0 + k * 64); }
+#define UPH_TAIL_B(k) if (k < MW && k >= whB && k < wB) { const int p = pB + k * 64 + lane; cB##k = NTLOAD(scB + p); vB##k = NTLOAD(svB + p); }
+#define UPH_TAIL_C(k) if (k < MW && k >= whC && k < wC) { const int p = pC + k * 64 + lane; cC##k = NTLOAD(scC + p); vC##k = NTLOAD(svC + p); }
+#define UPH_DECL_G(k) T gB##k = vzero((const T *)nullptr), gC##k = vzero((const T *)nullptr);
+#define UPH_GATHER_B(k) if (k < MW && k < wB) gB##k = b[cB##k];
+#define UPH_GATHER_C(k) if (k < MW && k < wC) gC##k = xc[cC##k];
+#define UPH_FMA_B(k) if (k < MW && k < wB) a = vfma((double)vB##k, gB##k, a);
+#define UPH_FMA_C(k) if (k < MW && k < wC) a = vfma((double)vC##k, gC##k, a);
+  UPH_ALL(UPH_DECL)
+  const size_t hB0 = (size_t)sl * whB * 64 + lane, hC0 = (size_t)sl * whC * 64 + lane;
+  UPH_ALL(UPH_HEAD_B)
+  UPH_ALL(UPH_HEAD_C)
+  // lengths and pointers: scalar loads, in flight together with the head (and before the epilogue's operands, whose flag the
+  // compiler waits for where it is requested)
+  const int wB = head_slice_len(hlB, sl), pB = spB[sl];
+  int pC = 0, wC = 0;
+  if (spC) { wC = head_slice_len(hlC, sl); pC = spC[sl]; }
+  double e_zh = 0.0, e_r = 0.0;
+  unsigned e_f = 0;
+  if (epbc) { e_f = epbc[row]; e_zh = ezH[row]; e_r = er[row]; }
+  // the tail inside the first chunk (slices wider than the head)
+  UPH_ALL(UPH_TAIL_B)
+  UPH_ALL(UPH_TAIL_C)
+  {
+    UPH_ALL(UPH_DECL_G)
+    UPH_ALL(UPH_GATHER_B)
+    UPH_ALL(UPH_GATHER_C)
+    UPH_ALL(UPH_FMA_B)
+    UPH_ALL(UPH_FMA_C)
+  }
+#undef UPH_ALL
+#undef UPH_DECL
+#undef UPH_HEAD_B
+#undef UPH_HEAD_C
+#undef UPH_TAIL_B
+#undef UPH_TAIL_C
+#undef UPH_DECL_G
+#undef UPH_GATHER_B
+#undef UPH_GATHER_C
+#undef UPH_FMA_B
+#undef UPH_FMA_C
+  if (WIDE) {
+    const int wmax = wB > wC ? wB : wC;
+    int cB[MW], cC[MW];
+    float vB[MW], vC[MW];
+    for (int k0 = MW; k0 < wmax; k0 += MW) {
+#pragma unroll
+      for (int k = 0; k < MW; k++) if (k0 + k < wB) { const int p = pB + (k0 + k) * 64 + lane; cB[k] = NTLOAD(scB + p); vB[k] = NTLOAD(svB + p); }
+#pragma unroll
+      for (int k = 0; k < MW; k++) if (k0 + k < wC) { const int p = pC + (k0 + k) * 64 + lane; cC[k] = NTLOAD(scC + p); vC[k] = NTLOAD(svC + p); }
+      T gB[MW], gC[MW];
+#pragma unroll
+      for (int k = 0; k < MW; k++) if (k0 + k < wB) gB[k] = b[cB[k]];
+#pragma unroll
+      for (int k = 0; k < MW; k++) if (k0 + k < wC) gC[k] = xc[cC[k]];
+#pragma unroll
+      for (int k = 0; k < MW; k++) if (k0 + k < wB) a = vfma((double)vB[k], gB[k], a);
+#pragma unroll
+      for (int k = 0; k < MW; k++) if (k0 + k < wC) a = vfma((double)vC[k], gC[k], a);
+    }
+  } else {
+    for (int k = MW; k < wB; k++) { const int p = pB + k * 64 + lane; a = vfma((double)svB[p], b[scB[p]], a); }
+    for (int k = MW; k < wC; k++) { const int p = pC + k * 64 + lane; a = vfma((double)svC[p], xc[scC[p]], a); }
+  }
+  x[row] = epbc ? epi_value(a, e_f, ea, eb, e_zh, e_r) : a;
+}
 // x = Sb b + D bc with the dense folded coarse correction D [n][nc] (fp32), one wave per row
 template <typename T>
 __global__ __launch_bounds__(TPB) void fused_up_dense_kernel(int n, const int *__restrict__ rpB, const int *__restrict__ clB,
@@ -576,10 +722,28 @@ __global__ __launch_bounds__(TPB) void fused_up_dense_kernel(int n, const int *_
   if (row < n && l == 0) x[row] = a;
 }
 
+// x = Sb b (+ Sc xc) on nrow rows over SELL-64: through the head copies when every operator involved has one, the pointers otherwise
+template <typename T, bool WIDE>
+static void launch_up_sell(cfdh_ctx *c, int nrow, const CsrDev &Sb, const T *b, const CsrDev *Sc, const T *xc, T *x, double ea, double eb,
+                           const double *ezH, const double *er, const unsigned char *epbc) {
+  constexpr int MW = sizeof(T) > 8 ? 8 : 10;
+  const dim3 grid((unsigned)((nrow + TPB - 1) / TPB)), block(TPB);
+  const int *spC = Sc ? Sc->sptr.p : nullptr, *scC = Sc ? Sc->scol.p : nullptr;
+  const float *svC = Sc ? Sc->sval.p : nullptr;
+  const auto has_head = [](const CsrDev &M) { return M.head_w > 0 && M.head_w <= MW; };
+  if (has_head(Sb) && (!Sc || has_head(*Sc)))
+    hipLaunchKernelGGL((fused_up_sell_head_kernel<T, WIDE>), grid, block, 0, c->stream, nrow, Sb.sptr.p, Sb.scol.p, Sb.sval.p, Sb.hcol.p,
+                       Sb.hvalf.p, Sb.hlen.p, Sb.head_w, b, spC, scC, svC, Sc ? Sc->hcol.p : (const int *)nullptr,
+                       Sc ? Sc->hvalf.p : (const float *)nullptr, Sc ? Sc->hlen.p : (const unsigned short *)nullptr, Sc ? Sc->head_w : 0, xc,
+                       x, ea, eb, ezH, er, epbc);
+  else
+    hipLaunchKernelGGL((fused_up_sell_kernel<T, WIDE>), grid, block, 0, c->stream, nrow, Sb.sptr.p, Sb.scol.p, Sb.sval.p, b, spC, scC, svC, xc,
+                       x, ea, eb, ezH, er, epbc);
+}
+
 template <typename VT, typename T>
 static void launch_down(cfdh_ctx *c, const CsrDev &G, const VT *val, const T *x, T *y) {
-  const long long avg = G.n > 0 ? (G.nnz + G.n - 1) / G.n : 1;
-  const int lpr = avg > 96 ? 64 : (avg > 48 ? 32 : (avg > 20 ? 16 : 8));  // 2-4 entries per lane, loaded together
+  const int lpr = cfdh_down_lpr(G);  // 2-4 entries per lane, loaded together
   dim3 block(TPB), grid((unsigned)(((long long)G.n * lpr + TPB - 1) / TPB));
   if (lpr == 64) hipLaunchKernelGGL((fused_down_kernel<64, VT, T>), grid, block, 0, c->stream, G.n, G.rowptr.p, G.col.p, val, x, y);
   else if (lpr == 32) hipLaunchKernelGGL((fused_down_kernel<32, VT, T>), grid, block, 0, c->stream, G.n, G.rowptr.p, G.col.p, val, x, y);
@@ -622,10 +786,7 @@ static int amg_cycle_fused(cfdh_ctx *c, AmgHier &H, const T *b, T *x, int prof, 
       if (H.coarse_n > 0)
         hipLaunchKernelGGL((dense_mv_kernel<T>), dim3(H.coarse_n), dim3(64), 0, c->stream, H.coarse_n, H.coarse_inv.p, bl, xl);
       else if (L->sell)
-        hipLaunchKernelGGL((fused_up_sell_kernel<T, true>), dim3((unsigned)((L->n + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, L->n,
-                           L->Sb.sptr.p, L->Sb.scol.p, L->Sb.sval.p, bl, (const int *)nullptr, (const int *)nullptr,
-                           (const float *)nullptr, (const T *)nullptr, xl, 0.0, 0.0, (const double *)nullptr, (const double *)nullptr,
-                           (const unsigned char *)nullptr);
+        launch_up_sell<T, true>(c, L->n, L->Sb, bl, nullptr, (const T *)nullptr, xl, 0.0, 0.0, nullptr, nullptr, nullptr);
       else
         hipLaunchKernelGGL((fused_up_csr_kernel<T>), dim3((unsigned)((8ll * L->n + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, L->n,
                            L->Sb.rowptr.p, L->Sb.col.p, L->Sb.val.p, bl, (const int *)nullptr, (const int *)nullptr,
@@ -651,13 +812,9 @@ static int amg_cycle_fused(cfdh_ctx *c, AmgHier &H, const T *b, T *x, int prof, 
     // a few longer rows (irregular vertices of a triangle mesh) go through the tail loop of the one-chunk kernel; the chunked
     // kernel is for meshes whose typical row exceeds a chunk (tetrahedra)
     if (L->sell && L->Sb.sell_maxw <= 14 && L->Sc.sell_maxw <= 14)
-      hipLaunchKernelGGL((fused_up_sell_kernel<T, false>), dim3((unsigned)((nrow + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, nrow,
-                         L->Sb.sptr.p, L->Sb.scol.p, L->Sb.sval.p, bl, L->Sc.sptr.p, L->Sc.scol.p, L->Sc.sval.p, (const T *)N->x.p, xl,
-                         ea, eb, ezH, er, epbc);
+      launch_up_sell<T, false>(c, nrow, L->Sb, bl, &L->Sc, (const T *)N->x.p, xl, ea, eb, ezH, er, epbc);
     else if (L->sell)
-      hipLaunchKernelGGL((fused_up_sell_kernel<T, true>), dim3((unsigned)((nrow + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, nrow,
-                         L->Sb.sptr.p, L->Sb.scol.p, L->Sb.sval.p, bl, L->Sc.sptr.p, L->Sc.scol.p, L->Sc.sval.p, (const T *)N->x.p, xl,
-                         ea, eb, ezH, er, epbc);
+      launch_up_sell<T, true>(c, nrow, L->Sb, bl, &L->Sc, (const T *)N->x.p, xl, ea, eb, ezH, er, epbc);
     else
       hipLaunchKernelGGL((fused_up_csr_kernel<T>), dim3((unsigned)((8ll * nrow + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, nrow,
                          L->Sb.rowptr.p, L->Sb.col.p, L->Sb.val.p, bl, L->Sc.rowptr.p, L->Sc.col.p, L->Sc.val.p, (const T *)N->x.p, xl,

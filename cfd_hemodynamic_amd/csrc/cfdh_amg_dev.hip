@@ -865,6 +865,7 @@ struct Builder {
 
   // fp32 CSR copy / SELL-64 of a finished operator
   int formats(CsrDev &M, int parts, const double *colw = nullptr) {
+    M.drop_head();
     if (parts & CFDH_UP_CSRF) {
       HIPCHK(c, M.valf.alloc((size_t)std::max(M.nnz, 1)));
       if (M.nnz > 0) hipLaunchKernelGGL(to_float_kernel, dim3((M.nnz + TPB - 1) / TPB), dim3(TPB), 0, s, M.nnz, M.val.p, M.valf.p);
@@ -1267,6 +1268,7 @@ int cfdh_amg_setup_dev(cfdh_ctx *c, AmgHier &H, CsrDev &A0, bool singular, int n
   }
   H.valid = true;
   HIPCHK(c, hipStreamSynchronize(s));
+  CHK(cfdh_amg_heads(c, H));
   if (c->opt.verbose) {
     fprintf(stderr, "[cfdh] AMG hierarchy built on the device in %.1f ms (ncol %d%s):", now_ms() - t_begin, ncol, H.fused ? ", fused" : "");
     for (AmgLevel *l : H.lev) fprintf(stderr, " (%d, nnz %d; G %d Sb %d Sc %d D %d)", l->n, l->A.nnz, l->G.nnz, l->Sb.nnz, l->Sc.nnz, l->Dn);
@@ -1286,6 +1288,87 @@ int cfdh_level_setup_dev(cfdh_ctx *c, AmgLevel &L, CsrDev &A, double ratio, int 
   CHK(B.work_vectors(L, ncol));
   move_csr(L.A, A);
   CHK(B.formats(L.A, CFDH_UP_SELL, L.wdinv.p));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return cfdh_level_head(c, L);
+}
+
+// ---- head copies of the SELL-64 sweep operators (CsrDev::hcol / hvalf / hlen).  Written from the finished
+// device arrays, so the host build and the device build share them.  Width: the widest head whose padding (head slots beyond the
+// slice's width, which a sweep requests before it knows the width) stays within 1/8 of the operator's entries and which 7/8 of
+// the slices fit into (head_width_by_rule); CFDH_AMG_HEAD_W forces it.  CSR operators (G, Sb / Sc of the coarse levels) get none:
+// their rows spread too widely for the rule, and their head kernels measured slower even with every row inside the head.
+namespace {
+template <typename VT>
+__global__ __launch_bounds__(TPB) void head_sell_fill_kernel(long long total, int wh, const int *__restrict__ sptr, const int *__restrict__ scol,
+                                                             const VT *__restrict__ sval, int *__restrict__ hcol, VT *__restrict__ hval,
+                                                             unsigned short *__restrict__ hlen) {
+  const long long gid = (long long)blockIdx.x * TPB + threadIdx.x;
+  if (gid >= total) return;
+  const int lane = (int)(gid & 63);
+  const long long t = gid >> 6;
+  const int k = (int)(t % wh), sl = (int)(t / wh);
+  const int p0 = sptr[sl], w = (sptr[sl + 1] - p0) >> 6;
+  int cj = 0;
+  VT v = 0;
+  if (k < w) { const size_t p = (size_t)p0 + (size_t)k * 64 + lane; cj = scol[p]; v = sval[p]; }
+  hcol[gid] = cj; hval[gid] = v;
+  if (k == 0 && lane == 0) hlen[sl] = (unsigned short)w;
+}
+// widest width w = 1 .. cap whose padding over the given slice widths stays within 1/8 of their sum AND beyond which at most 1/8
+// of the slices go on; 0: none does.  The second condition is the measured one: a slice with a tail waits for its pointer as before
+// and tests its width on top, so a head that most slices outgrow makes the sweep slower.
+int head_width_by_rule(const std::vector<int> &len, int cap) {
+  long long total = 0;
+  for (int v : len) total += v;
+  int best = 0;
+  for (int w = 1; w <= cap; w++) {
+    long long pad = 0, tails = 0;
+    for (int v : len) { pad += w > v ? w - v : 0; tails += v > w; }
+    if (8 * pad <= total && 8 * tails <= (long long)len.size()) best = w;
+  }
+  return best;
+}
+
+// SELL-64 head of M from its SELL arrays; weighted: the values are svalw (Chebyshev matrix of H), sval otherwise
+int head_sell(cfdh_ctx *c, CsrDev &M, bool weighted, int cap) {
+  M.drop_head();
+  const float *sv = weighted ? M.svalw.p : M.sval.p;
+  if (!c->amg_head || !M.sptr.p || !M.scol.p || !sv || M.n <= 0) return 0;
+  const int ns = (M.n + 63) / 64;
+  std::vector<int> sp((size_t)ns + 1);
+  HIPCHK(c, hipMemcpyAsync(sp.data(), M.sptr.p, sizeof(int) * sp.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  std::vector<int> w((size_t)ns);
+  int maxw = 0;
+  for (int s = 0; s < ns; s++) { w[s] = (sp[s + 1] - sp[s]) >> 6; maxw = std::max(maxw, w[s]); }
+  if (maxw > 65535) return 0;
+  const int wh = c->amg_head_w > 0 ? std::min(c->amg_head_w, cap) : head_width_by_rule(w, cap);
+  if (wh <= 0) return 0;
+  const long long total = (long long)ns * wh * 64;
+  HIPCHK(c, M.hcol.alloc((size_t)total)); HIPCHK(c, M.hvalf.alloc((size_t)total));
+  HIPCHK(c, M.hlen.alloc(((size_t)ns + 2) & ~(size_t)1)); HIPCHK(c, M.hlen.zero(c->stream));
+  hipLaunchKernelGGL((head_sell_fill_kernel<float>), dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, total, wh, M.sptr.p,
+                     M.scol.p, sv, M.hcol.p, M.hvalf.p, M.hlen.p);
+  HIPCHK(c, hipGetLastError());
+  M.head_w = wh;
+  return 0;
+}
+}  // namespace
+
+int cfdh_amg_heads(cfdh_ctx *c, AmgHier &H) {
+  if (!H.fused) return 0;
+  for (AmgLevel *L : H.lev) {
+    if (!L->sell) continue;
+    CHK(head_sell(c, L->Sb, false, cfdh_sell_chunk(H.ncol)));
+    CHK(head_sell(c, L->Sc, false, cfdh_sell_chunk(H.ncol)));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+int cfdh_level_head(cfdh_ctx *c, AmgLevel &L) {
+  L.A.drop_head();
+  if (&L != &c->Hlev) return 0;  // the one level sell_cheb2_scale_kernel runs on (the levels of a host-built hierarchy come here too)
+  if (cfdh_cheb2_sell(L.A.nnz, L.n) && L.A.has_sell_weighted()) CHK(head_sell(c, L.A, true, 10));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }

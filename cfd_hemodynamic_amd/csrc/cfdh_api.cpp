@@ -108,6 +108,8 @@ static int create_ctx(cfdh_ctx **out, int device, int gdim, int etype, int64_t n
   cfdh_default_options(&c->opt);
   { const char *e = getenv("CFDH_NO_GRAPH"); c->use_graph = !(e && e[0] == '1'); }
   { const char *e = getenv("CFDH_SOLVE_LEAN"); c->lean = !(e && e[0] == '0'); }  // 0: the solve paths without the lean prologue / epilogue / kept coupling product (A/B runs, tests)
+  { const char *e = getenv("CFDH_AMG_HEAD"); c->amg_head = !(e && e[0] == '0'); }  // 0: the AMG sweeps address through sptr / rowptr only (A/B runs, tests)
+  { const char *e = getenv("CFDH_AMG_HEAD_W"); c->amg_head_w = e ? atoi(e) : 0; }  // forced head width (tests: tails on any mesh)
   {
     cfdh_ctx::SolveEnv &v = c->env;
     const char *e;
@@ -927,6 +929,22 @@ int cfdh_get_amg_operator(cfdh_ctx *c, int hier, int level, int which, int64_t *
     for (auto &e : row) { col[pos] = e.first; vals[pos] = e.second; pos++; }
   }
   rowptr[M.n] = (int32_t)pos;
+  return 0;
+}
+
+int cfdh_get_amg_head(cfdh_ctx *c, int hier, int level, int which, int32_t *width) {
+  NOT_IPCS(c, "cfdh_get_amg_head");
+  if (!c || !width) return CFDH_E_ARG;
+  ENTER(c);
+  AmgHier *H = nullptr;
+  AmgLevel *L = nullptr;
+  if (hier == CFDH_AMG_HIER_DL0) return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_head: the distributed level has no head copies");
+  CHK(amg_pick(c, "cfdh_get_amg_head", hier, level, &H, &L));
+  const bool single = hier == CFDH_AMG_HIER_H;
+  if (single ? which != CFDH_AMG_OP_A : (which != CFDH_AMG_OP_SB && which != CFDH_AMG_OP_SC))
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_get_amg_head: operator %d has no head copy", which);
+  const CsrDev &M = single ? L->A : which == CFDH_AMG_OP_SB ? L->Sb : L->Sc;
+  *width = M.head_w;
   return 0;
 }
 

@@ -99,6 +99,17 @@ struct CsrDev {
   // What a kernel of the preconditioner application asks before it takes the SELL arrays (CSR every operator has)
   bool has_sell() const { return sptr.p && scol.p && sval.p; }
   bool has_sell_weighted() const { return sptr.p && scol.p && svalw.p; }
+  // "Head" copy of a SELL-64 sweep operator (head_sell in cfdh_amg_dev.hip): the first head_w entries of
+  // every slice once more, at an address computed from the slice index alone, so that a sweep requests columns and values without
+  // waiting for sptr[].  Entries and their order are those of the SELL arrays above, which keep serving the remainder of wider
+  // slices (the tail), the old addressing (CFDH_AMG_HEAD=0) and the tests.
+  //   hcol / hvalf [(slice * head_w + k) * 64 + lane], k < head_w;  hlen[slice] = width of the slice
+  // head_w == 0: no head (switched off, rule not met): the kernels take the pointers.  (CSR operators have none: measured slower.)
+  int head_w = 0;
+  dbuf<int> hcol;
+  dbuf<float> hvalf;
+  dbuf<unsigned short> hlen;  // padded to an even count: a sweep reads its slice's width with a scalar 32-bit load
+  void drop_head() { head_w = 0; hcol.release(); hvalf.release(); hlen.release(); }
 };
 enum { CFDH_UP_CSR = 1, CFDH_UP_SELL = 2, CFDH_UP_CSRF = 4};  // parts of a CsrDev to upload
 
@@ -344,6 +355,8 @@ struct cfdh_ctx {
   double cc_alpha = 0, cc_beta = 0;
   // Cahouet-Chabard combination z_p = alpha t + beta zH (r on Dirichlet rows) applied in the epilogue of the last
   // kernel of the pressure cycle instead of a kernel of its own
+  bool amg_head = true;  // CFDH_AMG_HEAD=0: no head copies, the sweeps address through sptr / rowptr (A/B runs, tests)
+  int amg_head_w = 0;    // CFDH_AMG_HEAD_W=<w>: head width forced (entries per row), 0: by the rule (head_width_by_rule)
   int up0_rows = 0;  // > 0: the fused cycle's finest up-sweep computes the first up0_rows rows only (owned rows of the overlapping velocity cycle)
   struct Epilogue { bool on = false, done = false; double alpha = 0, beta = 0; const double *zH = nullptr, *r = nullptr; const unsigned char *pbc = nullptr; double *out = nullptr; } epi;
   std::vector<double> h_Lval, h_Ml;  // P1 stiffness on the vertex graph, lumped mass (geometry only)
@@ -518,6 +531,17 @@ int cfdh_aggregate_host_csr(const CsrHost &A, double theta, std::vector<int> &ag
 bool cfdh_amg_dev_enabled(const cfdh_ctx *c);  // fused Jacobi cycle requested and CFDH_AMG_HOST unset
 int cfdh_amg_setup_dev(cfdh_ctx *c, AmgHier &H, CsrDev &A0, bool singular, int ncol);   // A0 (device CSR) is consumed
 int cfdh_level_setup_dev(cfdh_ctx *c, AmgLevel &L, CsrDev &A, double ratio, int ncol);  // A is consumed
+// head copies of a finished hierarchy's SELL sweep operators (Sb, Sc of the levels of the fused cycle that take SELL-64) and of the
+// Chebyshev matrix of H; both builds call them last.  No-ops under CFDH_AMG_HEAD=0.
+int cfdh_amg_heads(cfdh_ctx *c, AmgHier &H);
+int cfdh_level_head(cfdh_ctx *c, AmgLevel &L);
+// lanes per row of the down-sweep over G (2-4 entries per lane, loaded together)
+inline int cfdh_down_lpr(const CsrDev &G) {
+  const long long avg = G.n > 0 ? (G.nnz + G.n - 1) / G.n : 1;
+  return avg > 96 ? 64 : (avg > 48 ? 32 : (avg > 20 ? 16 : 8));
+}
+// entries per row preloaded by the SELL up-sweep (registers: fewer for two / three right-hand sides); the widest SELL head
+inline int cfdh_sell_chunk(int ncol) { return ncol > 1 ? 8 : 10; }
 int cfdh_proxy_dev(cfdh_ctx *c, CsrDev &out);                       // scalar proxy of A00 on the owned vertices
 int cfdh_proxy_ras_dev(cfdh_ctx *c, CsrDev &out);                   // the same on owned + ghost vertices (collective: halo exchanges)
 int cfdh_cc_h_dev(cfdh_ctx *c, double alpha, double beta, CsrDev &out);  // H = (I + a'T) M_l + b' A11 (rows of ccPbc & 1: identity)

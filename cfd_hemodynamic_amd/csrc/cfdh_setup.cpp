@@ -456,6 +456,7 @@ static void transpose_host(const CsrHost &A, CsrHost &T) {
 static int upload_csr(cfdh_ctx *c, const CsrHost &H, CsrDev &D, const std::vector<double> *colw = nullptr,
                       int parts = CFDH_UP_CSR | CFDH_UP_SELL) {
   D.n = H.n; D.m = H.m; D.nnz = H.nnz();
+  D.drop_head();
   if (parts & (CFDH_UP_CSR | CFDH_UP_CSRF)) {
     HIPCHK(c, D.rowptr.upload(H.rowptr, c->stream));
     HIPCHK(c, D.col.upload(H.col, c->stream));
@@ -592,7 +593,7 @@ int cfdh_level_setup(cfdh_ctx *c, AmgLevel &L, const CsrHost &A, double ratio, i
   const size_t nn = (size_t)A.n * ncol;
   HIPCHK(c, L.x.alloc(nn)); HIPCHK(c, L.b.alloc(nn)); HIPCHK(c, L.r.alloc(nn));
   HIPCHK(c, L.d0.alloc(nn)); HIPCHK(c, L.d1.alloc(nn));
-  return 0;
+  return cfdh_level_head(c, L);
 }
 
 static double setup_ms() {
@@ -736,6 +737,7 @@ int cfdh_amg_setup(cfdh_ctx *c, AmgHier &H, const CsrHost &A0, bool singular, in
     H.valid = true;
     H.fine_nnz = A0.nnz();
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(cfdh_amg_heads(c, H));
     if (c->opt.verbose) {
       fprintf(stderr, "[cfdh] AMG hierarchy (ncol %d, smoothed coarsest level%s):", ncol, H.fused ? ", fused" : "");
       for (AmgLevel *l : H.lev) fprintf(stderr, " (%d, nnz %d; G %d Sb %d Sc %d)", l->n, l->A.nnz, l->G.nnz, l->Sb.nnz, l->Sc.nnz);
@@ -785,6 +787,7 @@ int cfdh_amg_setup(cfdh_ctx *c, AmgHier &H, const CsrHost &A0, bool singular, in
   H.fine_nnz = A0.nnz();
   H.valid = true;
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  CHK(cfdh_amg_heads(c, H));
   if (c->opt.verbose) {
     fprintf(stderr, "[cfdh] AMG hierarchy (ncol %d%s):", ncol, H.fused ? ", fused" : "");
     for (AmgLevel *l : H.lev) fprintf(stderr, " (%d, nnz %d; G %d Sb %d Sc %d D %d)", l->n, l->A.nnz, l->G.nnz, l->Sb.nnz, l->Sc.nnz, l->Dn);

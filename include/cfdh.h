@@ -352,6 +352,10 @@ int cfdh_get_amg_operator(cfdh_ctx *ctx, int hier, int level, int which, int64_t
 /* Vectors and scalars of the same, as doubles; *n receives the count, out may be NULL (query).  Level-0 vectors in the caller's
  * numbering.  Error codes as above. */
 int cfdh_get_amg_vectors(cfdh_ctx *ctx, int hier, int level, int which, int64_t *n, double *out);
+/* Head copy of one SELL-64 operator (tests): *width = entries per row that a sweep addresses from the slice index alone, 0 when the
+ * operator has no head.  which: CFDH_AMG_OP_SB / _SC of a hierarchy level, CFDH_AMG_OP_A of CFDH_AMG_HIER_H (the Chebyshev matrix).
+ * Error codes as above. */
+int cfdh_get_amg_head(cfdh_ctx *ctx, int hier, int level, int which, int32_t *width);
 
 /* ---- one Krylov vector kernel at a time (tests) ---------------------------------------------------------------------------
  * The small vector kernels of the linear solve (dot products, Gram-Schmidt updates, the fp32 basis copy, the prologue of the
