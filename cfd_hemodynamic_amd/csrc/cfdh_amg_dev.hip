@@ -1126,9 +1126,12 @@ int cfdh_amg_setup_dev(cfdh_ctx *c, AmgHier &H, CsrDev &A0, bool singular, int n
     const bool last = A.n <= o.amg_max_coarse || (int)H.lev.size() >= maxlev;
     int na = 0;
     dbuf<int> agg;
-    // P2 elements: the first coarse level is the P1 subspace (p-multigrid step) with its exact interpolation, not an aggregation
+    // P2 elements: the first coarse level is the P1 subspace (p-multigrid step) with its exact interpolation, not an aggregation.
+    // gen_P1 interpolates on the LOCAL node set (owned + ghost nodes, local numbering): it serves the hierarchies of this rank's own
+    // operators with exactly those rows.  The replicated global pressure space is numbered globally and must come out the same on every
+    // rank, so it never takes the step -- not even on a rank whose overlap happens to reach every node of the mesh (row counts equal).
     static const bool no_pmg = getenv("CFDH_NO_PMG") && getenv("CFDH_NO_PMG")[0] == '1';
-    const bool pmg = !last && !no_pmg && H.lev.size() == 1 && c->etype == 1 && c->gen_P1.n == A.n && c->gen_P1.m > 0;
+    const bool pmg = !last && !no_pmg && H.lev.size() == 1 && c->etype == 1 && &H != &c->hLg && c->gen_P1.n == A.n && c->gen_P1.m > 0;
     if (!last && !pmg) {
       if (host_agg) {
         CsrHost Ah;

@@ -3,10 +3,12 @@ plug-in, sets a random state taken from global arrays (so that all ranks agree),
 CFDH_AMG_KEEP=1 and writes what cfdh_get_amg_operator / cfdh_get_amg_vectors / cfdh_apply_preconditioner return to one .npz per rank.
 All comparisons happen in the parent, on the CPU.
 
-Environment: PPC_CASE (dfg16, dfg64, lid48, cube11: the mesh), PPC_BACKEND (host | rccl), PPC_CONFIGS ("schur_full:degree,..." applied in
+Environment: PPC_CASE (dfg16, dfg64, lid48, cube11: the mesh; p2tri, q1quad, p2tet, q1hex: a sheared node mesh of a generic element, whose
+part goes through cfdh_create_elem_part and cfdh_set_global_pressure_space's element branch), PPC_BACKEND (host | rccl), PPC_CONFIGS ("schur_full:degree,..." applied in
 turn, each with its own dump of the velocity hierarchy and of H), PPC_MAX_COARSE (amg_max_coarse),
 PPC_STEP_FIRST=1 (one time step before the random state: the singular-pressure flag is set by the Newton solver), PPC_MODE=step (one
-time step from the start state after -- or, with PPC_GETTERS=0, without -- the getter calls; the solution is the output)."""
+time step from the start state after -- or, with PPC_GETTERS=0, without -- the getter calls; the solution is the output),
+PPC_BDF2=1 (after everything else: the Jacobian and residual of the same state with BDF2 coefficients and a second history vector)."""
 import os
 import sys
 
@@ -40,7 +42,38 @@ def make_case(name):
         out = bnd[np.isclose(m.x[bnd, 0], 1.0)]
         wall = np.setdiff1d(bnd, out).astype(np.int32)
         return Case(m, [(0, wall, np.zeros((len(wall), 3))), (1, out, np.zeros(len(out)))], 0.01, 1.0, 1e-2, f=(0.0, 0.0, 0.0))
+    if name in GENERIC:
+        return generic_case(name)
     raise KeyError(name)
+
+
+# P2 / Q1 parts: node-mesh builder (gen_util / gen3_util), element, cells per edge, shear, quadrature points per cell of the library's element
+# stiffness (the length of its sums, for the bounds of the parent).  The meshes of the generic cases of tests/test_gpu_amg.py.
+GENERIC = {"p2tri": ("node_mesh", "P2", 12, 0.2, 49), "q1quad": ("node_mesh", "Q1", 16, 0.3, 49),
+           "p2tet": ("node_mesh3", "P2", 4, 0.25, 171), "q1hex": ("node_mesh3", "Q1", 6, 0.3, 343)}
+
+
+def generic_case(name):
+    """Sheared node mesh of a generic element (a transposed or mis-indexed inverse cell Jacobian changes its matrices) with no-slip walls
+    and a pressure-Dirichlet outlet (the face x = 1 before the shear), like `cube`.  case.mesh is the NODE mesh -- what is partitioned,
+    what the global vectors live on; case.solver_mesh / case.degree are what the plug-in is given: the geometric mesh with _degree=2 for
+    P2, the quadrilateral / hexahedral mesh itself for Q1."""
+    from util import Case
+    import gen3_util
+    import gen_util
+    mk, kind, n, distort, _ = GENERIC[name]
+    mk = getattr(gen_util if mk == "node_mesh" else gen3_util, mk)
+    m, flat = mk(kind, n, distort), mk(kind, n, 0.0)
+    d = m.x.shape[1]
+    bnd = np.unique(m.facet_vertices).astype(np.int32)
+    out = bnd[np.isclose(flat.x[bnd, 0], flat.x[:, 0].max())]
+    wall = np.setdiff1d(bnd, out).astype(np.int32)
+    case = Case(m, [(0, wall, np.zeros((len(wall), d))), (1, out, np.zeros(len(out)))], 0.01, 1.0, 1e-2, f=(0.0,) * d)
+    case.degree = 2 if kind == "P2" else 1
+    case.solver_mesh = m.base if kind == "P2" else m
+    if kind == "P2":
+        m.base._p2_nodes = m     # the plug-in's function spaces live on this very node mesh
+    return case
 
 
 def global_vectors(case, dim, seed):
@@ -121,7 +154,9 @@ def main():
     opts = dict(schur_full=configs[0][0], cc_smooth_degree=configs[0][1])
     if os.environ.get("PPC_MAX_COARSE"):
         opts["amg_max_coarse"] = int(os.environ["PPC_MAX_COARSE"])
-    solver = Solver(mesh, case.dt, case.rho, case.mu, list(case.f)[:dim], comm=comm, quiet=True, device=0, options=opts)
+    extra = dict(_degree=2) if getattr(case, "degree", 1) == 2 else {}
+    solver = Solver(getattr(case, "solver_mesh", mesh), case.dt, case.rho, case.mu, list(case.f)[:dim], comm=comm, quiet=True, device=0, options=opts,
+                    **extra)
     solver.setup([_FixedBC(n, v) for f, n, v in case.bcs if f == 0], [_FixedBC(n, v) for f, n, v in case.bcs if f == 1])
     ctx, part = solver.ctx, solver._part
     nv, nvo, l2g = part.nv, part.nvo, part.l2g
@@ -161,6 +196,8 @@ def main():
             if k == 0:
                 J = ctx.get_csr()
                 out["J_rp"], out["J_col"], out["J_val"], out["J_shape"] = J.indptr, J.indices, J.data, np.array(J.shape)
+                Fu, Fp = ctx.get_residual()
+                out["F_u"], out["F_p"] = Fu.reshape(nv, dim)[:nvo].copy(), Fp[:nvo].copy()
                 dump_replicated(ctx, out)
             dump_config(ctx, out, pre)
             singular = ctx.info(76) != 0
@@ -176,6 +213,15 @@ def main():
             if k == 0:
                 out[pre + "zu_vel"], out[pre + "zp_vel"] = apply(ru1, 0.0 * rp1)
                 out[pre + "zu_pres"], out[pre + "zp_pres"] = apply(0.0 * ru1, rp1)
+        if os.environ.get("PPC_BDF2") == "1":
+            un2, _, _ = global_vectors(case, dim, 18)
+            ctx.set_time_scheme(1.0, 1.5, -2.0, 0.5)
+            ctx.set_previous2(0.3 * un2[l2g])
+            ctx.assemble(True)
+            J = ctx.get_csr()
+            out["J2_rp"], out["J2_col"], out["J2_val"], out["J2_shape"] = J.indptr, J.indices, J.data, np.array(J.shape)
+            Fu, Fp = ctx.get_residual()
+            out["F2_u"], out["F2_p"] = Fu.reshape(nv, dim)[:nvo].copy(), Fp[:nvo].copy()
     np.savez(os.path.join(outdir, "rank%d.npz" % rank), **out)
     dist.barrier()
     dist.destroy_process_group()

@@ -9,8 +9,12 @@ are gated by the distance the float32 copies themselves cause (amg_twin.gate).
 Partitioned runs (the distributed finest level dl0, restricted additive Schwarz, the replicated hierarchy hLg) have their own file,
 tests/test_gpu_part_pc.py, which shares the checkers with this one (tests/amg_checks.py).
 
-Not covered here or there: parts of P2 / Q1 contexts (cfdh_create_elem_part), more than 3 ranks, a real RCCL transport, the pressure hierarchy of the pressure-correction contexts (cfdh_create_ipcs), the level-0 operator formulas of P2 contexts (their
-hierarchies are checked from the downloaded level-0 operator on), the float32 SELL copies of the sweep-by-sweep cycle, and the
+The level-0 operators of the generic elements (P2 triangles / tetrahedra, Q1 quadrilaterals / hexahedra: the cases p2, q1, p2tet, q1hex on
+sheared meshes) are checked against tests/cc_gen_twin.py; a P2 context takes the exact P1 interpolation as its first coarsening step
+(p-multigrid) and aggregates from there on, or from level 0 on with CFDH_NO_PMG=1.
+
+Not covered here or there: more than 3 ranks, a real RCCL transport, the pressure hierarchy of the pressure-correction contexts
+(cfdh_create_ipcs), the float32 SELL copies of the sweep-by-sweep cycle, and the
 prolongator formula of host-built hierarchies (pc_type 0's hS: the host build does not keep its aggregates; its P is checked for
 well-formedness and is the input of the composite and coarse-operator formulas)."""
 import os
@@ -23,8 +27,11 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import amg_twin as T
+import cc_gen_twin as CG
+import part_pc_twin as PPT
 import pcd_twin as P
 from amg_checks import HA, HH, HL, OPS, _assert, _raw, check_h_level, check_hierarchy, fp64_copy, shape_of, twin_hierarchy
+from gen3_util import node_mesh3
 from gen_util import node_mesh
 from util import dfg_case, lid_case
 
@@ -35,7 +42,11 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # deep: amg_max_coarse at its minimum carries the hierarchies on to five levels, the last of a handful of rows
-CASES = ["dfg64", "lid", "tet", "p2", "theta95", "deep"]
+CASES = ["dfg64", "lid", "tet", "p2", "theta95", "deep", "q1", "p2tet", "q1hex"]
+# the generic elements: builder, cells per edge, shear, library element type, amg_max_coarse that leaves three levels (P2: the P2 level, the P1
+# step, one aggregation at least), quadrature points per cell of the library's element stiffness (the length of its sums, for the bounds)
+GENERIC = {"p2": (node_mesh, "P2", 12, 0.2, 1, 100, 49), "q1": (node_mesh, "Q1", 16, 0.3, 2, 16, 49),
+           "p2tet": (node_mesh3, "P2", 4, 0.25, 1, 50, 171), "q1hex": (node_mesh3, "Q1", 6, 0.3, 2, 8, 343)}
 
 
 class _Case:
@@ -50,12 +61,18 @@ def _tet_case():
     return m, [(0, wall, np.zeros((len(wall), 3))), (1, out, np.zeros(len(out)))], 0.01, 1.0, 1e-2, 0
 
 
-def _p2_case():
-    m = node_mesh("P2", 24)
-    bnd = np.nonzero((np.abs(m.x - 0.5).max(axis=1) > 0.5 - 1e-12))[0].astype(np.int32)
-    out = bnd[np.isclose(m.x[bnd, 0], 1.0)]
+def _generic_case(name):
+    """Sheared mesh of a generic element (a transposed or mis-indexed inverse cell Jacobian changes its matrices): no-slip walls, pressure
+    Dirichlet on the face that is x = 1 before the shear."""
+    mk, kind, n, distort, etype, _, _ = GENERIC[name]
+    m, flat = mk(kind, n, distort), mk(kind, n, 0.0)
+    d = m.x.shape[1]
+    assert np.abs(m.x - flat.x).max() > 0.05 and np.array_equal(m.cells, flat.cells)
+    bnd = np.unique(m.facet_vertices).astype(np.int32)
+    out = bnd[np.isclose(flat.x[bnd, 0], flat.x[:, 0].max())]
     wall = np.setdiff1d(bnd, out).astype(np.int32)
-    return m, [(0, wall, np.zeros((len(wall), 2))), (1, out, np.zeros(len(out)))], 0.01, 1.0, 1e-2, 1
+    assert len(out) and len(wall)
+    return m, [(0, wall, np.zeros((len(wall), d))), (1, out, np.zeros(len(out)))], 0.01, 1.0, 1e-2, etype
 
 
 def make_case(name, state_scale=0.3, p_scale=1.0, **opts):
@@ -77,12 +94,14 @@ def make_case(name, state_scale=0.3, p_scale=1.0, **opts):
     elif name == "tet":
         m, bcs, dt, rho, mu, etype = _tet_case()
         opts = dict(opts, amg_max_coarse=500)     # three levels
-    elif name == "p2":
-        m, bcs, dt, rho, mu, etype = _p2_case()
+    elif name in GENERIC:
+        m, bcs, dt, rho, mu, etype = _generic_case(name)
+        opts = dict(opts, amg_max_coarse=GENERIC[name][5])
     else:
         raise KeyError(name)
     c.mesh, c.dt, c.rho, c.mu, c.etype = m, dt, rho, mu, etype
     c.has_pbc = any(f == 1 and len(n) for f, n, _ in bcs)
+    c.pnodes = np.unique(np.concatenate([np.asarray(n, dtype=np.int64) for f, n, _ in bcs if f == 1] + [np.zeros(0, dtype=np.int64)]))
     markers = m.facet_marker if getattr(m, "facet_marker", None) is not None else np.zeros(len(m.facet_cells), np.int32)
     ctx = _lib.Context(m.x, m.cells, m.facet_cells, m.facet_local, markers, etype=etype)
     c.dim, c.nv = ctx.dim, ctx.nv
@@ -270,6 +289,73 @@ def test_level0_operators_of_p1_contexts(name):
     assert (mld[pbc != 0] == 0.0).all() and np.abs(mld - ml)[pbc == 0].max() <= 16 * T.EPS * ml.max()
 
 
+def _generic_level0(c):
+    """Twin of the level-0 operators of a P2 / Q1 context.  The proxy of A00 is literally the P1 formula on the node graph (ProxyF in
+    csrc/cfdh_amg_dev.hip knows no element: the mean of the diagonal of every dim x dim node block, exact zeros off the diagonal dropped),
+    and so is H = (I + alpha T) M_l + beta A11; what the element contributes is the stiffness behind the Laplacian and behind
+    T = diag(A11) / diag(L), and the HRZ-lumped mass."""
+    ctx, d, nv, m = c.ctx, c.dim, c.nv, c.mesh
+    nq = GENERIC[c.name][6]
+    kind = CG.kind_of(d, np.asarray(m.cells).shape[1])
+    x = np.asarray(m.x)[:, :d]
+    proxy = PPT.proxy_rows(jacobian(c), d, nv, nv)
+    pbc = ctx.get_amg_vectors(HL, 0, _lib.AMG_VEC_CC_PBC).astype(np.int64)
+    Ld = CG.dirichlet_laplacian(kind, x, m.cells, pbc, nq)
+    Lp, _, terms = CG.stiffness(kind, x, m.cells, nq)
+    ml = CG.lumped_mass(kind, x, m.cells)
+    A11 = T.canonical(jacobian(c)[d * nv:, d * nv:])
+    alpha, beta = ctx.get_amg_vectors(HL, 0, _lib.AMG_VEC_CC_SCALARS)
+    # H from the device's own lumped mass where it is stored (it has its own check and its own, derived, tolerance); T carries the relative
+    # error of the diagonal of the stiffness, a sum of `terms` positive products: that many eps on top of the 4 x 4 of the P1 contexts
+    mld = ctx.get_amg_vectors(HL, 0, _lib.AMG_VEC_CC_ML)
+    Hm, Hb = T.h_operator(A11, Lp, np.where(pbc == 0, mld, ml), pbc, alpha, beta)
+    return proxy, Ld, (Hm, Hb, 4 + (terms + 3) // 4), ml, kind
+
+
+@pytest.mark.parametrize("name", list(GENERIC))
+def test_level0_operators_of_generic_contexts(name):
+    c = get_case(name)
+    ctx = c.ctx
+    proxy, Ld, Hm, ml, kind = _generic_level0(c)
+    report = []
+    try:
+        for nm, hier, tw in (("proxy of A00", HA, proxy), ("Laplacian", HL, Ld), ("H", HH, Hm)):
+            _assert(T.check_operator("%s level 0 %s" % (c.name, nm), _raw(ctx, hier, 0, "A"), tw), report)
+    finally:
+        _print(["%s: %.3g times the bound" % (v.where.split(": entry")[0], v.ratio) for v in report])
+    a, b = ctx.get_amg_vectors(HL, 0, _lib.AMG_VEC_CC_SCALARS)
+    assert a == c.rho * 1.0 / (0.5 * c.dt) and b == c.mu           # midpoint scheme: theta 1/2, a0 1
+    pbc = ctx.get_amg_vectors(HL, 0, _lib.AMG_VEC_CC_PBC)
+    want = np.zeros(c.nv)
+    want[c.pnodes] = 1.0                                            # boundary terms on: no second bit, the pressure-Dirichlet nodes alone
+    assert np.array_equal(pbc, want) and 0 < len(c.pnodes) < c.nv
+    mld = ctx.get_amg_vectors(HL, 0, _lib.AMG_VEC_CC_ML)
+    tol = CG.lumped_mass_tolerance(kind, c.mesh.cells)
+    err = np.abs(mld - ml)[pbc == 0].max() / ml.max()
+    _print(["%s level 0 lumped mass: %.3g eps of the largest entry, allowed %.3g eps (%.3g times the bound)" % (c.name, err / T.EPS, tol / T.EPS, err / tol)])
+    assert (mld[pbc != 0] == 0.0).all() and err <= tol
+    verts = np.unique(np.asarray(c.mesh.cells)[:, : CG.KINDS[kind][2]])
+    assert (mld[verts][pbc[verts] == 0] > 0).all(), "HRZ lumping is positive at the vertices of a P2 simplex"
+
+
+@pytest.mark.parametrize("name", list(GENERIC))
+def test_generic_cases_have_three_levels_and_p2_takes_the_p1_step(name):
+    """The sizes of the generic cases are the smallest that leave three levels; a P2 context takes the P1 subspace of its node space as
+    the first coarse level of both hierarchies (p-multigrid: `agg` false, P the exact interpolation, which check_hierarchy compares) and
+    aggregates from there on, a Q1 context aggregates from level 0 on."""
+    c = get_case(name)
+    p2 = c.etype == 1
+    nvert = len(np.unique(np.asarray(c.mesh.cells)[:, : c.dim + 1]))
+    for hier in (HA, HL):
+        sh = shape_of(c.ctx, hier)
+        assert sh["nl"] >= 3, "%s: levels %s" % (name, [q["n"] for q in sh["lev"]])
+        assert sh["lev"][0]["n"] == c.nv and sh["lev"][0]["agg"] == (not p2) and sh["lev"][1]["agg"]
+        if p2:
+            assert sh["lev"][1]["n"] == nvert < c.nv
+            Pd = c.ctx.get_amg_operator(hier, 0, OPS["P"])
+            assert set(np.unique(Pd.data)) == {0.5, 1.0} and (np.diff(Pd.indptr) <= 2).all()
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_one_application_of_each_cycle(name):
     c = get_case(name)
@@ -432,6 +518,15 @@ def _child(what):
             err = np.abs(z - zt).max() / np.abs(zt).max()
             report.append("dfg16: converged inner solves against sparse LU: %.3g" % err)
             assert err <= 1e-5, report[-1]
+        elif what == "nopmg":       # CFDH_NO_PMG=1: a P2 context aggregates its node graph from level 0 on
+            for name in ("p2", "p2tet"):
+                c = make_case(name)
+                for hier, label in ((HA, "hA"), (HL, "hL")):
+                    sh = shape_of(c.ctx, hier)
+                    assert sh["nl"] >= 2 and sh["lev"][0]["agg"], "%s %s: %s" % (name, label, sh["lev"])
+                    check_hierarchy(c, hier, label, report)       # ... by the aggregation formulas, level 0 included
+                op = cc_operators(c)
+                action_gate(c, op, rhs(c, 6), slice(None), report, "whole action without the P1 step")
         else:
             raise KeyError(what)
     finally:
@@ -459,6 +554,10 @@ def test_action_without_graph_capture():
 
 def test_sweep_by_sweep_cycle_matches_the_textbook_cycle():
     _run_child("sweeps", CFDH_NO_FUSED_AMG="1")
+
+
+def test_p2_contexts_aggregate_from_level0_without_the_p1_step():
+    _run_child("nopmg", CFDH_NO_PMG="1")
 
 
 def test_converged_inner_cycles_match_the_exact_action():

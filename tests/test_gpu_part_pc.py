@@ -8,8 +8,13 @@ computes; actions against tests/part_pc_twin.py through amg_twin.gate -- the dis
 where nothing on the way is float32.  The all-reduced coarse right-hand side is summed in the transport's order, so nothing behind it is
 compared bitwise with the twin.
 
-Not covered here: P2 / Q1 parts (cfdh_create_elem_part), more than 3 ranks in this file, a real RCCL transport (the shared-memory
-stand-in carries one case)."""
+P2 / Q1 parts (cfdh_create_elem_part, the element branch of cfdh_set_global_pressure_space) run the same tests on sheared node meshes
+(GEN_RUNS), their level-0 operators against tests/cc_gen_twin.py, and their Jacobian and residual against the whole-mesh oracle.  A P2
+part builds three hierarchy shapes (test_hierarchy_shapes_of_a_p2_part): the P1 step on the extended part mesh under restricted additive
+Schwarz, aggregation of the owned node graph otherwise, aggregation of the global node graph in the replicated pressure hierarchy.
+
+Not covered here: more than 3 ranks in this file, a real RCCL transport (the shared-memory stand-in carries two cases), PCD
+(pc_type 2) on parts."""
 import os
 import socket
 import subprocess
@@ -23,6 +28,7 @@ import scipy.sparse as sp
 
 import _gpu_part_pc_worker as W
 import amg_twin as T
+import cc_gen_twin as CG
 import part_pc_twin as PT
 from amg_checks import COARSE_FACTOR, HA, HH, _assert, _mat, check_h_level, check_hierarchy, fp64_copy, shape_of, twin_hierarchy
 
@@ -51,7 +57,14 @@ RUNS = {
     "nodl0": dict(world=2, case="dfg16", configs="2:2,1:2", env=dict(PPC_MAX_COARSE="4000")),
     # ... and behind an all-gather of the owned slices where the communicator speaks the NCCL API
     "nodl0gather": dict(world=2, case="dfg16", configs="2:2", rccl=True, env=dict(PPC_MAX_COARSE="4000")),
+    # P2 / Q1 parts on sheared node meshes of a few hundred nodes; amg_max_coarse small enough that the replicated hierarchy has two levels
+    # at least, so that the distributed level exists
+    "p2tri_w2": dict(world=2, case="p2tri", configs="2:2,1:2,0:2", env=dict(PPC_MAX_COARSE="100", PPC_BDF2="1")),
+    "q1quad_w3": dict(world=3, case="q1quad", configs="2:2", rccl=True, env=dict(PPC_MAX_COARSE="16")),
+    "p2tet_w2": dict(world=2, case="p2tet", configs="2:2,1:2", env=dict(PPC_MAX_COARSE="50")),
+    "q1hex_w2": dict(world=2, case="q1hex", configs="2:2", env=dict(PPC_MAX_COARSE="8")),
 }
+GEN_RUNS = ["p2tri_w2", "q1quad_w3", "p2tet_w2", "q1hex_w2"]
 
 
 def _free_port():
@@ -144,6 +157,11 @@ class Run:
         self.case = W.make_case(spec["case"])
         m = self.case.mesh
         self.dim, self.nvg = m.geometry.dim, m.num_vertices
+        # element: None for the P1 contexts, the kind of tests/cc_gen_twin.py for a node mesh of P2 / Q1 cells
+        self.generic = spec["case"] in W.GENERIC
+        self.kind = CG.kind_of(self.dim, np.asarray(m.cells).shape[1]) if self.generic else None
+        self.etype = (1 if self.kind.startswith("P2") else 2) if self.generic else 0
+        self.nq = W.GENERIC[spec["case"]][4] if self.generic else 1
         self.owner = partition_vertices_rcb(m.x, self.world)
         self.parts = [LocalPart(m, self.owner, r, layers=spec.get("layers", 2)) for r in range(self.world)]
         for p, d in zip(self.parts, self.d):
@@ -158,13 +176,31 @@ class Run:
         if "PPC_MAX_COARSE" in env:
             self.opt.amg_max_coarse = int(env["PPC_MAX_COARSE"])
         self.dl0_on = int(self.d[0]["dl0_n1"]) > 0
+        assert self.dl0_on or not self.generic, "the generic jobs are sized to have a distributed level"
         self._hLg = None
         self._ops = {}
 
     def cobj(self, r, k=0):
         """What amg_checks asks of a case: ctx, opt, theta, etype, name, singular, pg_singular."""
-        return SimpleNamespace(ctx=DumpCtx(self.d[r], "c%d_" % k), opt=self.opt, theta=0.02 if self.dim == 3 else 0.07, etype=0,
-                               name="%s rank %d" % (self.name, r), singular=False, pg_singular=not self.pbc_g.any(), has_pbc=True)
+        p = self.parts[r]      # the mesh a P1 step of this rank's hierarchies interpolates on: the part's own node mesh, ghosts included
+        return SimpleNamespace(ctx=DumpCtx(self.d[r], "c%d_" % k), opt=self.opt, theta=0.02 if self.dim == 3 else 0.07, etype=self.etype,
+                               name="%s rank %d" % (self.name, r), singular=False, pg_singular=not self.pbc_g.any(), has_pbc=True,
+                               dim=self.dim, mesh=SimpleNamespace(x=np.asarray(p.x)[:, : self.dim], cells=p.cells))
+
+    def laplacian(self, x, cells, pbc):
+        """(values, bound, terms) of the level-0 operator of a pressure hierarchy on the given mesh: the element's stiffness, Dirichlet rows."""
+        x = np.asarray(x)[:, : self.dim]
+        return CG.dirichlet_laplacian(self.kind, x, cells, pbc, self.nq) if self.generic else PT.dirichlet_laplacian(x, cells, pbc)
+
+    def lumped_mass(self):
+        """(M_l of the whole mesh, tolerance of a part's copy as a multiple of its largest entry): vol / (d + 1) per vertex and the
+        16 eps of the one-rank test for P1, the HRZ mass and the derived bound of its scaling factor for the generic elements (the
+        factor is one number for every mesh of affine cells of one element, tests/test_cc_gen_twin.py: the part's equals the global one)."""
+        m = self.case.mesh
+        x = np.asarray(m.x)[:, : self.dim]
+        if not self.generic:
+            return PT.lumped_mass(x, m.cells), [16 * T.EPS] * self.world
+        return CG.lumped_mass(self.kind, x, m.cells), [CG.lumped_mass_tolerance(self.kind, p.cells) for p in self.parts]
 
     def dl0_shape(self, r):
         s = self.d[r]["vec_%d_0_%d" % (HDL0, _lib.AMG_VEC_DL0_SHAPE)]
@@ -270,7 +306,7 @@ def _raw_of(d, key):
 
 
 # ---------------------------------------------------------------------------------------------------------------- operators
-OPS_RUNS = ["dfg16w2", "dfg16w3", "lid48w3", "cube11w2", "layers1", "hostasm"]
+OPS_RUNS = ["dfg16w2", "dfg16w3", "lid48w3", "cube11w2", "layers1", "hostasm"] + GEN_RUNS
 
 
 @pytest.mark.parametrize("name", OPS_RUNS + ["dfg64w2"])
@@ -284,8 +320,7 @@ def test_replicated_hierarchy_is_the_same_on_every_rank_and_its_level0_is_the_gl
         for k in keys:
             assert np.array_equal(run.d[0][k], run.d[r][k]), "%s differs between rank 0 and rank %d" % (k, r)
     m = run.case.mesh
-    v = T.check_operator("%s hLg level 0" % name, _raw_of(run.d[0], "op_%d_0_%d" % (HPG, _lib.AMG_OP_A)),
-                         PT.dirichlet_laplacian(m.x[:, : run.dim], m.cells, run.pbc_g))
+    v = T.check_operator("%s hLg level 0" % name, _raw_of(run.d[0], "op_%d_0_%d" % (HPG, _lib.AMG_OP_A)), run.laplacian(m.x, m.cells, run.pbc_g))
     _note("%s: hLg level 0 against the global Laplacian: %.3g times the bound" % (name, v.ratio))
     _assert(v)
 
@@ -406,6 +441,9 @@ def test_velocity_proxy_on_owned_and_ghost_rows(runs, name):
         finally:
             for ln in report:
                 _note(ln)
+        if run.etype == 1:     # a P2 part: the P1 step of the extended part mesh, which check_hierarchy compared with the exact interpolation
+            assert not sh["lev"][0]["agg"] and sh["lev"][0]["n"] == run.parts[r].nv
+            continue
         agg = run.d[r]["c0_vec_%d_0_%d" % (HA, _lib.AMG_VEC_AGG)]
         assert len(agg) == run.parts[r].nv, "CFDH_AMG_KEEP=1 keeps the aggregates of the overlapping hierarchy"
 
@@ -413,22 +451,27 @@ def test_velocity_proxy_on_owned_and_ghost_rows(runs, name):
 @pytest.mark.parametrize("name", OPS_RUNS + ["dfg64w2"])
 def test_h_lumped_mass_and_flags_of_a_part(runs, name):
     run = runs(name)
-    m = run.case.mesh
-    ml_g = PT.lumped_mass(m.x[:, : run.dim], m.cells)
+    ml_g, tols = run.lumped_mass()
     for r, p in enumerate(run.parts):
         c = run.cobj(r)
         pbc = c.ctx.get_amg_vectors(HH, 0, _lib.AMG_VEC_CC_PBC)
         assert np.array_equal(pbc, run.pbc_g[p.l2g[: p.nvo]].astype(np.float64))
         mld = c.ctx.get_amg_vectors(HH, 0, _lib.AMG_VEC_CC_ML)
         ref = ml_g[p.l2g[: p.nvo]]
-        assert (mld[pbc != 0] == 0.0).all() and np.abs(mld - ref)[pbc == 0].max() <= 16 * T.EPS * ml_g.max()
+        err = np.abs(mld - ref)[pbc == 0].max() / ml_g.max()
+        _note("%s rank %d: lumped mass %.3g eps of the largest entry, allowed %.3g eps" % (name, r, err / T.EPS, tols[r] / T.EPS))
+        assert (mld[pbc != 0] == 0.0).all() and err <= tols[r]
         alpha, beta = c.ctx.get_amg_vectors(HH, 0, _lib.AMG_VEC_CC_SCALARS)
         assert alpha == run.case.rho * 1.0 / (0.5 * run.case.dt) and beta == run.case.mu
         # H on the local operators with the ghost columns removed
         _, _, A11 = PT.jacobian_blocks(run.J(r), run.dim, p.nvo, p.nv)
-        Lp = T.canonical(PT.dirichlet_laplacian(p.x[:, : run.dim], p.cells, np.zeros(p.nv))[0][: p.nvo, : p.nvo])
-        Hm, Hb = T.h_operator(T.canonical(A11[:, : p.nvo]), Lp, ml_g[p.l2g[: p.nvo]], pbc, alpha, beta)
-        v = T.check_operator("%s rank %d H" % (name, r), c.ctx.get_amg_operator(HH, 0, _lib.AMG_OP_A, raw=True), (Hm, Hb, 4))
+        Lp, _, terms = run.laplacian(p.x, p.cells, np.zeros(p.nv))
+        Lp = T.canonical(Lp[: p.nvo, : p.nvo])
+        # generic elements (as in tests/test_gpu_amg.py): H from the device's own lumped mass where it is stored, and T = diag(A11) / diag(L)
+        # carries the relative error of a sum of `terms` positive products on top of the 4 x 4 eps of the P1 contexts
+        mlh, depth = (np.where(pbc == 0, mld, ref), 4 + (terms + 3) // 4) if run.generic else (ref, 4)
+        Hm, Hb = T.h_operator(T.canonical(A11[:, : p.nvo]), Lp, mlh, pbc, alpha, beta)
+        v = T.check_operator("%s rank %d H" % (name, r), c.ctx.get_amg_operator(HH, 0, _lib.AMG_OP_A, raw=True), (Hm, Hb, depth))
         _note("%s rank %d: H %.3g times the bound" % (name, r, v.ratio))
         _assert(v)
         check_h_level(c)
@@ -470,6 +513,117 @@ def test_branches_taken_by_the_small_cases(runs):
     lid = runs("lid48w3")
     assert all(str(d["backend"]) == "rccl" and int(d["rccl"]) == 1 for d in lid.d), "the in-stream all-reduce is the one under test"
     assert lid.singular(0) and not lid.pbc_g.any()
+
+
+@pytest.mark.parametrize("name", ["p2tri_w2", "p2tet_w2"])
+def test_hierarchy_shapes_of_a_p2_part(runs, name):
+    """One P2 context builds three hierarchy shapes.  The P1 subspace of a part (gen_P1) has one row per LOCAL node, ghosts included, and the
+    device build takes the p-multigrid step only where the level-0 operator has exactly those rows:
+      hA, schur_full 2   owned + ghost rows (restricted additive Schwarz): the exact P1 interpolation of the extended part mesh, then aggregation
+      hA, schur_full 1, 0   owned rows: aggregation of the owned node graph from level 0 on
+      hLg   the nodes of the whole mesh: aggregation from level 0 on, so the distributed level's P is rows of a smoothed-aggregation prolongator
+    (on one rank all of them take the P1 step, tests/test_gpu_amg.py)."""
+    run = runs(name)
+    assert run.etype == 1 and run.dl0_on
+    if name == "p2tet_w2":
+        # the overlap of rank 0 reaches every node of the mesh, so its local P1 subspace has as many rows as the GLOBAL operator: the
+        # row count alone must not make hLg take the (locally numbered) P1 step on that rank -- the ranks then disagree on the coarse size
+        # and the all-reduce of the coarse right-hand side aborts
+        assert run.parts[0].nv == run.nvg > run.parts[1].nv
+    for k, (sf, _) in enumerate(run.configs):
+        for r, p in enumerate(run.parts):
+            c = run.cobj(r, k)
+            sh = shape_of(c.ctx, HA)
+            lev0 = sh["lev"][0]
+            assert int(run.d[r]["c%d_ras" % k]) == (1 if sf == 2 else 0)
+            if sf == 2:
+                nvert = len(np.unique(np.asarray(p.cells)[:, : run.dim + 1]))
+                assert lev0["n"] == p.nv and not lev0["agg"] and sh["nl"] >= 2 and sh["lev"][1]["n"] == nvert, (name, k, r, sh["lev"])
+            else:
+                assert lev0["n"] == p.nvo and lev0["agg"] and sh["nl"] >= 2, (name, k, r, sh["lev"])
+                report = []
+                try:
+                    check_hierarchy(c, HA, "hA (schur_full %d)" % sf, report)      # level 0 by the aggregation formulas
+                finally:
+                    for ln in report:
+                        _note(ln)
+            _note("%s rank %d schur_full %d: hA levels %s, level 0 %s" % (name, r, sf, [q["n"] for q in sh["lev"]],
+                                                                          "aggregated" if lev0["agg"] else "P1 step"))
+    sh = shape_of(run.cobj(0).ctx, HPG)
+    nvert_g = len(np.unique(np.asarray(run.case.mesh.cells)[:, : run.dim + 1]))
+    assert sh["lev"][0]["n"] == run.nvg and sh["lev"][0]["agg"] and sh["lev"][1]["n"] != nvert_g
+    agg = run.d[0]["vec_%d_0_%d" % (HPG, _lib.AMG_VEC_AGG)]
+    assert len(agg) == run.nvg and agg.max() + 1 == sh["lev"][1]["n"] == run.dl0_shape(0)["n1"]
+    _note("%s: hLg levels %s, level 0 aggregated (%d vertices in the mesh)" % (name, [q["n"] for q in sh["lev"]], nvert_g))
+
+
+def test_q1_parts_aggregate_everywhere(runs):
+    for name in ("q1quad_w3", "q1hex_w2"):
+        run = runs(name)
+        assert run.etype == 2 and run.dl0_on
+        for r, p in enumerate(run.parts):
+            sh = shape_of(run.cobj(r).ctx, HA)
+            assert sh["lev"][0]["n"] == p.nv and (sh["nl"] == 1 or sh["lev"][0]["agg"])
+        sh = shape_of(run.cobj(0).ctx, HPG)
+        assert sh["nl"] >= 2 and sh["lev"][0]["agg"]
+    q = runs("q1quad_w3")
+    assert all(str(d["backend"]) == "rccl" and int(d["rccl"]) == 1 for d in q.d), "the in-stream all-reduce carries the Q1 parts"
+
+
+# ---------------------------------------------------------------------------------------------------------------- Jacobian and residual of a generic part
+def _whole_mesh_assembly(run, bdf2):
+    """Residual and Jacobian of the whole node mesh by the oracle (oracle/np_twin_gen.py, np_twin_gen3.py): the worker's global state and
+    Dirichlet data."""
+    import gen3_util
+    import gen_util
+    case, d, m = run.case, run.dim, run.case.mesh
+    mod, make = (gen_util.G, gen_util.problem) if d == 2 else (gen3_util.G3, gen3_util.problem3)
+    kw = dict(theta=1.0, a0=1.5, a1=-2.0, a2=0.5) if bdf2 else {}
+    pb = make(run.kind[:2], m, mod.Params(case.dt, case.rho, case.mu, np.asarray(case.f, dtype=np.float64)[:d], **kw))
+    for f, nodes, vals in case.bcs:
+        (pb.add_bc_u if f == 0 else pb.add_bc_p)(nodes, vals)
+    u, un, p = W.global_vectors(case, d, 17)
+    un2, _, _ = W.global_vectors(case, d, 18)
+    return pb.assemble(np.concatenate([0.3 * u.ravel(), p]), 0.3 * un, un2=0.3 * un2 if bdf2 else None)
+
+
+@pytest.mark.parametrize("name,bdf2", [(n, False) for n in GEN_RUNS] + [("p2tri_w2", True)])
+def test_jacobian_and_residual_of_a_generic_part(runs, monkeypatch, name, bdf2):
+    """A wrong Jacobian on a part is invisible to the end-to-end runs (Newton converges on the residual alone, FGMRES with any nonsingular
+    preconditioner): every rank's owned rows of cfdh_get_csr / cfdh_get_residual, mapped to global ids, against the whole-mesh oracle to the
+    tolerance one rank is held to (tests/test_gpu_gen.py, tests/test_gpu_gen3.py: 1e-12 of the largest entry).  bdf2: BDF2 coefficients
+    and a second history vector, whose ghost values the kernels read as well."""
+    from oracle import np_twin_gen, np_twin_gen3, orcg, orcg3
+    monkeypatch.setattr(np_twin_gen, "element_tensors", orcg.element_tensors)       # the oracle assembles with its C restatement, as in the
+    monkeypatch.setattr(np_twin_gen3, "element_tensors", orcg3.element_tensors)     # one-rank tests
+    run = runs(name)
+    d, nvg = run.dim, run.nvg
+    F, J = _whole_mesh_assembly(run, bdf2)
+    tag = "2" if bdf2 else ""
+    rows_seen = np.zeros((d + 1) * nvg, dtype=np.int64)
+    gr, gc, gv = [], [], []
+    Fg = np.zeros((d + 1) * nvg)
+    for r, p in enumerate(run.parts):
+        dd = run.d[r]
+        Jr = sp.csr_matrix((dd["J%s_val" % tag], dd["J%s_col" % tag], dd["J%s_rp" % tag]), shape=tuple(int(v) for v in dd["J%s_shape" % tag]))
+        assert Jr.shape == ((d + 1) * p.nvo, (d + 1) * p.nv)
+        l2g = np.asarray(p.l2g, dtype=np.int64)
+        rmap = np.concatenate([(d * l2g[: p.nvo, None] + np.arange(d)).ravel(), d * nvg + l2g[: p.nvo]])
+        cmap = np.concatenate([(d * l2g[:, None] + np.arange(d)).ravel(), d * nvg + l2g])
+        rows_seen[rmap] += 1
+        C = Jr.tocoo()
+        gr.append(rmap[C.row]), gc.append(cmap[C.col]), gv.append(C.data)
+        ghost = np.concatenate([np.arange(d * p.nvo, d * p.nv), np.arange(d * p.nv + p.nvo, (d + 1) * p.nv)])
+        assert abs(Jr[:, ghost]).sum() > 0, "rank %d: no ghost column in an owned row" % r
+        Fg[rmap] = np.concatenate([dd["F%s_u" % tag].ravel(), dd["F%s_p" % tag]])
+    assert (rows_seen == 1).all(), "every global row is owned by exactly one rank"
+    Jg = sp.coo_matrix((np.concatenate(gv), (np.concatenate(gr), np.concatenate(gc))), shape=J.shape).tocsr()
+    eF, eJ = np.abs(Fg - F).max() / np.abs(F).max(), abs(Jg - J).max() / abs(J).max()
+    _note("%s%s: residual %.3g, Jacobian %.3g of the largest entry (allowed 1e-12)" % (name, " BDF2" if bdf2 else "", eF, eJ))
+    assert eF <= 1e-12 and eJ <= 1e-12
+    if bdf2:     # the variant is another matrix: the time-scheme coefficients reached the assembly
+        F1, J1 = _whole_mesh_assembly(run, False)
+        assert abs(J1 - J).max() > 1e-3 * abs(J).max()
 
 
 # ---------------------------------------------------------------------------------------------------------------- actions
@@ -537,7 +691,7 @@ def _gate(run, k, tag, ru, rp, part, label):
     return (zu, zp), tr
 
 
-ACTION_RUNS = ["dfg16w2", "dfg16w3", "ghostrhs", "dfg64w2", "dfg64w3", "lid48w3", "cube11w2", "layers1", "hostasm", "sweeps", "nodl0", "nodl0gather"]
+ACTION_RUNS = ["dfg16w2", "dfg16w3", "ghostrhs", "dfg64w2", "dfg64w3", "lid48w3", "cube11w2", "layers1", "hostasm", "sweeps", "nodl0", "nodl0gather"] + GEN_RUNS
 
 
 @pytest.mark.parametrize("name", ACTION_RUNS)
