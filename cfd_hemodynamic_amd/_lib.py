@@ -51,7 +51,7 @@ SYMBOLS = [
     "cfdh_create", "cfdh_create_elem", "cfdh_create_elem_part", "cfdh_set_facet_markers", "cfdh_destroy", "cfdh_last_error", "cfdh_abi_version", "cfdh_set_params", "cfdh_default_options",
     "cfdh_set_options", "cfdh_clear_dirichlet", "cfdh_add_dirichlet", "cfdh_update_dirichlet", "cfdh_set_state", "cfdh_get_solution",
     "cfdh_get_previous", "cfdh_get_residual", "cfdh_advance", "cfdh_advance_field", "cfdh_set_time_scheme", "cfdh_set_previous2", "cfdh_get_previous2",
-    "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_set_formulation", "cfdh_set_pressure_boundaries", "cfdh_set_pressure_boundaries_ex", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
+    "cfdh_shift_history", "cfdh_set_boundary_terms", "cfdh_set_formulation", "cfdh_set_pressure_boundaries", "cfdh_set_pressure_boundaries_ex", "cfdh_set_traction_boundaries", "cfdh_assemble", "cfdh_get_csr", "cfdh_spmv", "cfdh_solve_step",
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
@@ -112,6 +112,7 @@ def lib():
     L.cfdh_set_formulation.argtypes = [vp, C.c_int]
     L.cfdh_set_pressure_boundaries.argtypes = [vp, C.c_int, ip, dp, C.c_double]
     L.cfdh_set_pressure_boundaries_ex.argtypes = [vp, C.c_int, ip, dp, C.c_double, C.POINTER(C.c_uint8), dp]
+    L.cfdh_set_traction_boundaries.argtypes = [vp, C.c_int, ip, dp, C.c_double, C.POINTER(C.c_uint8), dp]
     L.cfdh_get_residual.argtypes = [vp, dp, dp]
     L.cfdh_get_previous.argtypes = [vp, dp, dp]
     L.cfdh_advance.argtypes = [vp]
@@ -358,6 +359,23 @@ class Context:
         self._chk(self.L.cfdh_set_pressure_boundaries_ex(
             self.h, len(m), _ip(m), _dp(v), float(beta_nitsche),
             None if nit is None else nit.ctypes.data_as(C.POINTER(C.c_uint8)), None if bf is None else _dp(bf)))
+
+    def set_traction_boundaries(self, markers, values, beta_nitsche=0.0, tangential=None, beta_backflow=None):
+        """Traction boundaries of the convective form on the closed-form P1 kernels (cfdh_set_traction_boundaries): values[k] v . n
+        and the viscous boundary stress on the exterior facets of markers[k]; `tangential[k]` true (None: all on) makes it the weak
+        pressure inlet with its Nitsche tangential condition, `beta_backflow[k]` > 0 (None: none) adds the backflow stabilisation.
+        A call that changes only `values` keeps the Jacobian and the preconditioner; empty lists remove the terms."""
+        m = np.ascontiguousarray(markers, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if len(m) != len(v):
+            raise ValueError("one value per traction-boundary marker")
+        tg = None if tangential is None else np.ascontiguousarray(np.asarray(tangential, dtype=bool), dtype=np.uint8).reshape(-1)
+        bf = None if beta_backflow is None else np.ascontiguousarray(beta_backflow, dtype=np.float64).reshape(-1)
+        if (tg is not None and len(tg) != len(m)) or (bf is not None and len(bf) != len(m)):
+            raise ValueError("one tangential switch and one backflow coefficient per traction-boundary marker")
+        self._chk(self.L.cfdh_set_traction_boundaries(
+            self.h, len(m), _ip(m), _dp(v), float(beta_nitsche),
+            None if tg is None else tg.ctypes.data_as(C.POINTER(C.c_uint8)), None if bf is None else _dp(bf)))
 
     def wall_shear_stress(self, download=True):
         if not download:

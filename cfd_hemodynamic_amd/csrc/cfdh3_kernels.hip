@@ -493,8 +493,9 @@ int k3_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   if (mode == 1) hipLaunchKernelGGL((asm3q_kernel<1>), dim3(c->a3_nblk), dim3(TPB), lds, c->stream, a);
   else if (mode == 2) hipLaunchKernelGGL((asm3q_kernel<2>), dim3(c->a3_nblk), dim3(TPB), sizeof(double) * 4 * 64, c->stream, a);
   else hipLaunchKernelGGL((asm3q_kernel<0>), dim3(c->a3_nblk), dim3(TPB), sizeof(double) * 4 * 64, c->stream, a);
-  prof_end(c, 0);
   HIPCHK(c, hipGetLastError());
+  if (!c->tb_markers.empty()) CHK(k_traction(c, xstate, mode));  // traction boundaries: one small launch behind the volume pass
+  prof_end(c, 0);
   if (mode == 1) c->jac_valid = true;
   return 0;
 }

@@ -7,6 +7,7 @@
 
 #include "cfdh_internal.hpp"
 #include "cfdh_ipcs.hpp"
+#include "cfdh_traction_host.hpp"
 
 std::string g_cfdh_last_error;
 
@@ -494,6 +495,8 @@ int cfdh_set_boundary_terms(cfdh_ctx *c, int ds_terms, int backflow_marker, doub
   if (beta < 0) return cfdh_fail(c, CFDH_E_ARG, "backflow beta must be >= 0");
   if (beta > 0 && c->form == CFDH_FORM_ROTATIONAL)
     return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_boundary_terms: the rotational formulation takes its backflow term per pressure boundary (cfdh_set_pressure_boundaries_ex)");
+  if (!c->tb_markers.empty() && (ds_terms != 0 || beta > 0))
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_boundary_terms: traction boundaries are set (cfdh_set_traction_boundaries): they need ds_terms = 0 and carry their own backflow term");
   if (!(beta > 0)) backflow_marker = -1;
   const bool changed = (ds_terms != 0) != c->ds_terms || beta != c->bf_beta || backflow_marker != c->bf_marker;
   c->ds_terms = ds_terms != 0; c->bf_beta = beta; c->bf_marker = backflow_marker;
@@ -522,6 +525,8 @@ int cfdh_set_facet_markers(cfdh_ctx *c, int64_t nfacets, const int32_t *markers)
   if (c->pcd_set) { c->pcd_ready = false; c->pc_valid = false; }
   // the backflow term and the pressure boundaries follow the markers: refresh the per-cell flags (invalidates Jacobian and preconditioner)
   if (c->bf_marker >= 0 || !c->pb_markers.empty()) return upload_cell_facet_flags(c);
+  // ... and so do the traction boundaries: new work list at the next assembly
+  if (!c->tb_markers.empty()) { c->tb_ready = false; c->jac_valid = false; c->pc_valid = false; }
   return 0;
 }
 
@@ -542,6 +547,8 @@ int cfdh_set_formulation(cfdh_ctx *c, int form) {
   if (form != CFDH_FORM_CONVECTIVE && form != CFDH_FORM_ROTATIONAL) return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: unknown form %d", form);
   if (form == c->form) return 0;
   if (form == CFDH_FORM_ROTATIONAL) {
+    if (!c->tb_markers.empty())
+      return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: traction boundaries are set (they belong to the convective formulation)");
     CHK(rotational_supported(c, "cfdh_set_formulation"));
     if (c->bf_marker >= 0 && c->bf_beta > 0)
       return cfdh_fail(c, CFDH_E_ARG, "cfdh_set_formulation: the rotational formulation cannot be combined with the backflow term (beta > 0)");
@@ -604,6 +611,45 @@ int cfdh_set_pressure_boundaries_ex(cfdh_ctx *c, int n, const int32_t *markers, 
   NOT_IPCS(c, "cfdh_set_pressure_boundaries_ex");
   ENTER(c);
   return set_pressure_boundaries(c, n, markers, values, beta_nitsche, nitsche, beta_backflow);
+}
+
+int cfdh_set_traction_boundaries(cfdh_ctx *c, int n, const int32_t *markers, const double *values, double beta_nitsche, const uint8_t *tangential,
+                                 const double *beta_backflow) {
+  ENTER(c);
+  const char *who = "cfdh_set_traction_boundaries";
+  if (c->ipcs) return cfdh_fail(c, CFDH_E_ARG, "%s: not available on an incremental pressure-correction context (cfdh_create_ipcs)", who);
+  std::string why;
+  if (!cfdh_traction::check_boundaries(n, CFDH_MAX_PBND, markers, values, beta_nitsche, beta_backflow, why))
+    return cfdh_fail(c, CFDH_E_ARG, "%s: %s", who, why.c_str());
+  if (n > 0) {
+    if (c->gen) return cfdh_fail(c, CFDH_E_ARG, "%s: traction boundaries exist on the closed-form P1 kernels (cfdh_create), not on the generic element kernels", who);
+    if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_ARG, "%s: not available in partitioned runs", who);
+    if (c->form != CFDH_FORM_CONVECTIVE) return cfdh_fail(c, CFDH_E_ARG, "%s: traction boundaries belong to the convective formulation", who);
+    if (c->ds_terms) return cfdh_fail(c, CFDH_E_ARG, "%s: needs ds_terms = 0 (cfdh_set_boundary_terms)", who);
+    if (c->bf_marker >= 0 && c->bf_beta > 0)
+      return cfdh_fail(c, CFDH_E_ARG, "%s: the backflow term of cfdh_set_boundary_terms is active; give it per boundary (beta_backflow)", who);
+  }
+  unsigned tang = 0;
+  std::vector<double> bf((size_t)n, 0.0);
+  for (int k = 0; k < n; k++) {
+    if (!tangential || tangential[k]) tang |= 1u << k;
+    if (beta_backflow) bf[k] = beta_backflow[k];
+  }
+  bool same = (size_t)n == c->tb_markers.size() && beta_nitsche == c->tb_beta && tang == c->tb_tangential;
+  for (int k = 0; same && k < n; k++) same = markers[k] == c->tb_markers[k] && bf[k] == c->tb_backflow[k];
+  if (n == 0 && same) return 0;
+  c->tb_values.assign(values, values + n);
+  if (!same) {
+    c->tb_markers.assign(markers, markers + n);
+    c->tb_beta = beta_nitsche;
+    c->tb_tangential = tang;
+    c->tb_backflow = bf;
+    c->tb_ready = false;
+    c->jac_valid = false;
+    c->pc_valid = false;
+  }
+  if (n > 0) CHK(cfdh_traction_upload_coef(c));  // values only: they enter the residual, Jacobian and preconditioner stay valid
+  return 0;
 }
 
 int cfdh_set_schur_pcd(cfdh_ctx *c, int inlet_marker, int outlet_marker, int time_term) {
@@ -1575,6 +1621,8 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 77: return c->form;
     case 78: return c->opt.pc_type;   // Schur approximation in use: 0 SELFP, 1 Cahouet-Chabard, 2 PCD
     case 79: return c->ew_version;    // Eisenstat-Walker forcing version (0: off)
+    case 93: return (int64_t)c->tb_markers.size();  // traction boundaries set (cfdh_set_traction_boundaries)
+    case 94: return c->n_traction_launches;          // launches of the traction kernel since cfdh_create
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;

@@ -303,6 +303,17 @@ struct cfdh_ctx {
   double pb_beta = 0.0;              // Nitsche penalty beta of the tangential condition
   unsigned pb_nitsche = 0;           // bit k: boundary k carries the three tangential (Nitsche) terms (cfdh_set_pressure_boundaries_ex)
   std::vector<double> pb_backflow;   // per boundary: coefficient of the backflow term -beta_bf rho (u_prev . n)_- (u_mid . v), 0: none
+  // cfdh_set_traction_boundaries: traction boundaries of the convective form on the closed-form P1 kernels (cfdh_traction.hip)
+  std::vector<int> tb_markers;       // facet markers of the traction boundaries, at most CFDH_MAX_PBND
+  std::vector<double> tb_values;     // their values (residual only)
+  std::vector<double> tb_backflow;   // per boundary: coefficient of the backflow term, 0: none
+  double tb_beta = 0.0;              // Nitsche penalty of the tangential condition
+  unsigned tb_tangential = 0;        // bit k: boundary k carries the tangential terms
+  bool tb_ready = false;             // work list built for the current markers and switches
+  int tb_nrows = 0, tb_nslices = 0;  // destination rows, slices of 64 rows (cfdh_traction_host.hpp)
+  dbuf<int> tb_row, tb_sptr, tb_cell, tb_meta, tb_slot;
+  dbuf<double> tb_coef;              // values, then backflow coefficients, CFDH_MAX_PBND each
+  long long n_traction_launches = 0; // cfdh_info 94
   bool state_set = false;
 
   // reductions
@@ -586,6 +597,11 @@ int cfdh_pcd_supported(cfdh_ctx *c, const char *who);  // 0, or CFDH_E_ARG with 
 int cfdh_pcd_setup(cfdh_ctx *c);                       // incidences, inlet facets, SELL layout, 1 / diag(M)
 int k_pcd_assemble(cfdh_ctx *c, const double *xstate);  // K at the iterate xstate
 int k_pcd_apply(cfdh_ctx *c, const double *r, double *s);  // t = r / m_d, s = K t, q
+
+// ---- traction boundaries of the convective form on the closed-form P1 kernels (cfdh_traction.hip) -----------------------
+int cfdh_traction_setup(cfdh_ctx *c);        // work list for the current markers and switches
+int cfdh_traction_upload_coef(cfdh_ctx *c);  // values and backflow coefficients
+int k_traction(cfdh_ctx *c, const double *xstate, int mode);  // facet terms into F and A00, after the volume pass
 
 // ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------
 int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out [nvert][dim]: entries of the wall vertices only

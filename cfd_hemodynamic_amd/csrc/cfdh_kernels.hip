@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <utility>
 
 #include "cfdh_internal.hpp"
 #include "cfdh_quad_tri.h"
@@ -586,8 +587,9 @@ int k_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   else if (!hist2 && bf) CFDH_ASM_LAUNCH(false, true);
   else CFDH_ASM_LAUNCH(true, true);
 #undef CFDH_ASM_LAUNCH
-  prof_end(c, 0);
   HIPCHK(c, hipGetLastError());
+  if (!c->tb_markers.empty()) CHK(k_traction(c, xstate, mode));  // traction boundaries: one small launch behind the volume pass
+  prof_end(c, 0);
 #ifdef CFDH_ASM_TIMING
   if (mode == 1 && (++dbg_calls % 20) == 0) {
     std::vector<long long> h(8 * (size_t)c->nblk);
@@ -1306,6 +1308,13 @@ int k_wss(cfdh_ctx *c, double *out) {
 int k_functional(cfdh_ctx *c, int kind, int marker, double *out) {
   const int nb = 256;
   int nval = 2;  // rows of partial sums the kernel writes
+  if (kind == 8) {
+    // flux of u_prev: the kernels of kind 7 (every element family) read the iterate through c->x, so they run on the other vector
+    std::swap(c->x.p, c->xprev.p);
+    const int rc = k_functional(c, 7, marker, out);
+    std::swap(c->x.p, c->xprev.p);
+    return rc;
+  }
   if (kind >= 4 && kind <= 6) {
     const double *a = kind == 5 ? c->xprev.p : c->x.p;
     const double *b = kind == 6 ? c->xprev.p : nullptr;

@@ -17,7 +17,12 @@ Tolerance caveat (inherited, not changed): the solver removes the pressure mean 
 outlet rows.  On this millimetre-sized mesh the momentum and continuity rows are ~1e-9 of that misfit, so `snes_rtol`
 relative to it is met before those rows are solved; from ~1e6 DOF on the steps after the first then end after one Krylov
 iteration with a meaningless field.  `options={"remove_p_mean": 0}` skips the removal (the solve is then relative to the
-PDE rows alone); bench.py --config c5b does so and says so in its `config`."""
+PDE rows alone); bench.py --config c5b does so and says so in its `config`.
+
+Pressure-driven: with `--solver stabilized_schur_pressure_backflow --p_inlet P --R_resistance R` (solver keywords, in the
+non-dimensional units of this scenario) the inlet profile is not imposed: walls no-slip only, the inlet (tag 8) is the solver's weak
+pressure boundary, outlet 1 (tag 9, the scenario's `outlet` tag) its resistance outlet; `bcp` is ignored by that solver, which
+leaves outlet 2 (tag 10) a do-nothing boundary."""
 from __future__ import annotations
 
 import numpy as np
@@ -65,6 +70,8 @@ class MicrovasculatureSimulation(Scenario):
     inlet_marker = inlet_tag
     outlet_marker = outlet1_tag
     wall_marker = wall_tag
+    # solvers that drive the flow by `p_inlet` (a solver keyword) instead of the inlet profile
+    _pressure_driven = ("stabilized_schur_pressure_backflow",)
 
     @property
     def mesh(self):
@@ -95,6 +102,9 @@ class MicrovasculatureSimulation(Scenario):
             walls = self._ft.find(self.wall_tag)
             bc_w = BoundaryCondition(Function(self.solver.V))
             bc_w.initTopological(fdim, walls)
+            if self.solver_name in self._pressure_driven:
+                self._bcu = [bc_w]  # the inlet is a weak pressure boundary of the solver: walls only
+                return self._bcu
             u_in = Function(self.solver.V)
             u_in.interpolate(self.inlet_velocity(self.v_inlet, self.r_mesh_in))
             rim = np.unique(self.mesh.facet_vertices[walls])

@@ -264,6 +264,34 @@ int cfdh_set_pressure_boundaries(cfdh_ctx *ctx, int n, const int32_t *markers, c
 int cfdh_set_pressure_boundaries_ex(cfdh_ctx *ctx, int n, const int32_t *markers, const double *values, double beta_nitsche,
                                     const uint8_t *nitsche, const double *beta_backflow);
 
+/* ---- pressure-driven flow on the closed-form P1 kernels (the `stabilized_schur_pressure_backflow` variant) -------- */
+
+/* Traction boundaries of the CONVECTIVE form (stabilized_schur_pressure_backflow.py:191-217; its volume form is the one of
+ * stabilized_schur_backflow.py, which the closed-form kernels assemble).  On the exterior facets whose marker is markers[k]
+ * (k < n <= 8, distinct), with outward normal n, ubar = theta u + (1 - theta) u_prev of the time scheme in force,
+ * w_T = w - (w . n) n and the owning cell's size h (largest vertex distance, the h of tau), F_v gains
+ *   always                 + values[k] int v . n                                                          (residual only)
+ *   tangential[k] != 0     - int (2 mu eps(ubar) n) . v_T - int (2 mu eps(v) n) . ubar_T + (beta_nitsche mu / h) int ubar_T . v_T
+ *                          (the weak pressure inlet with its Nitsche tangential condition, :191-201)
+ *   tangential[k] == 0     - int (2 mu eps(ubar) n) . v                                          (the outlet, :208-209)
+ *   beta_backflow[k] > 0   - beta_backflow[k] rho int (u_prev . n)_- ubar . v,  (s)_- = (s - |s|) / 2        (:213-217)
+ * tangential NULL: all on; beta_backflow NULL: all 0.  The backflow term is integrated with the facet rule of
+ * cfdh_set_boundary_terms (2-point Gauss on edges, 6-point Strang-Fix on triangles), everything else in closed form.  The
+ * Jacobian is theta times the ubar-derivative; all of it lies in A00 on couplings of the vertices of one cell (the symmetry term
+ * reaches the row of the vertex opposite the facet as well).  values[k] and the pressure do not enter it: the caller passes the
+ * value the form should see (the reference's outlet passes p_c / 2).  One extra kernel per assembly, behind the volume pass; a
+ * context without traction boundaries never launches it (cfdh_info 93: boundaries set, 94: launches since creation).
+ * A call that changes only `values` keeps Jacobian and preconditioner valid; any other change, and a cfdh_set_facet_markers call
+ * while boundaries are set, invalidates both.  n = 0 removes the terms.
+ * Contexts: closed-form P1 contexts of cfdh_create (gdim 2 and 3), the whole mesh on one GPU, CFDH_FORM_CONVECTIVE, ds_terms = 0
+ * and no backflow term of cfdh_set_boundary_terms.  CFDH_E_ARG, with the context unchanged, on generic-element contexts, on
+ * contexts of cfdh_create_ipcs, on a part of a partitioned run, in the rotational form, with ds_terms != 0 or an active backflow
+ * term, for non-finite or negative coefficients, non-finite values and duplicate markers.  While boundaries are set,
+ * cfdh_set_boundary_terms with ds_terms != 0 or beta > 0 and cfdh_set_formulation(CFDH_FORM_ROTATIONAL) return CFDH_E_ARG.
+ * With ds_terms = 0 the preconditioner's pressure Laplacian takes Dirichlet rows on the open facets, these boundaries included. */
+int cfdh_set_traction_boundaries(cfdh_ctx *ctx, int n, const int32_t *markers, const double *values, double beta_nitsche,
+                                 const uint8_t *tangential, const double *beta_backflow);
+
 /* ---- pressure convection-diffusion preconditioner and forcing (the `stabilized_pcd` variant) ---------------- */
 
 /* Data of the PCD Schur approximation selected by cfdh_options.pc_type = 2 (fenicsx_pctools.pc.PCDPC_vY of
@@ -549,7 +577,8 @@ int cfdh_solve_step(cfdh_ctx *ctx, cfdh_stats *stats);
  * 2: ||u||_L2, 3: ||p||_L2 (/root/reference/src/scenario.py:315-324),
  * 4: ||u_sol||_inf, 5: ||u_prev||_inf, 6: ||u_sol-u_prev||_inf (scenario.py:268-280),
  * 7: volume flux  int u_sol . n ds  over the exterior facets of `marker` (outward normal; the outlet flow rates the
- * tree and bifurcation scenarios report).  Kinds 0/1 exist for gdim 2 only.
+ * tree and bifurcation scenarios report), 8: the same flux of u_prev (the resistance outlet of
+ * stabilized_schur_pressure_backflow.py:204-207, :383-392 is driven by it).  Kinds 0/1 exist for gdim 2 only.
  * Sums/maxima over the owned part; the caller (or the communicator) reduces. */
 int cfdh_functional(cfdh_ctx *ctx, int kind, int marker, double *out);
 
@@ -639,7 +668,8 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 74: preconditioner builds since cfdh_create, 75: 1 while the preconditioner is valid (built, not invalidated since), 76: 1 when the
  * last null-space test of cfdh_solve_step found the constant pressure in the null space of the Jacobian, 77: formulation (CFDH_FORM_*),
  * 78: Schur approximation in use (cfdh_options.pc_type: 0 SELFP, 1 Cahouet-Chabard, 2 PCD), 79: Eisenstat-Walker forcing version;
- * 90: accumulations of the wall shear indices since the last cfdh_wall_stats_reset (every context kind) */
+ * 90: accumulations of the wall shear indices since the last cfdh_wall_stats_reset (every context kind);
+ * 93: traction boundaries set (cfdh_set_traction_boundaries), 94: launches of the traction kernel since cfdh_create */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
