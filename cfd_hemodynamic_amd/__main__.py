@@ -2,7 +2,9 @@
 -- the `simulate` sub-command of the reference's CLI (/root/reference/main.py:87-139,253-254);
 unknown `--key value` pairs are literal-evaluated and passed to the scenario (main.py:12-31).
 `--wall_indices_from T0 --wall_indices_to T1` (defaults 0 and T; either switches it on) writes the cycle-averaged wall shear
-indices of that window next to the other results (wall_indices.npz / .vtu / .txt)."""
+indices of that window next to the other results (wall_indices.npz / .vtu / .txt).
+`--transport age` or `--transport bolus [--bolus_from T0 --bolus_to T1]` (defaults 0 and T), with `--transport_diffusivity D`, steps a
+passive scalar on the device behind every flow step and writes transport.npz and the `transport` VTU series."""
 from __future__ import annotations
 
 import argparse
@@ -44,6 +46,11 @@ def main(argv=None):
     # cycle-averaged wall shear indices (TAWSS, OSI, RRT) over the steps that end in (from, to]; either switch turns them on
     s.add_argument("--wall_indices_from", type=float, default=None)
     s.add_argument("--wall_indices_to", type=float, default=None)
+    # passive scalar on the device: blood age, or a contrast bolus with inlet c = 1 for the steps that end in (bolus_from, bolus_to]
+    s.add_argument("--transport", choices=["age", "bolus"], default=None)
+    s.add_argument("--transport_diffusivity", type=float, default=0.0)
+    s.add_argument("--bolus_from", type=float, default=None)
+    s.add_argument("--bolus_to", type=float, default=None)
     args, extra = ap.parse_known_args(argv)
     kw = _parse_extra(extra)
     try:
@@ -58,6 +65,12 @@ def main(argv=None):
     if args.wall_indices_from is not None or args.wall_indices_to is not None:
         solve_kw["wall_indices"] = (0.0 if args.wall_indices_from is None else args.wall_indices_from,
                                     args.T if args.wall_indices_to is None else args.wall_indices_to)
+    if args.transport == "age":
+        solve_kw["transport"] = "age"
+    elif args.transport == "bolus":
+        solve_kw["transport"] = ("bolus", 0.0 if args.bolus_from is None else args.bolus_from, args.T if args.bolus_to is None else args.bolus_to)
+    if args.transport:
+        solve_kw["transport_diffusivity"] = args.transport_diffusivity
     sim.solve(out, **solve_kw)
     print("results in", out)
     return 0

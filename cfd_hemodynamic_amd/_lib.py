@@ -43,6 +43,10 @@ class IpcsStats(C.Structure):
     ]
 
 
+class ScalarStats(C.Structure):
+    _fields_ = [("its", C.c_int32), ("reason", C.c_int32), ("rel_res", C.c_double), ("ms_assemble", C.c_double), ("ms_total", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, C.c_int, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, dp)
 
@@ -59,6 +63,8 @@ SYMBOLS = [
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
     "cfdh_ipcs_apply_pressure_pc", "cfdh_ipcs_krylov_solve", "cfdh_ipcs_set_scheme", "cfdh_ipcs_get_block_operator",
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
+    "cfdh_scalar_enable", "cfdh_scalar_set_dirichlet", "cfdh_scalar_set_state", "cfdh_scalar_get_state", "cfdh_scalar_set_tolerances",
+    "cfdh_scalar_step", "cfdh_scalar_get_operator", "cfdh_scalar_functional",
 ]
 
 
@@ -156,6 +162,14 @@ def lib():
     L.cfdh_wall_stats_reset.argtypes = [vp]
     L.cfdh_wall_stats_accumulate.argtypes = [vp, C.c_double]
     L.cfdh_wall_stats_get.argtypes = [vp, C.c_int, lp, dp]
+    L.cfdh_scalar_enable.argtypes = [vp, C.c_double, C.c_double, C.c_double]
+    L.cfdh_scalar_set_dirichlet.argtypes = [vp, C.c_int64, ip, dp]
+    L.cfdh_scalar_set_state.argtypes = [vp, dp]
+    L.cfdh_scalar_get_state.argtypes = [vp, dp]
+    L.cfdh_scalar_set_tolerances.argtypes = [vp, C.c_double, C.c_double, C.c_int32]
+    L.cfdh_scalar_step.argtypes = [vp, C.POINTER(ScalarStats)]
+    L.cfdh_scalar_get_operator.argtypes = [vp, lp, ip, ip, dp, dp]
+    L.cfdh_scalar_functional.argtypes = [vp, C.c_int, C.c_int, dp]
     _LIB = L
     return L
 
@@ -207,6 +221,9 @@ EW_DEFAULTS = (0.3, 0.9, 1.0, (1.0 + 5.0 ** 0.5) / 2.0, 0.1)
 # cfdh_wall_stats_get
 WALL_TAWSS, WALL_OSI, WALL_RRT, WALL_MEAN, WALL_PEAK, WALL_TOTALS = range(6)
 INFO_WALL_STATS_COUNT = 90  # cfdh_info: accumulations since the last cfdh_wall_stats_reset
+# cfdh_scalar_functional; cfdh_info: scalar enabled, scalar steps taken, launches of the scalar assembly kernel
+SCALAR_INTEGRAL, SCALAR_FLUX, SCALAR_MIN, SCALAR_MAX = range(4)
+INFO_SCALAR_ENABLED, INFO_SCALAR_STEPS, INFO_SCALAR_ASSEMBLIES = 95, 96, 97
 
 
 class Context:
@@ -562,6 +579,62 @@ class Context:
                                             float(scalar), int(flags), _dp(out1), _dp(out2), out32.ctypes.data_as(C.POINTER(C.c_float)),
                                             _ip(cnt), _dp(host), _dp(dev), _dp(mir)))
         return {"out1": out1, "out2": out2, "out32": out32, "host": host[:cnt[0]], "dev": dev[:cnt[1]], "mirror": mir[:cnt[2]]}
+
+    # -- passive scalar transport (cfdh_scalar_*): closed-form P1 contexts, one GPU ------------------------------------
+    def scalar_enable(self, D=0.0, s=0.0, theta_c=0.5):
+        """dc/dt + w . grad c - D lap c = s on the vertices, advected by the flow step's velocity; allocates on first use, a
+        later call changes the parameters and keeps c."""
+        self._chk(self.L.cfdh_scalar_enable(self.h, float(D), float(s), float(theta_c)))
+
+    def scalar_set_dirichlet(self, nodes, values):
+        """Replaces the Dirichlet set of the scalar; empty arrays clear it."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        values = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.float64), nodes.shape))
+        self._chk(self.L.cfdh_scalar_set_dirichlet(self.h, len(nodes), _ip(nodes), _dp(values)))
+
+    def scalar_state(self, c=None):
+        """Without an argument: the scalar field [nv]; with one: sets it."""
+        if c is None:
+            out = np.empty(self.nv)
+            self._chk(self.L.cfdh_scalar_get_state(self.h, _dp(out)))
+            return out
+        c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+        if c.size != self.nv:
+            raise ValueError("one value per vertex expected")
+        self._chk(self.L.cfdh_scalar_set_state(self.h, _dp(c)))
+        return None
+
+    def scalar_set_tolerances(self, rtol=1e-8, atol=1e-50, max_it=1000):
+        self._chk(self.L.cfdh_scalar_set_tolerances(self.h, float(rtol), float(atol), int(max_it)))
+
+    def scalar_step(self):
+        """One transport step, after solve_step() and before advance()."""
+        st = ScalarStats()
+        rc = self.L.cfdh_scalar_step(self.h, C.byref(st))
+        if rc != 0:
+            msg = self.L.cfdh_last_error(self.h).decode()
+            if rc == -4:
+                raise RuntimeError("Did not converge, reason: %d. (%s)" % (st.reason, msg))
+            _raise(rc, msg)
+        return st
+
+    def scalar_operator(self):
+        """(left-hand matrix as scipy CSR [nv x nv], right-hand side [nv]) of the next transport step at the current state."""
+        import scipy.sparse as sp
+        nnz = C.c_int64()
+        self._chk(self.L.cfdh_scalar_get_operator(self.h, C.byref(nnz), None, None, None, None))
+        rowptr = np.empty(self.nv + 1, dtype=np.int32)
+        col = np.empty(nnz.value, dtype=np.int32)
+        val = np.empty(nnz.value)
+        rhs = np.empty(self.nv)
+        self._chk(self.L.cfdh_scalar_get_operator(self.h, C.byref(nnz), _ip(rowptr), _ip(col), _dp(val), _dp(rhs)))
+        return sp.csr_matrix((val, col, rowptr), shape=(self.nv, self.nv)), rhs
+
+    def scalar_functional(self, kind, marker=0):
+        """SCALAR_INTEGRAL, SCALAR_FLUX (through the facets of `marker`), SCALAR_MIN, SCALAR_MAX."""
+        out = C.c_double()
+        self._chk(self.L.cfdh_scalar_functional(self.h, int(kind), int(marker), C.byref(out)))
+        return out.value
 
     def get_amg_operator(self, hier, level, which, raw=False):
         """One operator of a built hierarchy as scipy CSR (AMG_HIER_*, AMG_OP_*); level-0 indices in the caller's numbering.

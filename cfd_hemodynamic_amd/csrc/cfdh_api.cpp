@@ -183,6 +183,7 @@ void cfdh_destroy(cfdh_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   cfdh_ipcs_free(c);
+  cfdh_scalar_free(c);
   comm_finalize(c);
   c->hS.clear(); c->hL.clear(); c->hA.clear(); c->hLg.clear();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1623,6 +1624,9 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 79: return c->ew_version;    // Eisenstat-Walker forcing version (0: off)
     case 93: return (int64_t)c->tb_markers.size();  // traction boundaries set (cfdh_set_traction_boundaries)
     case 94: return c->n_traction_launches;          // launches of the traction kernel since cfdh_create
+    case 95: return c->sc ? 1 : 0;                   // passive scalar enabled (cfdh_scalar_enable)
+    case 96: return c->n_scalar_steps;               // scalar steps taken
+    case 97: return c->n_scalar_asm;                 // launches of the scalar assembly kernel since cfdh_create
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;
@@ -1634,6 +1638,53 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 25: { const AmgHier &h = c->opt.pc_type >= 1 ? c->hL : c->hS; return h.fused ? 1 : 0; }
     default: return -1;
   }
+}
+
+// ---- passive scalar transport (cfdh_scalar.hip) --------------------------------------------------------------------------------
+
+int cfdh_scalar_enable(cfdh_ctx *c, double D, double s, double theta_c) {
+  ENTER(c);
+  return cfdh_scalar_enable_impl(c, D, s, theta_c);
+}
+
+int cfdh_scalar_set_dirichlet(cfdh_ctx *c, int64_t n, const int32_t *nodes, const double *values) {
+  ENTER(c);
+  return cfdh_scalar_set_dirichlet_impl(c, n, nodes, values);
+}
+
+int cfdh_scalar_set_state(cfdh_ctx *c, const double *cc) {
+  ENTER(c);
+  if (!cc) return cfdh_fail(c, CFDH_E_ARG, "cfdh_scalar_set_state: null array");
+  return cfdh_scalar_state_impl(c, cc, nullptr);
+}
+
+int cfdh_scalar_get_state(cfdh_ctx *c, double *cc) {
+  ENTER(c);
+  if (!cc) return cfdh_fail(c, CFDH_E_ARG, "cfdh_scalar_get_state: null array");
+  return cfdh_scalar_state_impl(c, nullptr, cc);
+}
+
+int cfdh_scalar_set_tolerances(cfdh_ctx *c, double rtol, double atol, int32_t max_it) {
+  ENTER(c);
+  return cfdh_scalar_set_tolerances_impl(c, rtol, atol, max_it);
+}
+
+int cfdh_scalar_step(cfdh_ctx *c, cfdh_scalar_stats *stats) {
+  ENTER(c);
+  c->err.clear();
+  return cfdh_scalar_step_impl(c, stats);
+}
+
+int cfdh_scalar_get_operator(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *rhs) {
+  if (!c || !nnz) return CFDH_E_ARG;
+  ENTER(c);
+  return cfdh_scalar_get_operator_impl(c, nnz, rowptr, col, vals, rhs);
+}
+
+int cfdh_scalar_functional(cfdh_ctx *c, int kind, int marker, double *out) {
+  if (!out) return CFDH_E_ARG;
+  ENTER(c);
+  return cfdh_scalar_functional_impl(c, kind, marker, out);
 }
 
 // ---- incremental pressure correction (cfdh_ipcs.hip, cfdh_ipcs_krylov.hip, cfdh_ipcs_setup.cpp) ----------------------------------------------------------------------

@@ -179,6 +179,7 @@ struct ProfSlot {
 };
 
 struct IpcsData;  // incremental pressure-correction context (cfdh_ipcs.hpp)
+struct ScalarData;  // passive scalar transport of a closed-form P1 context (cfdh_scalar.hip)
 
 struct cfdh_ctx {
   int device = 0;
@@ -493,6 +494,9 @@ struct cfdh_ctx {
   int guess_last_rank = -1, guess_last_k = 0;  // rank and size of the last Gram system of a projected guess (cfdh_info 88, 89)
   long long n_iter_sync = 0;                 // host synchronisations inside the FGMRES cycles: batches of iterations, re-orthogonalisations (cfdh_info 87), reset likewise
   long long n_cycles = 0;                    // FGMRES cycles whose true residual was read back (cfdh_info 84), reset with the counters 13..17
+  // passive scalar transport (cfdh_scalar_*, cfdh_scalar.hip): everything it owns, allocated by the first cfdh_scalar_enable
+  ScalarData *sc = nullptr;
+  long long n_scalar_steps = 0, n_scalar_asm = 0;  // cfdh_info 96, 97
 };
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
@@ -602,6 +606,16 @@ int k_pcd_apply(cfdh_ctx *c, const double *r, double *s);  // t = r / m_d, s = K
 int cfdh_traction_setup(cfdh_ctx *c);        // work list for the current markers and switches
 int cfdh_traction_upload_coef(cfdh_ctx *c);  // values and backflow coefficients
 int k_traction(cfdh_ctx *c, const double *xstate, int mode);  // facet terms into F and A00, after the volume pass
+
+// ---- passive scalar transport on the closed-form P1 contexts (cfdh_scalar.hip; the entry points of include/cfdh.h minus ENTER) ----
+int cfdh_scalar_enable_impl(cfdh_ctx *c, double D, double s, double theta);
+int cfdh_scalar_set_dirichlet_impl(cfdh_ctx *c, int64_t n, const int32_t *nodes, const double *values);
+int cfdh_scalar_state_impl(cfdh_ctx *c, const double *set, double *get);
+int cfdh_scalar_set_tolerances_impl(cfdh_ctx *c, double rtol, double atol, int max_it);
+int cfdh_scalar_step_impl(cfdh_ctx *c, cfdh_scalar_stats *st);
+int cfdh_scalar_get_operator_impl(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *rhs);
+int cfdh_scalar_functional_impl(cfdh_ctx *c, int kind, int marker, double *out);
+void cfdh_scalar_free(cfdh_ctx *c);
 
 // ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------
 int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out [nvert][dim]: entries of the wall vertices only

@@ -118,12 +118,22 @@ class Scenario(ABC):
             print(f"Suggested cores: {(nV + nQ) / 20000:.1f}")
 
     def solve(self, output_folder: str = None, afterStepCallback: Callable[[float], None] = None,
-              device_resident: bool = True, max_steps: int = None, write_every: int = 1, wall_indices=None) -> str:
+              device_resident: bool = True, max_steps: int = None, write_every: int = 1, wall_indices=None, transport=None,
+              transport_diffusivity: float = 0.0) -> str:
         """wall_indices: None (default) -- nothing; True -- the cycle-averaged wall shear indices (TAWSS, OSI, RRT, mean and peak
         wall shear stress: wall_indices.py) over the whole run; (t0, t1) -- over the steps that end in (t0, t1].  They are accumulated
         on the device with weight dt right after the step's `assemble_wss()`; afterwards `self.wall_indices` holds the fields, `W` and
-        `steps`, and with an output folder wall_indices.npz / .vtu / .txt are written."""
+        `steps`, and with an output folder wall_indices.npz / .vtu / .txt are written.
+
+        transport: None (default) -- nothing; "age" -- blood age: source 1, c = 0 on the nodes of the facets tagged tags["inlet"];
+        ("bolus", t0, t1) -- a contrast bolus: no source, inlet c = 1 for the steps that end in (t0, t1], 0 otherwise.  A passive
+        scalar with diffusivity `transport_diffusivity`, stepped on the device right after the flow step and before the state is
+        advanced (closed-form P1 solvers on one GPU; NotImplementedError elsewhere).  A scenario without an inlet tag runs with no
+        Dirichlet set.  The field joins the VTU series as the point field `transport`; afterwards `self.transport` holds the field
+        and the per-step integral, and with an output folder transport.npz is written."""
         mesh, T, solver = self.mesh, self.T, self.solver
+        self.transport = None
+        tr = self._transport_setup(transport, transport_diffusivity)
         self.wall_indices = None
         if wall_indices is not None and wall_indices is not True:
             wall_indices = (float(wall_indices[0]), float(wall_indices[1]))
@@ -146,6 +156,8 @@ class Scenario(ABC):
                        VTUWriter(mesh.comm, f"{output_folder}/u_residual.bp", solver.u_residual, "u_residual"),
                        VTUWriter(mesh.comm, f"{output_folder}/p_residual.bp", solver.p_residual, "p_residual"),
                        VTUWriter(mesh.comm, f"{output_folder}/wss.bp", solver.shear_stress, "shear_stress")]
+            if tr is not None:
+                writers.append(VTUWriter(mesh.comm, f"{output_folder}/transport.bp", tr["function"], "transport"))
         t = 0.0
         solver.u_sol.interpolate(self.initial_velocity)
         if writers:
@@ -179,6 +191,8 @@ class Scenario(ABC):
                 self.errors.append((t, error))
                 if error_log:
                     error_log.write("t = %.3f: error = %.3g" % (t, error) + "\n")
+            if tr is not None:
+                self._transport_step(tr, t, bool(writers) and i % write_every == 0)
             solver.assemble_wss()
             if wall_indices is not None and step_in_window(t, self.dt, wall_indices):
                 solver.wall_stats_accumulate(self.dt)
@@ -241,11 +255,54 @@ class Scenario(ABC):
                     write_outputs(output_folder, solver.shear_stress.function_space.mesh, fields, fields["W"], fields["steps"])
             elif mesh.comm.rank == 0:
                 print("wall_indices: no step ended inside the window %s (the run stopped at t=%.6g): nothing written" % (wall_indices, t))
+        if tr is not None:
+            self.transport = {"mode": tr["mode"], "field": np.asarray(solver.transport_field()), "integral": np.array(tr["integral"]),
+                              "times": np.array(tr["times"]), "iterations": np.array(tr["its"], dtype=np.int64)}
+            if output_folder and mesh.comm.rank == 0:
+                np.savez(os.path.join(output_folder, "transport.npz"), x=mesh.x, cells=mesh.cells,
+                         **{k: v for k, v in self.transport.items() if k != "mode"})
         for w in writers:
             w.close()
         if error_log:
             error_log.close()
         return output_folder
+
+    def _transport_setup(self, transport, diffusivity):
+        """Parses `transport` of solve(), enables the scalar on the solver and sets the inlet Dirichlet set; None when off."""
+        if transport is None:
+            return None
+        if isinstance(transport, str):
+            transport = (transport,)
+        mode = transport[0]
+        if mode == "age" and len(transport) == 1:
+            window, source = None, 1.0
+        elif mode == "bolus" and len(transport) == 3:
+            window, source = (float(transport[1]), float(transport[2])), 0.0
+        else:
+            raise ValueError('transport must be None, "age" or ("bolus", t0, t1)')
+        solver = self.solver
+        inlet, ft = self.tags.get("inlet"), self.facet_tags
+        nodes = np.zeros(0, dtype=np.int32)
+        if inlet is not None and ft is not None:
+            nodes = np.unique(np.asarray(self.mesh.facet_vertices)[ft.find(inlet)]).astype(np.int32)
+        solver.transport_enable(D=float(diffusivity), s=source, theta_c=0.5, nodes=nodes, values=0.0)
+        solver.transport_field(np.zeros(self.mesh.num_vertices))
+        fn = Function(solver.Q, name="transport")
+        return {"mode": mode, "window": window, "nodes": nodes, "value": 0.0, "function": fn, "integral": [], "times": [], "its": []}
+
+    def _transport_step(self, tr, t, write):
+        solver = self.solver
+        if tr["window"] is not None and len(tr["nodes"]):
+            value = 1.0 if tr["window"][0] < t - 1e-12 * self.dt and t <= tr["window"][1] + 1e-12 * self.dt else 0.0
+            if value != tr["value"]:
+                solver.transport_set_dirichlet(tr["nodes"], value)
+                tr["value"] = value
+        st = solver.transport_step()
+        tr["integral"].append(solver.transport_functional(0))
+        tr["times"].append(t)
+        tr["its"].append(st.its)
+        if write:
+            tr["function"].x.array[:] = solver.transport_field()
 
     @staticmethod
     def _mass_weights(mesh):

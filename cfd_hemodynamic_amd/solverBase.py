@@ -120,6 +120,54 @@ class SolverBase(ABC):
         np.add.at(out, fv[:, 0], 0.5 * Tt)
         np.add.at(out, fv[:, 1], 0.5 * Tt)
 
+    # -- passive scalar transport on the device (cfdh_scalar_*: blood age, contrast bolus) -----------------------------------
+    def _transport_ctx(self):
+        """The context, when the scalar exists on it: closed-form P1 kernels, whole mesh on one GPU.  Raises before any device work
+        otherwise."""
+        from . import _lib
+        ctx = getattr(self, "ctx", None)
+        comm = getattr(self, "_comm", None)
+        why = None
+        if ctx is None:
+            why = "the solver holds no device context"
+        elif isinstance(ctx, _lib.IpcsContext):
+            why = "the pressure-correction (IPCS) solvers have no passive scalar"
+        elif int(getattr(ctx, "etype", 0)) != 0:
+            why = "the passive scalar runs on the closed-form P1 kernels, not on the generic-element (P2 / Q1) contexts"
+        elif getattr(self, "_part", None) is not None or (comm is not None and comm.size > 1):
+            why = "the passive scalar runs on one GPU, not on a part of a partitioned run"
+        if why:
+            raise NotImplementedError("transport: " + why)
+        return ctx
+
+    def transport_enable(self, D=0.0, s=0.0, theta_c=0.5, nodes=None, values=None, rtol=None):
+        """Switch on dc/dt + w . grad c - D lap c = s on the vertices (c = 0 at first use; a later call keeps c).  `nodes` /
+        `values`: the Dirichlet set (None keeps it)."""
+        ctx = self._transport_ctx()
+        ctx.scalar_enable(D, s, theta_c)
+        if rtol is not None:
+            ctx.scalar_set_tolerances(rtol=float(rtol))
+        if nodes is not None:
+            ctx.scalar_set_dirichlet(nodes, 0.0 if values is None else values)
+
+    def transport_set_dirichlet(self, nodes, values):
+        """Replace the Dirichlet set of the scalar (empty: none)."""
+        self._transport_ctx().scalar_set_dirichlet(nodes, values)
+
+    def transport_functional(self, kind, marker=0):
+        """0: int c dx, 1: int c (u_sol . n) ds over the facets of `marker`, 2 / 3: min / max."""
+        return self._transport_ctx().scalar_functional(kind, marker)
+
+    def transport_step(self):
+        """One step with the velocity of the flow step just solved: call after solveStep() and before advance() / the copy of
+        u_sol into u_prev."""
+        self.last_transport_stats = self._transport_ctx().scalar_step()
+        return self.last_transport_stats
+
+    def transport_field(self, c=None):
+        """The scalar on the vertices [nv]; with an argument: sets it."""
+        return self._transport_ctx().scalar_state(c)
+
     @staticmethod
     def _simplex_gradients(mesh):
         """grad(lambda_a) of every cell of a P1 simplex mesh, [nc, d + 1, d]."""

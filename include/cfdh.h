@@ -608,6 +608,62 @@ int cfdh_wall_stats_reset(cfdh_ctx *ctx);
 int cfdh_wall_stats_accumulate(cfdh_ctx *ctx, double weight);
 int cfdh_wall_stats_get(cfdh_ctx *ctx, int which, int64_t *n, double *out);
 
+/* ---- passive scalar transport (blood age, contrast bolus; not in the reference) ------------------------------------------
+ *
+ * dc/dt + w . grad c - D lap c = s for ONE P1 scalar c on the context's vertices, advected by the velocity the flow step has just
+ * computed: SUPG in space, a theta-scheme in time.  Call cfdh_scalar_step after cfdh_solve_step and before cfdh_advance: at that
+ * point u_sol and u_prev are the two ends of the step.
+ *
+ * Per cell K (a P1 simplex, d = gdim, local vertices a): g_a = grad(lambda_a), |K|, h = the cell size of the flow's tau (largest
+ * vertex distance); nodal advecting velocity w_a = theta_c u_sol,a + (1 - theta_c) u_prev,a with mean wbar = sum_a w_a / (d + 1);
+ *   tau_c = [(2 / dt)^2 + (2 |wbar| / h)^2 + (4 D / h^2)^2]^(-1/2),     p_a = tau_c wbar . g_a
+ * (the SUPG test function is lambda_a + p_a with the cell-mean velocity).  Element matrices, all closed form:
+ *   M_ab  = |K| (1 + delta_ab) / ((d + 1)(d + 2))                        Ms_ab = p_a |K| / (d + 1)
+ *   C_ab  = |K| / ((d + 1)(d + 2)) (sum_c w_c + w_a) . g_b               Cs_ab = p_a |K| wbar . g_b
+ *   K_ab  = D |K| g_a . g_b                                              b_a   = s |K| (1 / (d + 1) + p_a)
+ * The step, with dt of cfdh_set_params:
+ *   [(M + Ms) / dt + theta_c (C + K + Cs)] c1 = [(M + Ms) / dt - (1 - theta_c)(C + K + Cs)] c0 + b.
+ * Dirichlet rows become identity rows with the value on the right-hand side; columns are not eliminated.  Nothing is added on the
+ * other boundaries: zero diffusive flux, free advective outflow.  SUPG does not capture discontinuities: under- and overshoots
+ * next to a sharp front (a bolus) are expected and are not clipped.
+ *
+ * One assembly kernel per step writes the left-hand values on the vertex graph and the right-hand side (the right-hand operator is
+ * applied to c0 on the fly and never stored): one owner per row, fixed summation order, no atomics -- two assemblies give the same
+ * bytes.  The system is solved by BiCGStab + Jacobi on the true residual, |b - A c| <= max(rtol |b|, atol), from c0 with the
+ * Dirichlet values imposed.
+ *
+ * Contexts: closed-form P1 contexts of cfdh_create (gdim 2 and 3), the whole mesh on one GPU.  cfdh_scalar_enable returns
+ * CFDH_E_ARG, with the context unchanged, on generic-element contexts, on contexts of cfdh_create_ipcs and on a part of a
+ * partitioned run, for a non-finite or negative D, a non-finite s and theta_c outside (0, 1].  Every other cfdh_scalar_* call
+ * returns CFDH_E_STATE before cfdh_scalar_enable.  A context that never enables the scalar allocates nothing and launches nothing
+ * for it (cfdh_info 95: enabled, 96: scalar steps taken, 97: launches of the assembly kernel since cfdh_create). */
+typedef struct cfdh_scalar_stats {
+  int32_t its, reason;   /* BiCGStab iterations, CFDH_KSP_* */
+  double rel_res;        /* final true |b - A c| / |b| */
+  double ms_assemble;    /* the assembly kernel (device events) */
+  double ms_total;       /* the call (host clock) */
+} cfdh_scalar_stats;
+/* Allocates on first use (c = 0); a later call changes D, s and theta_c and keeps c, the Dirichlet set and the tolerances. */
+int cfdh_scalar_enable(cfdh_ctx *ctx, double D, double s, double theta_c);
+/* Replaces the Dirichlet set (caller's vertex numbering; a vertex listed twice keeps the later value); n = 0 clears it.  CFDH_E_ARG,
+ * with the set unchanged, for an out-of-range node or a non-finite value. */
+int cfdh_scalar_set_dirichlet(cfdh_ctx *ctx, int64_t n, const int32_t *nodes, const double *values);
+/* c [nv] in the caller's vertex numbering; CFDH_E_ARG for a non-finite entry. */
+int cfdh_scalar_set_state(cfdh_ctx *ctx, const double *c);
+int cfdh_scalar_get_state(cfdh_ctx *ctx, double *c);
+/* Defaults 1e-8, 1e-50, 1000.  CFDH_E_ARG for rtol outside [0, 1), atol < 0 or max_it < 1. */
+int cfdh_scalar_set_tolerances(cfdh_ctx *ctx, double rtol, double atol, int32_t max_it);
+/* One step.  CFDH_E_DIVERGED (reason CFDH_KSP_DIVERGED_ITS / _NANORINF) when the solve hits max_it or breaks down: c is then left
+ * unchanged.  Needs cfdh_set_params and a state (cfdh_set_state or a solved step): CFDH_E_STATE otherwise.  stats may be NULL. */
+int cfdh_scalar_step(cfdh_ctx *ctx, cfdh_scalar_stats *stats);
+/* Left-hand matrix (CSR in the caller's numbering, columns ascending) and right-hand side [nv] of the NEXT step at the current
+ * state, assembled by this call with the step's kernel.  Query convention of cfdh_get_csr (nnz first with rowptr = col = vals =
+ * rhs = NULL).  Exposed for parity tests, like cfdh_get_pcd_operator. */
+int cfdh_scalar_get_operator(cfdh_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *rhs);
+/* kind 0: int c dx, 1: int c (u_sol . n) ds over the exterior facets of `marker` (outward normal; exact for the P1 fields),
+ * 2 / 3: min / max of c over the vertices. */
+int cfdh_scalar_functional(cfdh_ctx *ctx, int kind, int marker, double *out);
+
 /* ---- multi-GPU ---------------------------------------------- */
 
 /* Halo plan in local vertex numbers: for neighbour k, send_idx[send_ptr[k]..send_ptr[k+1])
@@ -669,7 +725,9 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * last null-space test of cfdh_solve_step found the constant pressure in the null space of the Jacobian, 77: formulation (CFDH_FORM_*),
  * 78: Schur approximation in use (cfdh_options.pc_type: 0 SELFP, 1 Cahouet-Chabard, 2 PCD), 79: Eisenstat-Walker forcing version;
  * 90: accumulations of the wall shear indices since the last cfdh_wall_stats_reset (every context kind);
- * 93: traction boundaries set (cfdh_set_traction_boundaries), 94: launches of the traction kernel since cfdh_create */
+ * 93: traction boundaries set (cfdh_set_traction_boundaries), 94: launches of the traction kernel since cfdh_create;
+ * 95: 1 when the passive scalar is enabled (cfdh_scalar_enable), 96: scalar steps taken, 97: launches of the scalar assembly
+ * kernel since cfdh_create */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
