@@ -64,7 +64,7 @@ SYMBOLS = [
     "cfdh_ipcs_apply_pressure_pc", "cfdh_ipcs_krylov_solve", "cfdh_ipcs_set_scheme", "cfdh_ipcs_get_block_operator",
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
     "cfdh_scalar_enable", "cfdh_scalar_set_dirichlet", "cfdh_scalar_set_state", "cfdh_scalar_get_state", "cfdh_scalar_set_tolerances",
-    "cfdh_scalar_step", "cfdh_scalar_get_operator", "cfdh_scalar_functional",
+    "cfdh_scalar_step", "cfdh_scalar_get_operator", "cfdh_scalar_functional", "cfdh_scalar_krylov_solve", "cfdh_scalar_get_order",
 ]
 
 
@@ -170,6 +170,8 @@ def lib():
     L.cfdh_scalar_step.argtypes = [vp, C.POINTER(ScalarStats)]
     L.cfdh_scalar_get_operator.argtypes = [vp, lp, ip, ip, dp, dp]
     L.cfdh_scalar_functional.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.cfdh_scalar_krylov_solve.argtypes = [vp, dp, dp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(ScalarStats), dp, dp]
+    L.cfdh_scalar_get_order.argtypes = [vp, ip]
     _LIB = L
     return L
 
@@ -224,6 +226,9 @@ INFO_WALL_STATS_COUNT = 90  # cfdh_info: accumulations since the last cfdh_wall_
 # cfdh_scalar_functional; cfdh_info: scalar enabled, scalar steps taken, launches of the scalar assembly kernel
 SCALAR_INTEGRAL, SCALAR_FLUX, SCALAR_MIN, SCALAR_MAX = range(4)
 INFO_SCALAR_ENABLED, INFO_SCALAR_STEPS, INFO_SCALAR_ASSEMBLIES = 95, 96, 97
+# cfdh_scalar_krylov_solve: words of the scalar block
+SC_RHO, SC_RHO_OLD, SC_ALPHA, SC_OMEGA, SC_BETA, SC_TOL2, SC_BN2, SC_RN2, SC_DONE, SC_ITS, SC_BAD = range(11)
+SC_NSCAL = 16
 
 
 class Context:
@@ -635,6 +640,25 @@ class Context:
         out = C.c_double()
         self._chk(self.L.cfdh_scalar_functional(self.h, int(kind), int(marker), C.byref(out)))
         return out.value
+
+    def scalar_krylov_solve(self, b, x0, rtol, atol, max_it):
+        """The transport step's BiCGStab + Jacobi on the caller's right-hand side and initial guess, on the left-hand matrix of the
+        next step (cfdh_scalar_krylov_solve).  Returns (x, its, reason, rel_res, scalars, p): `scalars` holds the 16 words of the
+        device scalar block, indexed by SC_RHO .. SC_BAD, `p` the search direction.  A capped solve returns, it does not raise."""
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
+        if b.size != self.nv or x0.size != self.nv:
+            raise ValueError("one value per vertex expected")
+        x, p, scal, st = np.empty(self.nv), np.empty(self.nv), np.zeros(SC_NSCAL), ScalarStats()
+        self._chk(self.L.cfdh_scalar_krylov_solve(self.h, _dp(b), _dp(x0), float(rtol), float(atol), int(max_it), _dp(x), C.byref(st),
+                                                  _dp(scal), _dp(p)))
+        return x, st.its, st.reason, st.rel_res, scal, p
+
+    def scalar_order(self):
+        """The device row of every vertex (cfdh_scalar_get_order)."""
+        row = np.empty(self.nv, dtype=np.int32)
+        self._chk(self.L.cfdh_scalar_get_order(self.h, _ip(row)))
+        return row
 
     def get_amg_operator(self, hier, level, which, raw=False):
         """One operator of a built hierarchy as scipy CSR (AMG_HIER_*, AMG_OP_*); level-0 indices in the caller's numbering.

@@ -1687,6 +1687,22 @@ int cfdh_scalar_functional(cfdh_ctx *c, int kind, int marker, double *out) {
   return cfdh_scalar_functional_impl(c, kind, marker, out);
 }
 
+int cfdh_scalar_krylov_solve(cfdh_ctx *c, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,
+                             cfdh_scalar_stats *stats, double *scalars, double *p) {
+  ENTER(c);
+  if (!b || !x0 || !x || !stats) return cfdh_fail(c, CFDH_E_ARG, "cfdh_scalar_krylov_solve: null array");
+  if (!(rtol >= 0) || !(rtol < 1) || !(atol >= 0) || max_it < 1)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_scalar_krylov_solve: 0 <= rtol < 1, atol >= 0, max_it >= 1");
+  c->err.clear();
+  return cfdh_scalar_krylov_solve_impl(c, b, x0, rtol, atol, max_it, x, stats, scalars, p);
+}
+
+int cfdh_scalar_get_order(cfdh_ctx *c, int32_t *row) {
+  if (!row) return CFDH_E_ARG;
+  ENTER(c);
+  return cfdh_scalar_get_order_impl(c, row);
+}
+
 // ---- incremental pressure correction (cfdh_ipcs.hip, cfdh_ipcs_krylov.hip, cfdh_ipcs_setup.cpp) ----------------------------------------------------------------------
 
 int cfdh_create_ipcs(cfdh_ctx **out, int device, int gdim, int64_t nn, int64_t nvert, int64_t nc, const int32_t *cells, const double *node_coords,

@@ -615,6 +615,9 @@ int cfdh_scalar_set_tolerances_impl(cfdh_ctx *c, double rtol, double atol, int m
 int cfdh_scalar_step_impl(cfdh_ctx *c, cfdh_scalar_stats *st);
 int cfdh_scalar_get_operator_impl(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col, double *vals, double *rhs);
 int cfdh_scalar_functional_impl(cfdh_ctx *c, int kind, int marker, double *out);
+int cfdh_scalar_krylov_solve_impl(cfdh_ctx *c, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,
+                                  cfdh_scalar_stats *st, double *scalars, double *p);
+int cfdh_scalar_get_order_impl(cfdh_ctx *c, int32_t *row);
 void cfdh_scalar_free(cfdh_ctx *c);
 
 // ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------

@@ -115,9 +115,12 @@ __global__ __launch_bounds__(TPB) void ip_scal_kernel(int nb, const double *__re
     if (!isfinite(be) || !isfinite(a)) { S[IP_BAD] = 1.0; S[IP_DONE] = 1.0; }
   }
   if (check) {
+    // a finite |r|^2 within the tolerance is convergence whatever beta is (a BiCGStab solve that lands on the solution has s = 0,
+    // t = 0, omega = 0, r = 0 and beta = 0 * inf); above the tolerance a beta that is not finite is a breakdown
     const double rn2 = S[IP_RN2];
-    if (!isfinite(rn2) || (STAGE != 0 && STAGE != 7 && !isfinite(S[IP_BETA]))) { S[IP_BAD] = 1.0; S[IP_DONE] = 1.0; }
+    if (!isfinite(rn2)) { S[IP_BAD] = 1.0; S[IP_DONE] = 1.0; }
     else if (rn2 <= S[IP_TOL2]) S[IP_DONE] = 1.0;
+    else if (STAGE != 0 && STAGE != 7 && !isfinite(S[IP_BETA])) { S[IP_BAD] = 1.0; S[IP_DONE] = 1.0; }
   }
   // every stage publishes (|r|^2, done, its, bad): a breakdown found between two convergence tests freezes the kernels behind it,
   // so the stage that found it is the last one that can tell the host

@@ -21,8 +21,10 @@
 
 #define SC_NB 1024  // most blocks (= partial sums per dot product) of the reducing kernels
 
-// scalars of the Krylov loop (device array; [SC_RN2, SC_BAD] are mirrored into host-mapped memory)
-enum { SC_RHO = 0, SC_RHO_OLD, SC_ALPHA, SC_OMEGA, SC_BETA, SC_TOL2, SC_BN2, SC_RN2, SC_DONE, SC_ITS, SC_BAD, SC_NS = 16 };
+// scalars of the Krylov loop (device array; [SC_RN2, SC_BAD] are mirrored into host-mapped memory): the words SC_RHO .. SC_BAD are
+// part of cfdh_scalar_krylov_solve's contract (include/cfdh.h)
+enum { SC_NS = CFDH_SCALAR_NSCAL };
+struct ScTol { double rtol, atol; int max_it; };
 
 struct ScalarData {
   int n = 0;                         // vertices = rows
@@ -38,6 +40,10 @@ struct ScalarData {
   dbuf<double> S, P;                 // Krylov scalars, partial sums [2 SC_NB]
   double *h_mirror = nullptr, *h_mirror_dev = nullptr;  // pinned, host-mapped: |r|^2, done, its, bad
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // cfdh_scalar_krylov_solve: right-hand side and iterate of its own, and the scalar block as the last iteration left it
+  dbuf<double> hk_b, hk_x;
+  double snap[CFDH_SCALAR_NSCAL] = {};
+  bool snap_on = false, snap_set = false;
   ~ScalarData() {
     if (h_mirror) (void)hipHostFree(h_mirror);
     if (ev0) (void)hipEventDestroy(ev0);
@@ -241,9 +247,13 @@ __global__ __launch_bounds__(TPB) void sc_scal_kernel(int nb, const double *__re
     check = true;
   }
   if (check) {
+    // a finite |r|^2 within the tolerance is convergence whatever beta is: a solve that lands on the solution has s = 0, t = 0,
+    // omega = 0, r = 0 and beta = 0 * inf; the driver's true residual decides next, as after every stop.  A beta that is not
+    // finite above the tolerance is a breakdown (scalar_twin.bicgstab_jacobi takes the two tests in the same order)
     const double rn2 = S[SC_RN2];
-    if (!isfinite(rn2) || (STAGE != 0 && !isfinite(S[SC_BETA]))) { S[SC_BAD] = 1.0; S[SC_DONE] = 1.0; }
+    if (!isfinite(rn2)) { S[SC_BAD] = 1.0; S[SC_DONE] = 1.0; }
     else if (rn2 <= S[SC_TOL2]) S[SC_DONE] = 1.0;
+    else if (STAGE != 0 && !isfinite(S[SC_BETA])) { S[SC_BAD] = 1.0; S[SC_DONE] = 1.0; }
   }
   // every stage publishes (|r|^2, done, its, bad): a breakdown found between two convergence tests freezes the kernels behind it
   for (int i = 0; i < 4; i++) mirror[i] = S[SC_RN2 + i];
@@ -445,9 +455,9 @@ void sc_spmv(cfdh_ctx *c, const double *x, double *y, const double *q) {
       (const double *)S->S.p, S->P.p);
 }
 template <int STAGE>
-void sc_scal(cfdh_ctx *c, int nb, int first) {
+void sc_scal(cfdh_ctx *c, int nb, double rtol, double atol, int first) {
   ScalarData *S = c->sc;
-  SCL(c, sc_scal_kernel<STAGE>, 1, nb, (const double *)S->P.p, S->S.p, S->rtol, S->atol, first, S->h_mirror_dev);
+  SCL(c, sc_scal_kernel<STAGE>, 1, nb, (const double *)S->P.p, S->S.p, rtol, atol, first, S->h_mirror_dev);
 }
 // mirror: |r|^2, done, its, bad
 int sc_read(cfdh_ctx *c, double m[4]) {
@@ -456,15 +466,27 @@ int sc_read(cfdh_ctx *c, double m[4]) {
   return 0;
 }
 
+// cfdh_scalar_krylov_solve only: the closing true-residual stage resets the recurrence scalars, so the hook keeps the block as the
+// last iteration left it.  A step never takes this copy.
+int sc_snapshot(cfdh_ctx *c) {
+  ScalarData *D = c->sc;
+  if (!D->snap_on) return 0;
+  HIPCHK(c, hipMemcpyAsync(D->snap, D->S.p, sizeof D->snap, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  D->snap_set = true;
+  return 0;
+}
+
 // BiCGStab + Jacobi on the assembled system; x holds the initial guess (ip_bicgstab's structure)
-int sc_bicgstab(cfdh_ctx *c, const double *b, double *x, cfdh_scalar_stats *st) {
+int sc_bicgstab(cfdh_ctx *c, ScTol tol, const double *b, double *x, cfdh_scalar_stats *st) {
   ScalarData *D = c->sc;
   const int n = D->n, nbv = sc_nb(n, TPB * 4), nbs = sc_nb(n, TPB / 8);
-  const int max_it = D->max_it, batch = 4;
+  const double rtol = tol.rtol, atol = tol.atol;
+  const int max_it = tol.max_it, batch = 4;
   const double *S = D->S.p;
   double m[4];
   sc_spmv<2>(c, x, D->kr.p, b);
-  sc_scal<0>(c, nbs, 1);
+  sc_scal<0>(c, nbs, rtol, atol, 1);
   HIPCHK(c, hipGetLastError());
   CHK(sc_read(c, m));
   // `launched` bounds the loop on the host, whatever the device counter says: at most max_it iterations are ever launched
@@ -479,21 +501,22 @@ int sc_bicgstab(cfdh_ctx *c, const double *b, double *x, cfdh_scalar_stats *st) 
       for (int k = 0; k < nbatch; k++) {
         SCL(c, sc_bicg1_kernel, nbv, n, S, (const double *)D->kr.p, (const double *)D->kv.p, (const double *)D->dinv.p, D->kp.p, D->ky.p);
         sc_spmv<0>(c, D->ky.p, D->kv.p, D->krh.p);
-        sc_scal<1>(c, nbs, 0);
+        sc_scal<1>(c, nbs, 0, 0, 0);
         SCL(c, sc_bicg2_kernel, nbv, n, S, (const double *)D->kr.p, (const double *)D->kv.p, (const double *)D->dinv.p, D->ks.p, D->kz.p);
         sc_spmv<1>(c, D->kz.p, D->kt.p, D->ks.p);
-        sc_scal<2>(c, nbs, 0);
+        sc_scal<2>(c, nbs, 0, 0, 0);
         SCL(c, sc_bicg3_kernel, nbv, n, S, (const double *)D->ky.p, (const double *)D->kz.p, (const double *)D->ks.p, (const double *)D->kt.p,
             (const double *)D->krh.p, x, D->kr.p, D->P.p);
-        sc_scal<3>(c, nbv, 0);
+        sc_scal<3>(c, nbv, 0, 0, 0);
       }
       HIPCHK(c, hipGetLastError());
       CHK(sc_read(c, m));
       if (m[1] != 0.0) break;
     }
     if (m[3] != 0.0) break;
+    CHK(sc_snapshot(c));
     sc_spmv<2>(c, x, D->kr.p, b);  // the recurrence says converged (or the cap is reached): the true residual decides
-    sc_scal<0>(c, nbs, 0);
+    sc_scal<0>(c, nbs, rtol, atol, 0);
     HIPCHK(c, hipGetLastError());
     CHK(sc_read(c, m));
   }
@@ -618,7 +641,7 @@ int cfdh_scalar_step_impl(cfdh_ctx *c, cfdh_scalar_stats *stats) {
   const auto t0 = std::chrono::steady_clock::now();
   CHK(sc_assemble(c, true));
   SCL(c, sc_guess_kernel, sc_nb(S->n, TPB * 4), S->n, (const double *)S->c.p, (const unsigned char *)S->bcflag.p, (const double *)S->bcval.p, S->cn.p);
-  CHK(sc_bicgstab(c, S->rhs.p, S->cn.p, &st));
+  CHK(sc_bicgstab(c, ScTol{S->rtol, S->atol, S->max_it}, S->rhs.p, S->cn.p, &st));
   const bool ok = st.reason > 0;
   if (ok) {
     HIPCHK(c, hipMemcpyAsync(S->c.p, S->cn.p, sizeof(double) * S->n, hipMemcpyDeviceToDevice, c->stream));
@@ -660,6 +683,52 @@ int cfdh_scalar_get_operator_impl(cfdh_ctx *c, int64_t *nnz, int32_t *rowptr, in
     rhs[vu] = b[r];
   }
   rowptr[S->n] = (int32_t)pos;
+  return 0;
+}
+
+// One solve on the caller's b and x0 (cfdh_scalar_krylov_solve) with the caller's tolerances; b and x live in buffers of the hook's
+// own, the assembly counter (cfdh_info 97) is put back.
+int cfdh_scalar_krylov_solve_impl(cfdh_ctx *c, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,
+                                  cfdh_scalar_stats *st, double *scalars, double *p) {
+  const char *who = "cfdh_scalar_krylov_solve";
+  CHK(sc_ready(c, who));
+  ScalarData *S = c->sc;
+  hipStream_t s = c->stream;
+  const int n = S->n;
+  for (int v = 0; v < n; v++)
+    if (!cfdh_scalar::finite(b[v]) || !cfdh_scalar::finite(x0[v])) return cfdh_fail(c, CFDH_E_ARG, "%s: entry %d of b or x0 is not finite", who, v);
+  memset(st, 0, sizeof *st);
+  HIPCHK(c, S->hk_b.alloc((size_t)n)); HIPCHK(c, S->hk_x.alloc((size_t)n));
+  const long long asm0 = c->n_scalar_asm;
+  CHK(sc_assemble(c, false));
+  c->n_scalar_asm = asm0;
+  std::vector<double> hb((size_t)n), hx((size_t)n);
+  for (int v = 0; v < n; v++) { hb[c->perm[v]] = b[v]; hx[c->perm[v]] = x0[v]; }
+  HIPCHK(c, hipMemcpyAsync(S->hk_b.p, hb.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(S->hk_x.p, hx.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  S->snap_on = true; S->snap_set = false;
+  const int rc = sc_bicgstab(c, ScTol{rtol, atol, max_it}, S->hk_b.p, S->hk_x.p, st);
+  S->snap_on = false;
+  CHK(rc);
+  double h[SC_NS];
+  HIPCHK(c, hipMemcpyAsync(hx.data(), S->hk_x.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(h, S->S.p, sizeof h, hipMemcpyDeviceToHost, s));
+  if (p) HIPCHK(c, hipMemcpyAsync(hb.data(), S->kp.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (int v = 0; v < n; v++) x[v] = hx[c->perm[v]];
+  if (p) for (int v = 0; v < n; v++) p[v] = hb[c->perm[v]];
+  if (scalars) {
+    for (int k = 0; k < SC_NS; k++) scalars[k] = h[k];
+    if (S->snap_set)
+      for (int k = SC_RHO; k <= SC_BETA; k++) scalars[k] = S->snap[k];
+  }
+  return 0;
+}
+
+int cfdh_scalar_get_order_impl(cfdh_ctx *c, int32_t *row) {
+  CHK(sc_need(c, "cfdh_scalar_get_order"));
+  for (int v = 0; v < c->sc->n; v++) row[v] = c->perm[v];
   return 0;
 }
 

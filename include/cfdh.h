@@ -663,6 +663,31 @@ int cfdh_scalar_get_operator(cfdh_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32
 /* kind 0: int c dx, 1: int c (u_sol . n) ds over the exterior facets of `marker` (outward normal; exact for the P1 fields),
  * 2 / 3: min / max of c over the vertices. */
 int cfdh_scalar_functional(cfdh_ctx *ctx, int kind, int marker, double *out);
+/* The step's BiCGStab + Jacobi driver on data of the caller's: the left-hand matrix of the NEXT step at the current state (assembled
+ * by this call, as cfdh_scalar_get_operator does), b, x0, x: [nv] host arrays in the caller's vertex numbering; the same kernels,
+ * Jacobi weights and work vectors as in cfdh_scalar_step, with rtol, atol and max_it of this call.  c, the tolerances of
+ * cfdh_scalar_set_tolerances and cfdh_info 96 / 97 stay as they were; b and x live in two buffers of the hook's own, allocated by
+ * its first call.  A capped or broken-down solve is no failed call: 0 is returned, x is the last iterate and stats->reason says
+ * what happened (of stats only its / reason / rel_res are meaningful).  CFDH_E_ARG, before anything is launched, for a null b / x0
+ * / x / stats, a non-finite entry of b or x0, max_it < 1, rtol outside [0, 1) or atol < 0; CFDH_E_STATE before cfdh_scalar_enable,
+ * cfdh_set_params or a state.  scalars (or NULL) receives the CFDH_SCALAR_NSCAL words of the device's scalar block after the solve:
+ *    0 SC_RHO      rh . r after the last iteration                 5 SC_TOL2  max(rtol |b|, atol)^2
+ *    1 SC_RHO_OLD  the one before                                  6 SC_BN2   |b|^2
+ *    2 SC_ALPHA    of the last iteration                           7 SC_RN2   |b - A x|^2 of the returned x
+ *    3 SC_OMEGA    of the last iteration                           8 SC_DONE  1 when the solve stopped by itself
+ *    4 SC_BETA     computed last: by iteration k for k + 1         9 SC_ITS   iterations
+ *                                                                 10 SC_BAD   1 after a NaN / inf or a breakdown
+ * On the device the closing true-residual stage resets words 0 .. 4 (to |r|^2, 1, 1, 1, 0, for a restart); the call returns them
+ * as they were just before it, as the last iteration left them.  A solve that ends at its = 0 returns the reset values.
+ * p (or NULL) receives the search direction [nv] as the last launched iteration left it.  Exposed for tests, like
+ * cfdh_ipcs_krylov_solve. */
+enum { SC_RHO = 0, SC_RHO_OLD, SC_ALPHA, SC_OMEGA, SC_BETA, SC_TOL2, SC_BN2, SC_RN2, SC_DONE, SC_ITS, SC_BAD };
+#define CFDH_SCALAR_NSCAL 16
+int cfdh_scalar_krylov_solve(cfdh_ctx *ctx, const double *b, const double *x0, double rtol, double atol, int max_it, double *x,
+                             cfdh_scalar_stats *stats, double *scalars, double *p);
+/* row [nv]: the device row of every vertex (the library renumbers the vertices; the kernels' grid-stride loops, block partial
+ * sums and the slices of the assembly's work list run over device rows).  Exposed for tests that place data on chosen rows. */
+int cfdh_scalar_get_order(cfdh_ctx *ctx, int32_t *row);
 
 /* ---- multi-GPU ---------------------------------------------- */
 

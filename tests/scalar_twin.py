@@ -97,14 +97,18 @@ def step(x, cells, u_sol, u_prev, c0, dt, D, s, theta, dir_nodes=(), dir_vals=()
 
 def bicgstab_jacobi(A, b, x0, rtol, atol=1e-50, max_it=1000):
     """Right-preconditioned BiCGStab with Jacobi, stopped on the recurrence |r| <= max(rtol |b|, atol) and then checked on the true
-    residual (restart from it when it is not there yet) -- the algorithm of the device driver in plain NumPy."""
+    residual (restart from it when it is not there yet) -- the algorithm of the device driver in plain NumPy.  As in stage 3 of
+    sc_scal_kernel, a finite recurrence |r| within the tolerance is convergence whatever beta is (a solve that lands on the solution
+    has s = t = 0, omega = 0, r = 0 and beta = 0 * inf); a beta that is not finite above the tolerance is a breakdown and ends the
+    solve where it is."""
     A = sp.csr_matrix(A)
     dinv = 1.0 / A.diagonal()
     x = np.array(x0, dtype=np.float64)
     tol = max(rtol * np.linalg.norm(b), atol)
     its = 0
     r = b - A @ x
-    while np.linalg.norm(r) > tol and its < max_it:
+    broken = False
+    while np.linalg.norm(r) > tol and its < max_it and not broken:
         rh, p, v = r.copy(), np.zeros_like(r), np.zeros_like(r)
         rho, rho_old, alpha, omega, beta = r @ r, 1.0, 1.0, 1.0, 0.0
         while its < max_it:
@@ -122,7 +126,10 @@ def bicgstab_jacobi(A, b, x0, rtol, atol=1e-50, max_it=1000):
             rho_old, rho = rho, rh @ r
             beta = (rho / rho_old) * (alpha / omega) if omega != 0 else np.inf
             its += 1
-            if not np.isfinite(beta) or np.linalg.norm(r) <= tol:
+            if np.linalg.norm(r) <= tol:
+                break
+            if not np.isfinite(beta):
+                broken = True
                 break
         r = b - A @ x
     return x, its

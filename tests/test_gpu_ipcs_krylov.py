@@ -360,6 +360,28 @@ def test_edges_of_the_convergence_test(case, which, name):
     assert rel_res <= 1e-6 and rel_res == np.sqrt(S[IP_RN2])
 
 
+def test_identity_system_converges_in_its_first_half_step():
+    """Every velocity node constrained: A1 = I, alpha = rho / rho = 1 and s = r - v = 0 exactly, so t = 0, omega = 0, r = 0 and
+    beta = 0 * inf.  That is convergence at iteration 1 on the exact solution, not a breakdown (stage 3 of ip_scal_kernel looks at
+    |r|^2 <= tol^2 before it looks at beta)."""
+    m, nm, mk, par, _, bcp, u0 = setup("sq8")
+    nn = len(nm.x)
+    ctx = _ctx(m, nm, mk, par["dt"], par["rho"], par["mu"], np.zeros(2), [(np.arange(nn, dtype=np.int32), np.zeros((nn, 2)))], bcp)
+    z = np.zeros(m.num_vertices)
+    ctx.set_state(u_prev=u0.ravel(), p_prev=z, u=u0.ravel(), p=z)
+    ctx.set_previous2(u0.ravel())
+    A = ctx.get_operator(0)
+    import scipy.sparse as sp
+    assert abs(A - sp.identity(nn)).max() == 0.0
+    rng = np.random.default_rng(51)
+    x0, b = rng.integers(-4, 5, size=(nn, 2)).astype(np.float64), rng.integers(-4, 5, size=(nn, 2)).astype(np.float64)
+    x, its, reason, rel_res, S = ctx.krylov_solve(0, b, x0, 1e-8, 0.0, 50)
+    print("ipcs identity system: its %d reason %d rel_res %.2e bad %g alpha %g omega %g beta %g" % (its, reason, rel_res, S[IP_BAD], S[IP_ALPHA], S[IP_OMEGA], S[IP_BETA]))
+    assert reason == CONVERGED and its == 1 and x.tobytes() == b.tobytes() and S[IP_BAD] == 0.0 and S[IP_DONE] == 1.0 and rel_res == 0.0
+    assert S[IP_ALPHA] == 1.0 and S[IP_OMEGA] == 0.0
+    ctx.close()
+
+
 @pytest.mark.parametrize("which", [0, 1, 2])
 def test_unattainable_tolerance_keeps_the_invariants(case, which):
     """rtol = 1e-16, max_it = 200 on _case(2): the recurrence residual sinks below what the true residual can reach, so the outer
