@@ -123,6 +123,7 @@ static int create_ctx(cfdh_ctx **out, int device, int gdim, int etype, int64_t n
     if ((e = getenv("CFDH_L_CYCLES"))) v.l_cycles = atoi(e);
     if ((e = getenv("CFDH_A_CYCLES"))) v.a_cycles = atoi(e);
     e = getenv("CFDH_DL0_COARSE_SWEEPS"); v.dl0_coarse_sweeps = e && e[0] == '1';
+    e = getenv("CFDH_ASM_STAGE"); v.asm_stage = !(e && e[0] == '0');  // 0: the assembly addresses its lists through blk_vptr / blk_cptr (A/B runs, tests)
   }
   // No hipGraph replay under a rocprofiler-sdk tool on a HIP runtime >= 7.2.  That runtime submits the kernel packets of a graph
   // launch with ONE doorbell; ROCr's intercepted queue hands such a batch to the profiler's queue interceptor as (pointer into
@@ -1627,6 +1628,11 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 95: return c->sc ? 1 : 0;                   // passive scalar enabled (cfdh_scalar_enable)
     case 96: return c->n_scalar_steps;               // scalar steps taken
     case 97: return c->n_scalar_asm;                 // launches of the scalar assembly kernel since cfdh_create
+    case 98: return c->blk_vl_max;                   // P1 triangle assembly: longest / shortest per-block vertex list ...
+    case 99: return c->blk_vl_min;
+    case 100: return c->blk_cl_max;                  // ... and cell list (0 on contexts that do not build them)
+    case 101: return c->blk_cl_min;
+    case 102: return c->env.asm_stage ? 1 : 0;       // fixed-stride lists in use (CFDH_ASM_STAGE as this context read it)
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;

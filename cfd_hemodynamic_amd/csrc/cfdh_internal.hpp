@@ -252,6 +252,11 @@ struct cfdh_ctx {
   dbuf<int> blk_row;         // [nblk+1]
   dbuf<int> blk_vptr, blk_vlist;  // per-block list of the vertices its cells touch
   dbuf<int> blk_cptr, blk_clist;  // per-block list of distinct cells
+  // second copy of the two lists at a fixed stride, [nblk][CFDH_MAX_BV] / [nblk][CFDH_MAX_BC], -1 beyond a block's count: the
+  // assembly kernel addresses them by block and lane alone, one memory trip less than through blk_vptr / blk_cptr
+  // (env.asm_stage; empty otherwise)
+  dbuf<int> blk_vfix, blk_cfix;
+  int blk_vl_min = 0, blk_vl_max = 0, blk_cl_min = 0, blk_cl_max = 0;  // shortest / longest list over the blocks (cfdh_info 98..101)
   dbuf<unsigned> inc_loc;    // per lane: lcell | lv0<<8 | lv1<<16 | lv2<<24 (block-local, rotated); ~0u = idle lane
   dbuf<int> wave_maxlen;     // per wavefront: longest row (bound of the segmented reduction)
 
@@ -488,6 +493,7 @@ struct cfdh_ctx {
     double gs_eta2 = 1e-6;            // CFDH_GS_ETA2: refine when |w'|^2 <= eta2 |w|^2
     int l_cycles = 1, a_cycles = 1;   // CFDH_L_CYCLES, CFDH_A_CYCLES: V-cycles per pressure / velocity solve of the preconditioner
     bool dl0_coarse_sweeps = false;   // CFDH_DL0_COARSE_SWEEPS=1: sweep-by-sweep cycle on the replicated levels below a distributed level 0
+    bool asm_stage = true;            // CFDH_ASM_STAGE=0: the P1 triangle assembly reads its lists through blk_vptr / blk_cptr, not blk_vfix / blk_cfix
   } env;
   dbuf<double> qu;                           // [2 nvo] A01 z_p of the last preconditioner application; its address is baked into the captured graphs
   long long n_guess_projections = 0;         // linear solves whose prologue projected a guess, used or not (cfdh_info 86), reset likewise

@@ -130,6 +130,7 @@ int k_moments(cfdh_ctx *c) {
 struct AsmArgs {
   const double *coords, *mom, *x, *un, *un2, *bcval, *bcmult;
   const int *vptr, *blk_row, *blk_vptr, *blk_vlist, *blk_cptr, *blk_clist, *wave_maxlen;
+  const int *blk_vfix, *blk_cfix;  // the two lists at the fixed strides CFDH_MAX_BV / CFDH_MAX_BC, -1 padded (STG)
   const unsigned *inc_slot, *inc_rank, *inc_loc;
   const unsigned char *cflag, *bcflag;
   double *A00, *A01, *A10, *A11, *F;
@@ -161,7 +162,18 @@ struct AsmArgs {
 #ifndef MOMS
 #define MOMS 5
 #endif
-template <int MODE, bool HIST2 = false, bool BF = false, int OCC = (BF ? CFDH_BF_OCC : CFDH_ASM_OCC)>
+// STG false: the lists through blk_vptr / blk_cptr -- three dependent memory trips before the barrier (descriptors -> lists ->
+//            gathers);
+//     true:  the lists through blk_vfix / blk_cfix, whose address is a function of block and lane alone: the ids are requested
+//            together with the descriptors and the lane records, the gathers follow one trip later.  Padded slots (-1) load
+//            nothing and write nothing, so LDS holds the same values in the same places and everything behind the barrier is
+//            the same code: F and the matrix agree bit for bit (tests/test_gpu_asm_stage.py).
+namespace asm_stage {
+constexpr int VT = (CFDH_MAX_BV + CFDH_MAX_INC - 1) / CFDH_MAX_INC;      // list entries a lane requests: vertices ...
+constexpr int CT = (4 * CFDH_MAX_BC + CFDH_MAX_INC - 1) / CFDH_MAX_INC;  // ... and quarters of cell records
+static_assert(CFDH_MAX_INC % 4 == 0, "the quarter of a cell record a lane copies must not depend on the trip");
+}  // namespace asm_stage
+template <int MODE, bool HIST2 = false, bool BF = false, bool STG = false, int OCC = (BF ? CFDH_BF_OCC : CFDH_ASM_OCC)>
 __global__ __launch_bounds__(CFDH_MAX_INC, OCC) void asm_kernel(AsmArgs p) {
   constexpr bool JAC = (MODE != 0);
   constexpr bool WJ = (MODE == 1);
@@ -187,7 +199,40 @@ __global__ __launch_bounds__(CFDH_MAX_INC, OCC) void asm_kernel(AsmArgs p) {
   const size_t lk = (size_t)blk * CFDH_MAX_INC + t;
   const unsigned loc = p.inc_loc[lk], meta = p.inc_slot[lk], seg = p.inc_rank[lk];
   const int wmax = p.wave_maxlen[blk * (CFDH_MAX_INC / 64) + (t >> 6)];
-  {
+  if (STG) {
+    int vid[asm_stage::VT], cid[asm_stage::CT];
+#pragma unroll
+    for (int k = 0; k < asm_stage::VT; k++) {
+      const int i = t + k * CFDH_MAX_INC;
+      vid[k] = i < CFDH_MAX_BV ? p.blk_vfix[(size_t)blk * CFDH_MAX_BV + i] : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < asm_stage::CT; k++) {
+      const int i = t + k * CFDH_MAX_INC;
+      cid[k] = i < 4 * CFDH_MAX_BC ? p.blk_cfix[(size_t)blk * CFDH_MAX_BC + (i >> 2)] : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < asm_stage::VT; k++) {
+      const int i = t + k * CFDH_MAX_INC, v = vid[k];
+      if (v < 0) continue;
+      const int uo = uoff(v, nvo), po = poff(v, nvo);
+      sVid[i] = v;
+      sX[i] = *(const double2 *)(p.coords + 2 * (size_t)v);
+      sU[i] = make_double2(p.x[uo], p.x[uo + 1]);
+      sP[i] = p.x[po];
+      sUn[i] = make_double2(p.un[uo], p.un[uo + 1]);
+      if (HIST2) sUn2[i] = make_double2(p.un2[uo], p.un2[uo + 1]);
+      sFl[i] = p.bcflag[v];
+    }
+#pragma unroll
+    for (int k = 0; k < asm_stage::CT; k++) {  // 4 x 16 B per cell record, consecutive lanes; the lane of the first quarter brings the flags
+      const int i = t + k * CFDH_MAX_INC, e = cid[k];
+      if (e < 0) continue;
+      sMom[MOMS * (i >> 2) + (i & 3)] = *(const double2 *)(p.mom + 8 * (size_t)e + 2 * (i & 3));
+      if ((t & 3) == 0) sCf[i >> 2] = p.cflag[e];
+    }
+    for (int i = t; i <= nrows; i += CFDH_MAX_INC) sRow[i] = p.vptr[row0 + i];
+  } else {
     const int v0 = p.blk_vptr[blk], nvl = p.blk_vptr[blk + 1] - v0;
     for (int i = t; i < nvl; i += CFDH_MAX_INC) {
       const int vid = p.blk_vlist[v0 + i];
@@ -560,7 +605,7 @@ int k_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   a.coords = c->coords.p; a.mom = c->mom.p; a.x = xstate; a.un = c->xprev.p; a.un2 = c->xprev2.p; a.bcval = c->bcval.p; a.bcmult = c->bcmult.p;
   a.vptr = c->vptr.p;
   a.blk_vptr = c->blk_vptr.p; a.blk_vlist = c->blk_vlist.p; a.blk_cptr = c->blk_cptr.p; a.blk_clist = c->blk_clist.p; a.inc_loc = c->inc_loc.p; a.wave_maxlen = c->wave_maxlen.p;
-  a.blk_row = c->blk_row.p;
+  a.blk_row = c->blk_row.p; a.blk_vfix = c->blk_vfix.p; a.blk_cfix = c->blk_cfix.p;
   a.inc_slot = c->inc_slot.p; a.inc_rank = c->inc_rank.p; a.cflag = c->cflag.p; a.bcflag = c->bcflag.p;
   a.A00 = c->A00.p; a.A01 = c->A01.p; a.A10 = c->A10.p; a.A11 = c->A11.p; a.F = c->F.p;
   a.nvo = c->nvo; a.dt = c->dt; a.rho = c->rho; a.mu = c->mu; a.muf = c->muf; a.fx = c->f[0]; a.fy = c->f[1];
@@ -576,16 +621,22 @@ int k_assemble(cfdh_ctx *c, const double *xstate, int mode) {
   prof_begin(c, 0);
   const dim3 gr(c->nblk), bl(CFDH_MAX_INC);
   const bool bf = c->bf_beta > 0.0 && c->bf_marker >= 0;
-#define CFDH_ASM_LAUNCH(H2, BFV)                                                                   \
+#define CFDH_ASM_LAUNCH3(H2, BFV, STG)                                                             \
   do {                                                                                             \
-    if (mode == 1) hipLaunchKernelGGL((asm_kernel<1, H2, BFV>), gr, bl, 0, c->stream, a);         \
-    else if (mode == 2) hipLaunchKernelGGL((asm_kernel<2, H2, BFV>), gr, bl, 0, c->stream, a);    \
-    else hipLaunchKernelGGL((asm_kernel<0, H2, BFV>), gr, bl, 0, c->stream, a);                   \
+    if (mode == 1) hipLaunchKernelGGL((asm_kernel<1, H2, BFV, STG>), gr, bl, 0, c->stream, a);    \
+    else if (mode == 2) hipLaunchKernelGGL((asm_kernel<2, H2, BFV, STG>), gr, bl, 0, c->stream, a); \
+    else hipLaunchKernelGGL((asm_kernel<0, H2, BFV, STG>), gr, bl, 0, c->stream, a);              \
+  } while (0)
+#define CFDH_ASM_LAUNCH(H2, BFV)                          \
+  do {                                                    \
+    if (c->env.asm_stage) CFDH_ASM_LAUNCH3(H2, BFV, true); \
+    else CFDH_ASM_LAUNCH3(H2, BFV, false);                \
   } while (0)
   if (!hist2 && !bf) CFDH_ASM_LAUNCH(false, false);
   else if (hist2 && !bf) CFDH_ASM_LAUNCH(true, false);
   else if (!hist2 && bf) CFDH_ASM_LAUNCH(false, true);
   else CFDH_ASM_LAUNCH(true, true);
+#undef CFDH_ASM_LAUNCH3
 #undef CFDH_ASM_LAUNCH
   HIPCHK(c, hipGetLastError());
   if (!c->tb_markers.empty()) CHK(k_traction(c, xstate, mode));  // traction boundaries: one small launch behind the volume pass

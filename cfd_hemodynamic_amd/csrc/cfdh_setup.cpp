@@ -5,6 +5,7 @@
 // Sp = A11 - A10 diag(A00)^-1 A01 (stabilized_schur.py:235).
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -298,6 +299,21 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
   }
   std::vector<unsigned> inc_slot(lane_meta), inc_rank(lane_seg), inc_loc(lane_loc);
   c->nblk = (int)blk_row.size() - 1;
+  // ---- the two lists once more at a fixed stride (-1 beyond the block's count)
+  std::vector<int> blk_vfix, blk_cfix;
+  c->blk_vl_min = c->blk_cl_min = c->nblk ? INT_MAX : 0; c->blk_vl_max = c->blk_cl_max = 0;
+  for (int b = 0; b < c->nblk; b++) {
+    const int nvl = blk_vptr[b + 1] - blk_vptr[b], ncl = blk_cptr[b + 1] - blk_cptr[b];
+    c->blk_vl_min = std::min(c->blk_vl_min, nvl); c->blk_vl_max = std::max(c->blk_vl_max, nvl);
+    c->blk_cl_min = std::min(c->blk_cl_min, ncl); c->blk_cl_max = std::max(c->blk_cl_max, ncl);
+  }
+  if (c->env.asm_stage) {
+    blk_vfix.assign((size_t)c->nblk * CFDH_MAX_BV, -1); blk_cfix.assign((size_t)c->nblk * CFDH_MAX_BC, -1);
+    for (int b = 0; b < c->nblk; b++) {
+      std::copy(blk_vlist.begin() + blk_vptr[b], blk_vlist.begin() + blk_vptr[b + 1], blk_vfix.begin() + (size_t)b * CFDH_MAX_BV);
+      std::copy(blk_clist.begin() + blk_cptr[b], blk_clist.begin() + blk_cptr[b + 1], blk_cfix.begin() + (size_t)b * CFDH_MAX_BC);
+    }
+  }
 
   // ---- uploads
   hipStream_t s = c->stream;
@@ -313,6 +329,7 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
   HIPCHK(c, c->blk_row.upload(blk_row, s));
   HIPCHK(c, c->blk_vptr.upload(blk_vptr, s)); HIPCHK(c, c->blk_cptr.upload(blk_cptr, s));
   HIPCHK(c, c->blk_vlist.upload(blk_vlist, s)); HIPCHK(c, c->blk_clist.upload(blk_clist, s));
+  if (c->env.asm_stage) { HIPCHK(c, c->blk_vfix.upload(blk_vfix, s)); HIPCHK(c, c->blk_cfix.upload(blk_cfix, s)); }
   HIPCHK(c, c->inc_loc.upload(inc_loc, s));
   HIPCHK(c, c->wave_maxlen.upload(wave_maxlen, s));
   {

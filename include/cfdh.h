@@ -752,7 +752,9 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 90: accumulations of the wall shear indices since the last cfdh_wall_stats_reset (every context kind);
  * 93: traction boundaries set (cfdh_set_traction_boundaries), 94: launches of the traction kernel since cfdh_create;
  * 95: 1 when the passive scalar is enabled (cfdh_scalar_enable), 96: scalar steps taken, 97: launches of the scalar assembly
- * kernel since cfdh_create */
+ * kernel since cfdh_create;
+ * 98 / 99: longest / shortest per-workgroup vertex list of the P1 triangle assembly, 100 / 101: the same of its cell lists (0 on
+ * other contexts), 102: 1 when that assembly reads them at a fixed stride (CFDH_ASM_STAGE, read by cfdh_create) */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus

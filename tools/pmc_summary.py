@@ -24,6 +24,8 @@ NAMES = {
     "spmv_a01_resid_kernel": "coupling_product_A01",
     "fused_up_sell_kernel<HIP_vector_type<double, 2": "amg_up0_velocity_2rhs",
     "fused_up_sell_kernel<double": "amg_up0_pressure",
+    "fused_up_sell_head_kernel<HIP_vector_type<double, 2": "amg_up0_velocity_2rhs",  # the same sweeps on the head copies
+    "fused_up_sell_head_kernel<double": "amg_up0_pressure",
     "fused_down_kernel<16, float, HIP_vector_type<double, 2": "amg_down0_velocity_2rhs",
     "fused_down_kernel<16, float, double": "amg_down0_pressure",
     "sell_cheb2_scale_kernel": "cheb2_scale_H",
