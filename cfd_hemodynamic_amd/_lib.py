@@ -47,6 +47,16 @@ class ScalarStats(C.Structure):
     _fields_ = [("its", C.c_int32), ("reason", C.c_int32), ("rel_res", C.c_double), ("ms_assemble", C.c_double), ("ms_total", C.c_double)]
 
 
+class FgmresTrace(C.Structure):
+    _fields_ = [
+        ("m", C.c_int32), ("max_res", C.c_int32), ("max_cycles", C.c_int32),
+        ("cycles", C.c_int32), ("k", C.c_int32), ("guess_used", C.c_int32), ("fp32_used", C.c_int32), ("n_res", C.c_int32), ("pad_", C.c_int32),
+        ("bn", C.c_double), ("tol", C.c_double), ("beta", C.c_double),
+        ("V", dp), ("Z", dp), ("H", dp), ("ww", dp), ("nrm2", dp), ("y", dp), ("x0", dp), ("x_start", dp), ("res", dp),
+        ("cycle_beta", dp), ("cycle_est", dp), ("second_pass", ip),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, C.c_int, C.c_int)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, dp, dp)
 
@@ -59,7 +69,7 @@ SYMBOLS = [
     "cfdh_functional", "cfdh_wall_shear_stress", "cfdh_set_global_pressure_space", "cfdh_set_halo", "cfdh_comm_unique_id", "cfdh_comm_init", "cfdh_comm_set_callbacks",
     "cfdh_profile_enable", "cfdh_profile_get", "cfdh_profile_reset", "cfdh_info",
     "cfdh_set_schur_pcd", "cfdh_set_ksp_forcing", "cfdh_get_newton_history", "cfdh_get_pcd_operator", "cfdh_apply_preconditioner", "cfdh_apply_operator",
-    "cfdh_get_amg_operator", "cfdh_get_amg_vectors", "cfdh_get_amg_head", "cfdh_krylov_vec_op",
+    "cfdh_get_amg_operator", "cfdh_get_amg_vectors", "cfdh_get_amg_head", "cfdh_krylov_vec_op", "cfdh_fgmres_solve",
     "cfdh_create_ipcs", "cfdh_ipcs_set_form", "cfdh_ipcs_set_tolerances", "cfdh_ipcs_step", "cfdh_ipcs_get_operator", "cfdh_ipcs_get_intermediate",
     "cfdh_ipcs_apply_pressure_pc", "cfdh_ipcs_krylov_solve", "cfdh_ipcs_set_scheme", "cfdh_ipcs_get_block_operator",
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
@@ -149,6 +159,7 @@ def lib():
     L.cfdh_get_amg_head.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
     L.cfdh_krylov_vec_op.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int, dp, dp,
                                      C.POINTER(C.c_float), ip, dp, dp, dp]
+    L.cfdh_fgmres_solve.argtypes = [vp, dp, C.c_int, dp, ip, ip, C.POINTER(FgmresTrace)]
     L.cfdh_create_ipcs.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, ip, dp, C.c_int64, ip, ip, ip]
     L.cfdh_ipcs_set_form.argtypes = [vp, C.c_double, C.c_double]
     L.cfdh_ipcs_set_tolerances.argtypes = [vp, dp, C.c_double, ip]
@@ -302,6 +313,7 @@ class Context:
 
     def set_options(self, o):
         self._chk(self.L.cfdh_set_options(self.h, C.byref(o)))
+        self._ksp_restart = int(o.ksp_restart)  # sizes the trace arrays of fgmres_solve
 
     def clear_dirichlet(self):
         self._chk(self.L.cfdh_clear_dirichlet(self.h))
@@ -558,6 +570,36 @@ class Context:
         w = np.zeros((self.dim + 1) * self.nvo)
         self._chk(self.L.cfdh_apply_operator(self.h, _dp(r), _dp(z), _dp(w)))
         return z, w
+
+    def fgmres_solve(self, b, newton_index=-1, trace=True, max_res=4096, max_cycles=256):
+        """The step's own FGMRES on the caller's right-hand side (cfdh_fgmres_solve; test entry, one GPU): J d = b under the context's
+        current options, from zero (newton_index -1) or from the projected guess of that Newton index's ring, which a converged solve
+        then feeds.  Returns (x, its, reason, trace): `trace` (None unless asked for) is a dict describing the LAST cycle -- k, beta,
+        V [k + 1, n], Z [k, n], H [k + 1, k] unrotated, ww / nrm2 / second_pass [k] of the first Gram-Schmidt pass, y [k], x_start --
+        and the whole solve: bn, tol, cycles, guess_used, fp32_used, x0, res [its], cycle_beta / cycle_est [cycles]."""
+        n = (self.dim + 1) * self.nv
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.size != n:
+            raise ValueError("monolithic vector of (gdim + 1) nv entries expected")
+        x = np.zeros(n)
+        its, reason = C.c_int32(), C.c_int32()
+        if not trace:
+            self._chk(self.L.cfdh_fgmres_solve(self.h, _dp(b), int(newton_index), _dp(x), C.byref(its), C.byref(reason), None))
+            return x, its.value, reason.value, None
+        m = getattr(self, "_ksp_restart", None) or int(self.default_options().ksp_restart)
+        a = {"V": np.zeros((m + 1, n)), "Z": np.zeros((m, n)), "H": np.zeros((m, m + 1)), "ww": np.zeros(m), "nrm2": np.zeros(m),
+             "y": np.zeros(m), "x0": np.zeros(n), "x_start": np.zeros(n), "res": np.zeros(max_res), "cycle_beta": np.zeros(max_cycles),
+             "cycle_est": np.zeros(max_cycles)}
+        sp2 = np.zeros(m, dtype=np.int32)
+        t = FgmresTrace(m=m, max_res=max_res, max_cycles=max_cycles, second_pass=_ip(sp2), **{k: _dp(v) for k, v in a.items()})
+        self._chk(self.L.cfdh_fgmres_solve(self.h, _dp(b), int(newton_index), _dp(x), C.byref(its), C.byref(reason), C.byref(t)))
+        k = t.k
+        out = {"k": k, "cycles": t.cycles, "guess_used": bool(t.guess_used), "fp32_used": bool(t.fp32_used), "bn": t.bn, "tol": t.tol,
+               "beta": t.beta, "V": a["V"][:k + 1].copy(), "Z": a["Z"][:k].copy(), "H": a["H"][:k, :k + 1].T.copy(),
+               "ww": a["ww"][:k].copy(), "nrm2": a["nrm2"][:k].copy(), "second_pass": sp2[:k].copy(), "y": a["y"][:k].copy(),
+               "x0": a["x0"], "x_start": a["x_start"], "res": a["res"][:min(t.n_res, max_res)].copy(),
+               "cycle_beta": a["cycle_beta"][:min(t.cycles, max_cycles)].copy(), "cycle_est": a["cycle_est"][:min(t.cycles, max_cycles)].copy()}
+        return x, its.value, reason.value, out
 
     def krylov_vec_op(self, op, n, ld, nvec=1, A=None, B=None, x=None, y=None, coef=None, scalar=0.0, flags=0):
         """One Krylov vector wrapper (KVOP_*) on caller data, launched as the solver launches it (test entry; one GPU).

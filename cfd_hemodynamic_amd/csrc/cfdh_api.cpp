@@ -768,6 +768,63 @@ int cfdh_apply_operator(cfdh_ctx *c, const double *r, double *z, double *w) {
   return 0;
 }
 
+// ---- test hook: the step's FGMRES on the caller's right-hand side, with a trace of its last cycle -------------------------------
+int cfdh_fgmres_solve(cfdh_ctx *c, const double *b, int newton_index, double *x, int32_t *its, int32_t *reason, cfdh_fgmres_trace *trace) {
+  NOT_IPCS(c, "cfdh_fgmres_solve");
+  ENTER(c);
+  if (!b || !x || !its || !reason) return cfdh_fail(c, CFDH_E_ARG, "cfdh_fgmres_solve: null array");
+  if (newton_index < -1 || newton_index >= cfdh_ctx::GUESS_NEWTON)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_fgmres_solve: newton_index = %d outside -1 .. %d", newton_index, cfdh_ctx::GUESS_NEWTON - 1);
+  if (trace && trace->m < c->opt.ksp_restart)
+    return cfdh_fail(c, CFDH_E_ARG, "cfdh_fgmres_solve: the trace holds %d columns, ksp_restart is %d", (int)trace->m, c->opt.ksp_restart);
+  if (c->nranks > 1 || c->nvo != c->nv) return cfdh_fail(c, CFDH_E_STATE, "cfdh_fgmres_solve: one GPU only");
+  if (!c->jac_valid) return cfdh_fail(c, CFDH_E_STATE, "no Jacobian assembled yet");
+  HIPCHK(c, c->hook_b.alloc(c->NL)); HIPCHK(c, c->hook_x.alloc(c->NL));
+  std::vector<double> h;
+  pack_vec(c, b, b + (size_t)c->dim * c->nv, h, nullptr);
+  CHK(upload_vec(c, h, c->hook_b.p));
+  FgmresTrace tr;
+  int kits = 0, kreason = 0;
+  CHK(cfdh_fgmres_hook(c, c->hook_b.p, c->hook_x.p, newton_index, &kits, &kreason, trace ? &tr : nullptr));
+  *its = kits; *reason = kreason;
+  const int d = c->dim, nv = c->nv;
+  const size_t n = (size_t)(d + 1) * nv;
+  std::vector<double> o;
+  auto fetch = [&](const double *dev, double *out) -> int {  // one device vector into the caller's numbering
+    if (!out) return 0;
+    CHK(download_vec(c, dev, o));
+    unpack_vec(c, o, out, out + (size_t)d * nv);
+    return 0;
+  };
+  CHK(fetch(c->hook_x.p, x));
+  if (!trace) return 0;
+  const int m = c->opt.ksp_restart, k = tr.k, M = trace->m;
+  trace->cycles = tr.cycles; trace->k = k; trace->guess_used = tr.guess_used ? 1 : 0; trace->fp32_used = tr.fp32_used ? 1 : 0;
+  trace->bn = tr.bn; trace->tol = tr.tol; trace->beta = tr.beta;
+  trace->n_res = (int32_t)tr.res.size();
+  CHK(fetch(tr.x0.p, trace->x0));
+  CHK(fetch(tr.x_start.p, trace->x_start));
+  const size_t ld = ((size_t)c->NL + 1) & ~(size_t)1;  // leading dimension of the Krylov workspace
+  if (trace->V && tr.cycles > 0) {
+    CHK(fetch(tr.v0.p, trace->V));
+    for (int i = 1; i <= k; i++) CHK(fetch(c->kV.p + (size_t)i * ld, trace->V + (size_t)i * n));
+  }
+  if (trace->Z) for (int j = 0; j < k; j++) CHK(fetch(c->kZ.p + (size_t)j * ld, trace->Z + (size_t)j * n));
+  for (int j = 0; j < k; j++) {
+    if (trace->H) for (int i = 0; i <= j + 1; i++) trace->H[(size_t)j * (M + 1) + i] = tr.H[(size_t)j * (m + 1) + i];
+    if (trace->ww) trace->ww[j] = tr.ww[j];
+    if (trace->nrm2) trace->nrm2[j] = tr.nrm2[j];
+    if (trace->second_pass) trace->second_pass[j] = tr.second_pass[j];
+    if (trace->y && j < (int)tr.y.size()) trace->y[j] = tr.y[j];
+  }
+  if (trace->res) for (int i = 0; i < (int)tr.res.size() && i < trace->max_res; i++) trace->res[i] = tr.res[i];
+  for (int i = 0; i < (int)tr.cycle_beta.size() && i < trace->max_cycles; i++) {
+    if (trace->cycle_beta) trace->cycle_beta[i] = tr.cycle_beta[i];
+    if (trace->cycle_est) trace->cycle_est[i] = i < (int)tr.cycle_est.size() ? tr.cycle_est[i] : std::nan("");
+  }
+  return 0;
+}
+
 // ---- test hook: ONE Krylov vector wrapper (v_* of cfdh_krylov_vec.hip) on caller data, launched as the solver launches it ------
 int cfdh_krylov_vec_op(cfdh_ctx *c, int op, int n, int ld, int nvec, const double *A, const double *B, const double *x, const double *y,
                        const double *coef, double scalar, int flags, double *out1, double *out2, float *out32, int32_t *nscal,

@@ -353,6 +353,7 @@ struct cfdh_ctx {
   bool krylov_fp32_ok = true;   // cleared when the orthogonality watchdog trips on a cycle that used the copy
   int guess_last_its[4] = {0, 0, 0, 0};  // iterations of the last solve per Newton index (expected length of the next)
   dbuf<double> ky;
+  dbuf<double> hook_b, hook_x;  // cfdh_fgmres_solve: right-hand side and iterate of its own, NL each
 
   // preconditioner
   dbuf<double> dinvA;          // 1/diag(A00), [2*nvo]
@@ -735,7 +736,19 @@ int cfdh_pc_apply(cfdh_ctx *c, const double *r, double *z);
 int ensure_krylov(cfdh_ctx *c);  // Krylov workspace (kV, kZ, kw, kh, ky, the read-back ring) for the current ksp_restart
 int cfdh_apply_operator_dev(cfdh_ctx *c, const double *r, double *z);  // z = P^-1 r, kw = J z: the pair of one FGMRES iteration
 int cfdh_host_threads();  // cfdh_setup.cpp: thread count of the host loops (CFDH_HOST_THREADS, default 8)
-int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its, int *reason, double bnorm = -1.0);
+// What cfdh_fgmres_solve reports of a solve: the last cycle and the residual history (include/cfdh.h).  Device copies are made
+// only when a trace is handed in; the normal path launches nothing for it.
+struct FgmresTrace {
+  int m = 0, cycles = 0, k = 0;
+  bool guess_used = false, fp32_used = false;
+  double bn = 0.0, tol = 0.0, beta = 0.0;
+  dbuf<double> x0, x_start, v0;  // NL each: iterate before the first / the last cycle, V_0 of the last cycle
+  std::vector<double> H, ww, nrm2, y, res, cycle_beta, cycle_est;
+  std::vector<int> second_pass;
+};
+int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its, int *reason, double bnorm = -1.0, FgmresTrace *tr = nullptr);
+// cfdh_fgmres_solve on device vectors: b [NO], x [NL]
+int cfdh_fgmres_hook(cfdh_ctx *c, const double *b, double *x, int newton_index, int *its, int *reason, FgmresTrace *tr);
 int v_norm2_pair(cfdh_ctx *c, int n, const double *x, const double *y, double *nx, double *ny);
 int cfdh_newton_step(cfdh_ctx *c, cfdh_stats *st);
 int cfdh_download_blocks(cfdh_ctx *c, std::vector<double> &a00, std::vector<double> &a01, std::vector<double> &a10,

@@ -1,5 +1,5 @@
 // The arithmetic of the linear solve that needs no device: the Gram system of the projected guess, the least-squares problem of
-// the Arnoldi recurrence, the scale of a Gram-Schmidt pass and the launch-ahead policy.  Plain C++17 without HIP and without the
+// the Arnoldi recurrence, the scale of a Gram-Schmidt pass, the launch-ahead policy and the checks between two cycles.  Plain C++17 without HIP and without the
 // context, so that the CPU tests compile it with the host compiler (tests/krylov_host_shim.cpp); gram_solve and gs_scale are also
 // called from kernels (cfdh_krylov_vec.hip), which is what keeps the host and the device to ONE copy of each.
 #pragma once
@@ -229,5 +229,40 @@ struct LaunchAhead {
     need = std::max(1, e_its > 0 ? std::min(n_rem, std::max(e_its - its, 1) + 2) : n_rem);
   }
 };
+
+// What the checks between two cycles decide, from the true residual beta formed after a cycle of j_prev columns that started at
+// the true residual beta_start and ended with the recurrence estimate est_prev.  Pure: the caller carries out the effects (the
+// take-back x -= Z y of a retry, the switches on the context).
+//   watchdog  the recurrence lost the true residual (beta > 10 max(est_prev, tol)): the fp32 copy of the basis is the first
+//             suspect and is switched off; otherwise long cycles are re-orthogonalised from now on, and the cycle is taken back
+//             (retry) when it made the residual worse.  A context that re-orthogonalises already does neither again.
+//   stop      attainable accuracy: a second cycle IN A ROW ended converged by the recurrence without halving the true residual,
+//             within 10 tol or six orders below |b|.  last_true: the true residual of the last such cycle, -1 after any other.
+enum class BetweenFlow { proceed, retry, stop };
+enum class BetweenWatchdog { quiet, fp32_off, refine_on };
+struct BetweenCycles {
+  BetweenFlow flow = BetweenFlow::proceed;
+  BetweenWatchdog watchdog = BetweenWatchdog::quiet;
+  double last_true = -1.0;
+};
+inline BetweenCycles between_cycles(int j_prev, double beta, double est_prev, double tol, double bn, double beta_start, double last_true,
+                                    bool use32, bool gs_refine_long, bool no_attainable_stop) {
+  BetweenCycles d;
+  d.last_true = last_true;
+  const bool lost = j_prev > 0 && beta > 10.0 * std::max(est_prev, tol);
+  if (use32 && lost) {
+    d.watchdog = BetweenWatchdog::fp32_off;
+  } else if (!gs_refine_long && lost) {
+    d.watchdog = BetweenWatchdog::refine_on;
+    if (beta > beta_start) { d.flow = BetweenFlow::retry; return d; }
+  }
+  if (j_prev > 0 && est_prev <= tol && beta > tol && !no_attainable_stop) {
+    if (last_true > 0.0 && beta > 0.5 * last_true && (beta <= 10.0 * tol || beta <= 1e-6 * bn)) { d.flow = BetweenFlow::stop; return d; }
+    d.last_true = beta;
+  } else {
+    d.last_true = -1.0;  // a cycle that ended without recurrence convergence (restart): the floor has to be seen twice IN A ROW
+  }
+  return d;
+}
 
 }  // namespace cfdh_krylov

@@ -1058,6 +1058,7 @@ struct Fgmres {
   double beta_start = 0.0;    // true residual at its start
   double last_true = -1.0;    // true residual at the last disagreement between recurrence and true residual
   bool kept_copy = false;     // the copy guess_store makes is current (written by the last update of x)
+  FgmresTrace *tr = nullptr;  // cfdh_fgmres_solve only
   Fgmres(cfdh_ctx *c_, const double *b_, double *x_)
       : c(c_), b(b_), x(x_), n(c_->NO), m(c_->kry_m), ld(krylov_ld(c_)), ld32((ld + 3) & ~(size_t)3),  // columns of the copy start on 16-B boundaries (float4 loads)
         lsq(c_->kry_m), hh(HH_WORDS(c_->kry_m)) {}
@@ -1156,15 +1157,16 @@ static int fgmres_between_cycles(Fgmres &s, double beta, Between *next) {
   // the recurrence then reports convergence while the true residual, formed here after every cycle anyway, does not
   // follow.  Once that is seen on a context, long cycles are re-orthogonalised (DGKS) from then on, and a cycle that
   // made the residual worse is taken back.
-  const bool lost = j_prev > 0 && beta > 10.0 * std::max(est_prev, tol);
-  if (s.use32 && lost) {
+  const cfdh_krylov::BetweenCycles d = cfdh_krylov::between_cycles(j_prev, beta, est_prev, tol, s.bn, s.beta_start, s.last_true, s.use32,
+                                                                   c->gs_refine_long, c->env.no_attainable_stop != 0);
+  if (d.watchdog == cfdh_krylov::BetweenWatchdog::fp32_off) {
     // the fp32 copy is the first suspect: this solve and all later ones of the context go back to the fp64 basis
     s.use32 = false; c->krylov_fp32_ok = false;
     if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e vs recurrence %.3e after a %d-vector cycle with the fp32 basis copy: switched off\n", beta, est_prev, j_prev);
-  } else if (!c->gs_refine_long && lost) {
+  } else if (d.watchdog == cfdh_krylov::BetweenWatchdog::refine_on) {
     c->gs_refine_long = true;
     if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e vs recurrence %.3e after a %d-vector cycle: re-orthogonalising long cycles from now on\n", beta, est_prev, j_prev);
-    if (beta > s.beta_start) {
+    if (d.flow == cfdh_krylov::BetweenFlow::retry) {
       std::vector<double> &y = s.lsq.y;
       for (int i = 0; i < j_prev; i++) y[i] = -y[i];
       HIPCHK(c, hipMemcpyAsync(c->ky.p, y.data(), sizeof(double) * j_prev, hipMemcpyHostToDevice, c->stream));
@@ -1185,19 +1187,47 @@ static int fgmres_between_cycles(Fgmres &s, double beta, Between *next) {
   // orders below |b| (beyond what the reference's rtol = 1e-5 ever asks for); anything else runs on to ksp_max_it and fails
   // like PETSc's DIVERGED_ITS.  It returns its own reason code (CFDH_KSP_CONVERGED_ATTAINABLE) and is counted
   // (cfdh_info 72).  CFDH_NO_ATTAINABLE_STOP=1 disables it.
-  if (j_prev > 0 && est_prev <= tol && beta > tol && !c->env.no_attainable_stop) {
-    if (s.last_true > 0.0 && beta > 0.5 * s.last_true && (beta <= 10.0 * tol || beta <= 1e-6 * s.bn)) {
-      if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e stays above the tolerance %.3e although the recurrence converged twice: attainable accuracy, stopping\n", beta, tol);
-      s.reason = CFDH_KSP_CONVERGED_ATTAINABLE;
-      c->n_attainable_stops++;
-      *next = Between::stop;
-      return 0;
-    }
-    s.last_true = beta;
-  } else {
-    s.last_true = -1.0;  // a cycle that ended without recurrence convergence (restart): the floor has to be seen twice IN A ROW
+  // (the decision itself: cfdh_krylov::between_cycles, tested on the CPU)
+  s.last_true = d.last_true;
+  if (d.flow == cfdh_krylov::BetweenFlow::stop) {
+    if (o.verbose) fprintf(stderr, "[cfdh]     fgmres: true residual %.3e stays above the tolerance %.3e although the recurrence converged twice: attainable accuracy, stopping\n", beta, tol);
+    s.reason = CFDH_KSP_CONVERGED_ATTAINABLE;
+    c->n_attainable_stops++;
+    *next = Between::stop;
+    return 0;
   }
   s.beta_start = beta;
+  return 0;
+}
+
+// cfdh_fgmres_solve only: the iterate before the first cycle
+static int trace_solve_start(Fgmres &s, bool guessed) {
+  FgmresTrace *t = s.tr;
+  cfdh_ctx *c = s.c;
+  t->m = s.m; t->cycles = 0; t->k = 0;
+  t->guess_used = guessed; t->fp32_used = false;
+  t->bn = s.bn; t->tol = s.tol; t->beta = 0.0;
+  t->H.assign((size_t)(s.m + 1) * s.m, 0.0);
+  t->ww.assign(s.m, 0.0); t->nrm2.assign(s.m, 0.0); t->second_pass.assign(s.m, 0);
+  t->y.clear(); t->res.clear(); t->cycle_beta.clear(); t->cycle_est.clear();
+  HIPCHK(c, t->x0.alloc(c->NL)); HIPCHK(c, t->x_start.alloc(c->NL)); HIPCHK(c, t->v0.alloc(c->NL));
+  HIPCHK(c, t->v0.zero(c->stream));
+  HIPCHK(c, hipMemcpyAsync(t->x0.p, s.x, sizeof(double) * c->NL, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t->x_start.p, s.x, sizeof(double) * c->NL, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+// ... and at the start of a cycle: the iterate, and V_0 before the next true residual overwrites it
+static int trace_cycle_start(Fgmres &s, double beta) {
+  FgmresTrace *t = s.tr;
+  cfdh_ctx *c = s.c;
+  t->cycles++; t->k = 0; t->beta = beta; t->fp32_used = s.use32;
+  t->cycle_beta.push_back(beta);
+  std::fill(t->H.begin(), t->H.end(), 0.0);
+  std::fill(t->ww.begin(), t->ww.end(), 0.0); std::fill(t->nrm2.begin(), t->nrm2.end(), 0.0);
+  std::fill(t->second_pass.begin(), t->second_pass.end(), 0);
+  t->y.clear();
+  HIPCHK(c, hipMemcpyAsync(t->x_start.p, s.x, sizeof(double) * c->NL, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t->v0.p, c->kV.p, sizeof(double) * s.n, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -1313,16 +1343,25 @@ static int fgmres_cycle(Fgmres &s, double beta) {
       // 1e-2 -- rounds 2 and 3 -- sent a third of all iterations of the headline run through the second pass for nothing.)
       const double eta2 = (o.ksp_rtol < 1e-7 || j >= refine_from) ? 0.5 : c->env.gs_eta2;
       double hnorm = std::sqrt(nrm2);
+      int refined = 0;
       if (!(nrm2 > eta2 * ww)) {
         // what ran ahead used the unrefined vector: it is launched again, and its ring slots are not consumed by this batch
+        refined = jl > j + 1 ? 2 : 1;
         if (jl > j + 1) { c->n_krylov_discarded += jl - (j + 1); jl = j + 1; upto = jl; }
         CHK(fgmres_second_pass(s, j, hs, ww, hh2, &hnorm));
+      }
+      if (s.tr) {
+        double *Hj = &s.tr->H[(size_t)j * (s.m + 1)];
+        for (int i = 0; i <= j; i++) Hj[i] = hh[i];
+        Hj[j + 1] = hnorm;
+        s.tr->ww[j] = ww; s.tr->nrm2[j] = nrm2; s.tr->second_pass[j] = refined;
       }
       const bool ok = s.lsq.add_column(j, hh, hnorm);
       j++;
       if (!ok) { s.reason = -9; break; }
       s.its++;
       const double res = s.lsq.residual(j);
+      if (s.tr) s.tr->res.push_back(res);
       if (o.verbose > 1) fprintf(stderr, "[cfdh]     fgmres %3d  |r|/|b| = %.3e\n", s.its, res / s.bn);
       if (res <= s.tol) { s.converged = true; break; }
       ahead.observe(res, s.tol, s.its);
@@ -1350,6 +1389,7 @@ static int fgmres_update_x(Fgmres &s) {
   else CHK(v_lincomb(c, s.n, c->kZ.p, (int)s.ld, j, c->ky.p, s.x));
   s.kept_copy = keep != nullptr;
   s.est_prev = s.lsq.residual(j);
+  if (s.tr) { s.tr->y.assign(y, y + j); s.tr->k = j; s.tr->cycle_est.push_back(s.est_prev); }
   return 0;
 }
 
@@ -1357,12 +1397,14 @@ static int fgmres_update_x(Fgmres &s) {
 // residual norm relative to |b| (KSP defaults: rtol, atol; KSP_NORM_UNPRECONDITIONED
 // for FGMRES).  Classical Gram-Schmidt with one re-orthogonalisation pass; the
 // 2j+3 scalars of an iteration come back in a single read.
-int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reason_out, double bnorm) {
+int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reason_out, double bnorm, FgmresTrace *tr) {
   CHK(ensure_krylov(c));
   Fgmres s(c, b, x);
+  s.tr = tr;
   V0From src = V0From::rhs;
   double beta = 0.0;
   CHK(fgmres_start(s, bnorm, &src, &beta));
+  if (tr) CHK(trace_solve_start(s, src != V0From::rhs));
   if (s.reason != 0) { *its_out = 0; *reason_out = s.reason; return 0; }
   double *V = c->kV.p;
   for (;;) {
@@ -1381,6 +1423,7 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
     else if (src != V0From::guess_scaled) CHK(v_scale(c, s.n, 1.0 / beta, V));
     if (s.use32) CHK(v_store32(c, s.n, V, s.V32));
     src = V0From::residual;
+    if (tr) CHK(trace_cycle_start(s, beta));
     CHK(fgmres_cycle(s, beta));
     if (s.reason == -9) break;
     CHK(fgmres_update_x(s));
@@ -1390,6 +1433,27 @@ int cfdh_fgmres(cfdh_ctx *c, const double *b, double *x, int *its_out, int *reas
   *reason_out = s.reason;
   if (c->guess_slot >= 0 && c->guess_slot < cfdh_ctx::GUESS_NEWTON) c->guess_last_its[c->guess_slot] = s.its;
   if (s.reason > 0) CHK(guess_store(c, x, s.kept_copy));
+  return 0;
+}
+
+// The solve of cfdh_fgmres_solve (include/cfdh.h): the preconditioner as cfdh_apply_preconditioner builds it, |b| handed over as
+// the Newton iteration hands over |F| (the lean prologue needs it), the ring of the projected guess chosen by newton_index.
+int cfdh_fgmres_hook(cfdh_ctx *c, const double *b, double *x, int newton_index, int *its, int *reason, FgmresTrace *tr) {
+  CHK(cfdh_pc_update(c, false));
+  CHK(guess_ensure(c));
+  const int slot_before = c->guess_slot;
+  const double relres_before = c->ksp_last_relres;
+  const bool fp32_ok_before = c->krylov_fp32_ok, refine_before = c->gs_refine_long;
+  double bn = 0.0;
+  CHK(v_norm2(c, c->NO, b, &bn));
+  c->guess_slot = newton_index;
+  if (newton_index >= 0) c->guess_stored[newton_index] = false;
+  const int rc = cfdh_fgmres(c, b, x, its, reason, bn, tr);
+  c->guess_slot = slot_before;
+  c->ksp_last_relres = relres_before;
+  if (newton_index < 0) { c->krylov_fp32_ok = fp32_ok_before; c->gs_refine_long = refine_before; }
+  if (rc) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -565,6 +565,42 @@ int cfdh_get_csr(cfdh_ctx *ctx, int64_t *nnz, int32_t *rowptr, int32_t *col, dou
  * local vector, y: owned rows [gdim*nv_owned | nv_owned]. */
 int cfdh_spmv(cfdh_ctx *ctx, const double *x, double *y);
 
+/* The step's own FGMRES on a right-hand side of the caller's: J d = b with cfdh_fgmres itself -- the same kernels, workspace,
+ * read-back ring, stream and captured graphs as inside cfdh_solve_step -- on the assembled Jacobian, with the preconditioner built
+ * as cfdh_apply_preconditioner builds it, under the context's current options (ksp_rtol, ksp_atol, ksp_max_it, ksp_restart,
+ * ksp_guess) and environment switches.  b [gdim*nv | nv] and x [gdim*nv | nv] are monolithic host arrays in the caller's numbering,
+ * as for cfdh_spmv; they live in two device buffers of the hook's own, allocated by its first call.  One GPU only (CFDH_E_STATE on
+ * a part of a partitioned run, and before a Jacobian is assembled).
+ * newton_index selects the ring of the projected initial guess: -1 leaves every ring untouched and starts from zero; 0 .. 3 use
+ * and feed that ring exactly as the Newton solve of that index does (the returned x is kept only after a converged solve).
+ * A capped, broken-down or attainable-accuracy solve is no failed call: 0 is returned, x is the last iterate, *its and *reason
+ * (CFDH_KSP_*) say what happened.  CFDH_E_ARG, before anything is launched, for a null b / x / its / reason, for newton_index
+ * outside -1 .. 3, and for a trace whose m is below ksp_restart.  The time state, F, the Newton history, the options and the
+ * tolerances stay as they were; with newton_index -1 so do the watchdog's switches (fp32 copy, refinement of long cycles); the
+ * statistics counters of cfdh_info may advance.
+ *
+ * trace (or NULL) describes the LAST cycle of the solve and the residual history of the whole solve.  The caller sets the three
+ * capacities and the array pointers (each may be NULL: not wanted); n = (gdim + 1) nv.  A solve without a trace launches exactly
+ * what cfdh_solve_step launches; with one, the iterate and V_0 are copied on the device at the start of every cycle (V_0 is
+ * overwritten by the next true residual).
+ *   V  [(m + 1) n]  column i at V + i n: the basis v_0 .. v_k            Z  [m n]  z_j = P^-1 v_j, j < k
+ *   H  [(m + 1) m]  column j at H + j (m + 1): [h_0 .. h_j ; hnorm], UNROTATED, the values handed to the least-squares update
+ *   ww, nrm2 [m]    w.w and the squared norm of the FIRST Gram-Schmidt pass of column j (what the refinement criterion saw)
+ *   second_pass [m] 0: one pass; 1: refined; 2: refined while later iterations were in flight (they were launched again)
+ *   y  [m]          the k coefficients of the update x = x_start + Z y
+ *   x0 [n]          the iterate before the first cycle (zero or the projected guess); x_start [n]: before the last cycle
+ *   res [max_res]   recurrence residual after every processed iteration of the whole solve (n_res of them, its unless capped)
+ *   cycle_beta, cycle_est [max_cycles]  per cycle: the true residual norm it started from, the recurrence estimate it ended with */
+typedef struct cfdh_fgmres_trace {
+  int32_t m, max_res, max_cycles;              /* in: capacities */
+  int32_t cycles, k, guess_used, fp32_used;    /* out: cycles run, columns of the last one, projected guess used, fp32 basis copy in use in the last cycle */
+  int32_t n_res, pad_;
+  double bn, tol, beta;                        /* |b|, the absolute tolerance, the true residual norm the last cycle started from */
+  double *V, *Z, *H, *ww, *nrm2, *y, *x0, *x_start, *res, *cycle_beta, *cycle_est;
+  int32_t *second_pass;
+} cfdh_fgmres_trace;
+int cfdh_fgmres_solve(cfdh_ctx *ctx, const double *b, int newton_index, double *x, int32_t *its, int32_t *reason, cfdh_fgmres_trace *trace);
+
 /* ---- the step ------------------------------------------------------------- */
 
 /* solveStep (stabilized_schur.py:313-334): null-space handling, Newton with

@@ -29,4 +29,13 @@ void kh_ahead_set_need(void *p, int need) { ((LaunchAhead *)p)->need = need; }
 int kh_ahead_in_flight(void *p, int sync_now, int lagmax) { return ((LaunchAhead *)p)->in_flight(sync_now != 0, lagmax); }
 int kh_ahead_process_upto(void *p, int j, int jl, int maxl, int sync_now) { return ((LaunchAhead *)p)->process_upto(j, jl, maxl, sync_now != 0); }
 
+// flow: 0 proceed, 1 retry, 2 stop; watchdog: 0 quiet, 1 fp32 copy off, 2 refinement on
+void kh_between_cycles(int j_prev, double beta, double est_prev, double tol, double bn, double beta_start, double last_true, int use32,
+                       int gs_refine_long, int no_attainable_stop, int *flow, int *watchdog, double *last_true_out) {
+  const BetweenCycles d = between_cycles(j_prev, beta, est_prev, tol, bn, beta_start, last_true, use32 != 0, gs_refine_long != 0, no_attainable_stop != 0);
+  *flow = (int)d.flow;
+  *watchdog = (int)d.watchdog;
+  *last_true_out = d.last_true;
+}
+
 }

@@ -38,6 +38,20 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_lib.Stats) == 4 * 4 + 6 * 8
 
 
+def test_fgmres_trace_layout_matches_header(tmp_path):
+    """cfdh_fgmres_trace as the C compiler lays it out against the ctypes structure: size and the offset of every member"""
+    import subprocess
+    names = [f[0] for f in _lib.FgmresTrace._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cfdh.h"\nint main(void) {\n  printf("%zu\\n", sizeof(cfdh_fgmres_trace));\n'
+                   + "".join('  printf("%%zu\\n", offsetof(cfdh_fgmres_trace, %s));\n' % n for n in names) + "  return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert got[0] == ctypes.sizeof(_lib.FgmresTrace)
+    assert got[1:] == [getattr(_lib.FgmresTrace, n).offset for n in names]
+
+
 def test_bad_arguments_return_error_codes_not_crashes():
     L = _lib.lib()
     h = ctypes.c_void_p()

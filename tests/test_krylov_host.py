@@ -40,6 +40,9 @@ def kh(tmp_path_factory):
     L.kh_ahead_set_need.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.kh_ahead_in_flight.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     L.kh_ahead_process_upto.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 4
+    ipt = ctypes.POINTER(ctypes.c_int)
+    L.kh_between_cycles.argtypes = [ctypes.c_int] + [ctypes.c_double] * 6 + [ctypes.c_int] * 3 + [ipt, ipt, dp]
+    L.kh_between_cycles.restype = None
     return L
 
 
@@ -211,3 +214,84 @@ def test_gs_scale(kh):
     assert kh.kh_gs_scale(4.0, 5.0) == 2.0               # nrm2 < 0
     assert kh.kh_gs_scale(4.0, -5.0) == 2.0              # nrm2 > ww
     assert kh.kh_gs_scale(0.0, 0.0) == 0.0
+
+
+# ---- the checks between two cycles -----------------------------------------------------------------------------------------
+PROCEED, RETRY, STOP = 0, 1, 2
+QUIET, FP32_OFF, REFINE_ON = 0, 1, 2
+
+
+def between(kh, j_prev=5, beta=1.0, est_prev=1.0, tol=1e-5, bn=1.0, beta_start=10.0, last_true=-1.0, use32=0, refine=0, no_stop=0):
+    flow, dog, lt = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_double(np.nan)
+    kh.kh_between_cycles(j_prev, beta, est_prev, tol, bn, beta_start, last_true, use32, refine, no_stop,
+                         ctypes.byref(flow), ctypes.byref(dog), ctypes.byref(lt))
+    return flow.value, dog.value, lt.value
+
+
+def test_between_watchdog_threshold(kh):
+    # trips strictly above 10 max(est, tol); the estimate bounds it when it is the larger of the two, the tolerance otherwise
+    est, tol = 3e-4, 1e-5
+    up = np.nextafter(10.0 * est, np.inf)
+    assert between(kh, beta=10.0 * est, est_prev=est, tol=tol) == (PROCEED, QUIET, -1.0)
+    assert between(kh, beta=up, est_prev=est, tol=tol) == (PROCEED, REFINE_ON, -1.0)
+    est, tol = 1e-7, 1e-5
+    up = np.nextafter(10.0 * tol, np.inf)
+    assert between(kh, beta=10.0 * tol, est_prev=est, tol=tol, no_stop=1) == (PROCEED, QUIET, -1.0)
+    assert between(kh, beta=up, est_prev=est, tol=tol, no_stop=1) == (PROCEED, REFINE_ON, -1.0)
+    # no cycle behind this residual (first pass after a take-back is j_prev > 0; j_prev = 0 never trips)
+    assert between(kh, j_prev=0, beta=1e3, est_prev=1e-9) == (PROCEED, QUIET, -1.0)
+    # the fp32 copy is the first suspect, whether or not the context refines already; no take-back with it
+    for refine in (0, 1):
+        assert between(kh, beta=1.0, est_prev=1e-3, beta_start=0.5, use32=1, refine=refine) == (PROCEED, FP32_OFF, -1.0)
+    assert between(kh, beta=1e-3, est_prev=1e-3, use32=1) == (PROCEED, QUIET, -1.0)
+
+
+def test_between_retry(kh):
+    # taken back only when the cycle made the true residual worse (strictly), and only by the trip that switches refinement on
+    assert between(kh, beta=1.0, est_prev=1e-3, beta_start=1.0) == (PROCEED, REFINE_ON, -1.0)
+    assert between(kh, beta=1.0, est_prev=1e-3, beta_start=np.nextafter(1.0, 0.0)) == (RETRY, REFINE_ON, -1.0)
+    assert between(kh, beta=1.0, est_prev=1e-3, beta_start=0.5, refine=1) == (PROCEED, QUIET, -1.0)
+    # a take-back leaves last_true alone (the cycle did not happen)
+    assert between(kh, beta=1.0, est_prev=1e-9, tol=1e-5, beta_start=0.5, last_true=0.25) == (RETRY, REFINE_ON, 0.25)
+    # not lost: no retry however the residual moved
+    assert between(kh, beta=1.0, est_prev=0.2, beta_start=0.5) == (PROCEED, QUIET, -1.0)
+
+
+def test_between_attainable_stop(kh):
+    tol, bn = 1e-5, 1.0
+    conv = dict(est_prev=0.9 * tol, tol=tol, bn=bn, refine=1)
+    # first recurrence-converged cycle whose true residual stays above the tolerance: remembered, no stop
+    assert between(kh, beta=3 * tol, last_true=-1.0, **conv) == (PROCEED, QUIET, 3 * tol)
+    # the second in a row stops if the residual was not halved (strictly above half) ...
+    assert between(kh, beta=3 * tol, last_true=4 * tol, **conv) == (STOP, QUIET, 4 * tol)
+    assert between(kh, beta=2 * tol, last_true=4 * tol, **conv) == (PROCEED, QUIET, 2 * tol)
+    assert between(kh, beta=np.nextafter(2 * tol, 1.0), last_true=4 * tol, **conv) == (STOP, QUIET, 4 * tol)
+    # ... and only within 10 tol or six orders below |b|
+    assert between(kh, beta=10 * tol, last_true=10 * tol, **conv) == (STOP, QUIET, 10 * tol)
+    b11 = np.nextafter(10 * tol, 1.0)
+    assert between(kh, beta=b11, last_true=b11, **conv) == (PROCEED, QUIET, b11)
+    big = dict(conv, bn=1e3)               # 1e-6 |b| = 1e-3 = 100 tol
+    assert between(kh, beta=1e-6 * 1e3, last_true=1e-3, **big) == (STOP, QUIET, 1e-3)
+    b = np.nextafter(1e-6 * 1e3, 1.0)
+    assert between(kh, beta=b, last_true=b, **big) == (PROCEED, QUIET, b)
+    # the recurrence estimate has to be at or below the tolerance, the true residual above it
+    assert between(kh, beta=3 * tol, est_prev=tol, tol=tol, last_true=4 * tol, refine=1) == (STOP, QUIET, 4 * tol)
+    assert between(kh, beta=3 * tol, est_prev=np.nextafter(tol, 1.0), tol=tol, last_true=4 * tol, refine=1) == (PROCEED, QUIET, -1.0)
+    assert between(kh, beta=tol, last_true=4 * tol, **conv) == (PROCEED, QUIET, -1.0)
+    # a cycle that ended at the restart length in between resets the memory: the next converged one is a FIRST again
+    f, w, lt = between(kh, beta=3 * tol, last_true=-1.0, **conv)
+    f, w, lt = between(kh, beta=3 * tol, est_prev=2.5 * tol, tol=tol, last_true=lt, refine=1)
+    assert (f, w, lt) == (PROCEED, QUIET, -1.0)
+    assert between(kh, beta=3 * tol, last_true=lt, **conv) == (PROCEED, QUIET, 3 * tol)
+    # no cycle yet
+    assert between(kh, j_prev=0, beta=3 * tol, last_true=4 * tol, **conv) == (PROCEED, QUIET, -1.0)
+    # the watchdog's switches do not shadow the stop: six orders below |b|, lost by more than 10 tol
+    assert between(kh, beta=50 * tol, est_prev=0.9 * tol, tol=tol, bn=1e3, last_true=60 * tol, use32=1) == (STOP, FP32_OFF, 60 * tol)
+    assert between(kh, beta=50 * tol, est_prev=0.9 * tol, tol=tol, bn=1e3, beta_start=1.0, last_true=60 * tol) == (STOP, REFINE_ON, 60 * tol)
+
+
+def test_between_no_attainable_stop_switch(kh):
+    tol = 1e-5
+    assert between(kh, beta=3 * tol, est_prev=0.9 * tol, tol=tol, last_true=4 * tol, refine=1, no_stop=0)[0] == STOP
+    # switched off: never a stop, and nothing is remembered
+    assert between(kh, beta=3 * tol, est_prev=0.9 * tol, tol=tol, last_true=4 * tol, refine=1, no_stop=1) == (PROCEED, QUIET, -1.0)
