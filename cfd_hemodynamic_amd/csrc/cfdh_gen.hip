@@ -676,8 +676,10 @@ __global__ __launch_bounds__(TPB) void gen_wss_kernel(int nfac, int nvo, const i
     const double Tn = Tv[0] * n[0] + Tv[1] * n[1];
     for (int a = 0; a < NL; a++) { acc[a][0] += wq * ph[a] * (Tv[0] - Tn * n[0]); acc[a][1] += wq * ph[a] * (Tv[1] - Tn * n[1]); }
   }
+  // only the facet's own nodes (cfdh_facet_nodes) receive: at the facet points the basis functions of the other nodes vanish only up
+  // to rounding ((1 - t) + t, 1 - x - y), and 1e-16 |Tt| on an interior node makes it a wall node for the wall shear indices (A > 0)
   for (int a = 0; a < NL; a++)
-    if (acc[a][0] != 0.0 || acc[a][1] != 0.0) { atomicAdd(out + 2 * (size_t)vs[a], acc[a][0]); atomicAdd(out + 2 * (size_t)vs[a] + 1, acc[a][1]); }
+    if (a == va || a == vb || (ET == 1 && a == 3 + f)) { atomicAdd(out + 2 * (size_t)vs[a], acc[a][0]); atomicAdd(out + 2 * (size_t)vs[a] + 1, acc[a][1]); }
 }
 
 // the reference tables on the host, filled on first use

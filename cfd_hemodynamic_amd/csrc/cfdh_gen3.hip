@@ -913,8 +913,18 @@ __global__ __launch_bounds__(TPB) void gen3_wss_kernel(int nfac, int nvo, const 
     for (int a = 0; a < NL; a++)
       for (int i = 0; i < 3; i++) acc[a][i] += w * phv[a] * (T[i] - Tn * n[i]);
   }
+  // only the facet's own nodes (cfdh_facet_nodes3) receive: at the facet points the basis functions of the other nodes vanish only
+  // up to rounding, and 1e-16 |Tt| on an interior node makes it a wall node for the wall shear indices (A > 0)
+  unsigned own = 0;
+  for (int q = 0; q < facet_nvert(ET); q++) own |= 1u << facet_vertex(ET, f, q);
+  if (ET == 1)
+    for (int e = 0; e < 6; e++) {
+      int i, j;
+      tet_edge(e, i, j);
+      if (i != f && j != f) own |= 1u << (4 + e);
+    }
   for (int a = 0; a < NL; a++)
-    if (acc[a][0] != 0.0 || acc[a][1] != 0.0 || acc[a][2] != 0.0)
+    if ((own >> a) & 1u)
       for (int i = 0; i < 3; i++) atomicAdd(out + 3 * (size_t)vs[a] + i, acc[a][i]);
 }
 

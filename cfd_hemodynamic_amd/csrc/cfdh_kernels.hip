@@ -1359,6 +1359,8 @@ int k_wss(cfdh_ctx *c, double *out) {
 int k_functional(cfdh_ctx *c, int kind, int marker, double *out) {
   const int nb = 256;
   int nval = 2;  // rows of partial sums the kernel writes
+  // (the generic branch below takes every kind <= 3: a negative kind ran the drag / lift kernel of a 2-D P2 / Q1 context)
+  if (kind < 0 || kind > 8) return cfdh_fail(c, CFDH_E_ARG, "unknown functional kind %d", kind);
   if (kind == 8) {
     // flux of u_prev: the kernels of kind 7 (every element family) read the iterate through c->x, so they run on the other vector
     std::swap(c->x.p, c->xprev.p);

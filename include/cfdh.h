@@ -614,13 +614,18 @@ int cfdh_solve_step(cfdh_ctx *ctx, cfdh_stats *stats);
  * 4: ||u_sol||_inf, 5: ||u_prev||_inf, 6: ||u_sol-u_prev||_inf (scenario.py:268-280),
  * 7: volume flux  int u_sol . n ds  over the exterior facets of `marker` (outward normal; the outlet flow rates the
  * tree and bifurcation scenarios report), 8: the same flux of u_prev (the resistance outlet of
- * stabilized_schur_pressure_backflow.py:204-207, :383-392 is driven by it).  Kinds 0/1 exist for gdim 2 only.
+ * stabilized_schur_pressure_backflow.py:204-207, :383-392 is driven by it).  Kinds 0/1 exist for gdim 2 only: for them on gdim 3, and for a kind outside 0 .. 8,
+ * the call returns CFDH_E_ARG on every context of cfdh_create / cfdh_create_elem (parts included) and leaves it usable.
  * Sums/maxima over the owned part; the caller (or the communicator) reduces. */
 int cfdh_functional(cfdh_ctx *ctx, int kind, int marker, double *out);
 
 /* Wall shear stress, the per-step `assemble_wss()` of solverBase.py:163-195,
  * (1/FacetArea) * inner(w, Tt) * ds with T = -sigma(u_sol, p_sol) n, Tt = T - (T.n) n, assembled on
- * the device from the current solution into a P1 vector field (zero away from the boundary).
+ * the device from the current solution into a vector field on the context's nodes.  On every kind of context a node that lies on no
+ * exterior facet holds exactly 0.0: each facet adds to its own nodes only (cfdh_wall_stats_* take A == 0 to mean "not a wall").
+ * On P1 and Q1 contexts the field is tested with the vertex basis, as the reference's CG1 `vector` space.  On a P2 context of
+ * cfdh_create_elem the field lives on ALL P2 nodes and is tested with the P2 basis (the edge nodes of a wall facet receive 2/3 of a
+ * constant Tt, its vertices 1/6 each in 2-D) -- unlike the reference's CG1 field and unlike the context of cfdh_create_ipcs below.
  * shear: nv x gdim host array, or NULL to compute without downloading.
  * On a context of cfdh_create_ipcs the field is that of the P2 u_sol on the VERTICES (the test space `vector` of
  * solverBase.py:144-162 is CG1 whatever the velocity degree): shear [nvert][gdim], T = -mu (grad u + grad u^T) n, and per vertex v

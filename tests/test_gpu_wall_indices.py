@@ -116,6 +116,18 @@ def _stats_ctx(kind):
     return ctx, d, m.num_vertices, m.num_vertices, m.num_vertices
 
 
+def _wall_mask(kind):
+    """The vertices of the wall-shear field of _stats_ctx(kind) that lie on an exterior facet, from the mesh alone."""
+    from post_twin import PostTwin
+    if kind in ("ipcs2d", "ipcs3d"):
+        m, _ = _ipcs_mesh(2 if kind == "ipcs2d" else 3)
+        mask = np.zeros(m.num_vertices, dtype=bool)
+        mask[np.unique(m.facet_vertices)] = True
+        return mask
+    m = {"p1tri": lambda: create_unit_square(4), "p1tet": lambda: create_unit_cube(3), "q1hex": lambda: node_mesh3("Q1"), "p2tri": lambda: node_mesh("P2")}[kind]()
+    return PostTwin(m.x, m.cells, m.facet_cells, m.facet_local).wall_nodes()
+
+
 def _set_state(ctx, u, p):
     if isinstance(ctx, _lib.IpcsContext):
         ctx.set_state(u=u.ravel(), p=p)
@@ -148,6 +160,14 @@ def test_sums_and_indices_match_numpy(kind):
     totals = ctx.wall_stats_get(_lib.WALL_TOTALS)
     wall = A > 0
     assert wall.any() and np.isfinite(ref["rrt"]).all()
+    # "zero away from the boundary": the accumulated field marks exactly the vertices on an exterior facet, and every index is 0 elsewhere
+    # (an interior vertex that received rounding noise would have A > 0, an OSI formed from noise and an RRT of order 1e16)
+    geo = _wall_mask(kind)
+    assert geo.shape == wall.shape and np.array_equal(wall, geo), "A > 0 on %d vertices off the wall" % int((wall & ~geo).sum())
+    assert (~geo).any()
+    for k in ("tawss", "osi", "rrt", "wss_peak"):
+        assert np.array_equal(dev[k][~geo], np.zeros(int((~geo).sum()))), k
+    assert np.array_equal(dev["wss_mean"][~geo], np.zeros((int((~geo).sum()), d)))
     errs = {k: np.abs(dev[k] - ref[k]).max() / np.abs(ref[k]).max() for k in ("tawss", "wss_mean", "wss_peak")}
     errs["osi"] = np.abs(dev["osi"] - ref["osi"]).max()
     errs["rrt"] = (np.abs(dev["rrt"] - ref["rrt"])[wall] / ref["rrt"][wall]).max()
