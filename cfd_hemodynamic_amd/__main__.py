@@ -4,7 +4,9 @@ unknown `--key value` pairs are literal-evaluated and passed to the scenario (ma
 `--wall_indices_from T0 --wall_indices_to T1` (defaults 0 and T; either switches it on) writes the cycle-averaged wall shear
 indices of that window next to the other results (wall_indices.npz / .vtu / .txt).
 `--transport age` or `--transport bolus [--bolus_from T0 --bolus_to T1]` (defaults 0 and T), with `--transport_diffusivity D`, steps a
-passive scalar on the device behind every flow step and writes transport.npz and the `transport` VTU series."""
+passive scalar on the device behind every flow step and writes transport.npz and the `transport` VTU series.
+`--particles N [--particles_every K --particles_nsub M]` releases N massless particles on the inlet (once at t = 0, or every K steps),
+tracks them on the device behind every flow step and writes particles.npz and the `particles` VTU point clouds."""
 from __future__ import annotations
 
 import argparse
@@ -51,6 +53,10 @@ def main(argv=None):
     s.add_argument("--transport_diffusivity", type=float, default=0.0)
     s.add_argument("--bolus_from", type=float, default=None)
     s.add_argument("--bolus_to", type=float, default=None)
+    # Lagrangian particles on the device: N per release on the inlet, released every K steps (default: once), M substeps per step
+    s.add_argument("--particles", type=int, default=None)
+    s.add_argument("--particles_every", type=int, default=None)
+    s.add_argument("--particles_nsub", type=int, default=None)
     args, extra = ap.parse_known_args(argv)
     kw = _parse_extra(extra)
     try:
@@ -71,6 +77,12 @@ def main(argv=None):
         solve_kw["transport"] = ("bolus", 0.0 if args.bolus_from is None else args.bolus_from, args.T if args.bolus_to is None else args.bolus_to)
     if args.transport:
         solve_kw["transport_diffusivity"] = args.transport_diffusivity
+    if args.particles is not None:
+        solve_kw["particles"] = {"n": args.particles}
+        if args.particles_every is not None:
+            solve_kw["particles"]["every"] = args.particles_every
+        if args.particles_nsub is not None:
+            solve_kw["particles"]["nsub"] = args.particles_nsub
     sim.solve(out, **solve_kw)
     print("results in", out)
     return 0

@@ -47,6 +47,11 @@ class ScalarStats(C.Structure):
     _fields_ = [("its", C.c_int32), ("reason", C.c_int32), ("rel_res", C.c_double), ("ms_assemble", C.c_double), ("ms_total", C.c_double)]
 
 
+class ParticleStats(C.Structure):
+    _fields_ = [("active", C.c_int64), ("exited", C.c_int64), ("lost", C.c_int64), ("stepped", C.c_int64), ("ms_kernel", C.c_double),
+                ("ms_total", C.c_double)]
+
+
 class FgmresTrace(C.Structure):
     _fields_ = [
         ("m", C.c_int32), ("max_res", C.c_int32), ("max_cycles", C.c_int32),
@@ -75,6 +80,7 @@ SYMBOLS = [
     "cfdh_wall_stats_reset", "cfdh_wall_stats_accumulate", "cfdh_wall_stats_get",
     "cfdh_scalar_enable", "cfdh_scalar_set_dirichlet", "cfdh_scalar_set_state", "cfdh_scalar_get_state", "cfdh_scalar_set_tolerances",
     "cfdh_scalar_step", "cfdh_scalar_get_operator", "cfdh_scalar_functional", "cfdh_scalar_krylov_solve", "cfdh_scalar_get_order",
+    "cfdh_particles_enable", "cfdh_particles_seed", "cfdh_particles_clear", "cfdh_particles_step", "cfdh_particles_get",
 ]
 
 
@@ -183,6 +189,11 @@ def lib():
     L.cfdh_scalar_functional.argtypes = [vp, C.c_int, C.c_int, dp]
     L.cfdh_scalar_krylov_solve.argtypes = [vp, dp, dp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(ScalarStats), dp, dp]
     L.cfdh_scalar_get_order.argtypes = [vp, ip]
+    L.cfdh_particles_enable.argtypes = [vp, C.c_int64, C.c_int32]
+    L.cfdh_particles_seed.argtypes = [vp, C.c_int64, dp, ip, C.c_double]
+    L.cfdh_particles_clear.argtypes = [vp]
+    L.cfdh_particles_step.argtypes = [vp, C.c_double, C.POINTER(ParticleStats)]
+    L.cfdh_particles_get.argtypes = [vp, C.c_int, lp, C.c_void_p]
     _LIB = L
     return L
 
@@ -240,6 +251,10 @@ INFO_SCALAR_ENABLED, INFO_SCALAR_STEPS, INFO_SCALAR_ASSEMBLIES = 95, 96, 97
 # cfdh_scalar_krylov_solve: words of the scalar block
 SC_RHO, SC_RHO_OLD, SC_ALPHA, SC_OMEGA, SC_BETA, SC_TOL2, SC_BN2, SC_RN2, SC_DONE, SC_ITS, SC_BAD = range(11)
 SC_NSCAL = 16
+# cfdh_particles_get; particle status; cfdh_info: particles enabled, particle steps taken, launches of the advection kernel
+PARTICLE_X, PARTICLE_CELL, PARTICLE_STATUS, PARTICLE_AGE, PARTICLE_PATH, PARTICLE_EXPOSURE, PARTICLE_T_END = range(7)
+PARTICLE_ACTIVE, PARTICLE_LOST = 0, -1  # an exit through a facet of marker m is 1 + m
+INFO_PARTICLES_ENABLED, INFO_PARTICLE_STEPS, INFO_PARTICLE_LAUNCHES = 103, 104, 105
 
 
 class Context:
@@ -695,6 +710,48 @@ class Context:
         self._chk(self.L.cfdh_scalar_krylov_solve(self.h, _dp(b), _dp(x0), float(rtol), float(atol), int(max_it), _dp(x), C.byref(st),
                                                   _dp(scal), _dp(p)))
         return x, st.its, st.reason, st.rel_res, scal, p
+
+    # -- Lagrangian particle tracking (cfdh_particles_*): closed-form P1 contexts, one GPU ------------------------------
+    def particles_enable(self, capacity, nsub=2):
+        """Room for `capacity` particles and the neighbour / affine-map tables; a later call may change nsub only."""
+        self._chk(self.L.cfdh_particles_enable(self.h, int(capacity), int(nsub)))
+
+    def particles_seed(self, x, cell, t_birth=0.0):
+        """Appends active particles at x [n, gdim] in the cells `cell` [n] (the constructor's cell numbering)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, self.dim)
+        cell = np.ascontiguousarray(cell, dtype=np.int32).reshape(-1)
+        if len(cell) != len(x):
+            raise ValueError("one cell per particle")
+        self._chk(self.L.cfdh_particles_seed(self.h, len(x), _dp(x), _ip(cell), float(t_birth)))
+
+    def particles_clear(self):
+        self._chk(self.L.cfdh_particles_clear(self.h))
+
+    def particles_step(self, t0):
+        """One step over [t0, t0 + dt], after solve_step() and before advance().  Returns the ParticleStats."""
+        st = ParticleStats()
+        self._chk(self.L.cfdh_particles_step(self.h, float(t0), C.byref(st)))
+        return st
+
+    def particles_count(self):
+        n = C.c_int64(0)
+        self._chk(self.L.cfdh_particles_get(self.h, PARTICLE_X, C.byref(n), None))
+        return int(n.value)
+
+    def particles_get(self, which):
+        """Field `which` (PARTICLE_X .. PARTICLE_T_END) of all particles in seeding order."""
+        n = C.c_int64(0)
+        self._chk(self.L.cfdh_particles_get(self.h, int(which), C.byref(n), None))
+        m = int(n.value)
+        if which == PARTICLE_X:
+            out = np.zeros((m, self.dim))
+        elif which in (PARTICLE_CELL, PARTICLE_STATUS):
+            out = np.zeros(m, dtype=np.int32)
+        else:
+            out = np.zeros(m)
+        if m:
+            self._chk(self.L.cfdh_particles_get(self.h, int(which), C.byref(n), out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def scalar_order(self):
         """The device row of every vertex (cfdh_scalar_get_order)."""

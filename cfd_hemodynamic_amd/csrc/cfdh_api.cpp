@@ -185,6 +185,7 @@ void cfdh_destroy(cfdh_ctx *c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   cfdh_ipcs_free(c);
   cfdh_scalar_free(c);
+  cfdh_particles_free(c);
   comm_finalize(c);
   c->hS.clear(); c->hL.clear(); c->hA.clear(); c->hLg.clear();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1690,6 +1691,9 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 100: return c->blk_cl_max;                  // ... and cell list (0 on contexts that do not build them)
     case 101: return c->blk_cl_min;
     case 102: return c->env.asm_stage ? 1 : 0;       // fixed-stride lists in use (CFDH_ASM_STAGE as this context read it)
+    case 103: return c->pt ? 1 : 0;                  // particles enabled (cfdh_particles_enable)
+    case 104: return c->n_particle_steps;            // particle steps taken
+    case 105: return c->n_particle_launches;         // launches of the advection kernel since cfdh_create
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;
@@ -1701,6 +1705,33 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 25: { const AmgHier &h = c->opt.pc_type >= 1 ? c->hL : c->hS; return h.fused ? 1 : 0; }
     default: return -1;
   }
+}
+
+// ---- Lagrangian particle tracking (cfdh_particles.hip) ------------------------------------------------------------------------
+
+int cfdh_particles_enable(cfdh_ctx *c, int64_t capacity, int32_t nsub) {
+  ENTER(c);
+  return cfdh_particles_enable_impl(c, capacity, nsub);
+}
+
+int cfdh_particles_seed(cfdh_ctx *c, int64_t n, const double *x, const int32_t *cell, double t_birth) {
+  ENTER(c);
+  return cfdh_particles_seed_impl(c, n, x, cell, t_birth);
+}
+
+int cfdh_particles_clear(cfdh_ctx *c) {
+  ENTER(c);
+  return cfdh_particles_clear_impl(c);
+}
+
+int cfdh_particles_step(cfdh_ctx *c, double t0, cfdh_particle_stats *stats) {
+  ENTER(c);
+  return cfdh_particles_step_impl(c, t0, stats);
+}
+
+int cfdh_particles_get(cfdh_ctx *c, int which, int64_t *n, void *out) {
+  ENTER(c);
+  return cfdh_particles_get_impl(c, which, n, out);
 }
 
 // ---- passive scalar transport (cfdh_scalar.hip) --------------------------------------------------------------------------------

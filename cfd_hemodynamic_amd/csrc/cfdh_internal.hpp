@@ -180,6 +180,7 @@ struct ProfSlot {
 
 struct IpcsData;  // incremental pressure-correction context (cfdh_ipcs.hpp)
 struct ScalarData;  // passive scalar transport of a closed-form P1 context (cfdh_scalar.hip)
+struct ParticleData;  // Lagrangian particles of a closed-form P1 context (cfdh_particles.hip)
 
 struct cfdh_ctx {
   int device = 0;
@@ -504,6 +505,9 @@ struct cfdh_ctx {
   // passive scalar transport (cfdh_scalar_*, cfdh_scalar.hip): everything it owns, allocated by the first cfdh_scalar_enable
   ScalarData *sc = nullptr;
   long long n_scalar_steps = 0, n_scalar_asm = 0;  // cfdh_info 96, 97
+  // Lagrangian particle tracking (cfdh_particles_*, cfdh_particles.hip): everything it owns, allocated by the first cfdh_particles_enable
+  ParticleData *pt = nullptr;
+  long long n_particle_steps = 0, n_particle_launches = 0;  // cfdh_info 104, 105
 };
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
@@ -626,6 +630,14 @@ int cfdh_scalar_krylov_solve_impl(cfdh_ctx *c, const double *b, const double *x0
                                   cfdh_scalar_stats *st, double *scalars, double *p);
 int cfdh_scalar_get_order_impl(cfdh_ctx *c, int32_t *row);
 void cfdh_scalar_free(cfdh_ctx *c);
+
+// ---- Lagrangian particle tracking on the closed-form P1 contexts (cfdh_particles.hip; the entry points of include/cfdh.h minus ENTER) ----
+int cfdh_particles_enable_impl(cfdh_ctx *c, int64_t capacity, int32_t nsub);
+int cfdh_particles_seed_impl(cfdh_ctx *c, int64_t n, const double *x, const int32_t *cell, double t_birth);
+int cfdh_particles_clear_impl(cfdh_ctx *c);
+int cfdh_particles_step_impl(cfdh_ctx *c, double t0, cfdh_particle_stats *st);
+int cfdh_particles_get_impl(cfdh_ctx *c, int which, int64_t *n, void *out);
+void cfdh_particles_free(cfdh_ctx *c);
 
 // ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------
 int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out [nvert][dim]: entries of the wall vertices only

@@ -119,7 +119,7 @@ class Scenario(ABC):
 
     def solve(self, output_folder: str = None, afterStepCallback: Callable[[float], None] = None,
               device_resident: bool = True, max_steps: int = None, write_every: int = 1, wall_indices=None, transport=None,
-              transport_diffusivity: float = 0.0) -> str:
+              transport_diffusivity: float = 0.0, particles=None) -> str:
         """wall_indices: None (default) -- nothing; True -- the cycle-averaged wall shear indices (TAWSS, OSI, RRT, mean and peak
         wall shear stress: wall_indices.py) over the whole run; (t0, t1) -- over the steps that end in (t0, t1].  They are accumulated
         on the device with weight dt right after the step's `assemble_wss()`; afterwards `self.wall_indices` holds the fields, `W` and
@@ -130,10 +130,21 @@ class Scenario(ABC):
         scalar with diffusivity `transport_diffusivity`, stepped on the device right after the flow step and before the state is
         advanced (closed-form P1 solvers on one GPU; NotImplementedError elsewhere).  A scenario without an inlet tag runs with no
         Dirichlet set.  The field joins the VTU series as the point field `transport`; afterwards `self.transport` holds the field
-        and the per-step integral, and with an output folder transport.npz is written."""
+        and the per-step integral, and with an output folder transport.npz is written.
+
+        particles: None (default) -- nothing; a dict -- massless particles tracked on the device (particles.py, cfdh_particles_*):
+        "n" particles per release on the facets tagged tags[release] ("release", default "inlet"), released at t = 0 and, with
+        "every": K, again after every K-th step; "nsub" midpoint substeps per flow step (default 2); "seed" of the random
+        positions (default 0).  They are moved right after the flow step and before the state is advanced (closed-form P1 solvers
+        on one GPU; NotImplementedError elsewhere) and stop for good at the first boundary facet they meet.  Afterwards
+        `self.particles` holds the final fields (x, cell, status, age, path, exposure, t_end), `seeded`, `counts` per status
+        (0 active, 1 + marker exit, -1 lost) and the residence-time `summary`; with an output folder particles.npz / .txt and, at
+        `write_every`, the point clouds particles/particles_NNNNNN.vtu are written."""
         mesh, T, solver = self.mesh, self.T, self.solver
         self.transport = None
         tr = self._transport_setup(transport, transport_diffusivity)
+        self.particles = None
+        pt = self._particles_setup(particles, output_folder if write_every else None)
         self.wall_indices = None
         if wall_indices is not None and wall_indices is not True:
             wall_indices = (float(wall_indices[0]), float(wall_indices[1]))
@@ -193,6 +204,8 @@ class Scenario(ABC):
                     error_log.write("t = %.3f: error = %.3g" % (t, error) + "\n")
             if tr is not None:
                 self._transport_step(tr, t, bool(writers) and i % write_every == 0)
+            if pt is not None:
+                self._particles_step(pt, t - self.dt, i, bool(write_every) and i % write_every == 0)
             solver.assemble_wss()
             if wall_indices is not None and step_in_window(t, self.dt, wall_indices):
                 solver.wall_stats_accumulate(self.dt)
@@ -261,11 +274,62 @@ class Scenario(ABC):
             if output_folder and mesh.comm.rank == 0:
                 np.savez(os.path.join(output_folder, "transport.npz"), x=mesh.x, cells=mesh.cells,
                          **{k: v for k, v in self.transport.items() if k != "mode"})
+        if pt is not None:
+            from . import particles as P
+            fields = solver.particles_get()
+            summary = P.residence_times(fields["status"], fields["age"])
+            self.particles = dict(fields, seeded=pt["seeded"], counts={s: r["count"] for s, r in summary.items()}, summary=summary,
+                                  stepped=np.array(pt["stepped"], dtype=np.int64), ms_kernel=np.array(pt["ms_kernel"]))
+            if output_folder and mesh.comm.rank == 0:
+                P.write_npz(os.path.join(output_folder, "particles.npz"), fields, summary)
+                P.write_summary(os.path.join(output_folder, "particles.txt"), summary, t)
         for w in writers:
             w.close()
         if error_log:
             error_log.close()
         return output_folder
+
+    def _particles_setup(self, particles, cloud_folder):
+        """Parses `particles` of solve(), enables the tracker on the solver and makes the first release; None when off."""
+        if particles is None:
+            return None
+        unknown = set(particles) - {"n", "release", "every", "nsub", "seed"}
+        if unknown or "n" not in particles or int(particles["n"]) < 1:
+            raise ValueError('particles must be None or a dict with "n" >= 1 and optionally "release", "every", "nsub", "seed"')
+        from . import particles as P
+        n, every = int(particles["n"]), particles.get("every")
+        if every is not None and int(every) < 1:
+            raise ValueError('particles["every"] must be >= 1')
+        release = particles.get("release", "inlet")
+        marker, ft = self.tags.get(release), self.facet_tags
+        if marker is None or ft is None or len(ft.find(marker)) == 0:
+            raise ValueError("particles: the scenario has no facets tagged %r to release from" % release)
+        nsteps = int(np.ceil(self.T / self.dt - 1e-9))
+        releases = 1 if every is None else 1 + (nsteps - 1) // int(every)
+        solver = self.solver
+        solver.particles_enable(n * releases, int(particles.get("nsub", 2)))
+        pt = {"n": n, "every": None if every is None else int(every), "facets": np.asarray(ft.find(marker)), "seeded": 0,
+              "rng": np.random.default_rng(int(particles.get("seed", 0))), "capacity": n * releases, "stepped": [], "ms_kernel": [],
+              "cloud": P.CloudWriter(os.path.join(cloud_folder, "particles")) if cloud_folder and self.mesh.comm.rank == 0 else None}
+        self._particles_release(pt, 0.0)
+        return pt
+
+    def _particles_release(self, pt, t):
+        from . import particles as P
+        if pt["seeded"] + pt["n"] > pt["capacity"]:
+            return
+        x, cells = P.sample_on_marker(self.mesh, pt["facets"], pt["n"], pt["rng"])
+        self.solver.particles_seed(x, cells, t)
+        pt["seeded"] += pt["n"]
+
+    def _particles_step(self, pt, t0, i, write):
+        st = self.solver.particles_step(t0)
+        pt["stepped"].append(st.stepped)
+        pt["ms_kernel"].append(st.ms_kernel)
+        if write and pt["cloud"] is not None:
+            pt["cloud"].write(t0 + self.dt, self.solver.particles_get())
+        if pt["every"] is not None and i % pt["every"] == 0 and t0 + self.dt < self.T:
+            self._particles_release(pt, t0 + self.dt)
 
     def _transport_setup(self, transport, diffusivity):
         """Parses `transport` of solve(), enables the scalar on the solver and sets the inlet Dirichlet set; None when off."""

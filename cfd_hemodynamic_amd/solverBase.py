@@ -121,9 +121,9 @@ class SolverBase(ABC):
         np.add.at(out, fv[:, 1], 0.5 * Tt)
 
     # -- passive scalar transport on the device (cfdh_scalar_*: blood age, contrast bolus) -----------------------------------
-    def _transport_ctx(self):
-        """The context, when the scalar exists on it: closed-form P1 kernels, whole mesh on one GPU.  Raises before any device work
-        otherwise."""
+    def _transport_ctx(self, what="transport", noun="passive scalar"):
+        """The context, when the scalar (or the particle tracker) exists on it: closed-form P1 kernels, whole mesh on one GPU.
+        Raises before any device work otherwise."""
         from . import _lib
         ctx = getattr(self, "ctx", None)
         comm = getattr(self, "_comm", None)
@@ -131,13 +131,13 @@ class SolverBase(ABC):
         if ctx is None:
             why = "the solver holds no device context"
         elif isinstance(ctx, _lib.IpcsContext):
-            why = "the pressure-correction (IPCS) solvers have no passive scalar"
+            why = "the pressure-correction (IPCS) solvers have no " + noun
         elif int(getattr(ctx, "etype", 0)) != 0:
-            why = "the passive scalar runs on the closed-form P1 kernels, not on the generic-element (P2 / Q1) contexts"
+            why = "the " + noun + " runs on the closed-form P1 kernels, not on the generic-element (P2 / Q1) contexts"
         elif getattr(self, "_part", None) is not None or (comm is not None and comm.size > 1):
-            why = "the passive scalar runs on one GPU, not on a part of a partitioned run"
+            why = "the " + noun + " runs on one GPU, not on a part of a partitioned run"
         if why:
-            raise NotImplementedError("transport: " + why)
+            raise NotImplementedError(what + ": " + why)
         return ctx
 
     def transport_enable(self, D=0.0, s=0.0, theta_c=0.5, nodes=None, values=None, rtol=None):
@@ -167,6 +167,32 @@ class SolverBase(ABC):
     def transport_field(self, c=None):
         """The scalar on the vertices [nv]; with an argument: sets it."""
         return self._transport_ctx().scalar_state(c)
+
+    # -- Lagrangian particle tracking on the device (cfdh_particles_*: pathlines, residence times, shear exposure) -----------
+    def _particles_ctx(self):
+        return self._transport_ctx("particles", "particle tracker")
+
+    def particles_enable(self, capacity, nsub=2):
+        """Room for `capacity` massless particles, `nsub` explicit-midpoint substeps per flow step (a later call changes nsub only)."""
+        self._particles_ctx().particles_enable(capacity, nsub)
+
+    def particles_seed(self, x, cells, t_birth=0.0):
+        """Append particles at x [n, gdim] in the mesh cells `cells` [n] (particles.py has helpers that produce both)."""
+        self._particles_ctx().particles_seed(x, cells, t_birth)
+
+    def particles_step(self, t0):
+        """Move the particles over [t0, t0 + dt] with the velocity of the flow step just solved: call after solveStep() and before
+        advance() / the copy of u_sol into u_prev."""
+        self.last_particle_stats = self._particles_ctx().particles_step(t0)
+        return self.last_particle_stats
+
+    def particles_get(self, which=None):
+        """One field (a _lib.PARTICLE_* code), or with no argument the dict x, cell, status, age, path, exposure, t_end."""
+        ctx = self._particles_ctx()
+        if which is not None:
+            return ctx.particles_get(which)
+        names = ("x", "cell", "status", "age", "path", "exposure", "t_end")  # the order of _lib.PARTICLE_X .. PARTICLE_T_END
+        return {k: ctx.particles_get(w) for w, k in enumerate(names)}
 
     @staticmethod
     def _simplex_gradients(mesh):

@@ -730,6 +730,59 @@ int cfdh_scalar_krylov_solve(cfdh_ctx *ctx, const double *b, const double *x0, d
  * sums and the slices of the assembly's work list run over device rows).  Exposed for tests that place data on chosen rows. */
 int cfdh_scalar_get_order(cfdh_ctx *ctx, int32_t *row);
 
+/* ---- Lagrangian particle tracking (pathlines, residence times, shear exposure; not in the reference) ---------------------
+ *
+ * Massless particles follow the velocity of the step the flow solver has just taken.  Call cfdh_particles_step after
+ * cfdh_solve_step and before cfdh_advance: over the step the velocity is w(x, s) = (1 - s) u_prev(x) + s u_sol(x), s in [0, 1],
+ * P1 in space on the context's cells.
+ *
+ * One step of one particle: nsub substeps of h = dt / nsub, substep k with s0 = k / nsub, explicit midpoint:
+ *   k1 = w(x, s0), from the barycentric coordinates lambda of x in the particle's cell;
+ *   xm = x + (h / 2) k1, located by the walk below; when that walk leaves the domain the substep degrades to Euler, k2 = k1,
+ *   otherwise k2 = w(xm, s0 + 1 / (2 nsub)) in the cell the walk ended in;
+ *   xn = x + h k2; the particle is moved from x to xn by the same walk;
+ *   path += |x_new - x| and exposure += tau mu gamma_dot, gamma_dot = sqrt(2 D:D), D = sym grad w at s0 + 1 / (2 nsub) in the
+ *   midpoint's cell (the start cell after the Euler fallback), tau = h, or the fraction of h travelled when the substep ends at
+ *   an exit.  mu is that of cfdh_set_params.
+ * The walk from x to a target y, starting in cell c: with lambda(y) in c, every lambda_f(y) >= -1e-12 ends the walk.  Otherwise,
+ * among the facets with lambda_f(y) < -1e-12 (facet f is opposite local vertex f), the one with the smallest crossing parameter
+ * t_f = lambda_f(x) / (lambda_f(x) - lambda_f(y)) is crossed, ties to the lowest f, and the walk goes on in the cell behind it
+ * with the same x and y.  At an exterior facet the particle stops at x + clamp(t_f, 0, 1)(y - x) with status 1 + the facet's
+ * CURRENT marker (cfdh_set_facet_markers needs no rebuild) and end time t0 + (k + clamp(t_f, 0, 1)) h, and never moves again:
+ * walls, inlets and outlets alike.  More than 64 crossings in one walk: status -1 (lost), the particle stays where the substep
+ * started, its end time is t0 + k h.
+ *
+ * One lane per particle, no atomics; two steps from the same state give the same bytes.  Contexts: closed-form P1 contexts of
+ * cfdh_create (gdim 2 and 3), the whole mesh on one GPU.  cfdh_particles_enable returns CFDH_E_ARG, with the context unchanged, on
+ * generic-element contexts, on contexts of cfdh_create_ipcs and on a part of a partitioned run, for nsub < 1 and capacity < 1.
+ * Every other cfdh_particles_* call returns CFDH_E_STATE before cfdh_particles_enable.  A context that never enables particles
+ * allocates nothing and launches nothing for them (cfdh_info 103: enabled, 104: particle steps taken, 105: launches of the
+ * advection kernel since cfdh_create). */
+typedef struct cfdh_particle_stats {
+  int64_t active, exited, lost;  /* particles with status 0 / > 0 / < 0 after the step */
+  int64_t stepped;               /* particles that were active when the step began */
+  double ms_kernel;              /* the advection kernel (device events) */
+  double ms_total;               /* the call (host clock) */
+} cfdh_particle_stats;
+/* Allocates room for `capacity` particles and builds the neighbour and affine-map tables.  A later call may change nsub only:
+ * another capacity is CFDH_E_ARG. */
+int cfdh_particles_enable(cfdh_ctx *ctx, int64_t capacity, int32_t nsub);
+/* Appends n active particles born at t_birth: x [n][gdim], cell [n] in the caller's cell numbering.  Every point must lie in its
+ * cell (every lambda >= -1e-9).  CFDH_E_ARG, with nothing appended, for a point outside its cell, a cell out of range, a
+ * non-finite coordinate or t_birth, and for more particles than the capacity still holds. */
+int cfdh_particles_seed(cfdh_ctx *ctx, int64_t n, const double *x, const int32_t *cell, double t_birth);
+/* Removes all particles; capacity, nsub and the tables stay. */
+int cfdh_particles_clear(cfdh_ctx *ctx);
+/* One step over [t0, t0 + dt] with dt of cfdh_set_params.  Needs cfdh_set_params and a state (cfdh_set_state or a solved step):
+ * CFDH_E_STATE otherwise; CFDH_E_ARG for a non-finite t0.  stats may be NULL. */
+int cfdh_particles_step(cfdh_ctx *ctx, double t0, cfdh_particle_stats *stats);
+/* Field `which` of all particles in seeding order; *n receives their number, out may be NULL (query).
+ *   0: x [n][gdim] double      1: cell [n] int32, caller's numbering      2: status [n] int32 (0 active, 1 + marker, -1 lost)
+ *   3: age [n] double = (t_end when stopped, else the time after the last step) - t_birth, 0 for a particle not stepped yet
+ *   4: path [n] double         5: exposure [n] double                     6: t_end [n] double, NaN while active
+ * An unknown which: CFDH_E_ARG. */
+int cfdh_particles_get(cfdh_ctx *ctx, int which, int64_t *n, void *out);
+
 /* ---- multi-GPU ---------------------------------------------- */
 
 /* Halo plan in local vertex numbers: for neighbour k, send_idx[send_ptr[k]..send_ptr[k+1])
@@ -795,7 +848,9 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 95: 1 when the passive scalar is enabled (cfdh_scalar_enable), 96: scalar steps taken, 97: launches of the scalar assembly
  * kernel since cfdh_create;
  * 98 / 99: longest / shortest per-workgroup vertex list of the P1 triangle assembly, 100 / 101: the same of its cell lists (0 on
- * other contexts), 102: 1 when that assembly reads them at a fixed stride (CFDH_ASM_STAGE, read by cfdh_create) */
+ * other contexts), 102: 1 when that assembly reads them at a fixed stride (CFDH_ASM_STAGE, read by cfdh_create);
+ * 103: 1 when particles are enabled (cfdh_particles_enable), 104: particle steps taken, 105: launches of the advection kernel
+ * since cfdh_create */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
