@@ -6,7 +6,10 @@ indices of that window next to the other results (wall_indices.npz / .vtu / .txt
 `--transport age` or `--transport bolus [--bolus_from T0 --bolus_to T1]` (defaults 0 and T), with `--transport_diffusivity D`, steps a
 passive scalar on the device behind every flow step and writes transport.npz and the `transport` VTU series.
 `--particles N [--particles_every K --particles_nsub M]` releases N massless particles on the inlet (once at t = 0, or every K steps),
-tracks them on the device behind every flow step and writes particles.npz and the `particles` VTU point clouds."""
+tracks them on the device behind every flow step and writes particles.npz and the `particles` VTU point clouds.
+`--flow_fields vorticity,q_criterion[,shear_rate,dissipation,helicity,lnh]` and / or `--flow_window_from T0 --flow_window_to T1`
+(defaults 0 and T; either switches the window averages on) compute the volumetric flow diagnostics on the device behind every flow
+step: the fields join the VTU series, the per-step energy integrals and the window averages go to flow_diagnostics.npz / .txt."""
 from __future__ import annotations
 
 import argparse
@@ -57,6 +60,10 @@ def main(argv=None):
     s.add_argument("--particles", type=int, default=None)
     s.add_argument("--particles_every", type=int, default=None)
     s.add_argument("--particles_nsub", type=int, default=None)
+    # volumetric flow diagnostics on the device: point fields for the VTU series, window (t0, t1] of the pulsatile averages
+    s.add_argument("--flow_fields", type=str, default=None)
+    s.add_argument("--flow_window_from", type=float, default=None)
+    s.add_argument("--flow_window_to", type=float, default=None)
     args, extra = ap.parse_known_args(argv)
     kw = _parse_extra(extra)
     try:
@@ -83,6 +90,13 @@ def main(argv=None):
             solve_kw["particles"]["every"] = args.particles_every
         if args.particles_nsub is not None:
             solve_kw["particles"]["nsub"] = args.particles_nsub
+    if args.flow_fields is not None or args.flow_window_from is not None or args.flow_window_to is not None:
+        solve_kw["flow_diagnostics"] = {}
+        if args.flow_fields is not None:
+            solve_kw["flow_diagnostics"]["fields"] = tuple(k for k in args.flow_fields.split(",") if k)
+        if args.flow_window_from is not None or args.flow_window_to is not None:
+            solve_kw["flow_diagnostics"]["window"] = (0.0 if args.flow_window_from is None else args.flow_window_from,
+                                                      args.T if args.flow_window_to is None else args.flow_window_to)
     sim.solve(out, **solve_kw)
     print("results in", out)
     return 0

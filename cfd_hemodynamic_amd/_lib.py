@@ -81,6 +81,7 @@ SYMBOLS = [
     "cfdh_scalar_enable", "cfdh_scalar_set_dirichlet", "cfdh_scalar_set_state", "cfdh_scalar_get_state", "cfdh_scalar_set_tolerances",
     "cfdh_scalar_step", "cfdh_scalar_get_operator", "cfdh_scalar_functional", "cfdh_scalar_krylov_solve", "cfdh_scalar_get_order",
     "cfdh_particles_enable", "cfdh_particles_seed", "cfdh_particles_clear", "cfdh_particles_step", "cfdh_particles_get",
+    "cfdh_flow_field", "cfdh_flow_integrals", "cfdh_flow_stats_reset", "cfdh_flow_stats_accumulate", "cfdh_flow_stats_get",
 ]
 
 
@@ -194,6 +195,11 @@ def lib():
     L.cfdh_particles_clear.argtypes = [vp]
     L.cfdh_particles_step.argtypes = [vp, C.c_double, C.POINTER(ParticleStats)]
     L.cfdh_particles_get.argtypes = [vp, C.c_int, lp, C.c_void_p]
+    L.cfdh_flow_field.argtypes = [vp, C.c_int, lp, dp]
+    L.cfdh_flow_integrals.argtypes = [vp, dp]
+    L.cfdh_flow_stats_reset.argtypes = [vp]
+    L.cfdh_flow_stats_accumulate.argtypes = [vp, C.c_double]
+    L.cfdh_flow_stats_get.argtypes = [vp, C.c_int, lp, dp]
     _LIB = L
     return L
 
@@ -255,6 +261,15 @@ SC_NSCAL = 16
 PARTICLE_X, PARTICLE_CELL, PARTICLE_STATUS, PARTICLE_AGE, PARTICLE_PATH, PARTICLE_EXPOSURE, PARTICLE_T_END = range(7)
 PARTICLE_ACTIVE, PARTICLE_LOST = 0, -1  # an exit through a facet of marker m is 1 + m
 INFO_PARTICLES_ENABLED, INFO_PARTICLE_STEPS, INFO_PARTICLE_LAUNCHES = 103, 104, 105
+# cfdh_flow_field; the names Scenario.solve and the command line use; cfdh_flow_integrals; cfdh_flow_stats_get; cfdh_info: a
+# flow-diagnostics buffer exists, launches of the cell-gradient pass, accumulations since the last reset, kernel times
+FLOW_GRADIENT, FLOW_VORTICITY, FLOW_Q, FLOW_SHEAR_RATE, FLOW_DISSIPATION, FLOW_HELICITY, FLOW_LNH = range(7)
+FLOW_FIELDS = {"gradient": FLOW_GRADIENT, "vorticity": FLOW_VORTICITY, "q_criterion": FLOW_Q, "shear_rate": FLOW_SHEAR_RATE,
+               "dissipation": FLOW_DISSIPATION, "helicity": FLOW_HELICITY, "lnh": FLOW_LNH}
+FLOW_INT_VOLUME, FLOW_INT_KINETIC, FLOW_INT_ENSTROPHY, FLOW_INT_DISSIPATION, FLOW_INT_HELICITY, FLOW_INT_DIV, FLOW_INT_Q, FLOW_INT_DIV2 = range(8)
+FLOW_MEAN_U, FLOW_FLUCTUATION, FLOW_MEAN_DISSIPATION, FLOW_MEAN_SHEAR_RATE, FLOW_PEAK_SHEAR_RATE, FLOW_TOTALS = range(6)
+INFO_FLOW_BUFFERS, INFO_FLOW_CELL_PASSES, INFO_FLOW_STATS_COUNT = 106, 107, 108
+INFO_FLOW_CELL_PASS_NS, INFO_FLOW_KERNEL_NS = 109, 110  # device time of the last cell pass / of the last vertex, accumulation or integral kernel
 
 
 class Context:
@@ -752,6 +767,41 @@ class Context:
         if m:
             self._chk(self.L.cfdh_particles_get(self.h, int(which), C.byref(n), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # -- volumetric flow diagnostics (cfdh_flow_*): closed-form P1 contexts, one GPU -------------------------------------------
+    def flow_field(self, which):
+        """FLOW_GRADIENT [nv, d, d], FLOW_VORTICITY [nv] (2-D) / [nv, 3], FLOW_Q / FLOW_SHEAR_RATE / FLOW_DISSIPATION / FLOW_HELICITY /
+        FLOW_LNH [nv] of the current u_sol, recovered to the vertices."""
+        n = C.c_int64()
+        self._chk(self.L.cfdh_flow_field(self.h, int(which), C.byref(n), None))
+        out = np.empty(n.value)
+        self._chk(self.L.cfdh_flow_field(self.h, int(which), C.byref(n), _dp(out)))
+        if int(which) == FLOW_GRADIENT:
+            return out.reshape(-1, self.dim, self.dim)
+        return out.reshape(-1, 3) if int(which) == FLOW_VORTICITY and self.dim == 3 else out
+
+    def flow_integrals(self):
+        """The 8 cell-exact integrals of the current u_sol (FLOW_INT_VOLUME .. FLOW_INT_DIV2)."""
+        out = np.empty(8)
+        self._chk(self.L.cfdh_flow_integrals(self.h, _dp(out)))
+        return out
+
+    def flow_stats_reset(self):
+        """Zero the accumulators of the window averages (allocated on first use)."""
+        self._chk(self.L.cfdh_flow_stats_reset(self.h))
+
+    def flow_stats_accumulate(self, weight):
+        """Add the current u_sol and its recovered shear rate / dissipation with this weight (the step's dt)."""
+        self._chk(self.L.cfdh_flow_stats_accumulate(self.h, float(weight)))
+
+    def flow_stats_get(self, which):
+        """FLOW_MEAN_U [nv, gdim], FLOW_FLUCTUATION / FLOW_MEAN_DISSIPATION / FLOW_MEAN_SHEAR_RATE / FLOW_PEAK_SHEAR_RATE [nv],
+        FLOW_TOTALS (W, count)."""
+        n = C.c_int64()
+        self._chk(self.L.cfdh_flow_stats_get(self.h, int(which), C.byref(n), None))
+        out = np.empty(n.value)
+        self._chk(self.L.cfdh_flow_stats_get(self.h, int(which), C.byref(n), _dp(out)))
+        return out.reshape(-1, self.dim) if int(which) == FLOW_MEAN_U else out
 
     def scalar_order(self):
         """The device row of every vertex (cfdh_scalar_get_order)."""

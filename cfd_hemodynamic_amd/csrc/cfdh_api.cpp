@@ -186,6 +186,7 @@ void cfdh_destroy(cfdh_ctx *c) {
   cfdh_ipcs_free(c);
   cfdh_scalar_free(c);
   cfdh_particles_free(c);
+  cfdh_flow_destroy(c);
   comm_finalize(c);
   c->hS.clear(); c->hL.clear(); c->hA.clear(); c->hLg.clear();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1630,6 +1631,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
       case 84: case 90: return c->ws_count;  // accumulations of the wall shear indices since the last reset
       case 91: return I->scheme;
       case 92: return I->n_assemblies;
+      case 106: case 107: case 108: case 109: case 110: return 0;  // flow diagnostics: refused on this kind of context
       default: return -1;
     }
   }
@@ -1694,6 +1696,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 103: return c->pt ? 1 : 0;                  // particles enabled (cfdh_particles_enable)
     case 104: return c->n_particle_steps;            // particle steps taken
     case 105: return c->n_particle_launches;         // launches of the advection kernel since cfdh_create
+    case 106: case 107: case 108: case 109: case 110: return cfdh_flow_info(c, what);  // flow diagnostics: buffers exist, cell passes, accumulations since the reset, ns of the last kernels
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;
@@ -1705,6 +1708,33 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 25: { const AmgHier &h = c->opt.pc_type >= 1 ? c->hL : c->hS; return h.fused ? 1 : 0; }
     default: return -1;
   }
+}
+
+// ---- volumetric flow diagnostics (cfdh_flow.hip) -------------------------------------------------------------------------------
+
+int cfdh_flow_field(cfdh_ctx *c, int which, int64_t *n, double *out) {
+  ENTER(c);
+  return cfdh_flow_field_impl(c, which, n, out);
+}
+
+int cfdh_flow_integrals(cfdh_ctx *c, double *out) {
+  ENTER(c);
+  return cfdh_flow_integrals_impl(c, out);
+}
+
+int cfdh_flow_stats_reset(cfdh_ctx *c) {
+  ENTER(c);
+  return cfdh_flow_stats_reset_impl(c);
+}
+
+int cfdh_flow_stats_accumulate(cfdh_ctx *c, double weight) {
+  ENTER(c);
+  return cfdh_flow_stats_accumulate_impl(c, weight);
+}
+
+int cfdh_flow_stats_get(cfdh_ctx *c, int which, int64_t *n, double *out) {
+  ENTER(c);
+  return cfdh_flow_stats_get_impl(c, which, n, out);
 }
 
 // ---- Lagrangian particle tracking (cfdh_particles.hip) ------------------------------------------------------------------------

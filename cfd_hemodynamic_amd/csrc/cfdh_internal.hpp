@@ -181,6 +181,7 @@ struct ProfSlot {
 struct IpcsData;  // incremental pressure-correction context (cfdh_ipcs.hpp)
 struct ScalarData;  // passive scalar transport of a closed-form P1 context (cfdh_scalar.hip)
 struct ParticleData;  // Lagrangian particles of a closed-form P1 context (cfdh_particles.hip)
+struct FlowData;  // volumetric flow diagnostics of a closed-form P1 context (cfdh_flow.hip)
 
 struct cfdh_ctx {
   int device = 0;
@@ -508,6 +509,11 @@ struct cfdh_ctx {
   // Lagrangian particle tracking (cfdh_particles_*, cfdh_particles.hip): everything it owns, allocated by the first cfdh_particles_enable
   ParticleData *pt = nullptr;
   long long n_particle_steps = 0, n_particle_launches = 0;  // cfdh_info 104, 105
+  // volumetric flow diagnostics (cfdh_flow_*, cfdh_flow.hip): everything they own, allocated by the first call that needs it
+  FlowData *fl = nullptr;
+  long long n_flow_cell_passes = 0;  // cfdh_info 107
+  hipEvent_t fl_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the last cell pass / the last kernel behind it (cfdh_info 109, 110)
+  bool fl_timed[2] = {false, false};
 };
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
@@ -638,6 +644,16 @@ int cfdh_particles_clear_impl(cfdh_ctx *c);
 int cfdh_particles_step_impl(cfdh_ctx *c, double t0, cfdh_particle_stats *st);
 int cfdh_particles_get_impl(cfdh_ctx *c, int which, int64_t *n, void *out);
 void cfdh_particles_free(cfdh_ctx *c);
+
+// ---- volumetric flow diagnostics on the closed-form P1 contexts (cfdh_flow.hip; the entry points of include/cfdh.h minus ENTER) ----
+int cfdh_flow_field_impl(cfdh_ctx *c, int which, int64_t *n, double *out);
+int cfdh_flow_integrals_impl(cfdh_ctx *c, double *out);
+int cfdh_flow_stats_reset_impl(cfdh_ctx *c);
+int cfdh_flow_stats_accumulate_impl(cfdh_ctx *c, double weight);
+int cfdh_flow_stats_get_impl(cfdh_ctx *c, int which, int64_t *n, double *out);
+int64_t cfdh_flow_info(const cfdh_ctx *c, int what);  // cfdh_info 106 .. 110
+void cfdh_flow_free(cfdh_ctx *c);
+void cfdh_flow_destroy(cfdh_ctx *c);  // ... and the timing events
 
 // ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------
 int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out [nvert][dim]: entries of the wall vertices only

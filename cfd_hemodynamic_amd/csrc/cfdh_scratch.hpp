@@ -15,10 +15,11 @@ enum {
   RO_LEAN_S2 = 12, RO_LEAN_S2_N = 1,         // squared residual norm of the lean prologue / epilogue
   RO_HOST_SCALAR = 16, RO_HOST_SCALAR_N = 1, // comm_allreduce_host: one host scalar on its way through the all-reduce
   RO_AMG_NORM = 20, RO_AMG_NORM_N = 1,       // power iteration of the device-side hierarchy set-up
-  RO_END = RO_AMG_NORM + RO_AMG_NORM_N
+  RO_FLOW = 24, RO_FLOW_N = 8,               // the 8 integrals of cfdh_flow_integrals (RO_RESULT holds 4)
+  RO_END = RO_FLOW + RO_FLOW_N
 };
 static_assert(RO_RESULT + RO_RESULT_N <= RO_POWER && RO_POWER + RO_POWER_N <= RO_MEAN && RO_MEAN + RO_MEAN_N <= RO_LEAN_S2 &&
-                  RO_LEAN_S2 + RO_LEAN_S2_N <= RO_HOST_SCALAR && RO_HOST_SCALAR + RO_HOST_SCALAR_N <= RO_AMG_NORM && RO_END <= RO_WORDS,
+                  RO_LEAN_S2 + RO_LEAN_S2_N <= RO_HOST_SCALAR && RO_HOST_SCALAR + RO_HOST_SCALAR_N <= RO_AMG_NORM && RO_AMG_NORM + RO_AMG_NORM_N <= RO_FLOW && RO_END <= RO_WORDS,
               "red_out slots overlap or leave the buffer");
 
 // h_pinned: HP_x = first word, HP_x_N = words

@@ -119,7 +119,7 @@ class Scenario(ABC):
 
     def solve(self, output_folder: str = None, afterStepCallback: Callable[[float], None] = None,
               device_resident: bool = True, max_steps: int = None, write_every: int = 1, wall_indices=None, transport=None,
-              transport_diffusivity: float = 0.0, particles=None) -> str:
+              transport_diffusivity: float = 0.0, particles=None, flow_diagnostics=None) -> str:
         """wall_indices: None (default) -- nothing; True -- the cycle-averaged wall shear indices (TAWSS, OSI, RRT, mean and peak
         wall shear stress: wall_indices.py) over the whole run; (t0, t1) -- over the steps that end in (t0, t1].  They are accumulated
         on the device with weight dt right after the step's `assemble_wss()`; afterwards `self.wall_indices` holds the fields, `W` and
@@ -139,8 +139,21 @@ class Scenario(ABC):
         on one GPU; NotImplementedError elsewhere) and stop for good at the first boundary facet they meet.  Afterwards
         `self.particles` holds the final fields (x, cell, status, age, path, exposure, t_end), `seeded`, `counts` per status
         (0 active, 1 + marker exit, -1 lost) and the residence-time `summary`; with an output folder particles.npz / .txt and, at
-        `write_every`, the point clouds particles/particles_NNNNNN.vtu are written."""
+        `write_every`, the point clouds particles/particles_NNNNNN.vtu are written.
+
+        flow_diagnostics: None (default) -- nothing; a dict -- the volumetric diagnostics of the velocity (cfdh_flow_*), computed on
+        the device right after the flow step and before the state is advanced (closed-form P1 solvers on one GPU;
+        NotImplementedError elsewhere).  The 8 integrals (volume, kinetic energy, enstrophy, viscous dissipation, helicity,
+        int div u, int Q, int (div u)^2) are recorded every step; "fields": a tuple of names out of vorticity, q_criterion,
+        shear_rate, dissipation, helicity, lnh (the last two in 3-D) joins the VTU series as point fields at `write_every`;
+        "window": True or (t0, t1) accumulates, with weight dt and the window rule of the wall indices, the mean velocity, the
+        fluctuation energy k' and the mean / peak shear rate and mean dissipation.  Afterwards `self.flow_diagnostics` holds
+        `integrals` [steps, 8], `times` and, under "window", those fields with `W`, `steps` and `energy_loss`; with an output folder
+        flow_diagnostics.npz and flow_diagnostics.txt (per-step kinetic energy, dissipation and enstrophy, and the window's
+        time-integrated dissipation: the energy loss) are written."""
         mesh, T, solver = self.mesh, self.T, self.solver
+        self.flow_diagnostics = None
+        fd = self._flow_setup(flow_diagnostics)
         self.transport = None
         tr = self._transport_setup(transport, transport_diffusivity)
         self.particles = None
@@ -169,10 +182,14 @@ class Scenario(ABC):
                        VTUWriter(mesh.comm, f"{output_folder}/wss.bp", solver.shear_stress, "shear_stress")]
             if tr is not None:
                 writers.append(VTUWriter(mesh.comm, f"{output_folder}/transport.bp", tr["function"], "transport"))
+            if fd is not None:
+                writers += [VTUWriter(mesh.comm, f"{output_folder}/{k}.bp", fn, k) for k, fn in fd["functions"].items()]
         t = 0.0
         solver.u_sol.interpolate(self.initial_velocity)
         if writers:
             solver.assemble_wss()
+            if fd is not None:
+                self._flow_fields(fd)
             for w in writers:
                 w.write(t)
         error_log = None
@@ -206,6 +223,8 @@ class Scenario(ABC):
                 self._transport_step(tr, t, bool(writers) and i % write_every == 0)
             if pt is not None:
                 self._particles_step(pt, t - self.dt, i, bool(write_every) and i % write_every == 0)
+            if fd is not None:
+                self._flow_step(fd, t, bool(writers) and i % write_every == 0)
             solver.assemble_wss()
             if wall_indices is not None and step_in_window(t, self.dt, wall_indices):
                 solver.wall_stats_accumulate(self.dt)
@@ -274,6 +293,14 @@ class Scenario(ABC):
             if output_folder and mesh.comm.rank == 0:
                 np.savez(os.path.join(output_folder, "transport.npz"), x=mesh.x, cells=mesh.cells,
                          **{k: v for k, v in self.transport.items() if k != "mode"})
+        if fd is not None:
+            self.flow_diagnostics = {"integrals": np.array(fd["integrals"]).reshape(-1, 8), "times": np.array(fd["times"])}
+            if fd["window_steps"] > 0:
+                self.flow_diagnostics["window"] = dict(solver.flow_stats(), energy_loss=fd["energy_loss"])
+            elif fd["window"] is not None and mesh.comm.rank == 0:
+                print("flow_diagnostics: no step ended inside the window %s (the run stopped at t=%.6g)" % (fd["window"], t))
+            if output_folder and mesh.comm.rank == 0:
+                self._flow_write(output_folder, self.flow_diagnostics)
         if pt is not None:
             from . import particles as P
             fields = solver.particles_get()
@@ -288,6 +315,63 @@ class Scenario(ABC):
         if error_log:
             error_log.close()
         return output_folder
+
+    FLOW_FIELD_NAMES = ("vorticity", "q_criterion", "shear_rate", "dissipation", "helicity", "lnh")
+
+    def _flow_setup(self, flow_diagnostics):
+        """Parses `flow_diagnostics` of solve() and resets the window averages on the solver; None when off."""
+        if flow_diagnostics is None:
+            return None
+        unknown = set(flow_diagnostics) - {"fields", "window"}
+        names = tuple(flow_diagnostics.get("fields", ()))
+        gdim = self.mesh.geometry.dim
+        bad = [k for k in names if k not in self.FLOW_FIELD_NAMES or (gdim == 2 and k in ("helicity", "lnh"))]
+        if unknown or bad:
+            raise ValueError('flow_diagnostics must be None or a dict with "fields" (out of %s; helicity and lnh in 3-D only) and "window"'
+                             % ", ".join(self.FLOW_FIELD_NAMES))
+        window = flow_diagnostics.get("window")
+        if window is not None and window is not True:
+            window = (float(window[0]), float(window[1]))
+        solver = self.solver
+        solver._flow_ctx()  # the solver kinds without the diagnostics raise here, before the time loop
+        if window is not None:
+            solver.flow_stats_reset()
+        functions = {k: Function(solver.V if (k == "vorticity" and gdim == 3) else solver.Q, name=k) for k in names}
+        return {"functions": functions, "window": window, "window_steps": 0, "energy_loss": 0.0, "integrals": [], "times": []}
+
+    def _flow_fields(self, fd):
+        for k, fn in fd["functions"].items():
+            fn.x.array[:] = np.asarray(self.solver.flow_field(k)).reshape(-1)
+
+    def _flow_step(self, fd, t, write):
+        from .wall_indices import step_in_window
+        solver = self.solver
+        fd["integrals"].append(solver.flow_integrals())
+        fd["times"].append(t)
+        if fd["window"] is not None and step_in_window(t, self.dt, fd["window"]):
+            solver.flow_stats_accumulate(self.dt)
+            fd["window_steps"] += 1
+            fd["energy_loss"] += self.dt * fd["integrals"][-1][3]
+        if write:
+            self._flow_fields(fd)
+
+    @staticmethod
+    def _flow_write(output_folder, fd):
+        """flow_diagnostics.npz (everything) and flow_diagnostics.txt (energies per step, the window's energy loss)."""
+        flat = {"integrals": fd["integrals"], "times": fd["times"]}
+        win = fd.get("window")
+        if win is not None:
+            flat.update({"window_" + k: np.asarray(v) for k, v in win.items()})  # the fields, W, steps, energy_loss
+        np.savez(os.path.join(output_folder, "flow_diagnostics.npz"), **flat)
+        with open(os.path.join(output_folder, "flow_diagnostics.txt"), "w") as f:
+            f.write("# t  kinetic_energy  viscous_dissipation  enstrophy\n")
+            for t, row in zip(fd["times"], fd["integrals"]):
+                f.write("%.9g %.12e %.12e %.12e\n" % (t, row[1], row[3], row[2]))
+            if win is not None:
+                f.write("# window: %d steps, W = %.9g\n" % (win["steps"], win["W"]))
+                f.write("# mean shear rate: max over the vertices %.12e; peak shear rate: %.12e\n"
+                        % (win["mean_shear_rate"].max(), win["peak_shear_rate"].max()))
+                f.write("# energy loss: time-integrated viscous dissipation over the window = %.12e\n" % win["energy_loss"])
 
     def _particles_setup(self, particles, cloud_folder):
         """Parses `particles` of solve(), enables the tracker on the solver and makes the first release; None when off."""

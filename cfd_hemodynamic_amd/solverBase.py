@@ -194,6 +194,45 @@ class SolverBase(ABC):
         names = ("x", "cell", "status", "age", "path", "exposure", "t_end")  # the order of _lib.PARTICLE_X .. PARTICLE_T_END
         return {k: ctx.particles_get(w) for w, k in enumerate(names)}
 
+    # -- volumetric flow diagnostics on the device (cfdh_flow_*: vorticity, Q, shear rate, dissipation, helicity, energy) ------
+    def _flow_ctx(self):
+        return self._transport_ctx("flow diagnostics", "flow diagnostics kernel")
+
+    def flow_field(self, name):
+        """One vertex field of the current u_sol, recovered from the cell gradients: "gradient" [nv, d, d], "vorticity" [nv] in 2-D
+        and [nv, 3] in 3-D, "q_criterion", "shear_rate", "dissipation", and in 3-D "helicity" and "lnh" [nv] (or a _lib.FLOW_* code)."""
+        from . import _lib
+        ctx = self._flow_ctx()
+        if isinstance(name, str):
+            if name not in _lib.FLOW_FIELDS:
+                raise ValueError("flow_field: unknown field %r (one of %s)" % (name, ", ".join(_lib.FLOW_FIELDS)))
+            name = _lib.FLOW_FIELDS[name]
+        return ctx.flow_field(name)
+
+    def flow_integrals(self):
+        """[8]: volume, kinetic energy, enstrophy, viscous dissipation, helicity, int div u, int Q, int (div u)^2 of the current u_sol
+        (_lib.FLOW_INT_*)."""
+        return self._flow_ctx().flow_integrals()
+
+    def flow_stats_reset(self):
+        """Zero the window averages of the flow field (allocated on first use)."""
+        self._flow_ctx().flow_stats_reset()
+
+    def flow_stats_accumulate(self, w):
+        """Add the current u_sol, its shear rate and dissipation to the window averages with weight w (the step's dt)."""
+        self._flow_ctx().flow_stats_accumulate(w)
+
+    def flow_stats(self):
+        """The window averages: mean_velocity [nv, d], fluctuation (k'), mean_dissipation, mean_shear_rate, peak_shear_rate [nv],
+        with W (the sum of the weights) and steps."""
+        from . import _lib
+        ctx = self._flow_ctx()
+        W, count = ctx.flow_stats_get(_lib.FLOW_TOTALS)
+        names = ("mean_velocity", "fluctuation", "mean_dissipation", "mean_shear_rate", "peak_shear_rate")  # _lib.FLOW_MEAN_U ..
+        out = {k: ctx.flow_stats_get(w) for w, k in enumerate(names)}
+        out["W"], out["steps"] = float(W), int(count)
+        return out
+
     @staticmethod
     def _simplex_gradients(mesh):
         """grad(lambda_a) of every cell of a P1 simplex mesh, [nc, d + 1, d]."""

@@ -783,6 +783,59 @@ int cfdh_particles_step(cfdh_ctx *ctx, double t0, cfdh_particle_stats *stats);
  * An unknown which: CFDH_E_ARG. */
 int cfdh_particles_get(cfdh_ctx *ctx, int which, int64_t *n, void *out);
 
+/* ---- volumetric flow diagnostics (vorticity, Q-criterion, shear rate, dissipation, helicity, energy; not in the reference) ----
+ *
+ * What the velocity does inside the lumen, from u_sol while it sits on the device (between cfdh_solve_step and cfdh_advance, or
+ * after cfdh_set_state).
+ *
+ * Per cell c: G_c[i][j] = d u_i / d x_j of the P1 velocity (one constant matrix per cell), |c| its area / volume,
+ * S = (G + G^T) / 2, W = (G - G^T) / 2.
+ * Per vertex v, the recovered gradient: G_v = sum_{c contains v} |c| G_c / sum_{c contains v} |c|, both sums over the cells of v in
+ * ascending cell index (the caller's numbering).  Every pointwise vertex quantity below is formed from G_v: S, W and the vorticity
+ * omega mean those of G_v; u_v is the nodal velocity.  A vertex of no cell has G_v = 0.
+ *
+ * cfdh_flow_field(ctx, which, &n, out): vertex fields in the caller's vertex numbering; *n receives the number of doubles,
+ * out == NULL only queries it.
+ *   0 gradient            G_v, row-major                                                      [nv][d d]
+ *   1 vorticity           2-D: G10 - G01 ; 3-D: (G21 - G12, G02 - G20, G10 - G01)             [nv] / [nv][3]
+ *   2 Q-criterion         (|W|_F^2 - |S|_F^2) / 2                                             [nv]
+ *   3 shear rate          gamma_dot = sqrt(2 S:S), the rate behind the particle exposure      [nv]
+ *   4 dissipation density phi = 2 mu S:S, mu of cfdh_set_params                               [nv]
+ *   5 helicity density    u_v . omega_v ; gdim 3 only                                         [nv]
+ *   6 LNH                 u_v . omega_v / (|u_v| |omega_v|), exactly 0 where either norm is 0 ; gdim 3 only   [nv]
+ * which 5 and 6 in 2-D and any other which: CFDH_E_ARG.  Without a state (and, for which 4, without cfdh_set_params): CFDH_E_STATE.
+ *
+ * cfdh_flow_integrals(ctx, out[8]): cell-exact integrals of the current u_sol, one launch and one read-back.
+ *   0 sum |c|
+ *   1 (rho / 2) int |u|^2, exact for P1: int_c |u|^2 = |c| (sum_a |u_a|^2 + |sum_a u_a|^2) / ((d + 1)(d + 2))
+ *   2 (1 / 2) int |omega|^2        3 int 2 mu S:S
+ *   4 int u . omega = sum |c| u_mean,c . omega_c (u_mean,c the cell mean); 0.0 in 2-D
+ *   5 int div u                    6 int Q                    7 int (div u)^2
+ * Entries 2, 3, 6 and 7 are sum |c| (value of G_c).  Needs cfdh_set_params and a state: CFDH_E_STATE otherwise.
+ *
+ * Window averages, shaped like cfdh_wall_stats_*: cfdh_flow_stats_reset allocates on first use and zeroes;
+ * cfdh_flow_stats_accumulate(weight) takes the current u_sol and adds, per vertex, w u [d], w |u|^2, w phi, w gamma_dot, and keeps
+ * max gamma_dot; per context W = sum w and the count.  weight must be finite and > 0 (CFDH_E_ARG); before a reset: CFDH_E_STATE.
+ * cfdh_flow_stats_get(ctx, which, &n, out):
+ *   0 mean velocity sum w u / W                                                     [nv][d]
+ *   1 fluctuation energy per unit mass k' = max(0, (sum w |u|^2 / W - |sum w u / W|^2) / 2)   [nv]
+ *   2 mean phi      3 mean gamma_dot      4 peak gamma_dot                          [nv]
+ *   5 {W, count}                                                                    [2]
+ * which 0 .. 4 with W == 0, or any which before a reset: CFDH_E_STATE; an unknown which: CFDH_E_ARG.
+ *
+ * A cell pass (one lane per cell) writes the rows (|c|, G_c); a vertex pass (one lane per vertex) gathers them through an inverted
+ * index and ends in the formula asked for.  No atomics: two calls on one state return the same bytes.  Contexts: closed-form P1
+ * contexts of cfdh_create (gdim 2 and 3), the whole mesh on one GPU.  Every entry point returns CFDH_E_ARG with a reason, before any
+ * device work and with the context unchanged, on generic-element contexts, on contexts of cfdh_create_ipcs and on a part of a
+ * partitioned run.  A context that never calls them allocates and launches nothing (cfdh_info 106: 1 once a flow-diagnostics
+ * buffer exists, 107: launches of the cell pass since cfdh_create, 108: accumulations since the last reset; 109 / 110: device time
+ * of the last cell pass / of the last kernel behind it, see cfdh_info). */
+int cfdh_flow_field(cfdh_ctx *ctx, int which, int64_t *n, double *out);
+int cfdh_flow_integrals(cfdh_ctx *ctx, double *out);
+int cfdh_flow_stats_reset(cfdh_ctx *ctx);
+int cfdh_flow_stats_accumulate(cfdh_ctx *ctx, double weight);
+int cfdh_flow_stats_get(cfdh_ctx *ctx, int which, int64_t *n, double *out);
+
 /* ---- multi-GPU ---------------------------------------------- */
 
 /* Halo plan in local vertex numbers: for neighbour k, send_idx[send_ptr[k]..send_ptr[k+1])
@@ -850,7 +903,10 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 98 / 99: longest / shortest per-workgroup vertex list of the P1 triangle assembly, 100 / 101: the same of its cell lists (0 on
  * other contexts), 102: 1 when that assembly reads them at a fixed stride (CFDH_ASM_STAGE, read by cfdh_create);
  * 103: 1 when particles are enabled (cfdh_particles_enable), 104: particle steps taken, 105: launches of the advection kernel
- * since cfdh_create */
+ * since cfdh_create;
+ * 106: 1 once a flow-diagnostics buffer exists (cfdh_flow_*), 107: launches of its cell-gradient pass since cfdh_create, 108:
+ * cfdh_flow_stats_accumulate calls since the last cfdh_flow_stats_reset, 109 / 110: nanoseconds, by device events, of the last
+ * cell-gradient pass / of the last vertex, accumulation or integral kernel (0 before the first; the call waits for that kernel) */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
