@@ -9,7 +9,12 @@ passive scalar on the device behind every flow step and writes transport.npz and
 tracks them on the device behind every flow step and writes particles.npz and the `particles` VTU point clouds.
 `--flow_fields vorticity,q_criterion[,shear_rate,dissipation,helicity,lnh]` and / or `--flow_window_from T0 --flow_window_to T1`
 (defaults 0 and T; either switches the window averages on) compute the volumetric flow diagnostics on the device behind every flow
-step: the fields join the VTU series, the per-step energy integrals and the window averages go to flow_diagnostics.npz / .txt."""
+step: the fields join the VTU series, the per-step energy integrals and the window averages go to flow_diagnostics.npz / .txt.
+`--probes "x,y[,z];x,y[,z];..."` and / or `--probe_line "x0,y0[,z0];x1,y1[,z1];n"` sample velocity and pressure at those points on
+the device after every `--sample_every`-th step (default 1) and write probes.npz; `--sample_grid_spacing H` samples them on a regular
+grid over the mesh's bounding box instead (grid/grid_NNNNNN.vti at `--sample_every`), and `--sample_window_from T0 --sample_window_to
+T1` (defaults 0 and T) adds the window means on that grid (grid_mean.vti).  Probes and a grid exclude each other (one sample set
+per run), and the window and `--sample_every` flags without the set they belong to are refused before the scenario is built."""
 from __future__ import annotations
 
 import argparse
@@ -38,6 +43,18 @@ def _parse_extra(extra):
     return out
 
 
+def _check_sampler_flags(ap, args):
+    """The sampler holds one sample set per context: probes or a grid, and the flags that belong to neither are refused."""
+    probes = args.probes is not None or args.probe_line is not None
+    grid = args.sample_grid_spacing is not None
+    if probes and grid:
+        ap.error("--probes / --probe_line and --sample_grid_spacing exclude each other: the sampler holds one sample set per run")
+    if not grid and (args.sample_window_from is not None or args.sample_window_to is not None):
+        ap.error("--sample_window_from / --sample_window_to need --sample_grid_spacing (the window means live on the grid)")
+    if not probes and not grid and args.sample_every is not None:
+        ap.error("--sample_every needs --probes, --probe_line or --sample_grid_spacing")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="cfd_hemodynamic_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -64,7 +81,15 @@ def main(argv=None):
     s.add_argument("--flow_fields", type=str, default=None)
     s.add_argument("--flow_window_from", type=float, default=None)
     s.add_argument("--flow_window_to", type=float, default=None)
+    # point sampler on the device: probe points / a line of probes, or a voxel grid with its window means
+    s.add_argument("--probes", type=str, default=None)
+    s.add_argument("--probe_line", type=str, default=None)
+    s.add_argument("--sample_grid_spacing", type=float, default=None)
+    s.add_argument("--sample_every", type=int, default=None)
+    s.add_argument("--sample_window_from", type=float, default=None)
+    s.add_argument("--sample_window_to", type=float, default=None)
     args, extra = ap.parse_known_args(argv)
+    _check_sampler_flags(ap, args)
     kw = _parse_extra(extra)
     try:
         mod = import_module(f"{__package__}.scenarios.{args.simulation}")
@@ -97,6 +122,24 @@ def main(argv=None):
         if args.flow_window_from is not None or args.flow_window_to is not None:
             solve_kw["flow_diagnostics"]["window"] = (0.0 if args.flow_window_from is None else args.flow_window_from,
                                                       args.T if args.flow_window_to is None else args.flow_window_to)
+    if args.probes is not None or args.probe_line is not None:
+        from .sampling import line
+        pts = []
+        if args.probes is not None:
+            pts += [[float(v) for v in q.split(",")] for q in args.probes.split(";") if q]
+        if args.probe_line is not None:
+            p0, p1, n = args.probe_line.split(";")
+            pts += line([float(v) for v in p0.split(",")], [float(v) for v in p1.split(",")], int(n)).tolist()
+        solve_kw["probes"] = {"points": pts}
+        if args.sample_every is not None:
+            solve_kw["probes"]["every"] = args.sample_every
+    if args.sample_grid_spacing is not None:
+        solve_kw["sample_grid"] = {"spacing": args.sample_grid_spacing}
+        if args.sample_every is not None:
+            solve_kw["sample_grid"]["every"] = args.sample_every
+        if args.sample_window_from is not None or args.sample_window_to is not None:
+            solve_kw["sample_grid"]["window"] = (0.0 if args.sample_window_from is None else args.sample_window_from,
+                                                 args.T if args.sample_window_to is None else args.sample_window_to)
     sim.solve(out, **solve_kw)
     print("results in", out)
     return 0

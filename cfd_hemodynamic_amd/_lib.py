@@ -82,6 +82,8 @@ SYMBOLS = [
     "cfdh_scalar_step", "cfdh_scalar_get_operator", "cfdh_scalar_functional", "cfdh_scalar_krylov_solve", "cfdh_scalar_get_order",
     "cfdh_particles_enable", "cfdh_particles_seed", "cfdh_particles_clear", "cfdh_particles_step", "cfdh_particles_get",
     "cfdh_flow_field", "cfdh_flow_integrals", "cfdh_flow_stats_reset", "cfdh_flow_stats_accumulate", "cfdh_flow_stats_get",
+    "cfdh_sample_set_points", "cfdh_sample_set_grid", "cfdh_sample_get_location", "cfdh_sample_now", "cfdh_sample_series_enable",
+    "cfdh_sample_record", "cfdh_sample_series_get", "cfdh_sample_mean_reset", "cfdh_sample_mean_accumulate", "cfdh_sample_mean_get",
 ]
 
 
@@ -200,6 +202,16 @@ def lib():
     L.cfdh_flow_stats_reset.argtypes = [vp]
     L.cfdh_flow_stats_accumulate.argtypes = [vp, C.c_double]
     L.cfdh_flow_stats_get.argtypes = [vp, C.c_int, lp, dp]
+    L.cfdh_sample_set_points.argtypes = [vp, C.c_int64, dp, C.c_double]
+    L.cfdh_sample_set_grid.argtypes = [vp, dp, dp, lp, C.c_double]
+    L.cfdh_sample_get_location.argtypes = [vp, lp, ip, dp, dp]
+    L.cfdh_sample_now.argtypes = [vp, lp, dp]
+    L.cfdh_sample_series_enable.argtypes = [vp, C.c_int64]
+    L.cfdh_sample_record.argtypes = [vp, C.c_double]
+    L.cfdh_sample_series_get.argtypes = [vp, lp, dp, dp]
+    L.cfdh_sample_mean_reset.argtypes = [vp]
+    L.cfdh_sample_mean_accumulate.argtypes = [vp, C.c_double]
+    L.cfdh_sample_mean_get.argtypes = [vp, C.c_int, lp, dp]
     _LIB = L
     return L
 
@@ -270,6 +282,13 @@ FLOW_INT_VOLUME, FLOW_INT_KINETIC, FLOW_INT_ENSTROPHY, FLOW_INT_DISSIPATION, FLO
 FLOW_MEAN_U, FLOW_FLUCTUATION, FLOW_MEAN_DISSIPATION, FLOW_MEAN_SHEAR_RATE, FLOW_PEAK_SHEAR_RATE, FLOW_TOTALS = range(6)
 INFO_FLOW_BUFFERS, INFO_FLOW_CELL_PASSES, INFO_FLOW_STATS_COUNT = 106, 107, 108
 INFO_FLOW_CELL_PASS_NS, INFO_FLOW_KERNEL_NS = 109, 110  # device time of the last cell pass / of the last vertex, accumulation or integral kernel
+# cfdh_sample_mean_get; cfdh_info: points in the sample set, points located, launches of the sample kernel, row blocks waiting in the
+# series, device time of the last locate / sample kernel, the bin grid (doublings of its edge, total and longest list)
+SAMPLE_MEAN_U, SAMPLE_MEAN_P, SAMPLE_FLUCTUATION, SAMPLE_TOTALS = range(4)
+SAMPLE_TOL = 1e-9  # the default containment tolerance on the barycentric coordinates
+INFO_SAMPLE_POINTS, INFO_SAMPLE_LOCATED, INFO_SAMPLE_LAUNCHES, INFO_SAMPLE_SERIES_ROWS = 111, 112, 113, 114
+INFO_SAMPLE_LOCATE_NS, INFO_SAMPLE_KERNEL_NS = 115, 116
+INFO_SAMPLE_BIN_DOUBLINGS, INFO_SAMPLE_BIN_TOTAL, INFO_SAMPLE_BIN_LONGEST = 117, 118, 119
 
 
 class Context:
@@ -802,6 +821,68 @@ class Context:
         out = np.empty(n.value)
         self._chk(self.L.cfdh_flow_stats_get(self.h, int(which), C.byref(n), _dp(out)))
         return out.reshape(-1, self.dim) if int(which) == FLOW_MEAN_U else out
+
+    # -- point sampler (cfdh_sample_*): closed-form P1 contexts, one GPU ---------------------------------------------------------
+    def sample_set_points(self, x, tol=SAMPLE_TOL):
+        """Explicit points [n, gdim]; located once, on the device.  An empty array removes the set."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1, self.dim))
+        self._chk(self.L.cfdh_sample_set_points(self.h, len(x), _dp(x) if len(x) else None, float(tol)))
+
+    def sample_set_grid(self, origin, spacing, dims, tol=SAMPLE_TOL):
+        """A regular grid: node (i, j, k) at origin + (i, j, k) * spacing, index i + dims[0] (j + dims[1] k); generated on the device."""
+        o, h, d = np.zeros(3), np.ones(3), np.ones(3, dtype=np.int64)
+        o[:len(origin)], h[:len(spacing)], d[:len(dims)] = origin, spacing, dims
+        self._chk(self.L.cfdh_sample_set_grid(self.h, _dp(o), _dp(h), _lp(d), float(tol)))
+
+    def sample_location(self):
+        """(cell [n] in the caller's numbering, -1: none; lambda [n, gdim + 1]; x [n, gdim] as the device used them)."""
+        n = C.c_int64()
+        self._chk(self.L.cfdh_sample_get_location(self.h, C.byref(n), None, None, None))
+        cell, lam, x = np.empty(n.value, dtype=np.int32), np.empty((n.value, self.dim + 1)), np.empty((n.value, self.dim))
+        if n.value:
+            self._chk(self.L.cfdh_sample_get_location(self.h, C.byref(n), _ip(cell), _dp(lam), _dp(x)))
+        return cell, lam, x
+
+    def sample_now(self):
+        """[n, gdim + 1]: the rows (u, p) of the current state at the points of the set; zeros at unlocated points."""
+        n = C.c_int64()
+        self._chk(self.L.cfdh_sample_now(self.h, C.byref(n), None))
+        out = np.empty((n.value, self.dim + 1))
+        self._chk(self.L.cfdh_sample_now(self.h, C.byref(n), _dp(out)))
+        return out
+
+    def sample_series_enable(self, rows):
+        """Room for `rows` row blocks on the device (0 frees it)."""
+        self._chk(self.L.cfdh_sample_series_enable(self.h, int(rows)))
+
+    def sample_record(self, t):
+        """Append the rows of the current state to the series: one launch, no synchronisation, no copy."""
+        self._chk(self.L.cfdh_sample_record(self.h, float(t)))
+
+    def sample_series_get(self):
+        """(t [rows], out [rows, n, gdim + 1]) of what was recorded; empties the buffer."""
+        rows = C.c_int64()
+        self._chk(self.L.cfdh_sample_series_get(self.h, C.byref(rows), None, None))
+        n = self.info(INFO_SAMPLE_POINTS)
+        t, out = np.empty(rows.value), np.empty((rows.value, n, self.dim + 1))
+        self._chk(self.L.cfdh_sample_series_get(self.h, C.byref(rows), _dp(t), _dp(out)))
+        return t, out
+
+    def sample_mean_reset(self):
+        """Zero the per-point accumulators of the means (allocated on first use)."""
+        self._chk(self.L.cfdh_sample_mean_reset(self.h))
+
+    def sample_mean_accumulate(self, weight):
+        """Add the rows of the current state with this weight (the step's dt)."""
+        self._chk(self.L.cfdh_sample_mean_accumulate(self.h, float(weight)))
+
+    def sample_mean_get(self, which):
+        """SAMPLE_MEAN_U [n, gdim], SAMPLE_MEAN_P / SAMPLE_FLUCTUATION [n], SAMPLE_TOTALS (W, count)."""
+        n = C.c_int64()
+        self._chk(self.L.cfdh_sample_mean_get(self.h, int(which), C.byref(n), None))
+        out = np.empty(n.value)
+        self._chk(self.L.cfdh_sample_mean_get(self.h, int(which), C.byref(n), _dp(out)))
+        return out.reshape(-1, self.dim) if int(which) == SAMPLE_MEAN_U else out
 
     def scalar_order(self):
         """The device row of every vertex (cfdh_scalar_get_order)."""

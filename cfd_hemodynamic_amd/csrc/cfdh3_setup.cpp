@@ -49,6 +49,7 @@ int cfdh_build_mesh3(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, con
       if (!(std::fabs(det) > 0)) return cfdh_fail(c, CFDH_E_ARG, "zero-volume cell %d", e);
       if (det < 0) { std::swap(v[2], v[3]); flipped[k] = 1; }
     }
+    c->cell_flipped = flipped;
     c->fac_cell.clear(); c->fac_local.clear(); c->fac_marker.clear(); c->fac_user.clear();
     c->nfac_user = nfac;
     for (int k = 0; k < nfac; k++) {

@@ -187,6 +187,7 @@ void cfdh_destroy(cfdh_ctx *c) {
   cfdh_scalar_free(c);
   cfdh_particles_free(c);
   cfdh_flow_destroy(c);
+  cfdh_sample_destroy(c);
   comm_finalize(c);
   c->hS.clear(); c->hL.clear(); c->hA.clear(); c->hLg.clear();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1632,6 +1633,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
       case 91: return I->scheme;
       case 92: return I->n_assemblies;
       case 106: case 107: case 108: case 109: case 110: return 0;  // flow diagnostics: refused on this kind of context
+      case 111: case 112: case 113: case 114: case 115: case 116: case 117: case 118: case 119: return 0;  // point sampler: the same
       default: return -1;
     }
   }
@@ -1697,6 +1699,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 104: return c->n_particle_steps;            // particle steps taken
     case 105: return c->n_particle_launches;         // launches of the advection kernel since cfdh_create
     case 106: case 107: case 108: case 109: case 110: return cfdh_flow_info(c, what);  // flow diagnostics: buffers exist, cell passes, accumulations since the reset, ns of the last kernels
+    case 111: case 112: case 113: case 114: case 115: case 116: case 117: case 118: case 119: return cfdh_sample_info(c, what);  // point sampler: points, located, sample launches, waiting row blocks, ns of the last locate / sample kernel, the bin grid
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;
@@ -1735,6 +1738,58 @@ int cfdh_flow_stats_accumulate(cfdh_ctx *c, double weight) {
 int cfdh_flow_stats_get(cfdh_ctx *c, int which, int64_t *n, double *out) {
   ENTER(c);
   return cfdh_flow_stats_get_impl(c, which, n, out);
+}
+
+// ---- point sampler (cfdh_sample.hip) -------------------------------------------------------------------------------------------
+
+int cfdh_sample_set_points(cfdh_ctx *c, int64_t n, const double *x, double tol) {
+  ENTER(c);
+  return cfdh_sample_set_points_impl(c, n, x, tol);
+}
+
+int cfdh_sample_set_grid(cfdh_ctx *c, const double *origin, const double *spacing, const int64_t *dims, double tol) {
+  ENTER(c);
+  return cfdh_sample_set_grid_impl(c, origin, spacing, dims, tol);
+}
+
+int cfdh_sample_get_location(cfdh_ctx *c, int64_t *n, int32_t *cell, double *lambda, double *x) {
+  ENTER(c);
+  return cfdh_sample_get_location_impl(c, n, cell, lambda, x);
+}
+
+int cfdh_sample_now(cfdh_ctx *c, int64_t *n, double *out) {
+  ENTER(c);
+  return cfdh_sample_now_impl(c, n, out);
+}
+
+int cfdh_sample_series_enable(cfdh_ctx *c, int64_t rows) {
+  ENTER(c);
+  return cfdh_sample_series_enable_impl(c, rows);
+}
+
+int cfdh_sample_record(cfdh_ctx *c, double t) {
+  ENTER(c);
+  return cfdh_sample_record_impl(c, t);
+}
+
+int cfdh_sample_series_get(cfdh_ctx *c, int64_t *rows, double *t, double *out) {
+  ENTER(c);
+  return cfdh_sample_series_get_impl(c, rows, t, out);
+}
+
+int cfdh_sample_mean_reset(cfdh_ctx *c) {
+  ENTER(c);
+  return cfdh_sample_mean_reset_impl(c);
+}
+
+int cfdh_sample_mean_accumulate(cfdh_ctx *c, double weight) {
+  ENTER(c);
+  return cfdh_sample_mean_accumulate_impl(c, weight);
+}
+
+int cfdh_sample_mean_get(cfdh_ctx *c, int which, int64_t *n, double *out) {
+  ENTER(c);
+  return cfdh_sample_mean_get_impl(c, which, n, out);
 }
 
 // ---- Lagrangian particle tracking (cfdh_particles.hip) ------------------------------------------------------------------------

@@ -182,6 +182,7 @@ struct IpcsData;  // incremental pressure-correction context (cfdh_ipcs.hpp)
 struct ScalarData;  // passive scalar transport of a closed-form P1 context (cfdh_scalar.hip)
 struct ParticleData;  // Lagrangian particles of a closed-form P1 context (cfdh_particles.hip)
 struct FlowData;  // volumetric flow diagnostics of a closed-form P1 context (cfdh_flow.hip)
+struct SampleData;  // point sampler of a closed-form P1 context (cfdh_sample.hip)
 
 struct cfdh_ctx {
   int device = 0;
@@ -222,6 +223,7 @@ struct cfdh_ctx {
   std::vector<int> iperm;  // internal -> user
   std::vector<int> h_cells;       // internal ids, [nc][3]
   std::vector<int> cell_user;     // internal cell -> user cell
+  std::vector<unsigned char> cell_flipped;  // closed-form builders: 1 where the internal cell has its last two vertices swapped (orientation)
   std::vector<double> h_coords;   // internal order [nv][2]
   std::vector<int> fac_cell, fac_local, fac_marker;  // internal cell ids
   std::vector<int> fac_user;  // index of the kept facet in the caller's facet list (cfdh_create order)
@@ -514,6 +516,12 @@ struct cfdh_ctx {
   long long n_flow_cell_passes = 0;  // cfdh_info 107
   hipEvent_t fl_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the last cell pass / the last kernel behind it (cfdh_info 109, 110)
   bool fl_timed[2] = {false, false};
+  // point sampler (cfdh_sample_*, cfdh_sample.hip): everything it owns, allocated by the first sample set
+  SampleData *sm = nullptr;
+  long long n_sample_launches = 0;  // cfdh_info 113
+  hipEvent_t sm_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the last locate / the last sample kernel (cfdh_info 115, 116)
+  bool sm_timed[2] = {false, false};
+  long long sm_bin_doublings = 0, sm_bin_total = 0, sm_bin_maxlen = 0;  // the bin grid built last (cfdh_info 117 .. 119)
 };
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
@@ -654,6 +662,21 @@ int cfdh_flow_stats_get_impl(cfdh_ctx *c, int which, int64_t *n, double *out);
 int64_t cfdh_flow_info(const cfdh_ctx *c, int what);  // cfdh_info 106 .. 110
 void cfdh_flow_free(cfdh_ctx *c);
 void cfdh_flow_destroy(cfdh_ctx *c);  // ... and the timing events
+
+// ---- point sampler on the closed-form P1 contexts (cfdh_sample.hip; the entry points of include/cfdh.h minus ENTER) ----------------
+int cfdh_sample_set_points_impl(cfdh_ctx *c, int64_t n, const double *x, double tol);
+int cfdh_sample_set_grid_impl(cfdh_ctx *c, const double *origin, const double *spacing, const int64_t *dims, double tol);
+int cfdh_sample_get_location_impl(cfdh_ctx *c, int64_t *n, int32_t *cell, double *lambda, double *x);
+int cfdh_sample_now_impl(cfdh_ctx *c, int64_t *n, double *out);
+int cfdh_sample_series_enable_impl(cfdh_ctx *c, int64_t rows);
+int cfdh_sample_record_impl(cfdh_ctx *c, double t);
+int cfdh_sample_series_get_impl(cfdh_ctx *c, int64_t *rows, double *t, double *out);
+int cfdh_sample_mean_reset_impl(cfdh_ctx *c);
+int cfdh_sample_mean_accumulate_impl(cfdh_ctx *c, double weight);
+int cfdh_sample_mean_get_impl(cfdh_ctx *c, int which, int64_t *n, double *out);
+int64_t cfdh_sample_info(const cfdh_ctx *c, int what);  // cfdh_info 111 .. 119
+void cfdh_sample_free(cfdh_ctx *c);
+void cfdh_sample_destroy(cfdh_ctx *c);  // ... and the timing events
 
 // ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------
 int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out [nvert][dim]: entries of the wall vertices only

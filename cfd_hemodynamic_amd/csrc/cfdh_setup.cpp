@@ -146,6 +146,7 @@ int cfdh_build_mesh(cfdh_ctx *c, int64_t nv64, int64_t nvo64, int64_t nc64, cons
       if (!(std::fabs(det) > 0)) return cfdh_fail(c, CFDH_E_ARG, "zero-area cell %d", c->cell_user[e]);
       if (det < 0) { std::swap(v[1], v[2]); flipped[e] = 1; }
     }
+    c->cell_flipped = flipped;
     for (int k = 0; k < c->nfac; k++)
       if (flipped[c->fac_cell[k]] && c->fac_local[k] != 0) c->fac_local[k] = 3 - c->fac_local[k];
   }

@@ -119,7 +119,7 @@ class Scenario(ABC):
 
     def solve(self, output_folder: str = None, afterStepCallback: Callable[[float], None] = None,
               device_resident: bool = True, max_steps: int = None, write_every: int = 1, wall_indices=None, transport=None,
-              transport_diffusivity: float = 0.0, particles=None, flow_diagnostics=None) -> str:
+              transport_diffusivity: float = 0.0, particles=None, flow_diagnostics=None, probes=None, sample_grid=None) -> str:
         """wall_indices: None (default) -- nothing; True -- the cycle-averaged wall shear indices (TAWSS, OSI, RRT, mean and peak
         wall shear stress: wall_indices.py) over the whole run; (t0, t1) -- over the steps that end in (t0, t1].  They are accumulated
         on the device with weight dt right after the step's `assemble_wss()`; afterwards `self.wall_indices` holds the fields, `W` and
@@ -150,8 +150,28 @@ class Scenario(ABC):
         fluctuation energy k' and the mean / peak shear rate and mean dissipation.  Afterwards `self.flow_diagnostics` holds
         `integrals` [steps, 8], `times` and, under "window", those fields with `W`, `steps` and `energy_loss`; with an output folder
         flow_diagnostics.npz and flow_diagnostics.txt (per-step kinetic energy, dissipation and enstrophy, and the window's
-        time-integrated dissipation: the energy loss) are written."""
+        time-integrated dissipation: the energy loss) are written.
+
+        probes: None (default) -- nothing; a dict -- (u, p) at the points "points" [n, gdim] (cfdh_sample_*, sampling.py), recorded
+        on the device after every "every"-th step (default 1) once the step's other features have run and before the state is
+        advanced; the series is downloaded when its device buffer ("rows" records, default 256) is full and at the end.
+        Afterwards `self.probes` holds t [records], x, cell (-1: outside the mesh; such a probe reads zeros), u [records, n, gdim]
+        and p [records, n]; with an output folder probes.npz holds the same.
+
+        sample_grid: None (default) -- nothing; a dict -- the velocity and the pressure on a regular grid over the mesh's bounding
+        box ("spacing": h, a number or one per axis, or "dims": nodes per axis; "pad": widening of the box, default 0), located
+        once on the device.  With an output folder grid/grid_NNNNNN.vti (ImageData: velocity, pressure and the mask `located`) is
+        written after every "every"-th step (default: `write_every`; 0: never); "window": True or (t0, t1) accumulates the means
+        with weight dt under the window rule of the wall indices and writes grid_mean.vti (mean_velocity, mean_pressure,
+        fluctuation).  Afterwards `self.sample_grid` holds origin, spacing, dims, cell, located and, under "window", the means with
+        `W` and `steps`.  The sampler holds one set: probes and sample_grid exclude each other (ValueError).  Closed-form P1
+        solvers on one GPU; NotImplementedError elsewhere.  The sample set, with its location and its means, stays on the solver
+        after solve() so that `solver.sample_now()`, `sample_location()` and `sample_mean()` can still be asked about the last
+        state (68 bytes per point in 3-D, 108 with the means: 1.1 to 1.8 GB for 1.6e7 nodes); only the probes' series buffer is
+        freed.  `solver.sample_set_points(np.zeros((0, gdim)))` frees the rest, and so does the next set or closing the context."""
         mesh, T, solver = self.mesh, self.T, self.solver
+        self.probes = self.sample_grid = None
+        pr, sg = self._sample_setup(probes, sample_grid, output_folder, write_every)
         self.flow_diagnostics = None
         fd = self._flow_setup(flow_diagnostics)
         self.transport = None
@@ -229,6 +249,10 @@ class Scenario(ABC):
             if wall_indices is not None and step_in_window(t, self.dt, wall_indices):
                 solver.wall_stats_accumulate(self.dt)
                 wi_steps += 1
+            if pr is not None and i % pr["every"] == 0:
+                self._probes_record(pr, t)
+            if sg is not None:
+                self._grid_step(sg, t, i)
             if writers and i % write_every == 0:
                 for w in writers:
                     w.write(t)
@@ -301,6 +325,26 @@ class Scenario(ABC):
                 print("flow_diagnostics: no step ended inside the window %s (the run stopped at t=%.6g)" % (fd["window"], t))
             if output_folder and mesh.comm.rank == 0:
                 self._flow_write(output_folder, self.flow_diagnostics)
+        if pr is not None:
+            self._probes_drain(pr)
+            solver._sample_ctx().sample_series_enable(0)  # the series buffer is of no use after the run; the set stays (docstring)
+            self.probes = {"t": np.concatenate(pr["t"]) if pr["t"] else np.zeros(0), "x": pr["x"], "cell": pr["cell"],
+                           "u": np.concatenate(pr["u"]) if pr["u"] else np.zeros((0,) + pr["x"].shape),
+                           "p": np.concatenate(pr["p"]) if pr["p"] else np.zeros((0, len(pr["x"])))}
+            if output_folder and mesh.comm.rank == 0:
+                from .sampling import write_npz
+                write_npz(os.path.join(output_folder, "probes.npz"), **self.probes)
+        if sg is not None:
+            self.sample_grid = {k: sg[k] for k in ("origin", "spacing", "dims", "cell", "located")}
+            if sg["window_steps"] > 0:
+                self.sample_grid["window"] = solver.sample_mean()
+                if output_folder and mesh.comm.rank == 0:
+                    from .sampling import write_vti
+                    win = self.sample_grid["window"]
+                    write_vti(os.path.join(output_folder, "grid_mean.vti"), sg["origin"], sg["spacing"], sg["dims"],
+                              {k: win[k] for k in ("mean_velocity", "mean_pressure", "fluctuation")}, located=sg["cell"] >= 0)
+            elif sg["window"] is not None and mesh.comm.rank == 0:
+                print("sample_grid: no step ended inside the window %s (the run stopped at t=%.6g)" % (sg["window"], t))
         if pt is not None:
             from . import particles as P
             fields = solver.particles_get()
@@ -315,6 +359,74 @@ class Scenario(ABC):
         if error_log:
             error_log.close()
         return output_folder
+
+    def _sample_setup(self, probes, sample_grid, output_folder, write_every):
+        """Parses `probes` and `sample_grid` of solve() and puts the sample set on the solver; (None, None) when off."""
+        if probes is None and sample_grid is None:
+            return None, None
+        if probes is not None and sample_grid is not None:
+            raise ValueError("the sampler holds one sample set: give either probes or sample_grid")
+        solver = self.solver
+        gdim = self.mesh.geometry.dim
+        if probes is not None:
+            if not isinstance(probes, dict) or set(probes) - {"points", "every", "rows"} or "points" not in probes:
+                raise ValueError('probes must be None or a dict with "points" and optionally "every" and "rows"')
+            pts = np.asarray(probes["points"], dtype=float).reshape(-1, gdim)
+            every, rows = int(probes.get("every", 1)), int(probes.get("rows", 256))
+            if len(pts) == 0 or every < 1 or rows < 1:
+                raise ValueError("probes: at least one point, every >= 1 and rows >= 1")
+            solver._sample_ctx()  # the solver kinds without the sampler raise here, before the time loop
+            solver.sample_set_points(pts)
+            cell, _, x = solver.sample_location()
+            solver._sample_ctx().sample_series_enable(rows)
+            return {"every": every, "rows": rows, "waiting": 0, "x": x, "cell": cell, "t": [], "u": [], "p": []}, None
+        if not isinstance(sample_grid, dict) or set(sample_grid) - {"spacing", "dims", "pad", "every", "window"}:
+            raise ValueError('sample_grid must be None or a dict with "spacing" or "dims" and optionally "pad", "every" and "window"')
+        from .sampling import grid_over
+        origin, spacing, dims = grid_over(self.mesh, spacing=sample_grid.get("spacing"), pad=float(sample_grid.get("pad", 0.0)),
+                                          dims=sample_grid.get("dims"))
+        window = sample_grid.get("window")
+        if window is not None and window is not True:
+            window = (float(window[0]), float(window[1]))
+        every = int(sample_grid.get("every", write_every or 0))
+        if every < 0:
+            raise ValueError("sample_grid: every >= 0")
+        solver._sample_ctx()
+        solver.sample_set_grid(origin, spacing, dims)
+        cell = solver.sample_location()[0]
+        if window is not None:
+            solver.sample_mean_reset()
+        folder = None
+        if output_folder and every and self.mesh.comm.rank == 0:
+            folder = os.path.join(output_folder, "grid")
+            os.makedirs(folder, exist_ok=True)
+        return None, {"origin": origin, "spacing": spacing, "dims": dims, "cell": cell, "located": int((cell >= 0).sum()), "every": every,
+                      "window": window, "window_steps": 0, "folder": folder, "frames": 0}
+
+    def _probes_record(self, pr, t):
+        if pr["waiting"] == pr["rows"]:
+            self._probes_drain(pr)
+        self.solver.sample_record(t)
+        pr["waiting"] += 1
+
+    def _probes_drain(self, pr):
+        if pr["waiting"]:
+            t, u, p = self.solver.sample_series()
+            pr["t"].append(t); pr["u"].append(u); pr["p"].append(p)
+            pr["waiting"] = 0
+
+    def _grid_step(self, sg, t, i):
+        from .wall_indices import step_in_window
+        solver = self.solver
+        if sg["window"] is not None and step_in_window(t, self.dt, sg["window"]):
+            solver.sample_mean_accumulate(self.dt)
+            sg["window_steps"] += 1
+        if sg["folder"] and i % sg["every"] == 0:
+            from .sampling import write_vti
+            u, p = solver.sample_now()
+            write_vti(os.path.join(sg["folder"], "grid_%06d.vti" % sg["frames"]), sg["origin"], sg["spacing"], sg["dims"],
+                      {"velocity": u, "pressure": p}, located=sg["cell"] >= 0)
+            sg["frames"] += 1
 
     FLOW_FIELD_NAMES = ("vorticity", "q_criterion", "shear_rate", "dissipation", "helicity", "lnh")
 

@@ -233,6 +233,59 @@ class SolverBase(ABC):
         out["W"], out["steps"] = float(W), int(count)
         return out
 
+    # -- point sampler on the device (cfdh_sample_*: probe points, lines, voxel grids) ------------------------------------------
+    def _sample_ctx(self):
+        return self._transport_ctx("sampling", "point sampler")
+
+    def sample_set_points(self, x, tol=1e-9):
+        """The sample set: explicit points [n, gdim], located once on the device (an empty array removes the set)."""
+        self._sample_ctx().sample_set_points(x, tol)
+
+    def sample_set_grid(self, origin, spacing, dims, tol=1e-9):
+        """The sample set: the nodes origin + (i, j, k) * spacing of a regular grid, in the point order of VTK ImageData."""
+        self._sample_ctx().sample_set_grid(origin, spacing, dims, tol)
+
+    def sample_location(self):
+        """(cell, lambda, x) of the set: the lowest-indexed cell that holds each point (-1: none), its barycentric coordinates and
+        the coordinates the device used."""
+        return self._sample_ctx().sample_location()
+
+    def sample_now(self):
+        """(u [n, gdim], p [n]) of the current u_sol at the points of the set; zeros at unlocated points."""
+        rows = self._sample_ctx().sample_now()
+        return rows[:, :-1], rows[:, -1]
+
+    def sample_record(self, t, rows=None):
+        """Append the current state to the series on the device (no copy, no synchronisation); `rows` (first call, or to resize)
+        is the capacity in records."""
+        ctx = self._sample_ctx()
+        if rows is not None:
+            ctx.sample_series_enable(rows)
+        ctx.sample_record(t)
+
+    def sample_series(self):
+        """(t [rows], u [rows, n, gdim], p [rows, n]) recorded since the last call; empties the device buffer."""
+        t, rows = self._sample_ctx().sample_series_get()
+        return t, rows[:, :, :-1], rows[:, :, -1]
+
+    def sample_mean_reset(self):
+        """Zero the per-point means (allocated on first use)."""
+        self._sample_ctx().sample_mean_reset()
+
+    def sample_mean_accumulate(self, w):
+        """Add the current state at the points of the set to the means with weight w (the step's dt)."""
+        self._sample_ctx().sample_mean_accumulate(w)
+
+    def sample_mean(self):
+        """The means: mean_velocity [n, gdim], mean_pressure, fluctuation (k') [n], with W (the sum of the weights) and steps."""
+        from . import _lib
+        ctx = self._sample_ctx()
+        W, count = ctx.sample_mean_get(_lib.SAMPLE_TOTALS)
+        names = ("mean_velocity", "mean_pressure", "fluctuation")  # _lib.SAMPLE_MEAN_U ..
+        out = {k: ctx.sample_mean_get(w) for w, k in enumerate(names)}
+        out["W"], out["steps"] = float(W), int(count)
+        return out
+
     @staticmethod
     def _simplex_gradients(mesh):
         """grad(lambda_a) of every cell of a P1 simplex mesh, [nc, d + 1, d]."""

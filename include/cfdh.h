@@ -836,6 +836,65 @@ int cfdh_flow_stats_reset(cfdh_ctx *ctx);
 int cfdh_flow_stats_accumulate(cfdh_ctx *ctx, double weight);
 int cfdh_flow_stats_get(cfdh_ctx *ctx, int which, int64_t *n, double *out);
 
+/* ---- point sampler: the solution at probe points, along lines and on voxel grids (not in the reference) ----
+ *
+ * The value of (u, p) of u_sol at places the caller chooses, taken while the state sits on the device (between cfdh_solve_step
+ * and cfdh_advance, or after cfdh_set_state), without a copy of the whole field.
+ *
+ * The sample set.  cfdh_sample_set_points(ctx, n, x[n][d], tol) takes explicit points.  cfdh_sample_set_grid(ctx, origin[3],
+ * spacing[3], dims[3], tol) takes a regular grid: node (i, j, k) is at origin + (i, j, k) * spacing (one rounding per coordinate:
+ * fma(index, spacing, origin)), its index is i + dims[0] * (j + dims[1] * k), the point order of VTK ImageData; in 2-D dims[2]
+ * must be 1 and origin[2], spacing[2] are not read.  The coordinates of a grid are generated on the device and never uploaded.
+ * A new call replaces the set and drops the series and the means below; n = 0 removes the set and frees its buffers.
+ * CFDH_E_ARG: a non-finite coordinate, origin or spacing; a spacing that is not positive; a dims entry below 1 or a product above
+ * 2^31 - 1; tol not finite or outside [0, 1e-3].
+ *
+ * Location, once per set.  Point x belongs to the cell with the lowest index, in the caller's cell numbering, among the cells in
+ * which every barycentric coordinate of x is >= -tol; its cell is -1 if there is none.  The answer does not depend on the order in
+ * which the context stores its cells nor on how the search is organised, and a point on a vertex, an edge or a face has one answer.
+ * The search goes through a uniform bin grid over the bounding box of the mesh, built on the host: per bin the cells whose bounding
+ * box, inflated by d tol times its diagonal (a point with lambda >= -tol can lie that far outside it), overlaps the bin, in
+ * ascending caller's index; the bin edge starts at the median cell-box edge and is doubled until the lists hold at most 16 nc
+ * entries (a mesh of more than 2^31 / 16 cells is refused: CFDH_E_ARG).  One lane per point scans the list of its bin in order and stops at the first cell that holds the point; a point outside
+ * the bounding box takes no trip.  Gather only: two calls return the same bytes.
+ * cfdh_sample_get_location(ctx, &n, cell[n], lambda[n][d + 1], x[n][d]): the cells in the caller's numbering, the barycentric
+ * coordinates in the order of the caller's vertices of that cell (0 for an unlocated point) and the coordinates the device used;
+ * any of the three may be NULL.  Without a set *n = 0.  A point that equals a vertex of a cell bit for bit lies in that cell with the
+ * unit row (1 at that vertex), whatever tol is: a probe on a mesh vertex returns the nodal values exactly.
+ *
+ * Sampling.  One lane per point gathers u and p at the d + 1 vertices of its cell and writes the row (u [d], p) = lambda . values;
+ * an unlocated point gets zeros.  All calls below need a set and a state (CFDH_E_STATE otherwise).
+ * cfdh_sample_now(ctx, &n, out[n][d + 1]): one launch and one download; *n receives the number of points, out == NULL only
+ * queries it.
+ * cfdh_sample_series_enable(ctx, rows) allocates a device buffer of `rows` row blocks [n][d + 1] (0 frees it; a negative rows or a
+ * buffer above 2^40 bytes: CFDH_E_ARG);
+ * cfdh_sample_record(ctx, t) appends the block of the current state and keeps t on the host: no synchronisation, no copy.  When the
+ * buffer is full: CFDH_E_STATE, the message names cfdh_sample_series_get(ctx, &rows, t[rows], out[rows][n][d + 1]), which
+ * downloads what was recorded and empties the buffer (out == NULL only queries *rows).
+ * Means, shaped like cfdh_flow_stats_*: cfdh_sample_mean_reset allocates on first use and zeroes;
+ * cfdh_sample_mean_accumulate(weight) adds, per point, w u [d], w p and w |u|^2, per context W = sum w and the count.  weight must
+ * be finite and > 0 (CFDH_E_ARG); before a reset: CFDH_E_STATE.  cfdh_sample_mean_get(ctx, which, &n, out):
+ *   0 mean velocity sum w u / W                                                      [n][d]
+ *   1 mean pressure sum w p / W                                                      [n]
+ *   2 fluctuation energy k' = max(0, (sum w |u|^2 / W - |sum w u / W|^2) / 2)         [n]
+ *   3 {W, count}                                                                     [2]
+ * which 0 .. 2 with W == 0, or any which before a reset: CFDH_E_STATE; an unknown which: CFDH_E_ARG.
+ *
+ * Contexts: closed-form P1 contexts of cfdh_create (gdim 2 and 3), the whole mesh on one GPU.  Every entry point returns
+ * CFDH_E_ARG with a reason, before any device work and with the context unchanged, on generic-element contexts, on contexts of
+ * cfdh_create_ipcs and on a part of a partitioned run.  A context that never calls them allocates and launches nothing
+ * (cfdh_info 111 .. 119). */
+int cfdh_sample_set_points(cfdh_ctx *ctx, int64_t n, const double *x, double tol);
+int cfdh_sample_set_grid(cfdh_ctx *ctx, const double *origin, const double *spacing, const int64_t *dims, double tol);
+int cfdh_sample_get_location(cfdh_ctx *ctx, int64_t *n, int32_t *cell, double *lambda, double *x);
+int cfdh_sample_now(cfdh_ctx *ctx, int64_t *n, double *out);
+int cfdh_sample_series_enable(cfdh_ctx *ctx, int64_t rows);
+int cfdh_sample_record(cfdh_ctx *ctx, double t);
+int cfdh_sample_series_get(cfdh_ctx *ctx, int64_t *rows, double *t, double *out);
+int cfdh_sample_mean_reset(cfdh_ctx *ctx);
+int cfdh_sample_mean_accumulate(cfdh_ctx *ctx, double weight);
+int cfdh_sample_mean_get(cfdh_ctx *ctx, int which, int64_t *n, double *out);
+
 /* ---- multi-GPU ---------------------------------------------- */
 
 /* Halo plan in local vertex numbers: for neighbour k, send_idx[send_ptr[k]..send_ptr[k+1])
@@ -906,7 +965,11 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * since cfdh_create;
  * 106: 1 once a flow-diagnostics buffer exists (cfdh_flow_*), 107: launches of its cell-gradient pass since cfdh_create, 108:
  * cfdh_flow_stats_accumulate calls since the last cfdh_flow_stats_reset, 109 / 110: nanoseconds, by device events, of the last
- * cell-gradient pass / of the last vertex, accumulation or integral kernel (0 before the first; the call waits for that kernel) */
+ * cell-gradient pass / of the last vertex, accumulation or integral kernel (0 before the first; the call waits for that kernel);
+ * 111: points in the sample set (cfdh_sample_*), 112: points located, 113: launches of the sample kernel since cfdh_create, 114:
+ * row blocks waiting in the series, 115 / 116: nanoseconds, by device events, of the last locate / of the last sample kernel (as
+ * 109 / 110), 117 .. 119: the bin grid built last: the number of times its edge was doubled, the total length of its
+ * lists, the longest list */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
