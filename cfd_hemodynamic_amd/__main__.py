@@ -14,7 +14,10 @@ step: the fields join the VTU series, the per-step energy integrals and the wind
 the device after every `--sample_every`-th step (default 1) and write probes.npz; `--sample_grid_spacing H` samples them on a regular
 grid over the mesh's bounding box instead (grid/grid_NNNNNN.vti at `--sample_every`), and `--sample_window_from T0 --sample_window_to
 T1` (defaults 0 and T) adds the window means on that grid (grid_mean.vti).  Probes and a grid exclude each other (one sample set
-per run), and the window and `--sample_every` flags without the set they belong to are refused before the scenario is built."""
+per run), and the window and `--sample_every` flags without the set they belong to are refused before the scenario is built.
+`--sections "ox,oy[,oz];nx,ny[,nz][;r] | ..."` integrates flow rate, pressure and energy flux exactly over those cut planes on the
+device after every `--sections_every`-th step (default 1) and writes sections.npz and sections.txt; `--sections_window_from T0
+--sections_window_to T1` (defaults 0 and T) adds the window means of the rows.  Sections go with every other feature."""
 from __future__ import annotations
 
 import argparse
@@ -55,6 +58,22 @@ def _check_sampler_flags(ap, args):
         ap.error("--sample_every needs --probes, --probe_line or --sample_grid_spacing")
 
 
+def parse_sections(text):
+    """The planes of `--sections`: "origin;normal[;radius]" separated by "|"."""
+    from .sections import plane
+    out = []
+    for part in text.split("|"):
+        if not part.strip():
+            continue
+        f = [q.strip() for q in part.split(";")]
+        if len(f) not in (2, 3):
+            raise ValueError("--sections: every plane is 'ox,oy[,oz];nx,ny[,nz][;r]', got %r" % part)
+        out.append(plane([float(v) for v in f[0].split(",")], [float(v) for v in f[1].split(",")], float(f[2]) if len(f) == 3 else None))
+    if not out:
+        raise ValueError("--sections: no plane given")
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="cfd_hemodynamic_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -88,8 +107,20 @@ def main(argv=None):
     s.add_argument("--sample_every", type=int, default=None)
     s.add_argument("--sample_window_from", type=float, default=None)
     s.add_argument("--sample_window_to", type=float, default=None)
+    # cut-plane sections on the device: planes, the recording interval and the window of the means
+    s.add_argument("--sections", type=str, default=None)
+    s.add_argument("--sections_every", type=int, default=None)
+    s.add_argument("--sections_window_from", type=float, default=None)
+    s.add_argument("--sections_window_to", type=float, default=None)
     args, extra = ap.parse_known_args(argv)
     _check_sampler_flags(ap, args)
+    if args.sections is None and (args.sections_every is not None or args.sections_window_from is not None or args.sections_window_to is not None):
+        ap.error("--sections_every / --sections_window_from / --sections_window_to need --sections")
+    if args.sections is not None:
+        try:
+            section_planes = parse_sections(args.sections)
+        except ValueError as e:
+            ap.error(str(e))
     kw = _parse_extra(extra)
     try:
         mod = import_module(f"{__package__}.scenarios.{args.simulation}")
@@ -140,6 +171,13 @@ def main(argv=None):
         if args.sample_window_from is not None or args.sample_window_to is not None:
             solve_kw["sample_grid"]["window"] = (0.0 if args.sample_window_from is None else args.sample_window_from,
                                                  args.T if args.sample_window_to is None else args.sample_window_to)
+    if args.sections is not None:
+        solve_kw["sections"] = {"planes": section_planes}
+        if args.sections_every is not None:
+            solve_kw["sections"]["every"] = args.sections_every
+        if args.sections_window_from is not None or args.sections_window_to is not None:
+            solve_kw["sections"]["window"] = (0.0 if args.sections_window_from is None else args.sections_window_from,
+                                              args.T if args.sections_window_to is None else args.sections_window_to)
     sim.solve(out, **solve_kw)
     print("results in", out)
     return 0

@@ -84,6 +84,8 @@ SYMBOLS = [
     "cfdh_flow_field", "cfdh_flow_integrals", "cfdh_flow_stats_reset", "cfdh_flow_stats_accumulate", "cfdh_flow_stats_get",
     "cfdh_sample_set_points", "cfdh_sample_set_grid", "cfdh_sample_get_location", "cfdh_sample_now", "cfdh_sample_series_enable",
     "cfdh_sample_record", "cfdh_sample_series_get", "cfdh_sample_mean_reset", "cfdh_sample_mean_accumulate", "cfdh_sample_mean_get",
+    "cfdh_section_set", "cfdh_section_get_cut", "cfdh_section_now", "cfdh_section_series_enable", "cfdh_section_record",
+    "cfdh_section_series_get", "cfdh_section_mean_reset", "cfdh_section_mean_accumulate", "cfdh_section_mean_get",
 ]
 
 
@@ -212,6 +214,16 @@ def lib():
     L.cfdh_sample_mean_reset.argtypes = [vp]
     L.cfdh_sample_mean_accumulate.argtypes = [vp, C.c_double]
     L.cfdh_sample_mean_get.argtypes = [vp, C.c_int, lp, dp]
+    i32p = C.POINTER(C.c_int32)
+    L.cfdh_section_set.argtypes = [vp, C.c_int32, dp, dp, dp]
+    L.cfdh_section_get_cut.argtypes = [vp, i32p, lp, ip, dp, ip]
+    L.cfdh_section_now.argtypes = [vp, i32p, dp]
+    L.cfdh_section_series_enable.argtypes = [vp, C.c_int64]
+    L.cfdh_section_record.argtypes = [vp, C.c_double]
+    L.cfdh_section_series_get.argtypes = [vp, lp, dp, dp]
+    L.cfdh_section_mean_reset.argtypes = [vp]
+    L.cfdh_section_mean_accumulate.argtypes = [vp, C.c_double]
+    L.cfdh_section_mean_get.argtypes = [vp, i32p, dp, dp]
     _LIB = L
     return L
 
@@ -289,6 +301,14 @@ SAMPLE_TOL = 1e-9  # the default containment tolerance on the barycentric coordi
 INFO_SAMPLE_POINTS, INFO_SAMPLE_LOCATED, INFO_SAMPLE_LAUNCHES, INFO_SAMPLE_SERIES_ROWS = 111, 112, 113, 114
 INFO_SAMPLE_LOCATE_NS, INFO_SAMPLE_KERNEL_NS = 115, 116
 INFO_SAMPLE_BIN_DOUBLINGS, INFO_SAMPLE_BIN_TOTAL, INFO_SAMPLE_BIN_LONGEST = 117, 118, 119
+# cut-plane sections (cfdh_section_*): the slots of a row; cfdh_info: sections, entries of the cut lists in all, the longest list,
+# evaluations launched, row blocks waiting in the series, device time of the last evaluation
+SECTION_NQ = 10
+(SECTION_AREA, SECTION_FLOW, SECTION_P, SECTION_UN2, SECTION_U2, SECTION_P_UN, SECTION_KINETIC_FLUX, SECTION_UX, SECTION_UY,
+ SECTION_UZ) = range(10)
+SECTION_MAX = 256
+INFO_SECTION_COUNT, INFO_SECTION_ENTRIES, INFO_SECTION_LONGEST, INFO_SECTION_LAUNCHES, INFO_SECTION_SERIES_ROWS = 120, 121, 122, 123, 124
+INFO_SECTION_KERNEL_NS = 125
 
 
 class Context:
@@ -883,6 +903,77 @@ class Context:
         out = np.empty(n.value)
         self._chk(self.L.cfdh_sample_mean_get(self.h, int(which), C.byref(n), _dp(out)))
         return out.reshape(-1, self.dim) if int(which) == SAMPLE_MEAN_U else out
+
+    # -- cut-plane sections (cfdh_section_*): closed-form P1 contexts, one GPU ----------------------------------------------------
+    def section_set(self, origin, normal, radius=None):
+        """K sections: origin [K, gdim], normal [K, gdim] (any non-zero length), radius [K] or None (<= 0: unbounded).  The cut is
+        built once, on the host.  Empty arrays remove the set."""
+        o = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(-1, self.dim))
+        n = np.ascontiguousarray(np.asarray(normal, dtype=np.float64).reshape(-1, self.dim))
+        if len(o) != len(n):
+            raise ValueError("section_set: %d origins and %d normals" % (len(o), len(n)))
+        r = None
+        if radius is not None:
+            r = np.ascontiguousarray(np.asarray(radius, dtype=np.float64).reshape(-1))
+            if len(r) != len(o):
+                raise ValueError("section_set: %d origins and %d radii" % (len(o), len(r)))
+        K = len(o)
+        self._chk(self.L.cfdh_section_set(self.h, K, _dp(o) if K else None, _dp(n) if K else None, _dp(r) if r is not None and K else None))
+
+    def section_get_cut(self):
+        """(ptr [K + 1], cell [entries] in the caller's numbering, measure [entries], straddling [K]) of the cut lists."""
+        K = C.c_int32()
+        self._chk(self.L.cfdh_section_get_cut(self.h, C.byref(K), None, None, None, None))
+        ptr, strad = np.zeros(K.value + 1, dtype=np.int64), np.zeros(K.value, dtype=np.int32)
+        if K.value:
+            self._chk(self.L.cfdh_section_get_cut(self.h, C.byref(K), _lp(ptr), None, None, _ip(strad)))
+        cell, meas = np.empty(int(ptr[-1]), dtype=np.int32), np.empty(int(ptr[-1]))
+        if ptr[-1]:
+            self._chk(self.L.cfdh_section_get_cut(self.h, C.byref(K), None, _ip(cell), _dp(meas), None))
+        return ptr, cell, meas, strad
+
+    def section_now(self):
+        """[K, 10]: the rows of the current state (SECTION_AREA .. SECTION_UZ)."""
+        K = C.c_int32()
+        self._chk(self.L.cfdh_section_now(self.h, C.byref(K), None))
+        out = np.empty((K.value, SECTION_NQ))
+        self._chk(self.L.cfdh_section_now(self.h, C.byref(K), _dp(out)))
+        return out
+
+    def section_series_enable(self, rows):
+        """Room for `rows` row blocks on the device (0 frees it)."""
+        self._chk(self.L.cfdh_section_series_enable(self.h, int(rows)))
+
+    def section_record(self, t):
+        """Append the rows of the current state to the series: no synchronisation, no copy."""
+        self._chk(self.L.cfdh_section_record(self.h, float(t)))
+
+    def section_series_get(self):
+        """(t [rows], out [rows, K, 10]) of what was recorded; empties the buffer."""
+        rows = C.c_int64()
+        self._chk(self.L.cfdh_section_series_get(self.h, C.byref(rows), None, None))
+        K = self.info(INFO_SECTION_COUNT)
+        t, out = np.empty(rows.value), np.empty((rows.value, K, SECTION_NQ))
+        self._chk(self.L.cfdh_section_series_get(self.h, C.byref(rows), _dp(t), _dp(out)))
+        return t, out
+
+    def section_mean_reset(self):
+        """Zero the K x 10 accumulators of the window means (allocated on first use)."""
+        self._chk(self.L.cfdh_section_mean_reset(self.h))
+
+    def section_mean_accumulate(self, weight):
+        """Add the rows of the current state with this weight (the step's dt)."""
+        self._chk(self.L.cfdh_section_mean_accumulate(self.h, float(weight)))
+
+    def section_mean_get(self):
+        """(rows [K, 10] = sum w row / W, or None while nothing is accumulated; W; count)."""
+        K, wc = C.c_int32(), np.zeros(2)
+        self._chk(self.L.cfdh_section_mean_get(self.h, C.byref(K), None, _dp(wc)))
+        if not wc[0] > 0.0:
+            return None, float(wc[0]), int(wc[1])
+        out = np.empty((K.value, SECTION_NQ))
+        self._chk(self.L.cfdh_section_mean_get(self.h, C.byref(K), _dp(out), _dp(wc)))
+        return out, float(wc[0]), int(wc[1])
 
     def scalar_order(self):
         """The device row of every vertex (cfdh_scalar_get_order)."""

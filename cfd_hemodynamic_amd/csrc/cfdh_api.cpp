@@ -188,6 +188,7 @@ void cfdh_destroy(cfdh_ctx *c) {
   cfdh_particles_free(c);
   cfdh_flow_destroy(c);
   cfdh_sample_destroy(c);
+  cfdh_section_destroy(c);
   comm_finalize(c);
   c->hS.clear(); c->hL.clear(); c->hA.clear(); c->hLg.clear();
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1634,6 +1635,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
       case 92: return I->n_assemblies;
       case 106: case 107: case 108: case 109: case 110: return 0;  // flow diagnostics: refused on this kind of context
       case 111: case 112: case 113: case 114: case 115: case 116: case 117: case 118: case 119: return 0;  // point sampler: the same
+      case 120: case 121: case 122: case 123: case 124: case 125: return 0;  // cut-plane sections: the same
       default: return -1;
     }
   }
@@ -1700,6 +1702,7 @@ int64_t cfdh_info(const cfdh_ctx *c, int what) {
     case 105: return c->n_particle_launches;         // launches of the advection kernel since cfdh_create
     case 106: case 107: case 108: case 109: case 110: return cfdh_flow_info(c, what);  // flow diagnostics: buffers exist, cell passes, accumulations since the reset, ns of the last kernels
     case 111: case 112: case 113: case 114: case 115: case 116: case 117: case 118: case 119: return cfdh_sample_info(c, what);  // point sampler: points, located, sample launches, waiting row blocks, ns of the last locate / sample kernel, the bin grid
+    case 120: case 121: case 122: case 123: case 124: case 125: return cfdh_section_info(c, what);  // cut-plane sections: sections, entries, longest list, evaluations, waiting row blocks, ns of the last evaluation
     case 72: return c->n_attainable_stops;  // solves stopped at the attainable accuracy (reason CFDH_KSP_CONVERGED_ATTAINABLE), above their tolerance
     case 27: return (int64_t)(1000.0 * c->ms_pc_build_dev);  // microseconds of the last device-side preconditioner build (0: host build)
     case 19: return c->opt.pc_type >= 1 ? c->hL.nnz_S0 : c->hS.nnz_S0;
@@ -1790,6 +1793,53 @@ int cfdh_sample_mean_accumulate(cfdh_ctx *c, double weight) {
 int cfdh_sample_mean_get(cfdh_ctx *c, int which, int64_t *n, double *out) {
   ENTER(c);
   return cfdh_sample_mean_get_impl(c, which, n, out);
+}
+
+// ---- cut-plane sections (cfdh_section.hip) ----------------------------------------------------------------------------------------
+
+int cfdh_section_set(cfdh_ctx *c, int32_t K, const double *origin, const double *normal, const double *radius) {
+  ENTER(c);
+  return cfdh_section_set_impl(c, K, origin, normal, radius);
+}
+
+int cfdh_section_get_cut(cfdh_ctx *c, int32_t *K, int64_t *ptr, int32_t *cell, double *measure, int32_t *straddling) {
+  ENTER(c);
+  return cfdh_section_get_cut_impl(c, K, ptr, cell, measure, straddling);
+}
+
+int cfdh_section_now(cfdh_ctx *c, int32_t *K, double *out) {
+  ENTER(c);
+  return cfdh_section_now_impl(c, K, out);
+}
+
+int cfdh_section_series_enable(cfdh_ctx *c, int64_t rows) {
+  ENTER(c);
+  return cfdh_section_series_enable_impl(c, rows);
+}
+
+int cfdh_section_record(cfdh_ctx *c, double t) {
+  ENTER(c);
+  return cfdh_section_record_impl(c, t);
+}
+
+int cfdh_section_series_get(cfdh_ctx *c, int64_t *rows, double *t, double *out) {
+  ENTER(c);
+  return cfdh_section_series_get_impl(c, rows, t, out);
+}
+
+int cfdh_section_mean_reset(cfdh_ctx *c) {
+  ENTER(c);
+  return cfdh_section_mean_reset_impl(c);
+}
+
+int cfdh_section_mean_accumulate(cfdh_ctx *c, double weight) {
+  ENTER(c);
+  return cfdh_section_mean_accumulate_impl(c, weight);
+}
+
+int cfdh_section_mean_get(cfdh_ctx *c, int32_t *K, double *out, double *w_count) {
+  ENTER(c);
+  return cfdh_section_mean_get_impl(c, K, out, w_count);
 }
 
 // ---- Lagrangian particle tracking (cfdh_particles.hip) ------------------------------------------------------------------------

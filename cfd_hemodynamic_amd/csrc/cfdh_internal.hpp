@@ -183,6 +183,7 @@ struct ScalarData;  // passive scalar transport of a closed-form P1 context (cfd
 struct ParticleData;  // Lagrangian particles of a closed-form P1 context (cfdh_particles.hip)
 struct FlowData;  // volumetric flow diagnostics of a closed-form P1 context (cfdh_flow.hip)
 struct SampleData;  // point sampler of a closed-form P1 context (cfdh_sample.hip)
+struct SectionData;  // cut-plane sections of a closed-form P1 context (cfdh_section.hip)
 
 struct cfdh_ctx {
   int device = 0;
@@ -522,6 +523,11 @@ struct cfdh_ctx {
   hipEvent_t sm_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the last locate / the last sample kernel (cfdh_info 115, 116)
   bool sm_timed[2] = {false, false};
   long long sm_bin_doublings = 0, sm_bin_total = 0, sm_bin_maxlen = 0;  // the bin grid built last (cfdh_info 117 .. 119)
+  // cut-plane sections (cfdh_section_*, cfdh_section.hip): everything they own, allocated by the first non-empty cfdh_section_set
+  SectionData *sec = nullptr;
+  long long n_section_launches = 0;  // cfdh_info 123
+  hipEvent_t sc_ev[2] = {nullptr, nullptr};  // around the last evaluation (cfdh_info 125)
+  bool sc_timed = false;
 };
 
 #define CFDH_MAX_PBND 8  // pressure boundaries per context (cfdh_set_pressure_boundaries)
@@ -677,6 +683,19 @@ int cfdh_sample_mean_get_impl(cfdh_ctx *c, int which, int64_t *n, double *out);
 int64_t cfdh_sample_info(const cfdh_ctx *c, int what);  // cfdh_info 111 .. 119
 void cfdh_sample_free(cfdh_ctx *c);
 void cfdh_sample_destroy(cfdh_ctx *c);  // ... and the timing events
+
+// ---- cut-plane sections on the closed-form P1 contexts (cfdh_section.hip; the entry points of include/cfdh.h minus ENTER) -----------
+int cfdh_section_set_impl(cfdh_ctx *c, int32_t K, const double *origin, const double *normal, const double *radius);
+int cfdh_section_get_cut_impl(cfdh_ctx *c, int32_t *K, int64_t *ptr, int32_t *cell, double *measure, int32_t *straddling);
+int cfdh_section_now_impl(cfdh_ctx *c, int32_t *K, double *out);
+int cfdh_section_series_enable_impl(cfdh_ctx *c, int64_t rows);
+int cfdh_section_record_impl(cfdh_ctx *c, double t);
+int cfdh_section_series_get_impl(cfdh_ctx *c, int64_t *rows, double *t, double *out);
+int cfdh_section_mean_reset_impl(cfdh_ctx *c);
+int cfdh_section_mean_accumulate_impl(cfdh_ctx *c, double weight);
+int cfdh_section_mean_get_impl(cfdh_ctx *c, int32_t *K, double *out, double *w_count);
+int64_t cfdh_section_info(const cfdh_ctx *c, int what);  // cfdh_info 120 .. 125
+void cfdh_section_destroy(cfdh_ctx *c);  // the buffers and the timing events
 
 // ---- wall shear stress of the P2/P1 context and the cycle-averaged wall shear indices (cfdh_wallstats.hip) ----------------
 int k_ipcs_wss(cfdh_ctx *c, double *out);                                 // out [nvert][dim]: entries of the wall vertices only

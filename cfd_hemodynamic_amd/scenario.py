@@ -119,7 +119,7 @@ class Scenario(ABC):
 
     def solve(self, output_folder: str = None, afterStepCallback: Callable[[float], None] = None,
               device_resident: bool = True, max_steps: int = None, write_every: int = 1, wall_indices=None, transport=None,
-              transport_diffusivity: float = 0.0, particles=None, flow_diagnostics=None, probes=None, sample_grid=None) -> str:
+              transport_diffusivity: float = 0.0, particles=None, flow_diagnostics=None, probes=None, sample_grid=None, sections=None) -> str:
         """wall_indices: None (default) -- nothing; True -- the cycle-averaged wall shear indices (TAWSS, OSI, RRT, mean and peak
         wall shear stress: wall_indices.py) over the whole run; (t0, t1) -- over the steps that end in (t0, t1].  They are accumulated
         on the device with weight dt right after the step's `assemble_wss()`; afterwards `self.wall_indices` holds the fields, `W` and
@@ -168,10 +168,22 @@ class Scenario(ABC):
         solvers on one GPU; NotImplementedError elsewhere.  The sample set, with its location and its means, stays on the solver
         after solve() so that `solver.sample_now()`, `sample_location()` and `sample_mean()` can still be asked about the last
         state (68 bytes per point in 3-D, 108 with the means: 1.1 to 1.8 GB for 1.6e7 nodes); only the probes' series buffer is
-        freed.  `solver.sample_set_points(np.zeros((0, gdim)))` frees the rest, and so does the next set or closing the context."""
+        freed.  `solver.sample_set_points(np.zeros((0, gdim)))` frees the rest, and so does the next set or closing the context.
+
+        sections: None (default) -- nothing; a dict -- exact integrals over cut planes inside the domain (cfdh_section_*,
+        sections.py): "planes" is a list of sections.plane(...) / sections.stations(...) entries, "every" (default 1) records the
+        ten-slot rows after every such step on the device, after the step's other features and before advance(), "rows" (default
+        256) is the capacity of the device buffer, which is emptied when full and at the end; "window" (t0, t1) adds the means of
+        the rows with weight dt under the window rule of the wall indices.  Afterwards `self.sections` holds t, origin, normal,
+        radius, rows [records, K, 10], straddling [K] and, under "window", window_mean [K, 10] with W and steps; with an output
+        folder sections.npz holds the same and sections.txt one block of lines per section.  The sections have state of their
+        own: they go with probes, a grid, particles and the flow diagnostics.  Closed-form P1 solvers on one GPU;
+        NotImplementedError elsewhere."""
         mesh, T, solver = self.mesh, self.T, self.solver
         self.probes = self.sample_grid = None
         pr, sg = self._sample_setup(probes, sample_grid, output_folder, write_every)
+        self.sections = None
+        sc = self._sections_setup(sections)
         self.flow_diagnostics = None
         fd = self._flow_setup(flow_diagnostics)
         self.transport = None
@@ -253,6 +265,8 @@ class Scenario(ABC):
                 self._probes_record(pr, t)
             if sg is not None:
                 self._grid_step(sg, t, i)
+            if sc is not None:
+                self._sections_step(sc, t, i)
             if writers and i % write_every == 0:
                 for w in writers:
                     w.write(t)
@@ -345,6 +359,8 @@ class Scenario(ABC):
                               {k: win[k] for k in ("mean_velocity", "mean_pressure", "fluctuation")}, located=sg["cell"] >= 0)
             elif sg["window"] is not None and mesh.comm.rank == 0:
                 print("sample_grid: no step ended inside the window %s (the run stopped at t=%.6g)" % (sg["window"], t))
+        if sc is not None:
+            self._sections_finish(sc, output_folder, t)
         if pt is not None:
             from . import particles as P
             fields = solver.particles_get()
@@ -402,6 +418,66 @@ class Scenario(ABC):
             os.makedirs(folder, exist_ok=True)
         return None, {"origin": origin, "spacing": spacing, "dims": dims, "cell": cell, "located": int((cell >= 0).sum()), "every": every,
                       "window": window, "window_steps": 0, "folder": folder, "frames": 0}
+
+    def _sections_setup(self, sections):
+        """Parses `sections` of solve() and puts the sections on the solver; None when off."""
+        if sections is None:
+            return None
+        if not isinstance(sections, dict) or set(sections) - {"planes", "every", "rows", "window"} or "planes" not in sections:
+            raise ValueError('sections must be None or a dict with "planes" and optionally "every", "rows" and "window"')
+        from .sections import as_arrays
+        origin, normal, radius = as_arrays(sections["planes"])
+        every, rows = int(sections.get("every", 1)), int(sections.get("rows", 256))
+        if len(origin) < 1 or every < 1 or rows < 1:
+            raise ValueError("sections: at least one plane, every >= 1 and rows >= 1")
+        window = sections.get("window")
+        if window is not None:
+            window = (float(window[0]), float(window[1]))
+        solver = self.solver
+        ctx = solver._section_ctx()  # the solver kinds without the sections raise here, before the time loop
+        solver.section_set((origin, normal, radius))
+        ctx.section_series_enable(rows)
+        if window is not None:
+            solver.section_mean_reset()
+        return {"origin": origin, "normal": normal, "radius": radius, "every": every, "rows": rows, "window": window, "window_steps": 0,
+                "straddling": solver.section_cut()[3], "t": [], "out": []}
+
+    def _sections_step(self, sc, t, i):
+        solver = self.solver
+        if sc["window"] is not None:
+            from .wall_indices import step_in_window
+            if step_in_window(t, self.dt, sc["window"]):
+                solver.section_mean_accumulate(self.dt)
+                sc["window_steps"] += 1
+        if i % sc["every"] == 0:
+            if solver._section_ctx().info(124) == sc["rows"]:
+                self._sections_drain(sc)
+            solver.section_record(t)
+
+    def _sections_drain(self, sc):
+        t, out = self.solver.section_series()
+        if len(t):
+            sc["t"].append(t)
+            sc["out"].append(out)
+
+    def _sections_finish(self, sc, output_folder, t):
+        solver = self.solver
+        self._sections_drain(sc)
+        solver._section_ctx().section_series_enable(0)  # the buffer is of no use after the run; the sections stay on the solver
+        K = len(sc["origin"])
+        self.sections = {"t": np.concatenate(sc["t"]) if sc["t"] else np.zeros(0), "origin": sc["origin"], "normal": sc["normal"],
+                         "radius": sc["radius"], "rows": np.concatenate(sc["out"]) if sc["out"] else np.zeros((0, K, 10)),
+                         "straddling": sc["straddling"]}
+        if sc["window_steps"] > 0:
+            win = solver.section_mean()
+            self.sections.update(window_mean=win["rows"], window_W=win["W"], window_steps=win["steps"])
+        elif sc["window"] is not None and self.mesh.comm.rank == 0:
+            print("sections: no step ended inside the window %s (the run stopped at t=%.6g)" % (sc["window"], t))
+        if output_folder and self.mesh.comm.rank == 0:
+            from .sections import write_npz, write_txt
+            write_npz(os.path.join(output_folder, "sections.npz"), **self.sections)
+            write_txt(os.path.join(output_folder, "sections.txt"), self.sections["t"], self.sections["rows"], sc["origin"], sc["normal"],
+                      sc["radius"], sc["straddling"])
 
     def _probes_record(self, pr, t):
         if pr["waiting"] == pr["rows"]:

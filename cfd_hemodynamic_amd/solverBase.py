@@ -286,6 +286,52 @@ class SolverBase(ABC):
         out["W"], out["steps"] = float(W), int(count)
         return out
 
+    # -- cut-plane sections on the device (cfdh_section_*: flow rate, mean pressure, energy flux through planes) -----------------
+    def _section_ctx(self):
+        return self._transport_ctx("sections", "section kernel")
+
+    def section_set(self, planes):
+        """The sections: a list of sections.plane(...) / sections.stations(...) entries, or (origin [K, gdim], normal [K, gdim],
+        radius [K] or None).  The cut is built once; an empty list removes the set."""
+        from . import sections
+        ctx = self._section_ctx()
+        origin, normal, radius = sections.as_arrays(planes)
+        ctx.section_set(origin, normal, radius)
+
+    def section_cut(self):
+        """(ptr [K + 1], cell [entries], measure [entries], straddling [K]): per section the cut and taken cells in ascending index,
+        the measure of their polygons and the number of polygons that straddle the clip ball."""
+        return self._section_ctx().section_get_cut()
+
+    def section_now(self):
+        """[K, 10]: area, flow rate, int p, int (u.n)^2, int |u|^2, int p u.n, int rho/2 |u|^2 u.n, int u_i of the current u_sol."""
+        return self._section_ctx().section_now()
+
+    def section_record(self, t, rows=None):
+        """Append the rows of the current state to the series on the device (no copy, no synchronisation); `rows` (first call, or
+        to resize) is the capacity in records."""
+        ctx = self._section_ctx()
+        if rows is not None:
+            ctx.section_series_enable(rows)
+        ctx.section_record(t)
+
+    def section_series(self):
+        """(t [rows], rows [rows, K, 10]) recorded since the last call; empties the device buffer."""
+        return self._section_ctx().section_series_get()
+
+    def section_mean_reset(self):
+        """Zero the window means of the rows (allocated on first use)."""
+        self._section_ctx().section_mean_reset()
+
+    def section_mean_accumulate(self, w):
+        """Add the rows of the current state to the window means with weight w (the step's dt)."""
+        self._section_ctx().section_mean_accumulate(w)
+
+    def section_mean(self):
+        """dict: rows [K, 10] (sum w row / W; None while nothing is accumulated), W and steps."""
+        rows, W, count = self._section_ctx().section_mean_get()
+        return {"rows": rows, "W": W, "steps": count}
+
     @staticmethod
     def _simplex_gradients(mesh):
         """grad(lambda_a) of every cell of a P1 simplex mesh, [nc, d + 1, d]."""

@@ -895,6 +895,73 @@ int cfdh_sample_mean_reset(cfdh_ctx *ctx);
 int cfdh_sample_mean_accumulate(cfdh_ctx *ctx, double weight);
 int cfdh_sample_mean_get(cfdh_ctx *ctx, int which, int64_t *n, double *out);
 
+/* ---- cut-plane sections: flow rate, mean pressure and energy flux through a plane inside the domain (not in the reference) ----
+ *
+ * Exact integrals of the P1 fields of u_sol over the intersection of a plane (a line in 2-D) with the mesh, taken while the state
+ * sits on the device, without a copy of the field.
+ *
+ * Definition.  Section k is a point o_k, a unit normal n_k and a radius r_k; r_k <= 0 (or radius == NULL) means unbounded.  The
+ * caller passes any non-zero normal and the library normalises it.  In 2-D the "plane" is the line through o with normal n.
+ *   Signed distance: s_v = n . (x_v - o), computed by one function once per vertex and section, so that two cells which share a
+ *     vertex agree on its sign.
+ *   Above and below: a vertex is above if s_v >= 0 and below otherwise.  Zero counts as above.
+ *   Cut cells: a cell is cut iff it has at least one vertex above and one below.
+ *   Polygon vertices: on the edges that join an above vertex a and a below vertex b, at t = s_a / (s_a - s_b) in [0, 1) from a.
+ *   Shapes: in 3-D a 1-3 split gives a triangle, a 2-2 split the convex quadrilateral (a0b0, a0b1, a1b1, a1b0), divided into two
+ *     triangles along the diagonal from a0b0 to a1b1.  In 2-D the cut is a segment.
+ *   Consequence: a facet that lies exactly in the plane belongs to the one cell on its below side (its t are 0 there) and the
+ *     cell above is not cut: it is counted once, never twice.  A section placed on a boundary whose outward normal is +n sees
+ *     that boundary's facets; on one whose outward normal is -n it sees nothing.
+ *   Clip ball: with r > 0 a cut polygon is taken whole if the arithmetic mean of its vertices lies within r of o, and dropped
+ *     otherwise; no polygon is clipped by the ball.  That picks one vessel out of a plane that crosses several.  The number of
+ *     taken or dropped polygons with vertices on both sides of the sphere is kept per section (straddling); a well placed ball
+ *     has 0.
+ * The row of a section has CFDH_SECTION_NQ = 10 doubles, integrals over the taken polygons (dA: area in 3-D, length in 2-D; rho
+ * of cfdh_set_params):
+ *   0 A = int dA              1 Q = int u.n dA          2 int p dA            3 int (u.n)^2 dA        4 int |u|^2 dA
+ *   5 int p (u.n) dA          6 int rho/2 |u|^2 (u.n) dA                      7 .. 9 int u_i dA (slot 9 is +0.0 in 2-D)
+ * All are exact up to rounding: the integrands have degree <= 3 and are integrated by 2-point Gauss on segments and a 7-point
+ * rule of degree 3 on triangles.  A section that cuts nothing returns ten +0.0.
+ *
+ * cfdh_section_set(ctx, K, origin[K][d], normal[K][d], radius[K] or NULL) builds the cut on the host, once: per section the cut
+ * and taken cells in ascending caller's cell index, each with the local edges that carry its polygon vertices, their t and the
+ * measures of its sub-simplices.  The device re-derives no sign and no t.  The lists do not depend on the order or orientation in
+ * which the context stores its cells.  A new call replaces the set and drops the series and the means; K = 0 removes the set and
+ * frees its buffers.  CFDH_E_ARG: K < 0 or K > 256, a non-finite origin, normal or radius, a zero normal, more than 2^31 - 1
+ * entries in all; a refused call leaves the previous set in place.
+ * cfdh_section_get_cut(ctx, &K, ptr[K + 1], cell, measure, straddling[K]): the lists as built, with the query convention of
+ * cfdh_get_csr: *K always; ptr and straddling when not NULL; cell (caller's ids) and measure (of the whole polygon) both or
+ * neither, ptr[K] entries each.  Without a set *K = 0.
+ *
+ * Evaluation.  One lane per entry gathers u and p at the d + 1 vertices of its cell and forms the ten partial integrals; a block
+ * holds entries of one section only and adds them in a fixed order, and the blocks of a section are added in block order.  No
+ * atomics: two calls return the same bytes, and the row of a section does not depend on the other sections of the set.  The calls
+ * below need a set, cfdh_set_params and a state (CFDH_E_STATE otherwise).
+ * cfdh_section_now(ctx, &K, out[K][10]): one evaluation and one download; out == NULL only queries *K.
+ * cfdh_section_series_enable(ctx, rows) allocates a device buffer of `rows` blocks [K][10] (0 frees it; negative or above 2^40
+ * bytes: CFDH_E_ARG).  cfdh_section_record(ctx, t) appends the block of the current state and keeps t on the host: no
+ * synchronisation, no copy.  When the buffer is full: CFDH_E_STATE, the message names cfdh_section_series_get(ctx, &rows, t[rows],
+ * out[rows][K][10]), which downloads what was recorded and empties the buffer (out == NULL only queries *rows).
+ * cfdh_section_mean_reset allocates K x 10 accumulators on first use and zeroes them; cfdh_section_mean_accumulate(weight) adds
+ * w times the current rows, W += w and count += 1 (weight finite and > 0, else CFDH_E_ARG; before a reset: CFDH_E_STATE);
+ * cfdh_section_mean_get(ctx, &K, out[K][10], w_count[2]) returns sum w row / W and {W, count}; either may be NULL; out with
+ * W == 0, or any call before a reset: CFDH_E_STATE.
+ *
+ * Contexts: as for cfdh_sample_*: closed-form P1 contexts of cfdh_create (gdim 2 and 3), the whole mesh on one GPU.  Every entry
+ * point returns CFDH_E_ARG with a reason, before any device work and with the context unchanged, on generic-element contexts, on
+ * contexts of cfdh_create_ipcs and on a part of a partitioned run.  A context that never sets sections allocates and launches
+ * nothing (cfdh_info 120 .. 125). */
+#define CFDH_SECTION_NQ 10
+int cfdh_section_set(cfdh_ctx *ctx, int32_t K, const double *origin, const double *normal, const double *radius);
+int cfdh_section_get_cut(cfdh_ctx *ctx, int32_t *K, int64_t *ptr, int32_t *cell, double *measure, int32_t *straddling);
+int cfdh_section_now(cfdh_ctx *ctx, int32_t *K, double *out);
+int cfdh_section_series_enable(cfdh_ctx *ctx, int64_t rows);
+int cfdh_section_record(cfdh_ctx *ctx, double t);
+int cfdh_section_series_get(cfdh_ctx *ctx, int64_t *rows, double *t, double *out);
+int cfdh_section_mean_reset(cfdh_ctx *ctx);
+int cfdh_section_mean_accumulate(cfdh_ctx *ctx, double weight);
+int cfdh_section_mean_get(cfdh_ctx *ctx, int32_t *K, double *out, double *w_count);
+
 /* ---- multi-GPU ---------------------------------------------- */
 
 /* Halo plan in local vertex numbers: for neighbour k, send_idx[send_ptr[k]..send_ptr[k+1])
@@ -969,7 +1036,9 @@ int cfdh_profile_reset(cfdh_ctx *ctx);
  * 111: points in the sample set (cfdh_sample_*), 112: points located, 113: launches of the sample kernel since cfdh_create, 114:
  * row blocks waiting in the series, 115 / 116: nanoseconds, by device events, of the last locate / of the last sample kernel (as
  * 109 / 110), 117 .. 119: the bin grid built last: the number of times its edge was doubled, the total length of its
- * lists, the longest list */
+ * lists, the longest list;
+ * 120: sections set (cfdh_section_*), 121: entries of their cut lists in all, 122: the longest list, 123: evaluations launched
+ * since cfdh_create, 124: row blocks waiting in the series, 125: nanoseconds, by device events, of the last evaluation (as 109) */
 int64_t cfdh_info(const cfdh_ctx *ctx, int what);
 
 #ifdef __cplusplus
